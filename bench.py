@@ -44,7 +44,7 @@ def baseline_metric():
         return "Cheb-TGCN fwd: G edge\u00b7timesteps/s + achieved HBM GB/s, K=5 on 160M-edge graph"
 
 
-HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s; ~6.3 TB/s measured copy)
+HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (8.0 TB/s; ~6.3 TB/s measured copy)
 
 
 def build_workload(name, labeling, device, n_override=None, nnz_override=None):
@@ -131,6 +131,29 @@ def make_input(op, spec, device, seed):
     else:
         shape = (q, n) if spec["f"] == 1 else (q, n, spec["f"])
     return torch.randn(shape, device=device, generator=g)
+
+
+DUMP_BYTES = 64_000_000     # --dump-outputs: all files of one run together, .npy headers included
+
+
+def dump_outputs(path, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every tensor as <path>/<name>.npy (float32, float64 kept).  One larger than its share of `budget` is replaced by a
+    fixed sample of its elements -- flat indices drawn with a seeded generator, sorted, de-duplicated, gathered on the device without a copy
+    of the whole tensor -- and the indices go next to it as <name>_index.npy (float64, exact below 2^53).  The same arguments give the same
+    sample, so two builds are compared element for element."""
+    os.makedirs(path, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    for name, t in arrays.items():
+        t = t.detach()
+        dt = np.float64 if t.dtype == torch.float64 else np.float32
+        if t.numel() * np.dtype(dt).itemsize + 128 <= share:
+            np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(dt))
+            continue
+        k = (share - 256) // (np.dtype(dt).itemsize + 8)      # values + float64 indices, two 128-byte headers
+        idx = np.unique(np.random.default_rng(20240531).integers(0, t.numel(), k, dtype=np.int64))
+        sub = tuple(torch.from_numpy(i).to(t.device) for i in np.unravel_index(idx, tuple(t.shape)))
+        np.save(os.path.join(path, name + ".npy"), t[sub].cpu().numpy().astype(dt))
+        np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
 
 
 def measured_copy_gbps(device, nbytes=2 << 30):
@@ -256,7 +279,7 @@ def host_description():
                 sched_affinity=len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else None)
 
 
-MFMA_BF16_PEAK_TFLOPS = 2500.0      # /opt/skills/guides/MI355X_MICROARCH.md: dense bf16 matrix peak (no sparsity)
+MFMA_BF16_PEAK_TFLOPS = 2500.0      # MI355X dense bf16 matrix peak (no sparsity)
 MFMA_F32_PEAK_TFLOPS = 157.3        # fp32 matrix peak
 
 
@@ -654,7 +677,11 @@ def main():
     ap.add_argument("--force-extras", action="store_true", help="run the vertex-sharded extras also at world 1 (one rank under a launcher: the collectives of the N > 1 path meet RCCL)")
     ap.add_argument("--extras-exchange", default="auto", choices=["auto", "halo", "allgather"], help="exchange form of the vertex-sharded runs (auto: all-gather when the halo is most of the graph)")
     ap.add_argument("--extras-budget", type=float, default=150.0, help="seconds after which the extra runs are abandoned and the headline line is printed without them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (64 MB in all; "
+                                                                         "a larger output is a fixed seeded sample with its flat indices in <name>_index.npy)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     launched = "WORLD_SIZE" in os.environ and "RANK" in os.environ      # started by torch.distributed.run (the driver's N > 1 command, or self_launch)
     if args.gpus > 1 and not launched:
@@ -750,6 +777,9 @@ def main():
         sync_all()
         dt = time.perf_counter() - t0
         prof = [] if rehearsal else _lib.profile_stop(65536)
+        if args.dump_outputs:
+            # each rank's own out: the whole output at world 1, the rank's time steps / vertex rows otherwise
+            dump_outputs(args.dump_outputs, {"out" if world == 1 else "out_rank%d" % rank: out}, DUMP_BYTES // world)
     per_rank = None
     if dist is not None:
         # what every rank measured on its own (the headline is the MAX): a scaling run that comes out below N x is read from these -- a slow rank,

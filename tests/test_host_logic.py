@@ -268,21 +268,98 @@ def test_compat_import_paths():
     subprocess.run([sys.executable, "-c", code], check=True)
 
 
-REFERENCE = "/root/reference"
+# A stand-in for a reference checkout behind compat/: a `gcn` package whose graph.py defines the helpers the shim delegates (written for
+# this test; small numpy / scipy versions of the same functions, not the reference's code).  The delegation under test does not care whose
+# graph.py it finds, only that it is the file behind compat/ on sys.path.
+_STANDIN_GRAPH = """
+import numpy as np
+import scipy.sparse
+import scipy.sparse.linalg
+import scipy.spatial.distance
 
 
-def _run_with_path(code, *entries):
+def grid(m, dtype=np.float32):
+    xx, yy = np.meshgrid(np.linspace(0, 1, m, dtype=dtype), np.linspace(0, 1, m, dtype=dtype))
+    return np.stack([xx.ravel(), yy.ravel()], axis=1)
+
+
+def distance_scipy_spatial(z, k=4, metric="euclidean"):
+    d = scipy.spatial.distance.squareform(scipy.spatial.distance.pdist(z, metric))
+    idx = np.argsort(d, axis=1)[:, 1:k + 1]
+    return np.take_along_axis(d, idx, axis=1), idx
+
+
+def distance_sklearn_metrics(z, k=4, metric="euclidean"):
+    return distance_scipy_spatial(z, k, metric)
+
+
+def adjacency(dist, idx):
+    n, k = dist.shape
+    sigma2 = np.mean(dist[:, -1]) ** 2
+    w = np.exp(-dist ** 2 / sigma2)
+    W = scipy.sparse.coo_matrix((w.ravel(), (np.repeat(np.arange(n), k), idx.ravel())), shape=(n, n)).tocsr()
+    W.setdiag(0)
+    return W.maximum(W.T)
+
+
+def laplacian(W, normalized=True):
+    d = np.asarray(W.sum(axis=0)).ravel()
+    if not normalized:
+        return scipy.sparse.diags(d) - W
+    s = 1 / np.sqrt(d + np.spacing(1))
+    D = scipy.sparse.diags(s)
+    return scipy.sparse.identity(W.shape[0], dtype=W.dtype) - D @ W @ D
+
+
+def lmax(L, normalized=True):
+    return 2.0 if normalized else float(scipy.sparse.linalg.eigsh(L, k=1, which="LM", return_eigenvectors=False)[0])
+
+
+def rescale_L(L, lmax=2):
+    return (2.0 / lmax) * L - scipy.sparse.identity(L.shape[0], dtype=L.dtype)
+
+
+def fourier(L):
+    return np.linalg.eigh(L.toarray())
+
+
+def lanczos(L, X, K):
+    raise NotImplementedError
+
+
+def replace_random_edges(A, noise_level):
+    return A
+
+
+def chebyshev(L, X, K):
+    raise NotImplementedError
+"""
+
+
+def _standin_reference(root):
+    """<root>/gcn/{__init__,graph}.py: what the shim looks for behind compat/ on sys.path"""
+    pkg = root / "gcn"
+    pkg.mkdir(parents=True)
+    (pkg / "__init__.py").write_text("")
+    (pkg / "graph.py").write_text(_STANDIN_GRAPH)
+    return str(root)
+
+
+def _run_with_path(code, cwd, *entries):
     import subprocess
     import sys
     env = dict(os.environ, PYTHONPATH=os.pathsep.join(entries), PYTHONDONTWRITEBYTECODE="1")
-    return subprocess.run([sys.executable, "-c", code], env=env, cwd="/tmp", capture_output=True, text=True)
+    return subprocess.run([sys.executable, "-c", code], env=env, cwd=str(cwd), capture_output=True, text=True)
 
 
-@pytest.mark.skipif(not os.path.isfile(os.path.join(REFERENCE, "gcn", "graph.py")), reason="no reference checkout (GPU box): nothing to delegate to")
-def test_compat_gcn_graph_delegates_to_the_reference():
+def test_compat_gcn_graph_delegates_to_the_reference(tmp_path):
     """With PYTHONPATH=compat:repo:reference `import gcn.graph as graph` serves chebyshev from this repo and every
-    other name from the reference's own gcn/graph.py, so examples/tgcn_mnist.py:52-54,173-175,194 and
-    examples/pytorch_based/pytorch_hcp_tgcn.py:13,52-57 run unchanged; nothing of the reference is copied or imported under its public name."""
+    other name from the checkout's own gcn/graph.py, so examples/tgcn_mnist.py:52-54,173-175,194 and
+    examples/pytorch_based/pytorch_hcp_tgcn.py:13,52-57 run unchanged; nothing of the reference is copied or imported under its public name.
+    The checkout is a stand-in written under tmp_path (_STANDIN_GRAPH), so the test needs nothing outside the repository."""
+    reference = _standin_reference(tmp_path / "reference")
+    work = tmp_path / "cwd"
+    work.mkdir()
     code = """
 import sys
 import numpy as np
@@ -312,12 +389,12 @@ else:
 import gcn
 assert any(p.startswith(%r) for p in gcn.__path__)      # gcn.models / gcn.utils resolve to the reference's files
 print("ok")
-""" % (os.path.join(REFERENCE, "gcn", "graph.py"), REFERENCE)
-    r = _run_with_path(code, os.path.join(ROOT, "compat"), ROOT, REFERENCE)
+""" % (os.path.join(reference, "gcn", "graph.py"), reference)
+    r = _run_with_path(code, work, os.path.join(ROOT, "compat"), ROOT, reference)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
 
 
-def test_compat_gcn_graph_without_a_reference_checkout_says_so():
+def test_compat_gcn_graph_without_a_reference_checkout_says_so(tmp_path):
     """Only chebyshev is native; asking for a delegated name without a checkout behind compat/ is an AttributeError naming the cause (so that
     attribute probes -- hasattr, getattr with a default, pickle.whichmodule -- see a miss), and an ImportError for `from gcn.graph import name`."""
     code = """
@@ -341,7 +418,7 @@ import pickle, sys
 assert pickle.whichmodule(len, "len") == "builtins"        # scans sys.modules with getattr(module, name, None): must not blow up on the shim
 print("ok")
 """
-    r = _run_with_path(code, os.path.join(ROOT, "compat"), ROOT)
+    r = _run_with_path(code, tmp_path, os.path.join(ROOT, "compat"), ROOT)
     assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr[-2000:]
 
 
