@@ -150,14 +150,14 @@ def test_random_module_vs_oracle(case, gpu_device):
 
 def test_random_modules_on_compact_hop_tensors(gpu_device, monkeypatch):
     """The same random cases (five classes, vertex 0 isolated in every graph, hubs, K = 1 ... 8, widths 1 ... 640) with the general path
-    FORCED onto compact hop tensors -- every layout (incl. the vertex-major form that is off by default), both recursions, the one-call driver
-    and the python-level pipeline, with the last hop fused into the projection where that form exists -- against the oracle."""
+    FORCED onto compact hop tensors wherever they exist (row layout 0; the vertex-major layout keeps full-size hop tensors) -- both
+    recursions, the one-call driver and the python-level pipeline, with the last hop fused into the projection where that form exists --
+    against the oracle."""
     from tgcn_amd import functional as F, graph, _lib
     monkeypatch.setattr(graph, "COMPACT_MIN_ROWS", 1)
     monkeypatch.setattr(graph, "COMPACT_MIN_EMPTY", 0.0)
     monkeypatch.setattr(F, "SMALL_PATH", False)
     monkeypatch.setattr(F, "PROJECT_FIRST", False)
-    monkeypatch.setattr(F, "COMPACT_LAYOUT1", True)
     used = {"drv": 0, "py": 0}
     real_drv, real_py = F.cheb_forward_compact, F.compact_forward
     monkeypatch.setattr(F, "cheb_forward_compact", lambda *a, **k: (used.__setitem__("drv", used["drv"] + 1), real_drv(*a, **k))[1])

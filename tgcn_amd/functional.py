@@ -4,6 +4,7 @@ Every product, sum and axpy of the forward runs in libtgcn_hip.so (include/tgcn_
 memory, the stream and autograd bookkeeping.  There is no CPU fallback.
 """
 import ctypes as C
+import dataclasses
 import functools
 import threading
 
@@ -64,6 +65,15 @@ def _aligned16(C_row, *tensors):
         if t is not None:
             ok = ok and t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0 and t.stride(1) % 4 == 0
     return ok
+
+
+def _aligned_input(x3):
+    """x3, copied when a batch slice data[i:i+bs] of odd-width rows starts off a 16-byte boundary: the drivers want 16 bytes"""
+    return x3.clone() if x3.data_ptr() % 16 else x3
+
+
+def _workspace(nbytes, device, floor=256):
+    return torch.empty(max(nbytes, floor), dtype=torch.uint8, device=device)
 
 
 def weight_layout(W_kcn, kind):
@@ -145,8 +155,7 @@ def csr_hop(op, x, z=None, alpha=1.0, beta=0.0, want_p=False, out=None, p_out=No
             csr_hop(op, x[sl], None if z is None else z[sl], alpha, beta, want_p, y[sl], None if p is None else p[sl],
                     None if z2 is None else z2[sl], gamma)
         return (y, p) if want_p else y
-    ws_bytes = L.tgcn_csr_hop_workspace_bytes(C.byref(sched.struct), nb, Crow, 1 if al else 0)
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=x.device)
+    ws = _workspace(L.tgcn_csr_hop_workspace_bytes(C.byref(sched.struct), nb, Crow, 1 if al else 0), x.device, floor=16)
     X, Y = _dense(x), _dense(y)
     Z = _dense(z) if z is not None else None
     P = _dense(p) if p is not None else None
@@ -191,8 +200,7 @@ def project_first(x3, Wcat, bias, bias_kind, K, N, rowmap=None):
     _lib.require_device(x3, Wcat, bias, rowmap)
     q, rows, Crow = x3.shape
     assert x3.is_contiguous() and Wcat.is_contiguous() and tuple(Wcat.shape) == (Crow, K * N) and (rowmap is None or (rowmap.dtype == torch.int32 and rowmap.numel() == rows))
-    if x3.data_ptr() % 16:
-        x3 = x3.clone()
+    x3 = _aligned_input(x3)
     Z = torch.empty((q, rows, K * N), dtype=torch.float32, device=x3.device)
     b = bias.contiguous() if bias is not None else None
     _lib.check(_lib.lib().tgcn_cheb_project_first_f32(_lib.stream_ptr(), q, rows, Crow, K, N, _lib.ptr(x3), _lib.ptr(Wcat), _lib.ptr(b),
@@ -289,6 +297,32 @@ def chebyshev_values_grad(op, x3, W_kcn, g, basis=None):
     return dval
 
 
+def _adjoint_hops(opT, G, mode):
+    """sum_k T_k(L^T) G[k] for the K per-term input gradients G (a list or a (K, ...) tensor of (q, n, C) terms): Horner for MODE_POWER
+    (b = G_j + L^T b), Clenshaw for MODE_CHEBYSHEV (b_{K-1} = G_{K-1}, b_k = G_k + 2 L^T b_{k+1} - b_{k+2}, result G_0 + L^T b_1 - b_2); one
+    hop launch per step.  K = 1: G[0] itself."""
+    K = len(G)
+    if K == 1:
+        return G[0]
+    if mode == MODE_POWER:
+        b = G[K - 1]
+        for j in range(K - 2, -1, -1):
+            b = csr_hop(opT, b, z=G[j], alpha=1.0, beta=1.0)
+        return b
+    b1, b2 = G[K - 1], None
+    for k in range(K - 2, 0, -1):
+        b1, b2 = csr_hop(opT, b1, z=b2, alpha=2.0, beta=-1.0, z2=G[k], gamma=1.0), b1
+    return csr_hop(opT, b1, z=b2, alpha=1.0, beta=-1.0, z2=G[0], gamma=1.0)
+
+
+def _bias_grad(g3, bias_kind, bias_shape, needed):
+    """gradient of a per-channel / per-(vertex, channel) bias from the (samples, n, N) output gradient (torch reductions), or None when
+    there is no bias or it needs none"""
+    if bias_shape is None or not needed:
+        return None
+    return (g3.sum(dim=(0, 1)) if bias_kind == BIAS_CHANNEL else g3.sum(dim=0)).reshape(bias_shape)
+
+
 @_on_device
 def _windows_forward(op, x3, W, bias, bias_kind, mode):
     """x3 (S, n, T) fp32 contiguous, W (K, H, N) in the WORKING basis (folded for MODE_POWER) -> (out, stack (K, S, n, T))"""
@@ -311,16 +345,15 @@ def _windows_forward(op, x3, W, bias, bias_kind, mode):
 class ChebWindowsFn(torch.autograd.Function):
     """Streaming time-window layer with its backward: the hops run once on the T columns of every recording in both directions.
     d series = sum_k T_k(L^T) G_k with G_k the per-term input gradients of the window projection (tgcn_cheb_windows_backward_f32),
-    folded by Horner (mode 0) / Clenshaw (mode 1) hops on L^T exactly as in layer_backward; dW from the same entry point."""
+    folded by Horner (mode 0) / Clenshaw (mode 1) hops on L^T (_adjoint_hops, as in layer_backward); dW from the same entry point."""
 
     @staticmethod
     @_on_device
     def forward(ctx, series, weight_khg, bias, op, mode, bias_kind):
         x3 = series.float().contiguous()
         W = weight_khg.float().contiguous()
-        K = W.shape[0]
-        fold = power_fold_matrix(K, W.device) if (mode == MODE_POWER and K > 2) else None
-        Wt = fold_weight(fold, W) if fold is not None else W
+        fold = _power_fold(mode, W)
+        Wt = _working_weight(fold, W)
         out, stack = _windows_forward(op, x3, Wt, bias, bias_kind, mode)
         ctx.save_for_backward(x3, Wt)
         ctx.stack = stack if ctx.needs_input_grad[1] else None       # the basis the weight gradient contracts with g
@@ -340,31 +373,14 @@ class ChebWindowsFn(torch.autograd.Function):
         need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         G = torch.empty((K, S, n, T), dtype=torch.float32, device=g.device) if need_x else None
         dW = torch.empty((K, H, N), dtype=torch.float32, device=g.device) if need_w else None
-        ws = torch.empty(max(L.tgcn_cheb_windows_wgrad_workspace_bytes(S, n, T, H, N, K), 16), dtype=torch.uint8, device=g.device)
+        ws = _workspace(L.tgcn_cheb_windows_wgrad_workspace_bytes(S, n, T, H, N, K), g.device, floor=16)
         _lib.check(L.tgcn_cheb_windows_backward_f32(_lib.stream_ptr(), S, n, T, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
                                                     _lib.ptr(Wt.reshape(K * H, N)), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel()))
         ctx.stack = None
-        gx = gb = None
-        if need_x:
-            opT = ctx.op.transpose()
-            if K == 1:
-                gx = G[0]
-            elif ctx.mode == MODE_POWER:                              # Horner: b = G_j + L^T b
-                b = G[K - 1]
-                for j in range(K - 2, -1, -1):
-                    b = csr_hop(opT, b, z=G[j], alpha=1.0, beta=1.0)
-                gx = b
-            else:                                                     # Clenshaw on L^T
-                b1, b2 = G[K - 1], None
-                for k in range(K - 2, 0, -1):
-                    t = csr_hop(opT, b1, z=b2, alpha=2.0, beta=-1.0, z2=G[k], gamma=1.0)
-                    b1, b2 = t, b1
-                gx = csr_hop(opT, b1, z=b2, alpha=1.0, beta=-1.0, z2=G[0], gamma=1.0)
+        gx = _adjoint_hops(ctx.op.transpose(), G, ctx.mode) if need_x else None
         if need_w and ctx.fold is not None:
             dW = fold_weight(ctx.fold, dW, transpose=True)
-        if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
-            g4 = g.view(S * nwin, n, N)
-            gb = (g4.sum(dim=(0, 1)) if ctx.bias_kind == BIAS_CHANNEL else g4.sum(dim=0)).reshape(ctx.bias_shape)
+        gb = _bias_grad(g.view(S * nwin, n, N), ctx.bias_kind, ctx.bias_shape, ctx.needs_input_grad[2])
         return gx, dW, gb, None, None, None
 
 
@@ -375,12 +391,9 @@ def cheb_time_windows(op, series, weight_khg, bias, bias_kind, mode=MODE_POWER):
     once on the T columns of each recording -- in the backward too (ChebWindowsFn), so the windows it replaces can be
     trained through."""
     _lib.require_device(series, weight_khg, bias)
-    if op.perm is not None:        # reordered operand: its hops work in their own labels (differentiable index ops, as in cheb_layer)
-        series = relabel_rows(series, op.perm, op.inv_perm)
-        if bias is not None and bias_kind == BIAS_VERTEX_CHANNEL:
-            bias = relabel_rows(bias.reshape(op.n, -1), op.perm, op.inv_perm, dim=0)
-        return relabel_rows(ChebWindowsFn.apply(series, weight_khg, bias, op, mode, bias_kind), op.inv_perm, op.perm)
-    return ChebWindowsFn.apply(series, weight_khg, bias, op, mode, bias_kind)
+    series, bias = _to_operand_labels(op, series, bias, bias_kind)
+    out = ChebWindowsFn.apply(series, weight_khg, bias, op, mode, bias_kind)
+    return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)
 
 
 @_on_device
@@ -394,8 +407,7 @@ def cheb_wgrad(terms, g2d):
     dW = torch.empty((T, Kc, N), dtype=torch.float32, device=g2d.device)
     for t0 in range(0, T, 32):
         nt = min(32, T - t0)
-        ws_bytes = L.tgcn_cheb_wgrad_workspace_bytes(M, Kc, N, nt)
-        ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=g2d.device)
+        ws = _workspace(L.tgcn_cheb_wgrad_workspace_bytes(M, Kc, N, nt), g2d.device, floor=16)
         a = (C.c_void_p * nt)(*[terms[t0 + i].data_ptr() for i in range(nt)])
         lda = (C.c_int64 * nt)(*[terms[t0 + i].stride(0) for i in range(nt)])
         _lib.check(L.tgcn_cheb_wgrad_f32(_lib.stream_ptr(), M, Kc, N, nt, a, lda, _lib.ptr(g2d), g2d.stride(0),
@@ -416,6 +428,15 @@ def choose_q_chunk(q, n, C_row):
     return int(max(1, min(q, (64 << 20) // max(per_q, 1))))
 
 
+def _hops_setup(op, q, Crow, layout, q_chunk):
+    """(layout, q_chunk, schedule) of the hops-then-projection drivers: the row layout and samples per pass default to choose_layout /
+    choose_q_chunk; layout 1 hops one (vertex, q*C) row per vertex"""
+    layout = choose_layout(q, op.n, Crow) if layout is None else layout
+    q_chunk = choose_q_chunk(q, op.n, Crow) if q_chunk is None else q_chunk
+    hop_C = q * Crow if layout == 1 else Crow
+    return layout, q_chunk, op.schedule_for(hop_C, hop_C % 4 == 0)
+
+
 @_on_device
 def cheb_forward_raw(op, x3, Wt, bias, bias_kind, mode, K, layout=None, q_chunk=None):
     """Fused layer forward through tgcn_cheb_forward_f32.  x3: (q, n, C) contiguous; Wt: (K*C, N)."""
@@ -424,16 +445,9 @@ def cheb_forward_raw(op, x3, Wt, bias, bias_kind, mode, K, layout=None, q_chunk=
     q, n, Crow = x3.shape
     N = Wt.shape[1]
     assert x3.is_contiguous() and Wt.is_contiguous() and Wt.shape[0] == K * Crow and n == op.n
-    if x3.data_ptr() % 16:          # a batch slice data[i:i+bs] of odd-width rows may start at any float: the driver wants 16 bytes
-        x3 = x3.clone()
-    if layout is None:
-        layout = choose_layout(q, n, Crow)
-    if q_chunk is None:
-        q_chunk = choose_q_chunk(q, n, Crow)
-    hop_C = q * Crow if layout == 1 else Crow
-    sched = op.schedule_for(hop_C, hop_C % 4 == 0)
-    ws_bytes = L.tgcn_cheb_forward_workspace_bytes(C.byref(sched.struct), K, q, n, Crow, layout, q_chunk)
-    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=x3.device)
+    x3 = _aligned_input(x3)
+    layout, q_chunk, sched = _hops_setup(op, q, Crow, layout, q_chunk)
+    ws = _workspace(L.tgcn_cheb_forward_workspace_bytes(C.byref(sched.struct), K, q, n, Crow, layout, q_chunk), x3.device)
     out = torch.empty((q, n, N), dtype=torch.float32, device=x3.device)
     _lib.check(L.tgcn_cheb_forward_f32(_lib.stream_ptr(), C.byref(op.struct), C.byref(sched.struct), mode, K, q, n, Crow,
                                        N, _lib.ptr(x3), _lib.ptr(Wt), _lib.ptr(bias), bias_kind, _lib.ptr(out), layout,
@@ -453,8 +467,7 @@ def cheb_forward_compact(plan, x3, Wt, bias, bias_kind, K, q_chunk=None, mode=MO
     q, n, Crow = x3.shape
     N = Wt.shape[1]
     assert x3.is_contiguous() and Wt.is_contiguous() and Wt.shape[0] == K * Crow and n == plan.n and K >= 2
-    if x3.data_ptr() % 16:
-        x3 = x3.clone()
+    x3 = _aligned_input(x3)
     auto_chunk = False
     if q_chunk is None:
         q_chunk = COMPACT_Q_CHUNK
@@ -485,7 +498,7 @@ def cheb_forward_compact(plan, x3, Wt, bias, bias_kind, K, q_chunk=None, mode=MO
     while True:
         ws_bytes = L.tgcn_cheb_compact_layer_workspace_bytes(C.byref(sched.struct), mode, K, q, plan.n_c, Crow, q_chunk, 1 if keep else 0)
         try:
-            ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=x3.device)
+            ws = _workspace(ws_bytes, x3.device)
             break
         except torch.OutOfMemoryError:
             if not auto_chunk or q_chunk <= 1:
@@ -502,27 +515,18 @@ def cheb_forward_compact(plan, x3, Wt, bias, bias_kind, K, q_chunk=None, mode=MO
     return out, terms
 
 
-COMPACT_LAYOUT1 = False           # compact hop tensors for the vertex-major layout too: built and tested, measured on cfg5n (TGCNCheb(L,1,64,5), q = 16 on the
-                                  # 10 M-vertex R-MAT): hop 2.08 -> 2.08 ms (64-byte rows: the launch is bound by its 160 M line requests, not by the rows it
-                                  # writes), row-mapped projection 10.3 -> 12.2 ms (41 GB of output through a row map instead of one stream) => off
 COMPACT_WS_FRACTION = 0.25       # share of the free device memory the compact hop tensors of one pass may take (cheb_forward_compact)
 COMPACT_SLAB_BYTES = 64 << 20    # a hop launch covers one sample when a sample's (n_c, C) slab is larger (the gather working set stays one slab)
 
 
 def compact_plan_for(op, mode, K, q, n, C_row, N=None):
     """The graph.CompactPlan a layer of this shape runs on, or None: square operands with enough vertices to leave out of the hop tensors
-    (graph.GraphOperand.compact_plan), 2 <= K <= 32; both row layouts (the vertex-major layout 1 of short per-sample rows runs its hops on
-    (n_c, q*C) rows).  Mode 0 keeps the rows with entries, mode 1 also every referenced vertex (closed form T_k[i] = x[i], 0, -x[i], ...
-    for the isolated rest)."""
-    if not COMPACT or not (2 <= K <= 32) or op.n != op.n_cols:
+    (graph.GraphOperand.compact_plan), 2 <= K <= 32, row layout 0 -- the vertex-major layout 1 of short per-sample rows has no compact
+    form (measured slower on cfg5n, docs/EXPERIMENTS.md A.4).  Mode 0 keeps the rows with entries, mode 1 also every referenced vertex
+    (closed form T_k[i] = x[i], 0, -x[i], ... for the isolated rest).  N is not used."""
+    if not COMPACT or not (2 <= K <= 32) or op.n != op.n_cols or choose_layout(q, n, C_row) == 1:
         return None
-    lay1 = choose_layout(q, n, C_row) == 1
-    if lay1 and not (COMPACT_LAYOUT1 and N is not None and K * C_row <= 16 and N % 4 == 0 and N <= 1024):
-        return None       # the vertex-major form needs the vector-ALU projection (row map + interleave: a few scalars per row)
-    plan = op.compact_plan("rows" if mode == MODE_POWER else "closed")
-    if plan is not None and lay1 and (plan.n_c * q < 4096 or 0 < plan.n_empty * q < 4096):
-        return None       # ... which takes problems of at least 4096 rows: both row classes must qualify (project_choose in the library)
-    return plan
+    return op.compact_plan("rows" if mode == MODE_POWER else "closed")
 
 
 def _compact_buffer(plan, q, C_row, device):
@@ -632,21 +636,7 @@ def compact_forward(plan, x3, Wt_kcn, bias, bias_kind, mode, keep=True):
     q, n, Crow = x3.shape
     K, _, N = Wt_kcn.shape
     assert x3.is_contiguous() and n == plan.n and 2 <= K <= 32
-    if x3.data_ptr() % 16:
-        x3 = x3.clone()
     b = bias.contiguous() if bias is not None else None
-    if choose_layout(q, n, Crow) == 1:
-        # short per-sample rows (COMPACT_LAYOUT1, off by default: slower on cfg5n): one long row per vertex for the gathers, (n, q*C) -- the hop
-        # tensors are (n_c + 1, q*C), the projections read them as (vertex, sample) rows of C floats and write the sample-major output through
-        # the row map (interleave = q); primitive calls of the library
-        xt = relayout_qnc_to_nqc(x3).view(1, n, q * Crow)
-        tt = compact_terms(plan, xt, K, mode)
-        out = torch.empty((q, n, N), dtype=torch.float32, device=x3.device)
-        W2 = Wt_kcn.reshape(K * Crow, N).contiguous()
-        project_mapped(tt, [0] * K, W2, b, bias_kind, n, plan.rows, 1 if mode == MODE_POWER else 0, q, out, interleave=q)
-        if plan.n_empty:
-            project_mapped([xt], [0], left_out_weight(Wt_kcn, mode), b, bias_kind, n, plan.empty, 1, q, out, interleave=q)
-        return out, None
     W_left = left_out_weight(Wt_kcn, mode) if (mode == MODE_CHEBYSHEV and plan.n_empty) else None
     res = cheb_forward_compact(plan, x3, Wt_kcn.reshape(K * Crow, N).contiguous(), b, bias_kind, K, mode=mode, W_left=W_left, keep=keep)
     return res if keep else (res, None)
@@ -682,16 +672,9 @@ def cheb_forward_pool(op, x3, Wt, bias, bias_kind, mode, K, pool, z, idx, layout
     q, n, Crow = x3.shape
     N = Wt.shape[1]
     assert x3.is_contiguous() and Wt.is_contiguous() and Wt.shape[0] == K * Crow and n == op.n and z.is_contiguous() and idx.is_contiguous()
-    if x3.data_ptr() % 16:
-        x3 = x3.clone()
-    if layout is None:
-        layout = choose_layout(q, n, Crow)
-    if q_chunk is None:
-        q_chunk = choose_q_chunk(q, n, Crow)
-    hop_C = q * Crow if layout == 1 else Crow
-    sched = op.schedule_for(hop_C, hop_C % 4 == 0)
-    ws_bytes = L.tgcn_cheb_forward_pool_workspace_bytes(C.byref(sched.struct), K, q, n, Crow, N, layout, q_chunk, pool)
-    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=x3.device)
+    x3 = _aligned_input(x3)
+    layout, q_chunk, sched = _hops_setup(op, q, Crow, layout, q_chunk)
+    ws = _workspace(L.tgcn_cheb_forward_pool_workspace_bytes(C.byref(sched.struct), K, q, n, Crow, N, layout, q_chunk, pool), x3.device)
     _lib.check(L.tgcn_cheb_forward_pool_f32(_lib.stream_ptr(), C.byref(op.struct), C.byref(sched.struct), mode, K, q, n, Crow, N,
                                             _lib.ptr(x3), _lib.ptr(Wt), _lib.ptr(bias), bias_kind, pool, _lib.ptr(z), _lib.ptr(idx),
                                             layout, q_chunk, _lib.ptr(ws), ws.numel()))
@@ -701,10 +684,7 @@ def cheb_forward_pool(op, x3, Wt, bias, bias_kind, mode, K, pool, z, idx, layout
 def pool_epilogue_is_fused(op, q, Crow, N, K, pool, layout=None, q_chunk=None):
     """True when cheb_forward_pool runs relu + pool inside the projection kernel for this shape (no scratch for the layer output)."""
     L = _lib.lib()
-    layout = choose_layout(q, op.n, Crow) if layout is None else layout
-    q_chunk = choose_q_chunk(q, op.n, Crow) if q_chunk is None else q_chunk
-    hop_C = q * Crow if layout == 1 else Crow
-    sched = op.schedule_for(hop_C, hop_C % 4 == 0)
+    layout, q_chunk, sched = _hops_setup(op, q, Crow, layout, q_chunk)
     base = L.tgcn_cheb_forward_workspace_bytes(C.byref(sched.struct), K, q, op.n, Crow, layout, q_chunk)
     return L.tgcn_cheb_forward_pool_workspace_bytes(C.byref(sched.struct), K, q, op.n, Crow, N, layout, q_chunk, pool) < base + q * op.n * N * 4
 
@@ -768,6 +748,16 @@ def fold_weight(fold, W, transpose=False):
     return out
 
 
+def _power_fold(mode, W_kcn):
+    """fold matrix of a (K, C, N) reference-basis weight for MODE_POWER with K > 2, else None (the two bases agree)"""
+    return power_fold_matrix(W_kcn.shape[0], W_kcn.device) if (mode == MODE_POWER and W_kcn.shape[0] > 2) else None
+
+
+def _working_weight(fold, W_kcn):
+    """the weight in the basis the kernels work in: folded to the monomial basis when there is a fold (tgcn_fold_weight_f32)"""
+    return fold_weight(fold, W_kcn) if fold is not None else W_kcn
+
+
 # ----------------------------------------------------------------------------------------- autograd
 def small_path_tile(op, C_row, mode, pool=False):
     """Channel tile (16 / 8) of the one-launch LDS-resident kernel, or 0 when the shape does not fit it
@@ -822,8 +812,7 @@ def cheb_forward_pf(op, x3, Wt_kcn, bias, bias_kind, mode):
     K, _, N = Wt_kcn.shape
     Wcat = weight_layout(Wt_kcn, 0)
     sched = op.schedule_for(N, N % 4 == 0)
-    ws_bytes = L.tgcn_cheb_forward_pf_workspace_bytes(C.byref(sched.struct), K, q, n, N)
-    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=x3.device)
+    ws = _workspace(L.tgcn_cheb_forward_pf_workspace_bytes(C.byref(sched.struct), K, q, n, N), x3.device)
     out = torch.empty((q, n, N), dtype=torch.float32, device=x3.device)
     _lib.check(L.tgcn_cheb_forward_pf_f32(_lib.stream_ptr(), C.byref(op.struct), C.byref(sched.struct), mode, K, q, n, Crow, N,
                                           _lib.ptr(x3), _lib.ptr(Wcat), _lib.ptr(bias), bias_kind, _lib.ptr(out), _lib.ptr(ws),
@@ -841,22 +830,58 @@ def use_project_first(q, n, C_row, N):
     return PROJECT_FIRST and 2 * N <= C_row and q <= 65535
 
 
+@dataclasses.dataclass(frozen=True)
+class LayerPath:
+    """How one single-GPU layer call runs (_layer_path).  kind "small": one launch, the graph in LDS (cheb_forward_small); "project_first":
+    cheb_forward_pf; "compact": hop tensors for the kept vertices of `plan` only (mode 0: cheb_forward_compact, mode 1 and training with the
+    basis kept: compact_forward); "hops": hops-then-projection on row `layout` (cheb_forward_raw, training: forward_keeping_basis).
+    pool_fused: relu + pool run inside the layer's launches (small-pool kernel, cheb_forward_pool), not as one more pass over its output."""
+    kind: str
+    plan: object = None
+    layout: int = 0
+    pool_fused: bool = False
+
+
+def _layer_path(op, q, n, C_row, N, K, mode, pool=0, general=None, compact=True):
+    """The one place that decides the LayerPath of a layer on (op, x (q, n, C_row), W (K, C_row, N)).
+    pool: relu + max-pool layer -- the small-pool kernel only when the operand has no dense copy for the matrix pipe (there the plain small
+    kernel + one relu / pool pass is faster: HCP shape 136 + 15 us against 330 us).
+    general: replaces the project-first test -- the input gradient, the layer on (L^T, g, W^T), takes a compact plan of L^T only when the
+    FORWARD shape is neither small nor project-first; "project_first" then means "neither small nor compact".
+    compact=False: decide without building the compact plan ("hops" then stands for both general paths)."""
+    if pool:
+        dense_mfma = op.dense is not None and (C_row <= 32 or (C_row <= 64 and op.n <= 128))
+        if small_path_tile(op, C_row, mode, pool=True) and not dense_mfma:
+            return LayerPath("small", pool_fused=True)
+    if small_path_tile(op, C_row, mode):
+        return LayerPath("small")
+    if general is None:
+        general = not use_project_first(q, n, C_row, N)
+    if not general:
+        return LayerPath("project_first")
+    plan = compact_plan_for(op, mode, K, q, n, C_row, N) if compact else None
+    if plan is not None:
+        return LayerPath("compact", plan=plan)
+    return LayerPath("hops", layout=choose_layout(q, n, C_row), pool_fused=bool(pool))
+
+
 @_on_device
-def layer_forward(op, x3, W, fold, b, bias_kind, mode):
-    """Forward of the layer on whichever path fits the shape (all in libtgcn_hip.so): the one-launch LDS kernel for
-    small graphs, project-first for wide inputs / narrow outputs, hops-then-projection otherwise."""
+def layer_forward(op, x3, W, fold, b, bias_kind, mode, path=None):
+    """Forward of the layer on its LayerPath (all in libtgcn_hip.so; `path`: a choice the caller has made already).  W: (K, C, N) in the
+    reference basis with its fold (the small-graph kernel folds inside), or in the working basis and fold None."""
     K, Crow, N = W.shape
-    if small_path_tile(op, Crow, mode):
+    if path is None:
+        path = _layer_path(op, x3.shape[0], x3.shape[1], Crow, N, K, mode)
+    if path.kind == "small":
         return cheb_forward_small(op, x3, W, fold, b, bias_kind, mode)
-    Wt = fold_weight(fold, W) if fold is not None else W
-    if use_project_first(x3.shape[0], x3.shape[1], Crow, N):
+    Wt = _working_weight(fold, W)
+    if path.kind == "project_first":
         return cheb_forward_pf(op, x3, Wt, b, bias_kind, mode)
-    plan = compact_plan_for(op, mode, K, x3.shape[0], x3.shape[1], Crow, N)
-    if plan is not None and mode == MODE_POWER and choose_layout(x3.shape[0], x3.shape[1], Crow) == 0:   # many structurally empty rows: compact hop tensors, one call
-        return cheb_forward_compact(plan, x3, Wt.reshape(K * Crow, N).contiguous(), b, bias_kind, K)
-    if plan is not None:                                   # the same for the Chebyshev recurrence (closed form for isolated vertices)
-        return compact_forward(plan, x3, Wt, b, bias_kind, mode, keep=False)[0]
-    return cheb_forward_raw(op, x3, Wt.reshape(K * Crow, N).contiguous(), b, bias_kind, mode, K)
+    if path.kind == "compact" and mode == MODE_POWER:       # many structurally empty rows: compact hop tensors, one call
+        return cheb_forward_compact(path.plan, x3, Wt.reshape(K * Crow, N).contiguous(), b, bias_kind, K)
+    if path.kind == "compact":                              # the same for the Chebyshev recurrence (closed form for isolated vertices)
+        return compact_forward(path.plan, x3, Wt, b, bias_kind, mode, keep=False)[0]
+    return cheb_forward_raw(op, x3, Wt.reshape(K * Crow, N).contiguous(), b, bias_kind, mode, K, layout=path.layout)
 
 
 @_on_device
@@ -874,15 +899,24 @@ def relayout_qnc_to_nqc(x3):
 KEEP_BASIS_BYTES = 2 << 30    # training on the hops-then-projection path keeps the hop tensors for the backward up to this size
 
 
+@dataclasses.dataclass(frozen=True)
+class KeptBasis:
+    """The basis a training forward kept for the weight gradient (ChebLayerFn -> layer_backward): compact_terms' list of compact hop
+    tensors for `plan` (compact_forward), or, with plan None, the K full-size terms as (q*n, C) row views (forward_keeping_basis), in
+    (vertex, sample) row order when vertex_major (layout 1), else (sample, vertex)."""
+    terms: list
+    plan: object = None
+    vertex_major: bool = False
+
+
 @_on_device
-def forward_keeping_basis(op, x3, Wt, bias, bias_kind, mode):
-    """Hops-then-projection forward that hands the K hop tensors to the caller (they ARE the basis the weight gradient
+def forward_keeping_basis(op, x3, Wt, bias, bias_kind, mode, layout):
+    """Hops-then-projection forward on row `layout` that hands the K hop tensors to the caller (they ARE the basis the weight gradient
     needs: monomials L^k x for the folded weight, Chebyshev T_k x for mode 1), instead of recomputing them in backward.
-    Same kernels as tgcn_cheb_forward_f32, one call per hop.  -> (out (q, n, N), terms as (q*n, C) row views, row order)
-    row order "nq": rows are (vertex, sample) -- layout 1, one long row per vertex for the gathers -- else (sample, vertex)."""
+    Same kernels as tgcn_cheb_forward_f32, one call per hop.  -> (out (q, n, N), KeptBasis)"""
     q, n, Crow = x3.shape
     K, _, N = Wt.shape
-    nq = choose_layout(q, n, Crow) == 1
+    nq = layout == 1
     x0 = relayout_qnc_to_nqc(x3).view(1, n, q * Crow) if nq else x3
     terms = [x0]
     for k in range(1, K):
@@ -892,7 +926,7 @@ def forward_keeping_basis(op, x3, Wt, bias, bias_kind, mode):
             terms.append(csr_hop(op, terms[k - 1], z=terms[k - 2], alpha=2.0, beta=-1.0))
     rows = [t.reshape(q * n, Crow) for t in terms]
     out = cheb_project(rows, Wt, bias, bias_kind, n, interleave=q if nq else 1).view(q, n, N)
-    return out, rows, nq
+    return out, KeptBasis(rows, vertex_major=nq)
 
 
 class ChebLayerFn(torch.autograd.Function):
@@ -911,24 +945,21 @@ class ChebLayerFn(torch.autograd.Function):
         x3 = x3.contiguous()
         W = W.contiguous()
         b = bias.contiguous() if bias is not None else None
-        fold = power_fold_matrix(K, W.device) if (mode == MODE_POWER and K > 2) else None
+        q, n, _ = x3.shape
+        fold = _power_fold(mode, W)
         ctx.basis = None
-        general = not small_path_tile(op, Crow, mode) and not use_project_first(x3.shape[0], x3.shape[1], Crow, N)
+        path = _layer_path(op, q, n, Crow, N, K, mode)
         # grad_mode: whether the CALLER records gradients (inside forward() grad mode is always off, and needs_input_grad only
         # mirrors requires_grad): an inference call under torch.no_grad() keeps nothing for a backward that never comes
-        plan = compact_plan_for(op, mode, K, x3.shape[0], x3.shape[1], Crow, N) if general else None
-        lay0 = choose_layout(x3.shape[0], x3.shape[1], Crow) == 0
-        if plan is not None and lay0 and grad_mode and ctx.needs_input_grad[1] and K * x3.shape[0] * (plan.n_c + 1) * Crow * 4 <= KEEP_BASIS_BYTES:
+        train = grad_mode and ctx.needs_input_grad[1]
+        if train and path.kind == "compact" and K * q * (path.plan.n_c + 1) * Crow * 4 <= KEEP_BASIS_BYTES:
             # training forward on an operand with left-out vertices: compact hop tensors, kept for the weight gradient
-            Wt = fold_weight(fold, W) if fold is not None else W
-            out, terms = compact_forward(plan, x3, Wt, b, bias_kind, mode)
-            ctx.basis = ("compact", plan, terms)
-        elif general and plan is None and K > 1 and grad_mode and ctx.needs_input_grad[1] and K * x3.numel() * 4 <= KEEP_BASIS_BYTES:
-            Wt = fold_weight(fold, W) if fold is not None else W
-            out, rows, nq = forward_keeping_basis(op, x3, Wt, b, bias_kind, mode)
-            ctx.basis = (rows, nq)
+            out, terms = compact_forward(path.plan, x3, _working_weight(fold, W), b, bias_kind, mode)
+            ctx.basis = KeptBasis(terms, plan=path.plan)
+        elif train and path.kind == "hops" and K > 1 and K * x3.numel() * 4 <= KEEP_BASIS_BYTES:
+            out, ctx.basis = forward_keeping_basis(op, x3, _working_weight(fold, W), b, bias_kind, mode, path.layout)
         else:
-            out = layer_forward(op, x3, W, fold, b, bias_kind, mode)
+            out = layer_forward(op, x3, W, fold, b, bias_kind, mode, path=path)
         ctx.save_for_backward(x3, W, None if values is None else values.detach())
         ctx.values_epoch = op.values_epoch
         ctx.op, ctx.mode, ctx.bias_kind, ctx.fold = op, mode, bias_kind, fold
@@ -942,14 +973,12 @@ class ChebLayerFn(torch.autograd.Function):
         _values_guard(ctx.op, ctx.values_epoch, vals)
         gx, gW, gb = layer_backward(ctx.op, ctx.mode, ctx.fold, x3, W, g, ctx.bias_kind, ctx.bias_shape, ctx.needs_input_grad,
                                     basis=ctx.basis)
-        values_basis = ctx.basis if (isinstance(ctx.basis, tuple) and len(ctx.basis) == 2 and ctx.mode == MODE_CHEBYSHEV) else None
-        ctx.basis = None
+        basis, ctx.basis = ctx.basis, None
         gv = None
         if len(ctx.needs_input_grad) > 7 and ctx.needs_input_grad[7]:
             kept = None
-            if values_basis is not None and not values_basis[1]:             # hop tensors kept by the forward in (sample, vertex) row order: T_0 .. T_{K-1}
-                q, n, Crow = x3.shape
-                kept = [r.view(q, n, Crow) for r in values_basis[0]]
+            if basis is not None and basis.plan is None and not basis.vertex_major and ctx.mode == MODE_CHEBYSHEV:
+                kept = [r.view(x3.shape) for r in basis.terms]              # full-size T_0 .. T_{K-1} in (sample, vertex) row order
             gv = chebyshev_values_grad(ctx.op, x3, W, g, basis=kept)
         return gx, gW, gb, None, None, None, None, gv
 
@@ -968,8 +997,8 @@ def _pad_rows(op, x3, weight_kcn, mode):
     projection kernels.  On the hops-then-projection path pad them with zero channels to the next multiple of 4 (zero
     rows in the weight): 7 % more hop traffic at C = 15, projection 0.37 -> 0.2 ms on the 59 k-vertex mesh shape.
     torch's pad is differentiable, so the gradients come back sliced."""
-    C, N = x3.shape[2], weight_kcn.shape[2]
-    if C % 4 == 0 or C < 7 or small_path_tile(op, C, mode) or use_project_first(x3.shape[0], x3.shape[1], C, N):
+    K, C, N = weight_kcn.shape
+    if C % 4 == 0 or C < 7 or _layer_path(op, x3.shape[0], x3.shape[1], C, N, K, mode, compact=False).kind != "hops":
         return x3, weight_kcn
     pad = (-C) % 4
     return torch.nn.functional.pad(x3, (0, pad)), torch.nn.functional.pad(weight_kcn, (0, 0, 0, pad))
@@ -1004,72 +1033,43 @@ def layer_backward(op, mode, fold, x3, W, g, bias_kind, bias_shape, needs, basis
     2(K-1) hops: the basis kernel for dW and the forward kernel on L^T for dx."""
     K, Crow, N = W.shape
     q, n, _ = x3.shape
-    Wt = W                                                            # the basis the kernels work in
-    if fold is not None and needs[0]:
-        Wt = fold_weight(fold, W)
+    Wt = _working_weight(fold, W) if needs[0] else W                   # the basis the kernels work in
     g = g.contiguous()
     g2d = g.reshape(q * n, N)
-    gx = gW = gb = None
-    general = not small_path_tile(op, Crow, mode) and not use_project_first(q, n, Crow, N)
-    plan = compact_plan_for(op, mode, K, q, n, Crow, N) if general else None
-    if needs[1] and (plan is not None or (basis is not None and basis[0] == "compact")):
-        # operand with left-out vertices: the basis exists (kept by the forward, or recomputed here) for the kept vertices only
-        if basis is not None and basis[0] == "compact":
-            plan_b, terms = basis[1], basis[2]
-        else:
-            plan_b, terms = plan, compact_terms(plan, x3.contiguous(), K, mode)
-        gW = compact_wgrad(plan_b, x3.contiguous(), terms, g, mode)
-        if fold is not None:
-            gW = fold_weight(fold, gW, transpose=True)
-    elif needs[1] and basis is not None:                              # hop tensors kept by the forward (forward_keeping_basis)
-        rows, nq = basis
-        g_rows = relayout_qnc_to_nqc(g).view(q * n, N) if nq else g2d     # same (vertex, sample) row order as the terms
-        gW = cheb_wgrad(rows, g_rows)
-        if fold is not None:
-            gW = fold_weight(fold, gW, transpose=True)
-    elif needs[1]:
+    gx = gW = None
+    path = _layer_path(op, q, n, Crow, N, K, mode)
+    if needs[1]:
         x3c = x3.contiguous()
-        if small_basis_tile(op, Crow, mode):                          # small graphs: the whole basis in one launch
-            basis = cheb_basis_small(op, x3c, K, mode)
+        if (basis is not None and basis.plan is not None) or path.kind == "compact":
+            # operand with left-out vertices: the basis exists (kept by the forward, or recomputed here) for the kept vertices only
+            if basis is None:
+                basis = KeptBasis(compact_terms(path.plan, x3c, K, mode), plan=path.plan)
+            gW = compact_wgrad(basis.plan, x3c, basis.terms, g, mode)
+        elif basis is not None:                                       # hop tensors kept by the forward (forward_keeping_basis)
+            g_rows = relayout_qnc_to_nqc(g).view(q * n, N) if basis.vertex_major else g2d     # same row order as the terms
+            gW = cheb_wgrad(basis.terms, g_rows)
         else:
-            basis = cheb_stack(op, x3c, K, MODE_CHEBYSHEV) if mode == MODE_CHEBYSHEV else _monomial_stack(op, x3c, K)
-        gW = cheb_wgrad([basis[k].reshape(q * n, Crow) for k in range(K)], g2d)
+            if small_basis_tile(op, Crow, mode):                      # small graphs: the whole basis in one launch
+                terms = cheb_basis_small(op, x3c, K, mode)
+            else:
+                terms = cheb_stack(op, x3c, K, MODE_CHEBYSHEV) if mode == MODE_CHEBYSHEV else _monomial_stack(op, x3c, K)
+            gW = cheb_wgrad([terms[k].reshape(q * n, Crow) for k in range(K)], g2d)
         if fold is not None:                                          # back to the reference basis
             gW = fold_weight(fold, gW, transpose=True)
-    if needs[0] and small_path_tile(op.transpose(), N, mode):
-        # small graphs: dx = sum_j (L^T)^j g W_j^T is the one-launch forward kernel on (L^T, g, W^T)
-        gx = cheb_forward_small(op.transpose(), g, weight_layout(Wt, 1), None, None, BIAS_NONE, mode)
-    elif needs[0] and general and compact_plan_for(op.transpose(), mode, K, q, n, N, Crow) is not None:
-        # dx = sum_k T_k(L^T) g W_k^T IS the layer on (L^T, g, W^T): with left-out vertices in L^T it runs on compact hop tensors too
-        planT = compact_plan_for(op.transpose(), mode, K, q, n, N, Crow)
-        WtT = weight_layout(Wt, 1)                                   # (K, N, C)
-        if mode == MODE_POWER:
-            gx = cheb_forward_compact(planT, g, WtT.reshape(K * N, Crow), None, BIAS_NONE, K)
-        else:
-            gx = compact_forward(planT, g, WtT, None, BIAS_NONE, mode, keep=False)[0]
-    elif needs[0]:
+    if needs[0]:
+        # dx = sum_k T_k(L^T) g W_k^T IS the layer on (L^T, g, W^T): on small graphs the one-launch kernel, with left-out vertices in L^T
+        # compact hop tensors -- the latter only where the forward shape is on a general path
         opT = op.transpose()
-        # G[m, k*C + c] = sum_n g[m, n] W[k, c, n]: one projection with the (N, K*C) transposed weight
-        Wcat = weight_layout(Wt, 2).view(1, N, K * Crow)
-        Gall = cheb_project([g2d], Wcat, None, BIAS_NONE, n).view(q, n, K * Crow)
-        G = [Gall[:, :, k * Crow:(k + 1) * Crow] for k in range(K)]        # strided views, rows contiguous
-        if mode == MODE_POWER:                                       # Horner: b = G_j + L^T b
-            b = G[K - 1]
-            for j in range(K - 2, -1, -1):
-                b = csr_hop(opT, b, z=G[j], alpha=1.0, beta=1.0)
-            gx = b.contiguous()
-        elif K == 1:
-            gx = G[0].contiguous()
-        else:                                                        # Clenshaw on L^T
-            b1, b2 = G[K - 1], None                                   # b_{K-1} = G_{K-1} (b_K = b_{K+1} = 0)
-            for k in range(K - 2, 0, -1):                             # b_k = G_k + 2 L^T b_{k+1} - b_{k+2}, one launch each
-                t = csr_hop(opT, b1, z=b2, alpha=2.0, beta=-1.0, z2=G[k], gamma=1.0)
-                b1, b2 = t, b1
-            gx = csr_hop(opT, b1, z=b2, alpha=1.0, beta=-1.0, z2=G[0], gamma=1.0)   # dx = G_0 + L^T b_1 - b_2
-    if bias_shape is not None and needs[2]:
-        gb = g.sum(dim=(0, 1)) if bias_kind == BIAS_CHANNEL else g.sum(dim=0)
-        gb = gb.reshape(bias_shape)
-    return gx, gW, gb
+        dx = _layer_path(opT, q, n, N, Crow, K, mode, general=path.kind in ("compact", "hops"))
+        if dx.kind in ("small", "compact"):
+            gx = layer_forward(opT, g, weight_layout(Wt, 1), None, None, BIAS_NONE, mode, path=dx)
+        else:
+            # G[m, k*C + c] = sum_n g[m, n] W[k, c, n]: one projection with the (N, K*C) transposed weight, then the adjoint hops
+            Wcat = weight_layout(Wt, 2).view(1, N, K * Crow)
+            Gall = cheb_project([g2d], Wcat, None, BIAS_NONE, n).view(q, n, K * Crow)
+            G = [Gall[:, :, k * Crow:(k + 1) * Crow] for k in range(K)]        # strided views, rows contiguous
+            gx = _adjoint_hops(opT, G, mode).contiguous()
+    return gx, gW, _bias_grad(g, bias_kind, bias_shape, needs[2])
 
 
 class ChebReluPoolFn(torch.autograd.Function):
@@ -1086,25 +1086,22 @@ class ChebReluPoolFn(torch.autograd.Function):
         b = bias.contiguous() if bias is not None else None
         q, n, _ = x3.shape
         assert n % pool == 0, "pooling needs n divisible by the pool size"
-        fold = power_fold_matrix(K, W.device) if (mode == MODE_POWER and K > 2) else None
+        fold = _power_fold(mode, W)
         z = torch.empty((q, n // pool, N), dtype=torch.float32, device=x3.device)
         idx = torch.empty((q, n // pool, N), dtype=torch.uint8, device=x3.device)
         L = _lib.lib()
-        # dense small operands run the layer on the matrix pipe (no fused epilogue there): layer + one relu/pool pass beats
-        # the fused vector-ALU kernel (HCP shape: 136 + 15 us against 330 us)
-        dense_mfma = op.dense is not None and (Crow <= 32 or (Crow <= 64 and op.n <= 128))
-        if small_path_tile(op, Crow, mode, pool=True) and not dense_mfma:
+        path = _layer_path(op, q, n, Crow, N, K, mode, pool=pool)
+        if path.pool_fused and path.kind == "small":
             _lib.check(L.tgcn_cheb_forward_small_pool_f32(_lib.stream_ptr(), C.byref(op.struct), mode, K, q, Crow, N, _lib.ptr(x3),
                                                           _lib.ptr(W), _lib.ptr(fold), _lib.ptr(b), bias_kind, 1, pool,
                                                           _lib.ptr(z), _lib.ptr(idx)))
-        elif (not small_path_tile(op, Crow, mode) and not use_project_first(q, n, Crow, N)
-              and compact_plan_for(op, mode, K, q, n, Crow, N) is None):
+        elif path.pool_fused:
             # hops-then-projection path: bias + relu + max over `pool` vertices inside the projection's epilogue where the shape allows
             # (tgcn_cheb_forward_pool_f32: the (q, n, N) layer output is then never written), one extra pass over scratch otherwise
-            Wt = fold_weight(fold, W) if fold is not None else W
-            cheb_forward_pool(op, x3, Wt.reshape(K * Crow, N).contiguous(), b, bias_kind, mode, K, pool, z, idx)
+            cheb_forward_pool(op, x3, _working_weight(fold, W).reshape(K * Crow, N).contiguous(), b, bias_kind, mode, K, pool, z, idx,
+                              layout=path.layout)
         else:
-            y = layer_forward(op, x3, W, fold, b, bias_kind, mode)
+            y = layer_forward(op, x3, W, fold, b, bias_kind, mode, path=path)
             _lib.check(L.tgcn_relu_pool_f32(_lib.stream_ptr(), _lib.ptr(y), _lib.ptr(z), _lib.ptr(idx), q, n, N, pool))
         ctx.save_for_backward(x3, W, z, idx)
         ctx.op, ctx.mode, ctx.bias_kind, ctx.fold, ctx.pool = op, mode, bias_kind, fold, pool
