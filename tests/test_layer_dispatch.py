@@ -80,6 +80,7 @@ class _Op:
 
 
 N_V = 64
+T_WIN = 12      # series length of the "windows" cases
 
 
 def _op(kind):
@@ -133,6 +134,10 @@ CASES = {
     "odd-width-padded": ("layer", "plain", 1, 15, 32, 3, 0, [], {}),
     "odd-width-small-not-padded": ("layer", "plain", 1, 15, 32, 3, 0, [("cheb_forward_small", 15)], {}),
     "reordered-vertex-bias": ("layer", "reordered", 2, 32, 32, 3, 1, [], {"bias_kind": 2}),
+    "reordered-project-first-cheb": ("layer", "reordered", 2, 64, 16, 3, 1, [], {}),
+    "reordered-project-first-power": ("layer", "reordered", 2, 64, 16, 3, 0, [], {}),
+    "reordered-hops-cheb-over-keep": ("layer", "reordered", 2, 32, 32, 3, 1, [], {"keep_bytes": 0}),
+    "reordered-hops-power-over-keep": ("layer", "reordered", 2, 32, 32, 3, 0, [], {"keep_bytes": 0}),
     "values-grad-kept-basis": ("layer", "plain", 2, 32, 32, 4, 1, [], {"values": True}),
     "values-grad-compact": ("layer", "compact", 2, 32, 32, 3, 1, [], {"values": True}),
     "values-grad-small": ("layer", "plain", 2, 8, 8, 3, 1, [("cheb_forward_small", 8), ("cheb_forward_small", 8)], {"values": True}),
@@ -142,19 +147,18 @@ CASES = {
     "pool-compact-unfused": ("pool", "compact", 2, 32, 32, 3, 1, [], {}),
     "pool-reordered": ("pool", "reordered", 2, 32, 32, 3, 0, [], {}),
     "windows-power-K3": ("windows", "plain", 2, 6, 8, 3, 0, [], {}),
-    "windows-cheb-K4-reordered": ("windows", "reordered", 2, 6, 8, 4, 1, [], {}),
+    "windows-cheb-K4-reordered-relabel-once": ("windows", "reordered", 2, 6, 8, 4, 1, [], {}),
     "windows-K1": ("windows", "plain", 2, 6, 8, 1, 1, [], {}),
 }
 
 
-def _run(case, train):
+def _run(case, train, after_forward=lambda: None):
     entry, kind, q, C, N, K, mode, _, extra = case
     op = _op(kind)
     bias_kind = extra.get("bias_kind", F.BIAS_CHANNEL)
     torch.manual_seed(0)
     if entry == "windows":
-        T = 12
-        x = torch.randn(q, N_V, T)
+        x = torch.randn(q, N_V, T_WIN)
         W = torch.randn(K, C, N)
         bias = torch.randn(N)
         leaves = [x, W, bias]
@@ -175,6 +179,7 @@ def _run(case, train):
             out = F.cheb_relu_pool(op, x, W, bias, bias_kind, mode, 4)
         else:
             out = F.cheb_time_windows(op, x, W, bias, bias_kind, mode)
+    after_forward()
     if train:
         out.backward(torch.ones_like(out))
 
@@ -188,6 +193,33 @@ def test_layer_launches(name, train, recorder, monkeypatch):
     rec = recorder(_small(case[7]))
     _run(case, train)
     assert rec.calls == EXPECTED["%s/%s" % (name, "training" if train else "inference")]
+
+
+def _relabels(calls):
+    """(rows, row width) of every pack_rows launch in `calls` -- its scalar arguments are (source stride, rows, row width)"""
+    return sorted(tuple(int(a) for a in c.split()[2:]) for c in calls if c.startswith("pack_rows "))
+
+
+@pytest.mark.parametrize("train", [False, True], ids=["inference", "training"])
+@pytest.mark.parametrize("name", [k for k, c in CASES.items() if c[1] == "reordered"])
+def test_reordered_operand_relabels_each_tensor_once(name, train, recorder, monkeypatch):
+    """A reordered operand relabels each data tensor exactly once on the way in (x / the series, and a per-vertex bias) and the result
+    once on the way out; the backward relabels the same tensors' gradients once each.  Any other pack_rows launch means that data
+    already in the operand's labels was relabelled again (cheb_stack called without _operand_labels), i.e. hops on the wrong matrix."""
+    entry, _, q, C, N, K, mode, small, extra = CASES[name]
+    if "keep_bytes" in extra:
+        monkeypatch.setattr(F, "KEEP_BASIS_BYTES", extra["keep_bytes"])
+    rec = recorder(_small(small))
+    fwd = []
+    _run(CASES[name], train, after_forward=lambda: fwd.extend(rec.calls))
+    if entry == "windows":
+        once = [(q * N_V, T_WIN), (q * (T_WIN - C + 1) * N_V, N)]
+    else:
+        once = [(q * N_V, C), (q * N_V, N)]
+    if extra.get("bias_kind") == F.BIAS_VERTEX_CHANNEL:
+        once.append((N_V, N))
+    assert _relabels(fwd) == sorted(once)
+    assert _relabels(rec.calls) == sorted(once * (2 if train else 1))
 
 
 # launches of the unchanged dispatch, one string per call: entry point (without tgcn_ / _f32) and its scalar arguments
@@ -463,6 +495,94 @@ EXPECTED = {
         'pack_rows 32 64 32',
         'pack_rows 32 128 32',
     ],
+    'reordered-project-first-cheb/inference': [
+        'pack_rows 64 128 64',
+        'weight_layout 3 64 16 0',
+        'cheb_forward_pf 1 3 2 64 64 16 1 1024',
+        'pack_rows 16 128 16',
+    ],
+    'reordered-project-first-cheb/training': [
+        'pack_rows 64 128 64',
+        'weight_layout 3 64 16 0',
+        'cheb_forward_pf 1 3 2 64 64 16 1 1024',
+        'pack_rows 16 128 16',
+        'pack_rows 16 128 16',
+        'csr_hop2 2 64 1 0 0 1024',
+        'csr_hop2 2 64 2 -1 0 1024',
+        'cheb_wgrad 128 64 16 3 16 1024',
+        'weight_layout 3 64 16 2',
+        'cheb_project 128 16 192 1 0 64 1 0 192',
+        'csr_hop2 2 64 2 -1 1 1024',
+        'csr_hop2 2 64 1 -1 1 1024',
+        'pack_rows 64 128 64',
+    ],
+    'reordered-project-first-power/inference': [
+        'pack_rows 64 128 64',
+        'fold_weight 3 1024 0',
+        'weight_layout 3 64 16 0',
+        'cheb_forward_pf 0 3 2 64 64 16 1 1024',
+        'pack_rows 16 128 16',
+    ],
+    'reordered-project-first-power/training': [
+        'pack_rows 64 128 64',
+        'fold_weight 3 1024 0',
+        'weight_layout 3 64 16 0',
+        'cheb_forward_pf 0 3 2 64 64 16 1 1024',
+        'pack_rows 16 128 16',
+        'pack_rows 16 128 16',
+        'fold_weight 3 1024 0',
+        'csr_hop2 2 64 1 0 0 1024',
+        'csr_hop2 2 64 1 0 0 1024',
+        'cheb_wgrad 128 64 16 3 16 1024',
+        'fold_weight 3 1024 1',
+        'weight_layout 3 64 16 2',
+        'cheb_project 128 16 192 1 0 64 1 0 192',
+        'csr_hop2 2 64 1 1 0 1024',
+        'csr_hop2 2 64 1 1 0 1024',
+        'pack_rows 64 128 64',
+    ],
+    'reordered-hops-cheb-over-keep/inference': [
+        'pack_rows 32 128 32',
+        'cheb_forward 1 3 2 64 32 32 1 0 2 1024',
+        'pack_rows 32 128 32',
+    ],
+    'reordered-hops-cheb-over-keep/training': [
+        'pack_rows 32 128 32',
+        'cheb_forward 1 3 2 64 32 32 1 0 2 1024',
+        'pack_rows 32 128 32',
+        'pack_rows 32 128 32',
+        'csr_hop2 2 32 1 0 0 1024',
+        'csr_hop2 2 32 2 -1 0 1024',
+        'cheb_wgrad 128 32 32 3 32 1024',
+        'weight_layout 3 32 32 2',
+        'cheb_project 128 32 96 1 0 64 1 0 96',
+        'csr_hop2 2 32 2 -1 1 1024',
+        'csr_hop2 2 32 1 -1 1 1024',
+        'pack_rows 32 128 32',
+    ],
+    'reordered-hops-power-over-keep/inference': [
+        'pack_rows 32 128 32',
+        'fold_weight 3 1024 0',
+        'cheb_forward 0 3 2 64 32 32 1 0 2 1024',
+        'pack_rows 32 128 32',
+    ],
+    'reordered-hops-power-over-keep/training': [
+        'pack_rows 32 128 32',
+        'fold_weight 3 1024 0',
+        'cheb_forward 0 3 2 64 32 32 1 0 2 1024',
+        'pack_rows 32 128 32',
+        'pack_rows 32 128 32',
+        'fold_weight 3 1024 0',
+        'csr_hop2 2 32 1 0 0 1024',
+        'csr_hop2 2 32 1 0 0 1024',
+        'cheb_wgrad 128 32 32 3 32 1024',
+        'fold_weight 3 1024 1',
+        'weight_layout 3 32 32 2',
+        'cheb_project 128 32 96 1 0 64 1 0 96',
+        'csr_hop2 2 32 1 1 0 1024',
+        'csr_hop2 2 32 1 1 0 1024',
+        'pack_rows 32 128 32',
+    ],
     'values-grad-kept-basis/inference': [
         'cheb_forward 1 4 2 64 32 32 1 0 2 1024',
     ],
@@ -641,24 +761,20 @@ EXPECTED = {
         'csr_hop2 2 12 1 1 0 1024',
         'fold_weight 3 48 1',
     ],
-    'windows-cheb-K4-reordered/inference': [
-        'pack_rows 12 128 12',
+    'windows-cheb-K4-reordered-relabel-once/inference': [
         'pack_rows 12 128 12',
         'csr_hop2 2 12 1 0 0 1024',
         'csr_hop2 2 12 2 -1 0 1024',
         'csr_hop2 2 12 2 -1 0 1024',
-        'pack_rows 12 512 12',
         'cheb_project_windows 64 12 6 8 4 1',
         'cheb_project_windows 64 12 6 8 4 1',
         'pack_rows 8 896 8',
     ],
-    'windows-cheb-K4-reordered/training': [
-        'pack_rows 12 128 12',
+    'windows-cheb-K4-reordered-relabel-once/training': [
         'pack_rows 12 128 12',
         'csr_hop2 2 12 1 0 0 1024',
         'csr_hop2 2 12 2 -1 0 1024',
         'csr_hop2 2 12 2 -1 0 1024',
-        'pack_rows 12 512 12',
         'cheb_project_windows 64 12 6 8 4 1',
         'cheb_project_windows 64 12 6 8 4 1',
         'pack_rows 8 896 8',

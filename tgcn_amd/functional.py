@@ -330,7 +330,8 @@ def _windows_forward(op, x3, W, bias, bias_kind, mode):
     S, n, T = x3.shape
     K, H, N = W.shape
     nwin = T - H + 1
-    stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV)   # (K, S, n, T)
+    # x3 is in the operand's labels already (cheb_time_windows relabelled it): cheb_stack must not relabel it again
+    stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)   # (K, S, n, T)
     out = torch.empty((S * nwin, n, N), dtype=torch.float32, device=x3.device)
     W2 = W.reshape(K * H, N).contiguous()
     b = bias.contiguous() if bias is not None else None
@@ -1052,7 +1053,8 @@ def layer_backward(op, mode, fold, x3, W, g, bias_kind, bias_shape, needs, basis
             if small_basis_tile(op, Crow, mode):                      # small graphs: the whole basis in one launch
                 terms = cheb_basis_small(op, x3c, K, mode)
             else:
-                terms = cheb_stack(op, x3c, K, MODE_CHEBYSHEV) if mode == MODE_CHEBYSHEV else _monomial_stack(op, x3c, K)
+                # x3c is in the operand's labels already (the layer relabels x on the way in): no second relabel inside cheb_stack
+                terms = cheb_stack(op, x3c, K, MODE_CHEBYSHEV, _operand_labels=True) if mode == MODE_CHEBYSHEV else _monomial_stack(op, x3c, K)
             gW = cheb_wgrad([terms[k].reshape(q * n, Crow) for k in range(K)], g2d)
         if fold is not None:                                          # back to the reference basis
             gW = fold_weight(fold, gW, transpose=True)
