@@ -188,6 +188,106 @@ def layer_backward(L, x, weight, grad_out, mode):
     return gx.reshape(x.shape), gW
 
 
+class _RowBlocks:
+    """L.dot in row blocks on a thread pool (scipy's sparse products release the GIL): every output row is the same sum in the same
+    order as L.dot, the blocks only run at once.  For the training-scale references, whose hops would otherwise take minutes."""
+
+    def __init__(self, L, threads):
+        self.L, self.threads = L, threads
+        cuts = np.linspace(0, L.shape[0], threads + 1).astype(np.int64)
+        self.blocks = [L[a:b] for a, b in zip(cuts[:-1], cuts[1:])]
+
+    def dot(self, X):
+        if self.threads <= 1:
+            return self.L.dot(X)
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(self.threads) as ex:
+            return np.concatenate(list(ex.map(lambda B: B.dot(X), self.blocks)))
+
+
+def _transpose64(L, threads):
+    LT = sp.csr_matrix(L, dtype=np.float64).T.tocsr()
+    return _RowBlocks(LT, threads) if threads > 1 else LT
+
+
+def layer_backward_gside(L, x, weight, grad_out, mode, threads=1):
+    """layer_backward's gradients, cheap at training scale: the hops run on g (N columns) instead of x and the K adjoint stacks.
+    T_k(L)^T = T_k(L^T) for both recursions (each term is a polynomial in L), and T_k acts on the vertex axis while W_k acts on the
+    channel axis, so with S_k = T_k(L^T) g (K-1 fp64 hops on N columns):  dW_k = x^T S_k  and  dx = sum_k S_k W_k^T.
+    One sample at a time (host memory: K (n, g) slabs).  x (q, n, *tail), weight (K, *tail, g), fp64 results."""
+    stack = stack_reference_power if mode == "power" else stack_chebyshev
+    K, gch = weight.shape[0], weight.shape[-1]
+    q, n = x.shape[:2]
+    LT = _transpose64(L, threads)
+    W = np.asarray(weight, np.float64).reshape(K, -1, gch)
+    gx = np.zeros((q, n, W.shape[1]))
+    gW = np.zeros_like(W)
+    for s in range(q):
+        S = stack(LT, np.asarray(grad_out[s], np.float64)[None], K)[:, 0]          # (K, n, g)
+        xs = np.asarray(x[s], np.float64).reshape(n, -1)
+        for k in range(K):
+            gW[k] += xs.T @ S[k]
+            gx[s] += S[k] @ W[k].T
+    return gx.reshape(x.shape), gW.reshape(weight.shape)
+
+
+def _power_coefficients(K):
+    """c[k, j]: stack_reference_power's term k as a polynomial in L, Xt[k] = sum_j c[k, j] L^j x (Xt[k] = 2 L^k x - Xt[k-2])."""
+    c = np.zeros((K, K))
+    for k in range(K):
+        c[k, k] = 1.0 if k < 2 else 2.0
+        if k >= 2:
+            c[k] -= c[k - 2]
+    return c
+
+
+def windows_projection_backward(stack, grad_out, weight):
+    """Adjoint of the window projection out[(s, w), i, :] = sum_k sum_h stack[k, s, i, w + h] W[k, h, :] in fp64, for any stack (K, S, n, T):
+    dW[k, h] = sum_{s, w} stack[k, s, :, w + h]^T g[(s, w)]  and  G[k, s, i, t] = sum_h g[(s, t - h), i, :] . W[k, h, :].  -> (dW, G)"""
+    K, S, n, T = stack.shape
+    H, gch = weight.shape[1], weight.shape[2]
+    nwin = T - H + 1
+    W = np.asarray(weight, np.float64)
+    gW = np.zeros((K, H, gch))
+    G = np.zeros((K, S, n, T))
+    for s in range(S):
+        gs = np.asarray(grad_out[s * nwin:(s + 1) * nwin], np.float64).reshape(nwin * n, gch)
+        for h in range(H):
+            win = np.ascontiguousarray(np.asarray(stack[:, s, :, h:h + nwin], np.float64).transpose(0, 2, 1)).reshape(K, nwin * n)  # (w, i) rows
+            gW[:, h] += win @ gs
+            del win
+            G[:, s, :, h:h + nwin] += (gs @ W[:, h].T).reshape(nwin, n, K).transpose(2, 1, 0)
+    return gW, G
+
+
+def windows_backward(L, series, weight, grad_out, mode, threads=1):
+    """Gradients of the streaming time-window layer out[(s, w), i, :] = sum_k sum_h (T_k series)[s, i, w + h] W[k, h, :] (+ bias) w.r.t.
+    series (S, n, T) and weight (K, H, g), in fp64 and on the series itself, without materialising the T-H+1 windows: what
+    layer_backward gives on the windowed batch x[s*(T-H+1) + w, i, h] = series[s, i, w + h], folded back onto the series.
+      dW[k, h] = sum_{s, w} (T_k series)[s, :, w + h]^T g[(s, w)]               (K-1 hops on the T columns of each recording)
+      d series = sum_k T_k(L^T) G_k,  G_k[s, i, t] = sum_h g[(s, t - h), i, :] . W[k, h, :]
+    the last sum by Horner on the monomials (mode "power") / Clenshaw (mode "chebyshev"): K-1 hops on L^T.  grad_out (S*(T-H+1), n, g)."""
+    stack = stack_reference_power if mode == "power" else stack_chebyshev
+    S, n, T = series.shape
+    K = weight.shape[0]
+    Lf = _RowBlocks(sp.csr_matrix(L, dtype=np.float64), threads)
+    LT = _RowBlocks(sp.csr_matrix(L, dtype=np.float64).T.tocsr(), threads)
+    Ts = stack(Lf, np.asarray(series, np.float64), K)                                # (K, S, n, T)
+    gW, G = windows_projection_backward(Ts, grad_out, weight)
+    del Ts
+    if mode == "power":
+        c = _power_coefficients(K)
+        r = np.einsum("k,ksit->sit", c[:, K - 1], G)
+        for j in range(K - 2, -1, -1):
+            r = _apply(LT, r) + np.einsum("k,ksit->sit", c[:, j], G)
+    else:
+        b1 = b2 = np.zeros((S, n, T))
+        for k in range(K - 1, 0, -1):
+            b1, b2 = G[k] + 2 * _apply(LT, b1) - b2, b1
+        r = G[0] + _apply(LT, b1) - b2
+    return r, gW
+
+
 # ----------------------------------------------------------------------------- COO SpMM helpers
 def spmm(index, value, m, matrix):
     """tgcn/nn/gcn.py:258-278: out[r] += v_e * matrix[c] over the FIRST axis (1-D input is
