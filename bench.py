@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Cheb-TGCN forward on MI355X: G edge.timesteps/s + achieved HBM GB/s against the roofline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg5|cfg4|cfg3|cfg2] [--labeling random|degree|natural]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg5|cfg4|cfg3|cfg2] [--labeling random|degree|natural] [--full]
 
 A "step" is ONE forward of the layer over one batch of synthetic input resident in HBM:
   cfg5 (default, BASELINE.json's metric): R-MAT n=10M / nnz=160M, TGCNCheb(L, 64, 64, K=5) semantics with q=T=16
@@ -15,14 +15,19 @@ aggregate.  --shard vertex / hybrid run the vertex-sharded layer (halo / all-gat
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel = hop_kernel,
 algorithmic bytes per launch / mean launch duration from hipEvents recorded around every hop launch of the timed
-steps) and `cpu_baseline` (oracle/cheb_ref.c, OpenMP, timed on this box's host cores on a bounded sample).
-`roofline.physical_*`: the same for the bytes a launch physically has to move once (entries, row pointers, and only the rows that exist in
+steps).  `roofline.physical_*`: the same for the bytes a launch physically has to move once (entries, row pointers, and only the rows that exist in
 the hop tensors -- compaction is fewer rows processed, not more bandwidth); `roofline.mean_launch_ms_by_hop`: by hop position.
-N > 1: the vertex-sharded / hybrid extras (`other_shardings`) size themselves to --extras-budget and never decide the exit code; they run through
-the sharded MODULES (tgcn_amd.dist.ShardedTGCNCheb / ShardedTGCNCheb_H).  `--shard vertex` without a launcher forms a one-rank group itself.
-The default run (cfg5, one GPU) also carries `other_workloads` -- the R-MAT with degree-sorted labels, cfg2 (f = 1 and 64), cfg3, cfg4, each with ms
-per forward, its dominant kernel's roofline and the GPU-vs-CPU errors, measured after the headline with its memory freed (--no-others skips them) --
-and times the CPU baseline on as many time steps as --cpu-budget seconds allow (`cpu_baseline.samples_timed`, `scaled_from`, `host`).
+`--shard vertex` without a launcher forms a one-rank group itself.
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  Everything else is measured and
+checked under --full (each part can still be skipped there with its own --no-* switch):
+  `cpu_baseline`: oracle/cheb_ref.c, OpenMP, on the host cores, on as many time steps as --cpu-budget seconds allow (`samples_timed`,
+        `scaled_from`, `host`), every one also a GPU-vs-CPU parity check; the single-thread scipy and the dense-L einsum restatements.
+  `roofline.copy_peak_measured` / `frac_of_copy_peak` (a device copy of its own) and `roofline.gather_ceiling_ms` (--no-ceiling).
+  `other_workloads` (default run, cfg5 on one GPU): the R-MAT with degree-sorted labels, cfg2 (f = 1 and 64), cfg3, cfg4, each with ms per
+        forward, its dominant kernel's roofline and the GPU-vs-CPU errors, measured after the headline with its memory freed (--no-others).
+  `other_shardings` (N > 1; also without --full under --force-extras): the vertex-sharded / hybrid extras, sized to --extras-budget, never
+        deciding the exit code; they run through the sharded MODULES (tgcn_amd.dist.ShardedTGCNCheb / ShardedTGCNCheb_H) (--no-extras).
 """
 import argparse
 import json
@@ -659,10 +664,13 @@ def main():
     ap.add_argument("--labeling", default="random")
     ap.add_argument("--vertices", type=int, default=None, help="override vertex count (cfg5 only; reported in config)")
     ap.add_argument("--entries", type=int, default=None)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--cpu-budget", type=float, default=100.0, help="seconds of CPU-baseline time on the headline workload: time steps are timed two at a time until this is used up (all 16 when it allows); the rest is scaled and said so")
-    ap.add_argument("--no-others", action="store_true", help="default run (cfg5, 1 GPU): skip `other_workloads` (cfg2 f=1 / f=64, cfg3, cfg4 measured after the headline)")
-    ap.add_argument("--no-ceiling", action="store_true", help="skip roofline.gather_ceiling_ms (one extra operand build + 4 hop launches after the timed steps)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need: the CPU baselines and their parity "
+                                                        "checks, the measured copy peak and the gather ceiling of the roofline, `other_workloads` (default run) "
+                                                        "and the vertex-sharded extras (N > 1)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--cpu-budget", type=float, default=100.0, help="--full: seconds of CPU-baseline time on the headline workload: time steps are timed two at a time until this is used up (all 16 when it allows); the rest is scaled and said so")
+    ap.add_argument("--no-others", action="store_true", help="--full, default run (cfg5, 1 GPU): skip `other_workloads` (cfg2 f=1 / f=64, cfg3, cfg4 measured after the headline)")
+    ap.add_argument("--no-ceiling", action="store_true", help="--full: skip roofline.gather_ceiling_ms (one extra operand build + 4 hop launches after the timed steps)")
     ap.add_argument("--shard", default="time", choices=["time", "vertex", "hybrid"], help="N > 1: time steps split over the ranks (no collective); vertex rows per rank with a halo / all-gather exchange per hop; hybrid: --vertex-shards ranks share a graph, groups split the time steps")
     ap.add_argument("--scaling", default="strong", choices=["strong", "weak"], help="N > 1, time sharding: strong = the workload's q time steps split over the ranks (default); weak = q time steps per rank")
     ap.add_argument("--vertex-shards", type=int, default=2, help="ranks per graph copy for --shard hybrid")
@@ -672,9 +680,9 @@ def main():
     ap.add_argument("--compact-q-chunk", type=int, default=None, help="developer: time steps per pass of the compacted forward")
     ap.add_argument("--no-compact", action="store_true", help="developer: hop tensors for all vertices even when many rows are empty")
     ap.add_argument("--tune", action="append", default=[], help="developer: key=value for tgcn_set_tuning (repeatable)")
-    ap.add_argument("--no-extras", action="store_true", help="N > 1, time sharding: skip the vertex-sharded / hybrid runs reported in `other_shardings`")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N > 1, time sharding: skip the vertex-sharded / hybrid runs reported in `other_shardings`")
     ap.add_argument("--rehearsal-cpu", action="store_true", help="tests only: run the N > 1 control flow on the CPU with the gloo backend and scipy stand-ins for the HIP calls; nothing measured in this mode is a result")
-    ap.add_argument("--force-extras", action="store_true", help="run the vertex-sharded extras also at world 1 (one rank under a launcher: the collectives of the N > 1 path meet RCCL)")
+    ap.add_argument("--force-extras", action="store_true", help="run the vertex-sharded extras, also without --full and also at world 1 (one rank under a launcher: the collectives of the N > 1 path meet RCCL)")
     ap.add_argument("--extras-exchange", default="auto", choices=["auto", "halo", "allgather"], help="exchange form of the vertex-sharded runs (auto: all-gather when the halo is most of the graph)")
     ap.add_argument("--extras-budget", type=float, default=150.0, help="seconds after which the extra runs are abandoned and the headline line is printed without them")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (64 MB in all; "
@@ -847,10 +855,8 @@ def main():
                 traffic_note = "%s (source hash %s)" % (os.path.relpath(tpath, ROOT), tj.get("source_hash"))
             else:
                 traffic_note = "%s is from other kernel sources (%s, loaded binary %s): stale, not reported" % (os.path.relpath(tpath, ROOT), tj.get("source_hash"), have)
-        copy_gbps = measured_copy_gbps(device)
         roofline = dict(bound="hbm", kernel="hop_kernel", achieved=round(achieved, 1), peak=HBM_PEAK_GBPS, unit="GB/s",
                         frac=round(achieved / HBM_PEAK_GBPS, 4), traffic=traffic, traffic_source=traffic_note,
-                        copy_peak_measured=round(copy_gbps, 1), frac_of_copy_peak=round(achieved / copy_gbps, 4),
                         algorithmic_bytes_per_launch=int(bytes_per_launch), launches_per_step=n_hop_launches,
                         path="project-first (hops on C_out-wide rows)" if pf_path else "hops-first",
                         mean_launch_ms=round(mean_ms, 4), hop_ms_per_step=round(float(np.sum(hop_ms)) / args.steps, 3),
@@ -858,6 +864,9 @@ def main():
                         hop_long_rows_only_ms_per_step=round(float(np.sum(hop_long_ms)) / args.steps, 3),
                         fixup_ms_per_step=round(float(np.sum(fix_ms)) / args.steps, 3),
                         project_ms_per_step=round(float(np.sum(proj_ms)) / args.steps, 3))
+        if args.full:
+            copy_gbps = measured_copy_gbps(device)
+            roofline.update(copy_peak_measured=round(copy_gbps, 1), frac_of_copy_peak=round(achieved / copy_gbps, 4))
         # what one hop launch PHYSICALLY has to move once: every stored entry, the row pointers, and each row that is
         # touched once in and once out -- on the compacted operand only the vertices with entries exist as rows, so this is less than the
         # SURVEY 8(d) figure above (which prices all n rows): a compaction gain is fewer rows processed, not more bandwidth
@@ -878,7 +887,7 @@ def main():
         if hop_long_ms:
             roofline["note"] = ("last hop fused into the projection: %d of the %d hop launches per step cover the rows above the threshold only and are NOT in "
                                 "mean_launch_ms; frac is for the full hop launches" % (len(hop_long_ms) // args.steps, n_hop_launches))
-        if world == 1 and not vertex_mode and not pf_path and not small_ms and args.workload in ("cfg5", "cfg5n") and not args.no_ceiling:
+        if args.full and world == 1 and not vertex_mode and not pf_path and not small_ms and args.workload in ("cfg5", "cfg5n") and not args.no_ceiling:
             # how far the measured launch is from the best any locality scheme could reach, in the driver's record
             try:
                 layout1 = _F.choose_layout(q, op.n, C_row) == 1
@@ -897,7 +906,7 @@ def main():
                                       note="SURVEY 8(d) recursion bytes of one rank's forward / its whole forward time (hops + fix-up + projection)")
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu and not (vertex_mode and rehearsal):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not (vertex_mode and rehearsal):
         # first AND last sample: the last one sits behind (q-1)*n*C elements (> 2^31 on cfg5), so the check also covers the
         # 64-bit address arithmetic of the run that was timed
         check = [0, q - 1] if (q > 1 and op.n * C_row * q >= 2 ** 31) else [0]
@@ -955,9 +964,10 @@ def main():
                     roofline=roofline, cpu_baseline=cpu)
         if per_rank is not None:
             line["ranks"] = per_rank
-    # ---- N > 1: the mandated vertex-sharded scheme (and the hybrid grid) on the same workload, reported next to the headline.
+    # ---- --full, N > 1: the mandated vertex-sharded scheme (and the hybrid grid) on the same workload, reported next to the headline.
     # A watchdog on every rank prints the headline without them and ends the process if they overrun their budget.
-    if dist is not None and (world > 1 or args.force_extras) and args.shard == "time" and not args.no_extras and spec["cls"] in ("TGCNCheb", "TGCNCheb_H"):
+    extras_wanted = (args.force_extras or (args.full and world > 1)) and not args.no_extras
+    if dist is not None and extras_wanted and args.shard == "time" and spec["cls"] in ("TGCNCheb", "TGCNCheb_H"):
         import threading
         printed = threading.Lock()         # exactly one JSON line, whoever gets there first
         progress = Progress()
@@ -991,8 +1001,8 @@ def main():
             line["other_shardings"] = extras
             print(json.dumps(line), flush=True)
     elif rank == 0:
-        if world == 1 and dist is None and args.workload == "cfg5" and not args.no_others and not rehearsal and args.vertices is None and args.entries is None:
-            # the driver's one command measures BASELINE.json's other configurations too, after the headline and with
+        if args.full and world == 1 and dist is None and args.workload == "cfg5" and not args.no_others and not rehearsal and args.vertices is None and args.entries is None:
+            # --full measures BASELINE.json's other configurations too, after the headline and with
             # everything of the headline freed; the headline's fields above are final at this point.  A failure here is reported, never fatal.
             del out, x, layer, op
             plan = plan_r = None

@@ -32,7 +32,7 @@ def _json_lines(out):
 
 
 def test_strong_time_sharding_and_extras_at_world_2():
-    r = _launch([])
+    r = _launch(["--full"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout
@@ -53,9 +53,20 @@ def test_strong_time_sharding_and_extras_at_world_2():
         assert sum(rk["owned_rows"] for rk in e["ranks"]) == 3000
 
 
+def test_plain_run_at_world_2_leaves_the_extras_to_full():
+    """without --full the N > 1 run measures the headline only: the same line, no `other_shardings`"""
+    r = _launch([])
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1, r.stdout
+    line = lines[0]
+    assert line["n_gpus"] == 2 and line["value"] > 0 and [r["rank"] for r in line["ranks"]] == [0, 1]
+    assert "other_shardings" not in line and "extras_abandoned" not in line and line["cpu_baseline"] is None
+
+
 def test_abandoned_extras_print_the_headline_and_still_exit_zero():
     """the time-sharded headline exits 0 whenever it was measured -- also when the extras run out of budget."""
-    r = _launch(["--extras-budget", "0.001"])
+    r = _launch(["--full", "--extras-budget", "0.001"])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout
@@ -65,7 +76,7 @@ def test_abandoned_extras_print_the_headline_and_still_exit_zero():
 
 def test_extras_size_themselves_to_a_small_budget():
     """A budget that does not hold all 8 time steps of a group: the entries still finish (fewer time steps, recorded), rc 0."""
-    r = _launch(["--extras-budget", "20", "--vertices", "20000", "--entries", "300000"])
+    r = _launch(["--full", "--extras-budget", "20", "--vertices", "20000", "--entries", "300000"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = _json_lines(r.stdout)[0]
     assert "extras_abandoned" not in line
@@ -125,7 +136,7 @@ def test_one_rank_under_the_launcher_runs_the_collectives_and_the_extras():
 def test_the_drivers_eight_rank_command_on_the_cpu():
     """The command an 8-GPU lease runs (`--gpus 8`, here self-launched, gloo, scipy stand-ins): 16 time steps split 2 per rank, the vertex-sharded
     extras over all 8 ranks and the hybrid grid (4 groups x 2 vertex shards), one line, rc 0.  Control flow only -- nothing here is a measurement."""
-    r = _bare(["--gpus", "8", "--steps", "2", "--warmup", "1", "--rehearsal-cpu", "--vertices", "4000", "--entries", "50000", "--extras-budget", "240"], timeout=600)
+    r = _bare(["--gpus", "8", "--steps", "2", "--warmup", "1", "--rehearsal-cpu", "--vertices", "4000", "--entries", "50000", "--full", "--extras-budget", "240"], timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1, r.stdout

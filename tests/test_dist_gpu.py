@@ -299,13 +299,13 @@ def test_vertex_sharded_two_ranks_two_gpus_rccl(exchange, banded):
 
 def test_bench_cfg4_shard_vertex_line_without_a_launcher(gpu_device):
     """`python bench.py --workload cfg4 --shard vertex`: the process forms a one-rank RCCL group itself, steps the sharded MODULE
-    (project-first inside, 32-float hop rows) and checks its output against oracle/cheb_ref.c like the single-GPU line"""
+    (project-first inside, 32-float hop rows) and, under --full, checks its output against oracle/cheb_ref.c like the single-GPU line"""
     import json
     import subprocess
     import sys
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg4", "--shard", "vertex", "--steps", "5", "--warmup", "2"], cwd=root,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "cfg4", "--shard", "vertex", "--steps", "5", "--warmup", "2", "--full"], cwd=root,
                        env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]

@@ -147,11 +147,11 @@ def test_training_step_is_hipgraph_capturable(gpu_device):
 
 @pytest.mark.parametrize("workload", ["cfg3", "cfg4", "cfg2w"])
 def test_bench_line_of_the_other_workloads(workload, gpu_device):
-    """`python bench.py --workload W` end to end for BASELINE.json's other configurations: one JSON line with `roofline` and a `cpu_baseline` whose
-    time-step loop also works when a time step takes microseconds (round 6: the budget loop divided by a rounded-to-zero duration on cfg3)."""
+    """`python bench.py --workload W --full` end to end for BASELINE.json's other configurations: one JSON line with `roofline` and a `cpu_baseline`
+    whose time-step loop also works when a time step takes microseconds (round 6: the budget loop divided by a rounded-to-zero duration on cfg3)."""
     import json
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "10", "--warmup", "3"], cwd=ROOT,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--steps", "10", "--warmup", "3", "--full"], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
@@ -163,3 +163,20 @@ def test_bench_line_of_the_other_workloads(workload, gpu_device):
     assert len(cpu["samples_timed"]) == {"cfg3": 64, "cfg4": 1, "cfg2w": 128}[workload]
     if workload != "cfg4":
         assert cpu["torch_dense_einsum"]["gpu_vs_cpu_rel_err"] <= 1e-5
+
+
+def test_plain_bench_line_is_the_headline_only(gpu_device):
+    """`python bench.py --workload cfg4` without --full: the headline fields and the roofline of the timed steps' own launch events, and nothing
+    that takes a measurement of its own (no CPU leg, no device copy for the copy peak)."""
+    import json
+    import subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg4", "--steps", "10", "--warmup", "3"], cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = lines[0]
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["steps"] == 10 and line["warmup"] == 3
+    assert line["unit"] == "G edge·timesteps/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+    assert line["roofline"]["frac"] > 0 and "copy_peak_measured" not in line["roofline"]
+    assert line["cpu_baseline"] is None and "other_workloads" not in line

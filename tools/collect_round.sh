@@ -7,10 +7,10 @@ cd "$(dirname "$0")/.."
 out=gpurun_out/$tag
 mkdir -p $out
 echo "== default bench" | tee -a $out/steps.log
-timeout -k 10 900 python3 bench.py > $out/bench_cfg5.json 2> $out/bench_cfg5.err || echo "bench rc=$?" | tee -a $out/steps.log
+timeout -k 10 900 python3 bench.py --full > $out/bench_cfg5.json 2> $out/bench_cfg5.err || echo "bench rc=$?" | tee -a $out/steps.log
 echo "== bench lines" | tee -a $out/steps.log
-timeout -k 10 1500 bash tools/collect_bench_lines.sh > $out/bench_lines.log 2>&1 || echo "bench lines rc=$?" | tee -a $out/steps.log
-python3 tools/merge_bench_lines.py $tag > $out/merge.log 2>&1
+timeout -k 10 1500 bash tools/collect_bench_lines.sh $out/bench_lines > $out/bench_lines.log 2>&1 || echo "bench lines rc=$?" | tee -a $out/steps.log
+python3 tools/merge_bench_lines.py $tag $out/bench_lines > $out/merge.log 2>&1
 echo "== traffic" | tee -a $out/steps.log
 timeout -k 10 1500 bash tools/collect_traffic.sh $tag > $out/traffic.log 2>&1 || echo "traffic rc=$?" | tee -a $out/steps.log
 echo "== projection limiter" | tee -a $out/steps.log
