@@ -235,6 +235,23 @@ int tgcn_csr_hop2_f32(void* stream, const tgcn_csr* A, const tgcn_csr_sched* sch
                       const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
                       const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes);
 
+/* ---- bf16 operands (the layers' bf16 path: a bf16 weight picks it; DESIGN.md "bf16 layers").  Element codes of the dtype flags: */
+#define TGCN_DTYPE_F32 0
+#define TGCN_DTYPE_BF16 1
+
+/* tgcn_csr_hop_f32 / tgcn_csr_hop2_f32 on rows of bf16 elements: X, Z, Z2, Y, P hold bf16 (tgcn_dense.ptr points at them, strides in
+ * ELEMENTS); the CSR values stay fp32.  Each row is accumulated in fp32 and rounded once, to nearest even, when it is stored; the partial
+ * rows of long rows in the workspace are fp32.  Geometry is keyed on row bytes: with every base 16-byte aligned and strides multiples of
+ * 8 elements (aligned16 != 0) and C % 8 == 0, a lane moves 8 elements and `sched` must be the schedule an fp32 row of C/2 floats takes
+ * (tgcn_hop_lanes_per_row(C/2, 1)); otherwise one element per lane, the schedule of tgcn_hop_lanes_per_row(C, 0). */
+size_t tgcn_csr_hop_bf16_workspace_bytes(const tgcn_csr_sched* sched, int32_t nb, int32_t C, int aligned16);
+int tgcn_csr_hop_bf16(void* stream, const tgcn_csr* A, const tgcn_csr_sched* sched, int32_t nb, int32_t C,
+                      const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Y,
+                      const tgcn_dense* P, void* workspace, size_t workspace_bytes);
+int tgcn_csr_hop2_bf16(void* stream, const tgcn_csr* A, const tgcn_csr_sched* sched, int32_t nb, int32_t C,
+                       const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
+                       const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes);
+
 /* The same hop in fp64 for the numpy twin gcn.graph.chebyshev(L, X, K) with a float64 operand: the reference computes in
  * L.dtype (gcn/graph.py:247, 256-265).  Plain CSR (int32 rowptr / col, fp64 val), X / Z / Y / P: rows of F contiguous doubles;
  * Y = alpha * (L X) + beta * Z (Z nullable), P = L X (nullable).  Entries are summed in stored order. */
@@ -300,6 +317,19 @@ int tgcn_cheb_windows_backward_f32(void* stream, int64_t S, int64_t n_vertices, 
 size_t tgcn_cheb_wgrad_workspace_bytes(int64_t M, int32_t Kc, int32_t N, int32_t nterms);
 int tgcn_cheb_wgrad_f32(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const float* const* a,
                         const int64_t* lda, const float* G, int64_t ldg, float* dW, void* workspace, size_t workspace_bytes);
+
+/* tgcn_cheb_project_f32's contraction on bf16 terms a[t] and a bf16 W ((nterms*Kc) x N): products on the bf16 matrix pipe, fp32 sums,
+ * bias (bias_dtype: TGCN_DTYPE_F32 or TGCN_DTYPE_BF16) added in fp32 to the first bias_cols columns (<= 0: all N; a per-vertex bias row
+ * then has bias_cols elements), accumulate adds the existing output; out (out_dtype) is fp32, or rounded once to bf16.  interleave as in
+ * tgcn_cheb_project_f32; k past nterms*Kc in the last 32-wide step reads zeros. */
+int tgcn_cheb_project_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const void* const* a, const int64_t* lda,
+                           const void* W, const void* bias, int32_t bias_kind, int32_t bias_dtype, int32_t bias_cols, int64_t n_vertices,
+                           int64_t interleave, int32_t accumulate, void* out, int64_t ldo, int32_t out_dtype);
+
+/* tgcn_cheb_wgrad_f32 on bf16 A_t and G (fp32 dW and partials): bf16 matrix pipe (exact products), the same two-stage reduction in fixed
+ * order (deterministic); workspace: tgcn_cheb_wgrad_workspace_bytes. */
+int tgcn_cheb_wgrad_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const void* const* a, const int64_t* lda,
+                         const void* G, int64_t ldg, float* dW, void* workspace, size_t workspace_bytes);
 
 /* (Q, n, C) -> (n, Q, C) re-layout so that short per-sample rows become one long row per vertex (LDS-tiled transpose for C <= 32, a
  * coalesced row copy for wider rows). */

@@ -73,6 +73,17 @@ SIGNATURES = {
     "tgcn_csr_hop2_f32": (C.c_int, [_P, C.POINTER(CsrStruct), C.POINTER(SchedStruct), C.c_int32, C.c_int32,
                                     C.POINTER(DenseStruct), C.POINTER(DenseStruct), C.c_float, C.c_float,
                                     C.POINTER(DenseStruct), C.c_float, C.POINTER(DenseStruct), C.POINTER(DenseStruct), _P, C.c_size_t]),
+    "tgcn_csr_hop_bf16_workspace_bytes": (C.c_size_t, [C.POINTER(SchedStruct), C.c_int32, C.c_int32, C.c_int]),
+    "tgcn_csr_hop_bf16": (C.c_int, [_P, C.POINTER(CsrStruct), C.POINTER(SchedStruct), C.c_int32, C.c_int32,
+                                    C.POINTER(DenseStruct), C.POINTER(DenseStruct), C.c_float, C.c_float,
+                                    C.POINTER(DenseStruct), C.POINTER(DenseStruct), _P, C.c_size_t]),
+    "tgcn_csr_hop2_bf16": (C.c_int, [_P, C.POINTER(CsrStruct), C.POINTER(SchedStruct), C.c_int32, C.c_int32,
+                                     C.POINTER(DenseStruct), C.POINTER(DenseStruct), C.c_float, C.c_float,
+                                     C.POINTER(DenseStruct), C.c_float, C.POINTER(DenseStruct), C.POINTER(DenseStruct), _P, C.c_size_t]),
+    "tgcn_cheb_project_bf16": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64), _P, _P,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, _P, C.c_int64, C.c_int32]),
+    "tgcn_cheb_wgrad_bf16": (C.c_int, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.POINTER(_P), C.POINTER(C.c_int64), _P,
+                                       C.c_int64, _P, _P, C.c_size_t]),
     "tgcn_cheb_forward_pf_workspace_bytes": (C.c_size_t, [C.POINTER(SchedStruct), C.c_int32, C.c_int64, C.c_int64, C.c_int32]),
     "tgcn_cheb_forward_pf_f32": (C.c_int, [_P, C.POINTER(CsrStruct), C.POINTER(SchedStruct), C.c_int32, C.c_int32, C.c_int64,
                                            C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.c_size_t]),
@@ -128,6 +139,7 @@ SIGNATURES = {
 
 _lib = None
 ABI_VERSION = 7      # include/tgcn_hip.h: TGCN_ABI_VERSION
+DTYPE_F32, DTYPE_BF16 = 0, 1     # TGCN_DTYPE_* of the bf16 entries' dtype flags
 
 
 def source_hash():

@@ -37,6 +37,9 @@ __device__ __forceinline__ void load_vec(const float* __restrict__ p, float (&v)
   if constexpr (VEC == 4) {
     const float4 t = *reinterpret_cast<const float4*>(p);
     v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else if constexpr (VEC == 8) {     // fp32 partial rows of the bf16 hop
+    const float4 t = *reinterpret_cast<const float4*>(p), u = *reinterpret_cast<const float4*>(p + 4);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; v[4] = u.x; v[5] = u.y; v[6] = u.z; v[7] = u.w;
   } else {
     v[0] = *p;
   }
@@ -48,6 +51,10 @@ __device__ __forceinline__ void load_vec_nt(const float* __restrict__ p, float (
     using f4 = __attribute__((ext_vector_type(4))) float;
     const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p));
     v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else if constexpr (VEC == 8) {
+    using f4 = __attribute__((ext_vector_type(4))) float;
+    const f4 t = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p)), u = __builtin_nontemporal_load(reinterpret_cast<const f4*>(p + 4));
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; v[4] = u.x; v[5] = u.y; v[6] = u.z; v[7] = u.w;
   } else {
     v[0] = __builtin_nontemporal_load(p);
   }
@@ -57,10 +64,85 @@ template <int VEC>
 __device__ __forceinline__ void store_vec(float* __restrict__ p, const float (&v)[VEC]) {
   if constexpr (VEC == 4) {
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+  } else if constexpr (VEC == 8) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+    *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
   } else {
     *p = v[0];
   }
 }
+
+// ---- bf16 rows (tgcn_csr_hop_bf16): a lane moves 16 B = 8 elements, widened to fp32 in registers; every sum is fp32 and a stored
+// row is rounded once, to nearest even (v_cvt_pk_bf16_f32).  Rows that are not 16-byte aligned take one element per lane.
+using hbf16 = __bf16;
+
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }
+__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
+  using b2 = __attribute__((ext_vector_type(2))) __bf16;
+  const b2 h = {(__bf16)a, (__bf16)b};
+  return __builtin_bit_cast(uint32_t, h);
+}
+
+template <int VEC>
+__device__ __forceinline__ void load_vec(const hbf16* __restrict__ p, float (&v)[VEC]) {
+  if constexpr (VEC == 8) {
+    const uint4 t = *reinterpret_cast<const uint4*>(p);
+    v[0] = bf16_lo(t.x); v[1] = bf16_hi(t.x); v[2] = bf16_lo(t.y); v[3] = bf16_hi(t.y);
+    v[4] = bf16_lo(t.z); v[5] = bf16_hi(t.z); v[6] = bf16_lo(t.w); v[7] = bf16_hi(t.w);
+  } else {
+    v[0] = bf16_lo(*reinterpret_cast<const uint16_t*>(p));
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void load_vec_nt(const hbf16* __restrict__ p, float (&v)[VEC]) {
+  if constexpr (VEC == 8) {
+    using u4 = __attribute__((ext_vector_type(4))) unsigned;
+    const u4 t = __builtin_nontemporal_load(reinterpret_cast<const u4*>(p));
+    v[0] = bf16_lo(t.x); v[1] = bf16_hi(t.x); v[2] = bf16_lo(t.y); v[3] = bf16_hi(t.y);
+    v[4] = bf16_lo(t.z); v[5] = bf16_hi(t.z); v[6] = bf16_lo(t.w); v[7] = bf16_hi(t.w);
+  } else {
+    v[0] = bf16_lo(__builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(p)));
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void store_vec(hbf16* __restrict__ p, const float (&v)[VEC]) {
+  if constexpr (VEC == 8) {
+    *reinterpret_cast<uint4*>(p) = make_uint4(pack_bf16(v[0], v[1]), pack_bf16(v[2], v[3]), pack_bf16(v[4], v[5]), pack_bf16(v[6], v[7]));
+  } else {
+    *p = (__bf16)v[0];
+  }
+}
+
+// One gathered X row piece of a lane as it sits in registers until its FMAs: VEC floats, or the packed bf16 words (4 VGPRs for 8
+// elements -- widening at load time would double the registers of the gathers in flight).
+template <class T, int VEC> struct HopElem {
+  using raw = float[VEC];
+  static __device__ __forceinline__ void zero(raw& r) {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) r[i] = 0.f;
+  }
+  static __device__ __forceinline__ void load(const float* __restrict__ p, raw& r) { load_vec<VEC>(p, r); }
+  static __device__ __forceinline__ float get(const raw& r, int i) { return r[i]; }
+};
+template <int VEC> struct HopElem<hbf16, VEC> {
+  using raw = uint32_t[(VEC + 1) / 2];
+  static __device__ __forceinline__ void zero(raw& r) {
+#pragma unroll
+    for (int i = 0; i < (VEC + 1) / 2; ++i) r[i] = 0u;
+  }
+  static __device__ __forceinline__ void load(const hbf16* __restrict__ p, raw& r) {
+    if constexpr (VEC == 8) {
+      const uint4 t = *reinterpret_cast<const uint4*>(p);
+      r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
+    } else {
+      r[0] = *reinterpret_cast<const uint16_t*>(p);
+    }
+  }
+  static __device__ __forceinline__ float get(const raw& r, int i) { return (i & 1) ? bf16_hi(r[i >> 1]) : bf16_lo(r[i >> 1]); }
+};
 
 // XCD-aware block id: blocks b and b+8 share an XCD (observed round-robin dispatch), so hand each XCD a
 // contiguous range of row blocks -- neighbouring rows share neighbour columns in its private L2.
@@ -88,6 +170,9 @@ __device__ __forceinline__ void store_vec_nt(float* __restrict__ p, const float 
   }
 }
 
+template <int VEC>
+__device__ __forceinline__ void store_vec_nt(hbf16* __restrict__ p, const float (&v)[VEC]) { store_vec<VEC>(p, v); }
+
 template <int NTM>
 __device__ __forceinline__ void load_edge(const tgcn_edge* __restrict__ ev, int e, int& c, float& v) {
   if constexpr (NTM & kNtEdges) {
@@ -102,16 +187,20 @@ __device__ __forceinline__ void load_edge(const tgcn_edge* __restrict__ ev, int 
   }
 }
 
-template <int VEC, int NTM>
+// T: element type of X / Z / Z2 / Y / P (float, or hbf16 for tgcn_csr_hop_bf16: HopParams then holds bf16 pointers, strides in elements)
+template <class T> __device__ __forceinline__ const T* hop_rows(const float* p) { return reinterpret_cast<const T*>(p); }
+template <class T> __device__ __forceinline__ T* hop_rows(float* p) { return reinterpret_cast<T*>(p); }
+
+template <int VEC, int NTM, class T = float>
 __device__ __forceinline__ void finish_row(const HopParams& p, int b, int r, int c0, const float (&s)[VEC]) {
   if (p.P) {
-    if constexpr (NTM & kNtStores) store_vec_nt<VEC>(p.P + (int64_t)b * p.p_bs + (int64_t)r * p.p_ld + c0, s);
-    else store_vec<VEC>(p.P + (int64_t)b * p.p_bs + (int64_t)r * p.p_ld + c0, s);
+    if constexpr (NTM & kNtStores) store_vec_nt<VEC>(hop_rows<T>(p.P) + (int64_t)b * p.p_bs + (int64_t)r * p.p_ld + c0, s);
+    else store_vec<VEC>(hop_rows<T>(p.P) + (int64_t)b * p.p_bs + (int64_t)r * p.p_ld + c0, s);
   }
   float y[VEC];
   if (p.Z) {
     float z[VEC];
-    load_vec_nt<VEC>(p.Z + (int64_t)b * p.z_bs + (int64_t)r * p.z_ld + c0, z);
+    load_vec_nt<VEC>(hop_rows<T>(p.Z) + (int64_t)b * p.z_bs + (int64_t)r * p.z_ld + c0, z);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) y[i] = fmaf(p.alpha, s[i], p.beta * z[i]);
   } else {
@@ -120,13 +209,13 @@ __device__ __forceinline__ void finish_row(const HopParams& p, int b, int r, int
   }
   if (p.Z2) {   // second addend (Clenshaw step of the project-first path): y += gamma * z2
     float z2[VEC];
-    load_vec_nt<VEC>(p.Z2 + (int64_t)b * p.z2_bs + (int64_t)r * p.z2_ld + c0, z2);
+    load_vec_nt<VEC>(hop_rows<T>(p.Z2) + (int64_t)b * p.z2_bs + (int64_t)r * p.z2_ld + c0, z2);
 #pragma unroll
     for (int i = 0; i < VEC; ++i) y[i] = fmaf(p.gamma, z2[i], y[i]);
   }
   if (p.Y) {
-    if constexpr (NTM & kNtStores) store_vec_nt<VEC>(p.Y + (int64_t)b * p.y_bs + (int64_t)r * p.y_ld + c0, y);
-    else store_vec<VEC>(p.Y + (int64_t)b * p.y_bs + (int64_t)r * p.y_ld + c0, y);
+    if constexpr (NTM & kNtStores) store_vec_nt<VEC>(hop_rows<T>(p.Y) + (int64_t)b * p.y_bs + (int64_t)r * p.y_ld + c0, y);
+    else store_vec<VEC>(hop_rows<T>(p.Y) + (int64_t)b * p.y_bs + (int64_t)r * p.y_ld + c0, y);
   }
 }
 
@@ -161,9 +250,10 @@ __device__ __forceinline__ int group_bcast(int v, int lane) {
 // round with in-register broadcasts (group_bcast); gathers are issued U at a time per row, so R*U 16-byte loads are in
 // flight per lane.  R > 1 keeps R independent rowptr -> entry -> gather chains going, which is what low-degree rows on wide
 // operands need (measured on the mesh config); entries are summed in stored order: deterministic.
-template <int LPR, int VEC, int UU, int R, int NTM>
+template <int LPR, int VEC, int UU, int R, int NTM, class T = float>
 __device__ __forceinline__ void accum_multi(const tgcn_edge* __restrict__ ev, const int (&e0)[R], const int (&e1)[R], int t,
-                                            const float* __restrict__ Xc, int64_t ldx, float (&acc)[R][VEC]) {
+                                            const T* __restrict__ Xc, int64_t ldx, float (&acc)[R][VEC]) {
+  using E = HopElem<T, VEC>;
   constexpr int U = LPR < UU ? LPR : UU;
   int len_max = 0;
 #pragma unroll
@@ -184,7 +274,7 @@ __device__ __forceinline__ void accum_multi(const tgcn_edge* __restrict__ ev, co
 #pragma unroll
     for (int j0 = 0; j0 < LPR; j0 += U) {        // fully unrolled: the broadcast lane is an immediate
       if (j0 < cmax) {
-        float xv[R][U][VEC];
+        typename E::raw xv[R][U];
         float vv[R][U];
 #pragma unroll
         for (int rr = 0; rr < R; ++rr)
@@ -192,15 +282,14 @@ __device__ __forceinline__ void accum_multi(const tgcn_edge* __restrict__ ev, co
           for (int u = 0; u < U; ++u) {
             const int c = group_bcast<LPR>(my_c[rr], j0 + u);
             vv[rr][u] = __int_as_float(group_bcast<LPR>(__float_as_int(my_v[rr]), j0 + u));   // 0 past the end of the row
-#pragma unroll
-            for (int i = 0; i < VEC; ++i) xv[rr][u][i] = 0.f;
+            E::zero(xv[rr][u]);
             if constexpr (NTM & kNtColdGather) {
               if (j0 + u < cnt[rr]) {
                 if (c < 0) load_vec_nt<VEC>(Xc + (int64_t)(c & 0x7fffffff) * ldx, xv[rr][u]);
                 else load_vec<VEC>(Xc + (int64_t)c * ldx, xv[rr][u]);
               }
             } else {
-              if (j0 + u < cnt[rr]) load_vec<VEC>(Xc + (int64_t)c * ldx, xv[rr][u]);
+              if (j0 + u < cnt[rr]) E::load(Xc + (int64_t)c * ldx, xv[rr][u]);
             }
           }
 #pragma unroll
@@ -208,13 +297,13 @@ __device__ __forceinline__ void accum_multi(const tgcn_edge* __restrict__ ev, co
 #pragma unroll
           for (int u = 0; u < U; ++u)
 #pragma unroll
-            for (int i = 0; i < VEC; ++i) acc[rr][i] = fmaf(vv[rr][u], xv[rr][u][i], acc[rr][i]);
+            for (int i = 0; i < VEC; ++i) acc[rr][i] = fmaf(vv[rr][u], E::get(xv[rr][u], i), acc[rr][i]);
       }
     }
   }
 }
 
-template <int LPR, int VEC, int UU, int R, int NTM>
+template <int LPR, int VEC, int UU, int R, int NTM, class T = float>
 __global__ __launch_bounds__(kBlock) void hop_kernel(const HopParams p) {
   constexpr int GPB = kBlock / LPR;
   const int tid = threadIdx.x;
@@ -224,7 +313,7 @@ __global__ __launch_bounds__(kBlock) void hop_kernel(const HopParams p) {
   const int b = blockIdx.y / p.nchunks;
   const int c0 = (chunk * LPR + t) * VEC;
   const bool cact = c0 < p.C;
-  const float* Xc = p.X + (int64_t)b * p.x_bs + (cact ? c0 : 0);
+  const T* Xc = hop_rows<T>(p.X) + (int64_t)b * p.x_bs + (cact ? c0 : 0);
   int bid = blockIdx.x;
   if (p.mix_period > 1) {
     // row blocks dealt evenly among the segment blocks (one every mix_period ids) instead of all in front: the short rows wait on
@@ -254,10 +343,10 @@ __global__ __launch_bounds__(kBlock) void hop_kernel(const HopParams p) {
 #pragma unroll
         for (int i = 0; i < VEC; ++i) acc[rr][i] = 0.f;
       }
-      accum_multi<LPR, VEC, UU, R, NTM>(p.ev, e0, e1, t, Xc, p.x_ld, acc);
+      accum_multi<LPR, VEC, UU, R, NTM, T>(p.ev, e0, e1, t, Xc, p.x_ld, acc);
 #pragma unroll
       for (int rr = 0; rr < R; ++rr)
-        if (live[rr] && cact) finish_row<VEC, NTM>(p, b, rb + rr * GPB, c0, acc[rr]);
+        if (live[rr] && cact) finish_row<VEC, NTM, T>(p, b, rb + rr * GPB, c0, acc[rr]);
     }
   } else {
     int sbid = bid - p.nblk;
@@ -282,7 +371,7 @@ __global__ __launch_bounds__(kBlock) void hop_kernel(const HopParams p) {
         float acc[1][VEC];
 #pragma unroll
         for (int i = 0; i < VEC; ++i) acc[0][i] = 0.f;
-        accum_multi<LPR, VEC, UU, 1, NTM>(p.ev, e0, e1, t, Xc, p.x_ld, acc);
+        accum_multi<LPR, VEC, UU, 1, NTM, T>(p.ev, e0, e1, t, Xc, p.x_ld, acc);
 #pragma unroll
         for (int off = LPR; off < 64; off <<= 1)
 #pragma unroll
@@ -290,7 +379,7 @@ __global__ __launch_bounds__(kBlock) void hop_kernel(const HopParams p) {
         if (s >= wlimit || gw != 0) return;
         const int slot = p.seg_slot[s];
         if (slot < 0) {
-          if (cact) finish_row<VEC, NTM>(p, b, p.seg_row[s], c0, acc[0]);
+          if (cact) finish_row<VEC, NTM, T>(p, b, p.seg_row[s], c0, acc[0]);
         } else {
           store_vec<VEC>(p.partial + ((int64_t)slot * p.nb + b) * p.cpad + (chunk * LPR + t) * VEC, acc[0]);
         }
@@ -309,14 +398,14 @@ __global__ __launch_bounds__(kBlock) void hop_kernel(const HopParams p) {
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[rr][i] = 0.f;
     }
-    accum_multi<LPR, VEC, UU, R, NTM>(p.ev, e0, e1, t, Xc, p.x_ld, acc);
+    accum_multi<LPR, VEC, UU, R, NTM, T>(p.ev, e0, e1, t, Xc, p.x_ld, acc);
 #pragma unroll
     for (int rr = 0; rr < R; ++rr) {
       const int s = sb + rr * GPB;
       if (s >= p.nseg) continue;
       const int slot = p.seg_slot[s];
       if (slot < 0) {
-        if (cact) finish_row<VEC, NTM>(p, b, p.seg_row[s], c0, acc[rr]);
+        if (cact) finish_row<VEC, NTM, T>(p, b, p.seg_row[s], c0, acc[rr]);
       } else {
         float* dst = p.partial + ((int64_t)slot * p.nb + b) * p.cpad + (chunk * LPR + t) * VEC;
         if constexpr (NTM & kNtPartials) store_vec_nt<VEC>(dst, acc[rr]);
@@ -329,7 +418,7 @@ __global__ __launch_bounds__(kBlock) void hop_kernel(const HopParams p) {
 // Folds the partial sums of rows that were cut into several segments, in slot order (deterministic).
 // Blocks [0, nhuge): one row each, the block's groups sum interleaved slots and combine through LDS in group
 // order; the remaining blocks: one row per lane group.
-template <int LPR, int VEC>
+template <int LPR, int VEC, class T = float>
 __global__ __launch_bounds__(kBlock) void hop_fixup_kernel(const HopParams p) {
   constexpr int GPB = kBlock / LPR;
   constexpr int UF = 4;
@@ -378,7 +467,7 @@ __global__ __launch_bounds__(kBlock) void hop_fixup_kernel(const HopParams p) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) acc[k] += red[(g * LPR + t) * VEC + k];
   }
-  if (valid && c0 < p.C) finish_row<VEC, 0>(p, b, row, c0, acc);
+  if (valid && c0 < p.C) finish_row<VEC, 0, T>(p, b, row, c0, acc);
 }
 
 struct HopGeom {
@@ -397,7 +486,22 @@ inline HopGeom hop_geom(int32_t C, int aligned16) {
   return g;
 }
 
-template <int LPR, int VEC, int U, int R, int NTM = 0>
+// Geometry of bf16 rows, keyed on row BYTES: a lane moves 16 B (8 elements) when every operand is 16-byte aligned, so a bf16 row of C
+// elements has the lane shape of an fp32 row of C/2 floats (and takes its schedule); otherwise one element per lane, like an unaligned fp32
+// row of C floats.  cpad stays in elements: the partial rows of long rows are fp32, cpad floats each.
+inline HopGeom hop_geom_bf16(int32_t C, int aligned16) {
+  HopGeom g;
+  g.vec = (aligned16 && (C % 8 == 0)) ? 8 : 1;
+  const int lanes = (C + g.vec - 1) / g.vec;
+  int lpr = 1;
+  while (lpr < lanes && lpr < 64) lpr <<= 1;
+  g.lpr = lpr;
+  g.nchunks = (lanes + lpr - 1) / lpr;
+  g.cpad = g.nchunks * lpr * g.vec;
+  return g;
+}
+
+template <int LPR, int VEC, int U, int R, int NTM = 0, class T = float>
 inline void launch_hop(hipStream_t st, const HopParams& p, dim3 grid) {
   constexpr int GPB = kBlock / LPR;
   const int seg_per_block = (p.seg_mode == 1 && LPR < 64 && R == 1) ? kBlock / 64 : GPB * R;
@@ -410,8 +514,8 @@ inline void launch_hop(hipStream_t st, const HopParams& p, dim3 grid) {
   else if (p.mix_period < 0) pk.mix_period = nsb > 0 ? -1 : 0;
   // "hop_lds_pad": unused dynamic LDS per workgroup = an occupancy limiter (160 KB / pad workgroups per CU) for A/B runs
   const int pad = g_hop_lds_pad.load();
-  if (pad > 65536) allow_large_lds((const void*)hop_kernel<LPR, VEC, U, R, NTM>, pad);
-  hipLaunchKernelGGL((hop_kernel<LPR, VEC, U, R, NTM>), grid, dim3(kBlock), (size_t)(pad > 0 ? pad : 0), st, pk);
+  if (pad > 65536) allow_large_lds((const void*)hop_kernel<LPR, VEC, U, R, NTM, T>, pad);
+  hipLaunchKernelGGL((hop_kernel<LPR, VEC, U, R, NTM, T>), grid, dim3(kBlock), (size_t)(pad > 0 ? pad : 0), st, pk);
 }
 
 // developer variants of the two float4 shapes that matter for the benchmarks (tools/hop_bench.py)
@@ -454,12 +558,23 @@ template <int L> struct HopRows { static constexpr int value = (L == 64) ? 4 : 1
 // gathers in flight per lane and row: 8 for 16-lane groups (cfg5 on the compacted operand: 3.840 -> 3.804 ms, four A/B runs), 4 otherwise
 template <int L> struct HopUnroll { static constexpr int value = (L == 16) ? 8 : 4; };
 
-template <int VEC>
+// The default form of lane width L for element type T: bf16 rows ship this form only (no developer variants, no non-temporal forms).
+template <int L, int VEC, class T>
+inline void launch_hop_default(hipStream_t st, const HopParams& p, dim3 grid) {
+  /* interleave rows only when the grid still fills the chip afterwards */
+  if (HopRows<L>::value > 1 && (int64_t)p.nblk * grid.y >= 4096)
+    launch_hop<L, VEC, 4, HopRows<L>::value, 0, T>(st, p, grid);
+  else launch_hop<L, VEC, HopUnroll<L>::value, 1, 0, T>(st, p, grid);
+}
+
+template <int VEC, class T = float>
 int launch_hop_vec(hipStream_t st, const HopParams& p, int lpr, dim3 grid, dim3 fix_grid) {
+  constexpr bool kF32 = std::is_same<T, float>::value;
 #define TGCN_HOP_CASE(L)                                                                    \
   case L: {                                                                                 \
     { ProfScope ps(p.long_rows_only ? TGCN_PROF_HOP_LONG : TGCN_PROF_HOP, st);              \
-      if (!(VEC == 4 && g_hop_variant.load() != 0 && launch_hop_variant(L, st, p, grid))) { \
+      if constexpr (!kF32) launch_hop_default<L, VEC, T>(st, p, grid);                      \
+      else if (!(VEC == 4 && g_hop_variant.load() != 0 && launch_hop_variant(L, st, p, grid))) { \
         /* interleave rows only when the grid still fills the chip afterwards */            \
         if (HopRows<L>::value > 1 && (int64_t)p.nblk * grid.y >= 4096)                       \
           launch_hop<L, VEC, 4, HopRows<L>::value>(st, p, grid);                            \
@@ -469,7 +584,7 @@ int launch_hop_vec(hipStream_t st, const HopParams& p, int lpr, dim3 grid, dim3 
         else launch_hop<L, VEC, HopUnroll<L>::value, 1>(st, p, grid);                       \
       } }                                                                                   \
     if (p.nlong > 0) { ProfScope ps(TGCN_PROF_HOP_FIXUP, st);                               \
-      hipLaunchKernelGGL((hop_fixup_kernel<L, VEC>), fix_grid, dim3(kBlock), 0, st, p); }   \
+      hipLaunchKernelGGL((hop_fixup_kernel<L, VEC, T>), fix_grid, dim3(kBlock), 0, st, p); } \
   } break;
   switch (lpr) {
     TGCN_HOP_CASE(1)
@@ -483,11 +598,17 @@ int launch_hop_vec(hipStream_t st, const HopParams& p, int lpr, dim3 grid, dim3 
       TGCN_FAIL(TGCN_ERR_INVALID, "hop: bad lanes_per_row %d", lpr);
   }
 #undef TGCN_HOP_CASE
-  TGCN_CHECK_LAUNCH("tgcn_csr_hop_f32");
+  TGCN_CHECK_LAUNCH(kF32 ? "tgcn_csr_hop_f32" : "tgcn_csr_hop_bf16");
   return TGCN_OK;
 }
 
 inline bool aligned4(const tgcn_dense* d) {
   return d == nullptr || d->ptr == nullptr ||
          (((uintptr_t)d->ptr & 15) == 0 && (d->batch_stride & 3) == 0 && (d->row_stride & 3) == 0);
+}
+
+// the same for bf16 rows: 16-byte base, strides in multiples of 8 elements
+inline bool aligned8(const tgcn_dense* d) {
+  return d == nullptr || d->ptr == nullptr ||
+         (((uintptr_t)d->ptr & 15) == 0 && (d->batch_stride & 7) == 0 && (d->row_stride & 7) == 0);
 }

@@ -1557,3 +1557,117 @@ __global__ __launch_bounds__(kBlock) void project_narrow_kernel(const ProjParams
     }
   }
 }
+
+// --------------------------------------------------------------------------------------------------
+// projection of bf16 operands (tgcn_cheb_project_bf16): out = sum_t A_t W_t + bias, one bf16 plane on the matrix pipe
+// --------------------------------------------------------------------------------------------------
+// The products of two bf16 values are exact in fp32, so unlike the bf16x3 kernels nothing is split: one v_mfma_f32_16x16x32_bf16
+// per 32 k.  The k axis runs over the concatenated terms (k = t * Kc + c) in chunks of kPbKch; a chunk of W (zero past nterms * Kc and
+// past N) is staged in LDS column-major, so that a B fragment (8 consecutive k of one column) is one 16-byte read.  A fragments come
+// straight from global memory (16 B per lane when every term is 16-byte aligned with Kc and lda multiples of 8, element by element
+// otherwise); k past the end reads zeros -- the zero-filled tail tile.  Workgroup: 4 waves x 32 rows, NT 16-column tiles.
+// The epilogue adds the bias in fp32 (fp32 or bf16 bias) and the existing output (accumulate), then stores fp32 or rounds once to bf16.
+struct ProjBf16Params {
+  const hbf16* a[kMaxTerms];
+  int64_t lda[kMaxTerms];
+  const hbf16* W;
+  const void* bias;
+  void* out;
+  int64_t M, ldo, n_vertices, interleave;
+  int32_t Kc, N, nterms, bias_kind, bias_bf16, bias_cols, accumulate, out_bf16;
+};
+
+constexpr int kPbKch = 64;                 // k per LDS chunk (two MFMA steps)
+constexpr int kPbLd = kPbKch + 8;          // LDS row of one W column: 144 B, 16-byte aligned
+
+__device__ __forceinline__ float pb_load_scalar(const ProjBf16Params& p, int64_t m, int kg, int ktot) {
+  if (m >= p.M || kg >= ktot) return 0.f;
+  const int t = kg / p.Kc, c = kg - t * p.Kc;
+  return bf16_lo(*reinterpret_cast<const uint16_t*>(p.a[t] + m * p.lda[t] + c));
+}
+
+template <int NT, bool VEC8>
+__global__ __launch_bounds__(256) void project_bf16_kernel(const ProjBf16Params p) {
+  constexpr int NW = NT * 16;
+  __shared__ __align__(16) hbf16 Ws[NW * kPbLd];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int64_t m0 = (int64_t)blockIdx.x * 128 + wave * 32;
+  const int n0 = blockIdx.y * NW;
+  const int ktot = p.nterms * p.Kc;
+  const int kpad = (ktot + 31) / 32 * 32;
+  f32x4 acc[2][NT];
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int i = 0; i < NT; ++i) acc[r][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int lr = lane & 15, lk = (lane >> 4) * 8;
+  for (int k0 = 0; k0 < kpad; k0 += kPbKch) {
+    __syncthreads();
+    for (int idx = tid; idx < kPbKch * NW; idx += 256) {
+      const int k = idx / NW, n = idx - k * NW;
+      const int kg = k0 + k;
+      hbf16 v = (hbf16)0.f;
+      if (kg < ktot && n0 + n < p.N) v = p.W[(int64_t)kg * p.N + n0 + n];
+      Ws[n * kPbLd + k] = v;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < kPbKch / 32; ++s) {
+      const int ks = k0 + s * 32;
+      if (ks >= kpad) break;
+      const int kg = ks + lk;
+      bf16x8 a[2];
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const int64_t m = m0 + r * 16 + lr;
+        if constexpr (VEC8) {
+          uint4 raw = make_uint4(0u, 0u, 0u, 0u);
+          if (m < p.M && kg < ktot) {
+            const int t = kg / p.Kc, c = kg - t * p.Kc;
+            raw = *reinterpret_cast<const uint4*>(p.a[t] + m * p.lda[t] + c);
+          }
+          a[r] = __builtin_bit_cast(bf16x8, raw);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) a[r][j] = (hbf16)pb_load_scalar(p, m, kg + j, ktot);
+        }
+      }
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const bf16x8 w = *reinterpret_cast<const bf16x8*>(&Ws[(nt * 16 + lr) * kPbLd + s * 32 + lk]);
+        acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0], w, acc[0][nt], 0, 0, 0);
+        acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[1], w, acc[1][nt], 0, 0, 0);
+      }
+    }
+  }
+  // D layout: col = lane & 15, row = (lane >> 4) * 4 + i
+#pragma unroll
+  for (int r = 0; r < 2; ++r)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int64_t m = m0 + r * 16 + (lane >> 4) * 4 + i;
+      if (m >= p.M) continue;
+      const int64_t orow = (p.interleave == 1) ? m : (m % p.interleave) * p.n_vertices + m / p.interleave;
+      const int64_t vert = orow < p.n_vertices ? orow : orow % p.n_vertices;
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const int col = n0 + nt * 16 + lr;
+        if (col >= p.N) continue;
+        float v = acc[r][nt][i];
+        if (p.bias_kind && col < p.bias_cols) {
+          const int64_t bi = (p.bias_kind == 2 ? vert * p.bias_cols : 0) + col;
+          v += p.bias_bf16 ? bf16_lo(reinterpret_cast<const uint16_t*>(p.bias)[bi]) : reinterpret_cast<const float*>(p.bias)[bi];
+        }
+        const int64_t o = orow * p.ldo + col;
+        if (p.out_bf16) {
+          hbf16* out = reinterpret_cast<hbf16*>(p.out);
+          if (p.accumulate) v += bf16_lo(reinterpret_cast<const uint16_t*>(out)[o]);
+          out[o] = (hbf16)v;
+        } else {
+          float* out = reinterpret_cast<float*>(p.out);
+          if (p.accumulate) v += out[o];
+          out[o] = v;
+        }
+      }
+    }
+}

@@ -25,6 +25,7 @@
 #include <numeric>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -116,7 +117,7 @@ int tgcn_csr_hop_f32(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, i
 
 static int hop_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
                     const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
-                    const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes, int long_rows_only);
+                    const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes, int long_rows_only, int bf16 = 0);
 
 int tgcn_csr_hop2_f32(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
                       const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
@@ -126,9 +127,10 @@ int tgcn_csr_hop2_f32(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, 
 
 // long_rows_only: the rows of more than row_thresh entries only (whole-row wave segments, lane-group segments + fix-up) -- the others are
 // left to the caller (the projection with the fused last hop gathers them itself); the rows it skips are not written.
+// bf16: rows of bf16 elements (tgcn_csr_hop_bf16; strides in elements, hop_geom_bf16), fp32 sums and partial rows.
 static int hop_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
                     const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
-                    const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes, int long_rows_only) {
+                    const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes, int long_rows_only, int bf16) {
   if (!A || !S || !X || !X->ptr) TGCN_FAIL(TGCN_ERR_INVALID, "hop: null operand");
   if (int drc = check_pointer_device(X->ptr, (hipStream_t)stream, "hop")) return drc;
   if ((!Y || !Y->ptr) && (!P || !P->ptr)) TGCN_FAIL(TGCN_ERR_INVALID, "hop: no output");
@@ -136,8 +138,9 @@ static int hop_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, in
     TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "hop: n=%lld nnz=%lld outside int32 index range", (long long)A->n, (long long)A->nnz);
   if (nb <= 0 || C <= 0) TGCN_FAIL(TGCN_ERR_INVALID, "hop: nb=%d C=%d", nb, C);
   if (!A->rowptr || (A->nnz > 0 && !A->edges) || !S->blk_row) TGCN_FAIL(TGCN_ERR_INVALID, "hop: null CSR/schedule array");
-  const int al = aligned4(X) && aligned4(Z) && aligned4(Z2) && aligned4(Y) && aligned4(P);
-  const HopGeom g = hop_geom(C, al);
+  const int al = bf16 ? (aligned8(X) && aligned8(Z) && aligned8(Z2) && aligned8(Y) && aligned8(P))
+                      : (aligned4(X) && aligned4(Z) && aligned4(Z2) && aligned4(Y) && aligned4(P));
+  const HopGeom g = bf16 ? hop_geom_bf16(C, al) : hop_geom(C, al);
   if (S->lanes_per_row != g.lpr)
     TGCN_FAIL(TGCN_ERR_INVALID, "hop: schedule built for %d lanes/row, C=%d (aligned16=%d) needs %d", S->lanes_per_row, C, al, g.lpr);
   if (S->nblk <= 0 || S->row_thresh <= 0) TGCN_FAIL(TGCN_ERR_INVALID, "hop: empty schedule");
@@ -173,7 +176,7 @@ static int hop_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, in
     const int mix = g_hop_mix.load();
     p.mix_period = (mix == 1 || (mix == 0 && S->row_mix)) ? 1 : (mix == 2 ? -1 : 0);
   }
-  p.stream_out = ((int64_t)A->n * C * (int64_t)sizeof(float) * nb > ((int64_t)256 << 20)) && g_hop_stream.load();
+  p.stream_out = !bf16 && ((int64_t)A->n * C * (int64_t)sizeof(float) * nb > ((int64_t)256 << 20)) && g_hop_stream.load();
   if (long_rows_only) {
     if (S->nseg == 0) return TGCN_OK;       // no row above the threshold: nothing to do
     p.nblk = 0;                             // no row blocks: every workgroup of the launch is a segment block
@@ -186,7 +189,25 @@ static int hop_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, in
   const int fix_blocks = S->nhuge + (S->nlong - S->nhuge + gpb - 1) / gpb;
   const dim3 fix_grid((unsigned)(fix_blocks > 0 ? fix_blocks : 1), (unsigned)(nb * g.nchunks));
   hipStream_t st = (hipStream_t)stream;
+  if (bf16) return g.vec == 8 ? launch_hop_vec<8, hbf16>(st, p, g.lpr, grid, fix_grid) : launch_hop_vec<1, hbf16>(st, p, g.lpr, grid, fix_grid);
   return g.vec == 4 ? launch_hop_vec<4>(st, p, g.lpr, grid, fix_grid) : launch_hop_vec<1>(st, p, g.lpr, grid, fix_grid);
+}
+
+size_t tgcn_csr_hop_bf16_workspace_bytes(const tgcn_csr_sched* sched, int32_t nb, int32_t C, int aligned16) {
+  if (!sched || C <= 0 || nb <= 0) return 0;
+  return (size_t)sched->npartial * (size_t)nb * (size_t)hop_geom_bf16(C, aligned16).cpad * sizeof(float);
+}
+
+int tgcn_csr_hop_bf16(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
+                      const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Y,
+                      const tgcn_dense* P, void* workspace, size_t workspace_bytes) {
+  return hop_impl(stream, A, S, nb, C, X, Z, alpha, beta, nullptr, 0.f, Y, P, workspace, workspace_bytes, 0, 1);
+}
+
+int tgcn_csr_hop2_bf16(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
+                       const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
+                       const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes) {
+  return hop_impl(stream, A, S, nb, C, X, Z, alpha, beta, Z2, gamma, Y, P, workspace, workspace_bytes, 0, 1);
 }
 
 static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const float* const* a,
@@ -547,6 +568,79 @@ int tgcn_cheb_wgrad_f32(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
   { ProfScope ps(TGCN_PROF_WGRAD, st);
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((int64_t)nterms * Kc * N + 63) / 64)), dim3(1024), 0, st, p); }
   TGCN_CHECK_LAUNCH("tgcn_cheb_wgrad_f32");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const void* const* a, const int64_t* lda,
+                           const void* W, const void* bias, int32_t bias_kind, int32_t bias_dtype, int32_t bias_cols, int64_t n_vertices,
+                           int64_t interleave, int32_t accumulate, void* out, int64_t ldo, int32_t out_dtype) {
+  if (M <= 0 || Kc <= 0 || N <= 0 || nterms <= 0 || !a || !lda || !W || !out || ldo < N) TGCN_FAIL(TGCN_ERR_INVALID, "project_bf16: bad argument");
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_bf16")) return drc;
+  if (nterms > kMaxTerms) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project_bf16: nterms %d > %d (chunk with accumulate=1)", nterms, kMaxTerms);
+  if ((int64_t)nterms * Kc >= (int64_t)INT32_MAX / 2) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project_bf16: nterms * Kc too large");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_bf16: bias_kind %d", bias_kind);
+  if ((bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) || (out_dtype != TGCN_DTYPE_F32 && out_dtype != TGCN_DTYPE_BF16))
+    TGCN_FAIL(TGCN_ERR_INVALID, "project_bf16: dtype codes %d / %d", bias_dtype, out_dtype);
+  if (interleave < 1 || n_vertices < 1) TGCN_FAIL(TGCN_ERR_INVALID, "project_bf16: interleave/n_vertices");
+  if (interleave > 1 && M != interleave * n_vertices) TGCN_FAIL(TGCN_ERR_INVALID, "project_bf16: M != interleave*n_vertices");
+  ProjBf16Params p;
+  memset(&p, 0, sizeof(p));
+  bool vec8 = Kc % 8 == 0;
+  for (int t = 0; t < nterms; ++t) {
+    if (!a[t]) TGCN_FAIL(TGCN_ERR_INVALID, "project_bf16: null term %d", t);
+    p.a[t] = (const hbf16*)a[t];
+    p.lda[t] = lda[t];
+    vec8 = vec8 && (((uintptr_t)a[t] & 15) == 0) && (lda[t] % 8 == 0);
+  }
+  p.W = (const hbf16*)W; p.bias = bias; p.out = out;
+  p.M = M; p.ldo = ldo; p.n_vertices = n_vertices; p.interleave = interleave;
+  p.Kc = Kc; p.N = N; p.nterms = nterms; p.bias_kind = bias_kind; p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
+  p.bias_cols = (bias_cols <= 0 || bias_cols > N) ? N : bias_cols;
+  p.accumulate = accumulate; p.out_bf16 = out_dtype == TGCN_DTYPE_BF16;
+  const int tiles = (N + 15) / 16;
+  const int nt = tiles <= 1 ? 1 : (tiles <= 2 ? 2 : 4);
+  const int64_t gx = (M + 127) / 128;
+  if (gx > (int64_t)INT32_MAX) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project_bf16: M too large");
+  const dim3 grid((unsigned)gx, (unsigned)((tiles + nt - 1) / nt));
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(TGCN_PROF_PROJECT, st);
+#define TGCN_PROJ_B(NTV)                                                                                      \
+  if (vec8) hipLaunchKernelGGL((project_bf16_kernel<NTV, true>), grid, dim3(256), 0, st, p);                  \
+  else hipLaunchKernelGGL((project_bf16_kernel<NTV, false>), grid, dim3(256), 0, st, p);
+  if (nt == 1) { TGCN_PROJ_B(1) } else if (nt == 2) { TGCN_PROJ_B(2) } else { TGCN_PROJ_B(4) }
+#undef TGCN_PROJ_B
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_bf16");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_wgrad_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const void* const* a, const int64_t* lda,
+                         const void* G, int64_t ldg, float* dW, void* workspace, size_t workspace_bytes) {
+  if (M <= 0 || Kc <= 0 || N <= 0 || nterms <= 0 || !a || !lda || !G || !dW) TGCN_FAIL(TGCN_ERR_INVALID, "wgrad_bf16: bad argument");
+  if (nterms > kMaxTerms) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "wgrad_bf16: nterms %d > %d", nterms, kMaxTerms);
+  const size_t need = tgcn_cheb_wgrad_workspace_bytes(M, Kc, N, nterms);
+  if (!workspace || workspace_bytes < need) TGCN_FAIL(TGCN_ERR_WORKSPACE, "wgrad_bf16: workspace %zu < %zu", workspace_bytes, need);
+  WgradBf16Params p;
+  memset(&p, 0, sizeof(p));
+  for (int t = 0; t < nterms; ++t) {
+    if (!a[t]) TGCN_FAIL(TGCN_ERR_INVALID, "wgrad_bf16: null term %d", t);
+    p.a[t] = (const hbf16*)a[t];
+    p.lda[t] = lda[t];
+  }
+  p.G = (const hbf16*)G; p.partial = (float*)workspace; p.M = M; p.ldg = ldg;
+  p.Kc = Kc; p.N = N; p.nterms = nterms;
+  p.rows_per_block = wgrad_rows_per_block(M);
+  WgradParams r;                   // the fold of the partials: wgrad_reduce_kernel reads partial, dW and the sizes only
+  memset(&r, 0, sizeof(r));
+  r.partial = p.partial; r.dW = dW; r.Kc = Kc; r.N = N; r.nterms = nterms; r.nblocks = wgrad_blocks(M);
+  const int ctiles = (Kc + 15) / 16;
+  const int tgroups = (nterms + kWgTerms - 1) / kWgTerms;
+  if ((N + 63) / 64 > 65535 || (int64_t)ctiles * tgroups > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "wgrad_bf16: Kc=%d N=%d too wide", Kc, N);
+  hipStream_t st = (hipStream_t)stream;
+  { ProfScope ps(TGCN_PROF_WGRAD, st);
+    hipLaunchKernelGGL(wgrad_bf16_partial_kernel, dim3(r.nblocks, (N + 63) / 64, ctiles * tgroups), dim3(64), 0, st, p); }
+  { ProfScope ps(TGCN_PROF_WGRAD, st);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)(((int64_t)nterms * Kc * N + 63) / 64)), dim3(1024), 0, st, r); }
+  TGCN_CHECK_LAUNCH("tgcn_cheb_wgrad_bf16");
   return TGCN_OK;
 }
 

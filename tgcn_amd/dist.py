@@ -37,6 +37,7 @@ tests/test_sharded_modules.py: overlapped against non-overlapped form bit for bi
 import torch
 import torch.distributed as dist
 
+from . import _lib
 from . import nn as _nn
 
 PROJECT_FIRST = True      # developer switch: project first inside a shard when the output is at most half as wide as an input row
@@ -719,7 +720,14 @@ class _ShardedMixin:
         self.overlap, self.depth = True, 2        # exchange of a hop under the interior rows and the other time steps of a group of `depth`
         self.force_sharded = False                # True: the exchange path also at world size 1 (first contact with the backend on one rank)
 
+    def _require_fp32(self):
+        """the sharded layers run fp32 parameters only: bf16 (and any other dtype) is refused before the shard is built or anything launches"""
+        from . import functional as F
+        if F.param_dtype(self.weight, self.bias, type(self).__name__) != torch.float32:
+            raise _lib.TgcnError("%s: bfloat16 parameters are not supported by the vertex-sharded layers (use the single-GPU module)" % type(self).__name__)
+
     def shard(self, device):
+        self._require_fp32()
         device = torch.device(device)
         sh = self._shards.get(str(device))
         if sh is None:
@@ -772,6 +780,7 @@ class ShardedTGCNCheb(_Sharded, _nn.TGCNCheb):
     """tgcn/nn/gcn.py:8-79 vertex-sharded: x_local (q, owned, f) -> (q, owned, g); weight (K, f, g), bias (1, n, g) with their GLOBAL shapes."""
 
     def forward(self, x_local):
+        self._require_fp32()
         if self._single_gpu():
             return _nn.TGCNCheb.forward(self, x_local)
         return self._sharded_layer(x_local.float(), self.weight, 2)
@@ -782,6 +791,7 @@ class ShardedTGCNCheb_H(_Sharded, _nn.TGCNCheb_H):
     horizon and few output channels (examples/pytorch_based/pytorch_hcp_tgcn.py:103-104) the shard projects first: hops and halo messages on g-wide rows."""
 
     def forward(self, x_local):
+        self._require_fp32()
         if self._single_gpu():
             return _nn.TGCNCheb_H.forward(self, x_local)
         if x_local.dim() == 3:
@@ -795,6 +805,7 @@ class ShardedGCNCheb(_Sharded, _nn.GCNCheb):
     """tgcn/nn/gcn.py:158-237 vertex-sharded: x_local (q, owned[, f]) -> (q, owned, g); weight (K, f, g), bias (1, 1, g)."""
 
     def forward(self, x_local):
+        self._require_fp32()
         if self._single_gpu():
             return _nn.GCNCheb.forward(self, x_local)
         if x_local.dim() == 2:
@@ -824,6 +835,7 @@ class _ShardedEdge(_ShardedMixin):
         return None if t is None else (t.data_ptr(), t._version, tuple(t.shape), str(t.device))
 
     def _edge_shard(self, device, edge_index, edge_weight, num_vertices):
+        self._require_fp32()
         if edge_weight is not None and edge_weight.requires_grad:
             raise ValueError("sharded edge-list layers take fixed edge weights (detach() them); the gradient w.r.t. edge_weight is the single-GPU modules'")
         device = torch.device(device)
@@ -853,6 +865,7 @@ class ShardedChebConv(_ShardedEdge, _nn.ChebConv):
     """tgcn/nn/gcn.py:348-442 vertex-sharded: forward(x_local (q, owned[, f]), edge_index (2, E) GLOBAL, edge_weight=None) -> (q, owned, g)."""
 
     def forward(self, x_local, edge_index, edge_weight=None, num_vertices=None):
+        self._require_fp32()
         if self._single_gpu():
             return _nn.ChebConv.forward(self, x_local, edge_index, edge_weight)
         sh = self._edge_shard(x_local.device, edge_index, edge_weight, num_vertices)
@@ -865,6 +878,7 @@ class ShardedChebTimeConv(_ShardedEdge, _nn.ChebTimeConv):
     """tgcn/nn/gcn.py:445-538 vertex-sharded: forward(x_local (q, owned, h[, f]), edge_index, edge_weight=None) -> (q, owned, g)."""
 
     def forward(self, x_local, edge_index, edge_weight=None, num_vertices=None):
+        self._require_fp32()
         if self._single_gpu():
             return _nn.ChebTimeConv.forward(self, x_local, edge_index, edge_weight)
         sh = self._edge_shard(x_local.device, edge_index, edge_weight, num_vertices)

@@ -391,6 +391,8 @@ def cheb_time_windows(op, series, weight_khg, bias, bias_kind, mode=MODE_POWER):
     windowed batch x[s*(T-H+1) + w, i, h] = series[s, i, w + h] (load/data_hcp.py:146-152), but the K-1 hops run
     once on the T columns of each recording -- in the backward too (ChebWindowsFn), so the windows it replaces can be
     trained through."""
+    if param_dtype(weight_khg, bias, "cheb_time_windows") == BF16:
+        raise _lib.TgcnError("forward_series / cheb_time_windows: bfloat16 parameters are not supported")
     _lib.require_device(series, weight_khg, bias)
     series, bias = _to_operand_labels(op, series, bias, bias_kind)
     out = ChebWindowsFn.apply(series, weight_khg, bias, op, mode, bias_kind)
@@ -1018,7 +1020,10 @@ def _to_operand_labels(op, x3, bias, bias_kind):
 
 def cheb_layer(op, x3, weight_kcn, bias, bias_kind, mode, values=None):
     """Differentiable fused layer; weight_kcn: (K, C, N) in the reference basis.  values: the operand's values (CSR order) as an autograd
-    tensor when they are learnable (nn._EdgeBase builds it from edge_weight)."""
+    tensor when they are learnable (nn._EdgeBase builds it from edge_weight).  The weight's dtype picks the path: float32, or bfloat16
+    (cheb_layer_bf16); any other is a TgcnError."""
+    if param_dtype(weight_kcn, bias, "cheb_layer") == BF16:
+        return cheb_layer_bf16(op, x3, weight_kcn, bias, bias_kind, mode, values)
     x3, weight_kcn = _pad_rows(op, x3, weight_kcn, mode)
     x3, bias = _to_operand_labels(op, x3, bias, bias_kind)
     out = ChebLayerFn.apply(x3, weight_kcn, bias, op, mode, bias_kind, torch.is_grad_enabled(), values)
@@ -1125,6 +1130,8 @@ class ChebReluPoolFn(torch.autograd.Function):
 
 def cheb_relu_pool(op, x3, weight_kcn, bias, bias_kind, mode, pool):
     """Differentiable relu + max-pool fused layer; weight in the reference basis."""
+    if param_dtype(weight_kcn, bias, "cheb_relu_pool") == BF16:
+        raise _lib.TgcnError("cheb_relu_pool: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)")
     x3, weight_kcn = _pad_rows(op, x3, weight_kcn, mode)
     if op.perm is not None:
         # pooling groups consecutive vertices of the CALLER's labelling, which are scattered rows of a reordered operand: the
@@ -1177,6 +1184,7 @@ class PoolMaxFn(torch.autograd.Function):
     @_on_device
     def forward(ctx, x, p):
         _lib.require_device(x)
+        ctx.bf16 = x.dtype == BF16       # a max is exact: a bf16 input runs the fp32 kernel and gets its result back in bf16, as torch.max would
         x = x.float().contiguous()       # the kernel reads fp32; the reference's torch.max takes any dtype (gcn.py:246-255)
         q, n, f = x.shape
         out = torch.empty((q, n // p, f), dtype=torch.float32, device=x.device)
@@ -1184,7 +1192,7 @@ class PoolMaxFn(torch.autograd.Function):
         _lib.check(_lib.lib().tgcn_pool_max_f32(_lib.stream_ptr(), _lib.ptr(x), _lib.ptr(out), _lib.ptr(idx), q, n, f, p))
         ctx.save_for_backward(idx)
         ctx.shape, ctx.p = (q, n, f), p
-        return out
+        return out.to(BF16) if ctx.bf16 else out
 
     @staticmethod
     @_on_device
@@ -1192,6 +1200,227 @@ class PoolMaxFn(torch.autograd.Function):
         (idx,) = ctx.saved_tensors
         q, n, f = ctx.shape
         gi = torch.empty((q, n, f), dtype=torch.float32, device=g.device)
-        _lib.check(_lib.lib().tgcn_pool_max_bwd_f32(_lib.stream_ptr(), _lib.ptr(g.contiguous()), _lib.ptr(idx), _lib.ptr(gi),
+        _lib.check(_lib.lib().tgcn_pool_max_bwd_f32(_lib.stream_ptr(), _lib.ptr(g.float().contiguous()), _lib.ptr(idx), _lib.ptr(gi),
                                                     q, n, f, ctx.p))
-        return gi, None
+        return (gi.to(BF16) if ctx.bf16 else gi), None
+
+
+# ----------------------------------------------------------------------------------------- bfloat16 layers
+BF16 = torch.bfloat16
+
+
+def param_dtype(weight, bias, what):
+    """The compute dtype a layer's parameters pick: float32 (the fp32 path) or bfloat16 (cheb_layer_bf16).  Any other dtype, or a weight
+    and a bias of two dtypes, is refused here, before anything launches (the kernels would read the buffers as something they are not)."""
+    wd = weight.dtype
+    if wd not in (torch.float32, BF16):
+        raise _lib.TgcnError("%s: parameters of dtype %s are not supported (float32, or bfloat16 for the bf16 path)" % (what, wd))
+    if bias is not None and bias.dtype != wd:
+        raise _lib.TgcnError("%s: weight is %s but bias is %s -- convert both (module.to(dtype))" % (what, wd, bias.dtype))
+    return wd
+
+
+def _dense_bf16(t):
+    """(nb, rows, C) bf16 view with a contiguous last dim -> tgcn_dense (strides in elements)"""
+    assert t.dim() == 3 and t.dtype == BF16 and (t.shape[2] == 1 or t.stride(2) == 1), (t.shape, t.stride())
+    return _lib.DenseStruct(t.data_ptr(), int(t.stride(0)), int(t.stride(1)))
+
+
+def _aligned16_bf16(C_row, *tensors):
+    ok = C_row % 8 == 0
+    for t in tensors:
+        if t is not None:
+            ok = ok and t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) % 8 == 0
+    return ok
+
+
+def schedule_for_bf16(op, C_row, aligned16):
+    """The schedule of a bf16 row of C_row elements: with 16-byte lanes it has the lane shape of an fp32 row of C_row/2 floats, otherwise
+    of an unaligned fp32 row of C_row (tgcn_csr_hop_bf16; the operand's schedule cache keys on lanes per row)."""
+    return op.schedule_for(C_row // 2, True) if aligned16 else op.schedule_for(C_row, False)
+
+
+@_on_device
+def csr_hop_bf16(op, x, z=None, alpha=1.0, beta=0.0, out=None, z2=None, gamma=0.0):
+    """csr_hop on bf16 rows (tgcn_csr_hop2_bf16): y = alpha * L x + beta * z (+ gamma * z2), fp32 sums, y rounded once to bf16."""
+    _lib.require_device(x, z, z2)
+    L = _lib.lib()
+    assert x.dim() == 3 and x.dtype == BF16 and x.shape[1] == op.n_cols, (x.shape, x.dtype, op.n_cols)
+    nb, _, Crow = x.shape
+    y = torch.empty((nb, op.n, Crow), dtype=BF16, device=x.device) if out is None else out
+    for t in (y, z, z2):
+        assert t is None or (tuple(t.shape) == (nb, op.n, Crow) and t.dtype == BF16), (t.shape, t.dtype)
+    al = _aligned16_bf16(Crow, x, z, y, z2)
+    nb_max = 65535 // max(1, -(-Crow // (512 if al else 64)))
+    if nb > nb_max:
+        for b0 in range(0, nb, nb_max):
+            sl = slice(b0, min(nb, b0 + nb_max))
+            csr_hop_bf16(op, x[sl], None if z is None else z[sl], alpha, beta, y[sl], None if z2 is None else z2[sl], gamma)
+        return y
+    sched = schedule_for_bf16(op, Crow, al)
+    ws = _workspace(L.tgcn_csr_hop_bf16_workspace_bytes(C.byref(sched.struct), nb, Crow, 1 if al else 0), x.device, floor=16)
+    X, Y = _dense_bf16(x), _dense_bf16(y)
+    Z = _dense_bf16(z) if z is not None else None
+    Z2 = _dense_bf16(z2) if z2 is not None else None
+    _lib.check(L.tgcn_csr_hop2_bf16(_lib.stream_ptr(), C.byref(op.struct), C.byref(sched.struct), nb, Crow, C.byref(X),
+                                    C.byref(Z) if Z is not None else None, float(alpha), float(beta),
+                                    C.byref(Z2) if Z2 is not None else None, float(gamma), C.byref(Y), None, _lib.ptr(ws), ws.numel()))
+    return y
+
+
+@_on_device
+def cheb_project_bf16(terms, W, bias, bias_kind, n_vertices, out_dtype=BF16, bias_cols=0, interleave=1):
+    """out = sum_t terms[t] @ W[t] + bias (tgcn_cheb_project_bf16): terms: list of (M, Kc) bf16 with contiguous rows, W: (T, Kc, N) bf16, bias
+    fp32 / bf16 on the first bias_cols columns (0: all); interleave as in cheb_project.  -> (M, N) in out_dtype (fp32, or rounded once to bf16)."""
+    _lib.require_device(W, bias, *terms)
+    L = _lib.lib()
+    T = len(terms)
+    M, Kc = terms[0].shape
+    N = W.shape[-1]
+    W = W.reshape(T * Kc, N).contiguous()
+    dt = out_dtype if T <= 32 else torch.float32       # more than 32 terms: fp32 partial sums across the chunks, one rounding at the end
+    out = torch.empty((M, N), dtype=dt, device=W.device)
+    b = bias.contiguous() if bias is not None else None
+    bdt = _lib.DTYPE_BF16 if (b is not None and b.dtype == BF16) else _lib.DTYPE_F32
+    for t0 in range(0, T, 32):
+        nt = min(32, T - t0)
+        last = t0 + nt >= T
+        a = (C.c_void_p * nt)(*[terms[t0 + i].data_ptr() for i in range(nt)])
+        lda = (C.c_int64 * nt)(*[terms[t0 + i].stride(0) for i in range(nt)])
+        _lib.check(L.tgcn_cheb_project_bf16(_lib.stream_ptr(), M, Kc, N, nt, a, lda, _lib.ptr(W[t0 * Kc:]), _lib.ptr(b) if last else None,
+                                            bias_kind if last else 0, bdt, bias_cols, n_vertices, interleave, 1 if t0 > 0 else 0, _lib.ptr(out), N,
+                                            _lib.DTYPE_BF16 if dt == BF16 else _lib.DTYPE_F32))
+    return out if dt == out_dtype else out.to(out_dtype)
+
+
+@_on_device
+def cheb_wgrad_bf16(terms, g2d):
+    """dW[t] = terms[t]^T @ g2d -> (T, Kc, N) fp32 (tgcn_cheb_wgrad_bf16); terms: list of (M, Kc) bf16 with contiguous rows, g2d: (M, N) bf16."""
+    _lib.require_device(g2d, *terms)
+    L = _lib.lib()
+    T = len(terms)
+    M, Kc = terms[0].shape
+    N = g2d.shape[1]
+    dW = torch.empty((T, Kc, N), dtype=torch.float32, device=g2d.device)
+    for t0 in range(0, T, 32):
+        nt = min(32, T - t0)
+        ws = _workspace(L.tgcn_cheb_wgrad_workspace_bytes(M, Kc, N, nt), g2d.device, floor=16)
+        a = (C.c_void_p * nt)(*[terms[t0 + i].data_ptr() for i in range(nt)])
+        lda = (C.c_int64 * nt)(*[terms[t0 + i].stride(0) for i in range(nt)])
+        _lib.check(L.tgcn_cheb_wgrad_bf16(_lib.stream_ptr(), M, Kc, N, nt, a, lda, _lib.ptr(g2d), g2d.stride(0),
+                                          _lib.ptr(dW[t0:]), _lib.ptr(ws), ws.numel()))
+    return dW
+
+
+def _working_weight_bf16(fold, W):
+    """the bf16 weight in the kernels' basis: the fold of the dense-L classes (coefficients +-1 / +-2) runs in fp32 on the upcast weight and
+    is rounded to bf16 once"""
+    return fold_weight(fold, W.float()).to(BF16) if fold is not None else W
+
+
+def _basis_bf16(op, x3, K, mode):
+    """the K terms of the layer's basis on bf16 rows, one bf16 hop each: monomials L^k x (MODE_POWER: the basis of the folded weight),
+    Chebyshev T_k x (MODE_CHEBYSHEV); term 0 is x3"""
+    terms = [x3]
+    for k in range(1, K):
+        if mode == MODE_POWER or k == 1:
+            terms.append(csr_hop_bf16(op, terms[k - 1]))
+        else:
+            terms.append(csr_hop_bf16(op, terms[k - 1], z=terms[k - 2], alpha=2.0, beta=-1.0))
+    return terms
+
+
+def _forward_pf_bf16(op, x3, Wt, b, bias_kind, mode):
+    """project-first form on a bf16 layer: Z = x . [W_0 | ... | W_{K-1}] in fp32 (bias on Z_0), the fp32 Horner / Clenshaw hops on the
+    N-wide rows, one rounding"""
+    q, n, Crow = x3.shape
+    K, _, N = Wt.shape
+    Wcat = weight_layout(Wt.float(), 0).to(BF16)                       # (C, K*N): a re-layout of bf16 values, exact
+    Z = cheb_project_bf16([x3.view(q * n, Crow)], Wcat.view(1, Crow, K * N), b, bias_kind, n, out_dtype=torch.float32,
+                          bias_cols=N).view(q, n, K * N)
+    return _adjoint_hops(op, [Z[:, :, k * N:(k + 1) * N] for k in range(K)], mode).to(BF16)
+
+
+class ChebLayerBf16Fn(torch.autograd.Function):
+    """The layer with bf16 parameters: bf16 tensors, fp32 sums, each rounding point once (DESIGN.md "bf16 layers").  Paths (_layer_path):
+    "small" -- the fp32 one-launch kernels on the upcast operands, output rounded; "project_first" -- _forward_pf_bf16; otherwise the bf16
+    hops (full size, layout 0: a compacted bf16 layer is out of scope) and tgcn_cheb_project_bf16.  Backward: dW = basis^T g on the bf16
+    matrix pipe (the kept basis, or recomputed with the bf16 hop), fold transposed in fp32, rounded; dx = the layer on (L^T, g, W^T) with
+    fp32 adjoint hops on the fp32 output of the bf16 projection, rounded; the bias gradient is reduced in fp32.  The small path's backward
+    is the fp32 layer_backward on the upcast operands, each gradient rounded."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, x3, W, bias, op, mode, bias_kind, grad_mode=True):
+        x3 = x3.to(BF16).contiguous()
+        W = W.contiguous()
+        b = bias.to(BF16).contiguous() if bias is not None else None
+        K, Crow, N = W.shape
+        q, n, _ = x3.shape
+        fold = _power_fold(mode, W)
+        path = _layer_path(op, q, n, Crow, N, K, mode, compact=False)
+        ctx.basis = None
+        if path.kind == "small":
+            out = cheb_forward_small(op, x3.float(), W.float(), fold, None if b is None else b.float(), bias_kind, mode).to(BF16)
+        else:
+            Wt = _working_weight_bf16(fold, W)
+            if path.kind == "project_first":
+                out = _forward_pf_bf16(op, x3, Wt, b, bias_kind, mode)
+            else:
+                terms = _basis_bf16(op, x3, K, mode)
+                out = cheb_project_bf16([t.view(q * n, Crow) for t in terms], Wt, b, bias_kind, n).view(q, n, N)
+                if grad_mode and ctx.needs_input_grad[1] and K * x3.numel() * 2 <= KEEP_BASIS_BYTES:
+                    ctx.basis = terms
+        ctx.save_for_backward(x3, W)
+        ctx.op, ctx.mode, ctx.bias_kind, ctx.fold, ctx.path = op, mode, bias_kind, fold, path
+        ctx.bias_shape = None if bias is None else bias.shape
+        return out
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, g):
+        x3, W = ctx.saved_tensors
+        needs = ctx.needs_input_grad
+        op, mode, fold = ctx.op, ctx.mode, ctx.fold
+        K, Crow, N = W.shape
+        q, n, _ = x3.shape
+        rnd = lambda t: None if t is None else t.to(BF16)
+        if ctx.path.kind == "small":
+            gx, gW, gb = layer_backward(op, mode, fold, x3.float(), W.float(), g.float(), ctx.bias_kind, ctx.bias_shape, needs[:3])
+            return rnd(gx), rnd(gW), rnd(gb), None, None, None, None
+        g = g.to(BF16).contiguous()
+        gx = gW = None
+        if needs[1]:
+            terms = ctx.basis if ctx.basis is not None else _basis_bf16(op, x3, K, mode)
+            dW = cheb_wgrad_bf16([t.view(q * n, Crow) for t in terms], g.view(q * n, N))
+            gW = (fold_weight(fold, dW, transpose=True) if fold is not None else dW).to(BF16)
+        ctx.basis = None
+        if needs[0]:
+            Wt = _working_weight_bf16(fold, W)
+            WT = weight_layout(Wt.float(), 2).to(BF16)                  # (N, K*C)
+            Gall = cheb_project_bf16([g.view(q * n, N)], WT.view(1, N, K * Crow), None, BIAS_NONE, n,
+                                     out_dtype=torch.float32).view(q, n, K * Crow)
+            gx = _adjoint_hops(op.transpose(), [Gall[:, :, k * Crow:(k + 1) * Crow] for k in range(K)], mode).to(BF16)
+        gb = rnd(_bias_grad(g.float(), ctx.bias_kind, ctx.bias_shape, needs[2]))
+        return gx, gW, gb, None, None, None, None
+
+
+def _pad_rows_bf16(op, x3, weight_kcn, mode):
+    """_pad_rows for bf16 rows: on the bf16 hops path rows of C >= 7 elements that are not a multiple of 8 get zero channels up to one
+    (16-byte lanes; zero rows in the weight)"""
+    K, C, N = weight_kcn.shape
+    if C % 8 == 0 or C < 7 or _layer_path(op, x3.shape[0], x3.shape[1], C, N, K, mode, compact=False).kind != "hops":
+        return x3, weight_kcn
+    pad = (-C) % 8
+    return torch.nn.functional.pad(x3, (0, pad)), torch.nn.functional.pad(weight_kcn, (0, 0, 0, pad))
+
+
+def cheb_layer_bf16(op, x3, weight_kcn, bias, bias_kind, mode, values=None):
+    """cheb_layer with bfloat16 parameters: x is cast to bf16 once, output and gradients are bf16 (ChebLayerBf16Fn)."""
+    if values is not None:
+        raise _lib.TgcnError("cheb_layer: learnable edge weights (edge_weight.requires_grad) are not supported with bfloat16 parameters")
+    x3 = x3.to(BF16)
+    x3, weight_kcn = _pad_rows_bf16(op, x3, weight_kcn, mode)
+    x3, bias = _to_operand_labels(op, x3, bias, bias_kind)        # (the relabelling kernel is fp32: bf16 values pass through it exactly)
+    out = ChebLayerBf16Fn.apply(x3, weight_kcn, bias, op, mode, bias_kind, torch.is_grad_enabled())
+    return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm).to(BF16)

@@ -75,6 +75,15 @@ def _np_fingerprint(L):
     return _fingerprint(L)
 
 
+def _compute_dtype(module, edge_weight=None):
+    """The dtype a module computes in, from its parameters (F.param_dtype): float32, or bfloat16 when the weight is bf16 -- the input is then
+    cast to bf16 once.  Refuses any other dtype, mixed weight / bias dtypes and, for bf16, learnable edge weights, before anything launches."""
+    dt = F.param_dtype(module.weight, module.bias, type(module).__name__)
+    if dt == torch.bfloat16 and edge_weight is not None and edge_weight.requires_grad:
+        raise _lib.TgcnError("%s: learnable edge weights (edge_weight.requires_grad) are not supported with bfloat16 parameters" % type(module).__name__)
+    return dt
+
+
 def _tensor_key(t):
     return None if t is None else (t.data_ptr(), t._version, tuple(t.shape), str(t.device))
 
@@ -126,7 +135,7 @@ class TGCNCheb(_DenseLBase):
         self.reset_parameters()
 
     def _layer_args(self, x):
-        x3 = x.float().contiguous()
+        x3 = x.to(_compute_dtype(self)).contiguous()
         return (self._operand(x3.device), x3, self.weight, self.bias,
                 F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER)
 
@@ -154,10 +163,11 @@ class TGCNCheb_H(_DenseLBase):
         self.reset_parameters()
 
     def _layer_args(self, x):
+        dt = _compute_dtype(self)
         if x.dim() == 3:
             x = x.unsqueeze(3)
         q, n, h, f = x.shape
-        x3 = x.float().reshape(q, n, h * f).contiguous()
+        x3 = x.to(dt).reshape(q, n, h * f).contiguous()
         W = self.weight.reshape(self.weight.shape[0], h * f, self.out_channels)
         return (self._operand(x3.device), x3, W, self.bias,
                 F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER)
@@ -175,6 +185,8 @@ class TGCNCheb_H(_DenseLBase):
         T-H+1 sliding windows of every recording, (S*(T-H+1), n, g), without materialising the windows
         (load/data_hcp.py:116-154 builds them on the host and the hops then run H times too often).
         in_channels must be 1.  Differentiable: the backward runs the hops once per recording too."""
+        if _compute_dtype(self) != torch.float32:
+            raise _lib.TgcnError("TGCNCheb_H.forward_series: bfloat16 parameters are not supported")
         assert self.in_channels == 1, "forward_series: in_channels must be 1"
         K, H = self.weight.shape[0], self.weight.shape[1]
         W = self.weight.reshape(K, H, self.out_channels)
@@ -200,9 +212,10 @@ class GCNCheb(_DenseLBase):
         self.reset_parameters()
 
     def _layer_args(self, x):
+        dt = _compute_dtype(self)
         if x.dim() == 2:
             x = x.unsqueeze(2)
-        x3 = x.float().contiguous()
+        x3 = x.to(dt).contiguous()
         return (self._operand(x3.device), x3, self.weight, self.bias,
                 F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_POWER)
 
@@ -366,10 +379,11 @@ class ChebConv(_EdgeBase):
         self.reset_parameters()
 
     def _layer_args(self, x, edge_index, edge_weight=None):
+        dt = _compute_dtype(self, edge_weight)
         op = self._operand(x, edge_index, edge_weight)
         if x.dim() < 3:
             x = x.unsqueeze(-1)
-        return (op, x.float().contiguous(), self.weight, self.bias,
+        return (op, x.to(dt).contiguous(), self.weight, self.bias,
                 F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV)
 
     def forward(self, x, edge_index, edge_weight=None):
@@ -392,12 +406,13 @@ class ChebTimeConv(_EdgeBase):
         self.reset_parameters()
 
     def _layer_args(self, x, edge_index, edge_weight=None):
+        dt = _compute_dtype(self, edge_weight)
         op = self._operand(x, edge_index, edge_weight)
         if x.dim() < 4:
             x = x.unsqueeze(-1)
         q, n, h, f = x.shape
         W = self.weight.reshape(self.weight.shape[0], h * f, self.out_channels)
-        return (op, x.float().reshape(q, n, h * f).contiguous(), W, self.bias,
+        return (op, x.to(dt).reshape(q, n, h * f).contiguous(), W, self.bias,
                 F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV)
 
     def forward(self, x, edge_index, edge_weight=None):
@@ -410,6 +425,8 @@ def cheb_relu_pool(layer, x, *graph_args, pool=4):
     """gcn_pool_4(F.relu(layer(x, ...)))  (pool=4)  /  gcn_pool(F.relu(layer(x, ...)))  (pool=2)  in one fused op:
     additive API for the pattern of examples/pytorch_based/pytorch_hcp_tgcn.py:134-141 and pytorch_mnist_gcn.py.
     `layer` is any of the five modules above; graph_args are ChebConv's (edge_index[, edge_weight])."""
+    if _compute_dtype(layer) != torch.float32:
+        raise _lib.TgcnError("cheb_relu_pool: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)")
     if len(graph_args) > 1 and graph_args[1] is not None and graph_args[1].requires_grad:
         # learnable edge weights: the gradient w.r.t. them belongs to the layer function; relu + pool as their own pass behind it
         return F.ReluPoolFn.apply(layer(x, *graph_args), pool)
