@@ -30,7 +30,7 @@ extern "C" {
 #define TGCN_ERR_WORKSPACE (-3)   /* caller workspace too small */
 #define TGCN_ERR_UNSUPPORTED (-4) /* shape outside what the kernels were built for */
 
-#define TGCN_ABI_VERSION 7
+#define TGCN_ABI_VERSION 8
 
 /* One stored entry of the sparse operand: 8 bytes, read with a single load. */
 typedef struct tgcn_edge {
@@ -179,8 +179,7 @@ void tgcn_sched_destroy(tgcn_sched* s);
 #define TGCN_PROF_SMALL 4
 #define TGCN_PROF_WGRAD 5
 #define TGCN_PROF_SMALL_BASIS 6
-#define TGCN_PROF_HOP_LONG 7     /* hop_kernel over the rows above the threshold only (last hop fused into the projection) */
-#define TGCN_PROF_PROJECT_GATHER 8 /* projection with the last hop's short rows gathered inside (project_x3_gather_kernel) */
+/* 7 and 8 are not used: they named the launches of the fused last hop, removed in ABI v8 */
 int tgcn_profile_start(int32_t capacity);
 int tgcn_profile_stop(int32_t* kinds, float* ms, int32_t capacity, int32_t* count);
 
@@ -189,7 +188,7 @@ int tgcn_profile_stop(int32_t* kinds, float* ms, int32_t capacity, int32_t* coun
  * tgcn_profile_*): a switch changes the launches the calling thread issues afterwards and nothing else -- the threads of an
  * nn.DataParallel process (examples/pytorch_based/pytorch_hcp_tgcn.py:270-273) and the autograd engine's workers keep the defaults,
  * which are what ships; the library holds no process-global mutable state, only caches of immutable per-device facts
- * (CU count, the LDS attribute of a kernel, one helper stream per device).  Same arithmetic, another kernel; TGCN_ERR_INVALID for unknown keys.
+ * (CU count, the LDS attribute of a kernel).  Same arithmetic, another kernel; TGCN_ERR_INVALID for unknown keys.
  *   "hop_variant"     0 shipped hop kernel; 1.. alternative unroll / row-interleave shapes of hop.h
  *   "hop_xcd_remap"   1 (default): each XCD gets a contiguous range of row blocks; 0: row blocks round robin over the XCDs
  *   "hop_seg_remap"   1: each XCD gets a contiguous range of the column-ordered segment blocks; 0 (default): round robin
@@ -202,10 +201,6 @@ int tgcn_profile_stop(int32_t* kinds, float* ms, int32_t capacity, int32_t* coun
  *                     4 exact-fp32 auto; 5 vector-ALU narrow kernel wherever it applies
  *   "x3_form"         2 (default) bf16x3 with A fragments from registers for >= 96 output columns; 1 both operands via LDS
  *   "x3_tail"         1 (default): the rows of a thinly filled last round of the wide bf16x3 kernel go out as 128-row tiles; 0: never
- *   "fuse_last_hop"   1: compacted forward with the last hop's rows of <= 32 entries gathered inside the projection kernel (the last hop tensor is
- *                     neither written nor read for them; the hop launch covers the longer rows only); bitwise the same result, measured slower
- *                     on cfg5 (290 -> 329 ms per forward), so default 0: hop + projection
- *   "overlap"         1: projection of pass i on a side stream under the hops of pass i+1 (default 0)
  *   "small_dense"     dense small operands: 2 (default) bf16x3 on the matrix pipe when the batch fills the chip, 1 exact
  *                     fp32 MFMA only, 0 vector-ALU one-launch kernels
  *   "small_narrow"    0: C <= 4 inputs use the output-side one-launch kernel (default 1: input-side recursion) */
@@ -355,9 +350,7 @@ int tgcn_cheb_forward_f32(void* stream, const tgcn_csr* A, const tgcn_csr_sched*
  * have entries only (compact ids = rank among them):
  *   A_first  n_c rows, columns in the caller's labels (hop 1 gathers from x);  A_rest  the same rows and entry order with
  *            columns in compact ids, entries whose column is an empty vertex pointing at the zero row n_c  (hops 2..K-1);
- *   rows[n_c] / empty_rows[n_empty]  caller's label of every compact / empty row, ascending;  sched: shared by both operands;
- *   compact_id[n] (nullable)  compact id of every vertex, n_c for the empty ones: lets the projection run as ONE launch over all
- *            vertices in order (tgcn_set_tuning("compact_proj", 1)) instead of one launch per row class.
+ *   rows[n_c] / empty_rows[n_empty]  caller's label of every compact / empty row, ascending;  sched: shared by both operands.
  * The projection reads x, bias and writes out through the row maps; hop tensors, hop writes and four of the five projection
  * terms shrink by n_empty / n.  Bitwise equal to tgcn_cheb_forward_f32 (layout 0) on the same operand.  K >= 2. */
 size_t tgcn_cheb_forward_compact_workspace_bytes(const tgcn_csr_sched* sched, int32_t K, int64_t q, int64_t n_c, int32_t C,
@@ -365,7 +358,7 @@ size_t tgcn_cheb_forward_compact_workspace_bytes(const tgcn_csr_sched* sched, in
 int tgcn_cheb_forward_compact_f32(void* stream, const tgcn_csr* A_first, const tgcn_csr* A_rest, const tgcn_csr_sched* sched,
                                   int32_t K, int64_t q, int64_t n, int32_t C, int32_t N, const float* x, const float* W,
                                   const float* bias, int32_t bias_kind, float* out, const int32_t* rows, const int32_t* empty_rows,
-                                  int64_t n_empty, const int32_t* compact_id, int64_t q_chunk, void* workspace, size_t workspace_bytes);
+                                  int64_t n_empty, int64_t q_chunk, void* workspace, size_t workspace_bytes);
 
 /* The compacted layer in general form (ABI v6): BOTH recurrences, and optionally the hop tensors handed back to the caller.
  *   mode 0  as tgcn_cheb_forward_compact_f32 (which is this function with mode 0, W_left = NULL, keep_terms = NULL).
@@ -385,7 +378,7 @@ size_t tgcn_cheb_compact_layer_workspace_bytes(const tgcn_csr_sched* sched, int3
 int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgcn_csr* A_rest, const tgcn_csr_sched* sched, int32_t mode,
                                 int32_t K, int64_t q, int64_t n, int32_t C, int32_t N, const float* x, const float* W, const float* W_left,
                                 const float* bias, int32_t bias_kind, float* out, const int32_t* rows, const int32_t* empty_rows,
-                                int64_t n_empty, const int32_t* compact_id, int64_t q_chunk, float* keep_terms, void* workspace,
+                                int64_t n_empty, int64_t q_chunk, float* keep_terms, void* workspace,
                                 size_t workspace_bytes);
 
 /* "Project first" form of the same layer for wide inputs and narrow outputs (N well below C = H*f, e.g.

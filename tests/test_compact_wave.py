@@ -111,13 +111,9 @@ def test_compact_forward_equals_plain_forward(q, C, N, K, bias_kind, symmetric, 
         plain = F.cheb_forward_raw(op, x, W2, bias, bias_kind, F.MODE_POWER, K, layout=0, q_chunk=1)
         comp = F.cheb_forward_compact(plan, x, W2, bias, bias_kind, K, q_chunk=1)
         comp2 = F.cheb_forward_compact(plan, x, W2, bias, bias_kind, K, q_chunk=2)
-        _lib.check(_lib.lib().tgcn_set_tuning(b"compact_proj", 1))      # ONE projection over all vertices, hop tensors through the id map
-        comp3 = F.cheb_forward_compact(plan, x, W2, bias, bias_kind, K, q_chunk=2)
     finally:
         _lib.check(_lib.lib().tgcn_set_tuning(b"project_variant", 0))
-        _lib.check(_lib.lib().tgcn_set_tuning(b"compact_proj", 0))
-    assert torch.equal(plain, comp) and torch.equal(comp, comp2) and torch.equal(comp, comp3)
-    assert np.array_equal(plan.cid.cpu().numpy()[plan.rows.cpu().numpy()], np.arange(plan.n_c)) and (plan.cid[plan.empty.long()] == plan.n_c).all()
+    assert torch.equal(plain, comp) and torch.equal(comp, comp2)
     # default kernels, through the dispatcher, against the C restatement of the reference's algorithm (unfolded weights)
     out = F.layer_forward(op, x, W, F.power_fold_matrix(K, x.device) if K > 2 else None, bias, bias_kind, F.MODE_POWER)
     rowptr = op.rowptr.cpu().numpy()
@@ -398,11 +394,10 @@ def test_compact_layers_equal_uncompacted_layers(cls, q, f, g_out, K, symmetric,
 
 @pytest.mark.parametrize("symmetric", [True, False], ids=["symmetric", "entries-into-empty-rows"])
 @pytest.mark.parametrize("q,C,N,K,bias_kind,q_chunk", [(3, 64, 64, 5, 2, 1), (4, 64, 64, 3, 2, 2), (2, 64, 32, 2, 1, 1), (1, 32, 16, 4, 0, 1), (2, 128, 64, 3, 2, 2)])
-def test_last_hop_fused_into_the_projection_is_bitwise_the_unfused_forward(q, C, N, K, bias_kind, q_chunk, symmetric, gpu_device, monkeypatch):
-    """the compacted driver gathers the rows of at most 32 entries of the LAST hop inside the projection
-    (project_x3_gather_kernel) and runs the hop launch for the longer rows only; the last hop tensor is not written for the others.
-    Same per-row arithmetic (stored-order fmaf chain, same bf16x3 split and MFMA order) => bitwise the result of hop + projection
-    (tgcn_set_tuning("fuse_last_hop", 0)), and within 1e-5 of the oracle.  K = 2: the fused hop gathers from x through the caller-label operand."""
+def test_compact_forward_with_long_rows_through_the_bf16x3_projection(q, C, N, K, bias_kind, q_chunk, symmetric, gpu_device, monkeypatch):
+    """The compacted driver on a schedule that has segments and long rows, its projection forced onto the bf16x3 kernel: one full hop launch
+    per hop and time step (no other hop kind), and the result within 1e-5 of the fp64 chain.  K = 2: the only hop gathers from x through the
+    caller-label operand."""
     from tgcn_amd import functional as F, graph, _lib
     monkeypatch.setattr(graph, "COMPACT_MIN_ROWS", 1)
     n = 40000
@@ -412,7 +407,7 @@ def test_last_hop_fused_into_the_projection_is_bitwise_the_unfused_forward(q, C,
     plan = op.compact_plan()
     assert plan is not None
     sched = plan.schedule_for(C, True)
-    assert sched.nseg > 0 and sched.nlong > 0           # rows above the threshold exist: they take the hop launch, the others the gather
+    assert sched.nseg > 0 and sched.nlong > 0           # rows above the threshold exist: segments and the long-row fix-up run
     x = _dev(rng.standard_normal((q, n, C)).astype(np.float32))
     W = _dev((rng.standard_normal((K, C, N)) / np.sqrt(K * C)).astype(np.float32))
     bias = None if bias_kind == 0 else _dev(rng.standard_normal((N,) if bias_kind == 1 else (n, N)).astype(np.float32))
@@ -420,19 +415,14 @@ def test_last_hop_fused_into_the_projection_is_bitwise_the_unfused_forward(q, C,
     L = _lib.lib()
     _lib.check(L.tgcn_set_tuning(b"project_variant", 3))          # the bf16x3 kernel at this size too (auto takes it from 8192 rows)
     try:
-        outs = []
-        for fuse in (1, 0):
-            _lib.check(L.tgcn_set_tuning(b"fuse_last_hop", fuse))
-            _lib.profile_start(256)
-            outs.append(F.cheb_forward_compact(plan, x, W2, bias, bias_kind, K, q_chunk=q_chunk))
-            prof = _lib.profile_stop(256)
-            full, long_only, gathered = (sum(1 for kind, _ in prof if kind == k) for k in (0, 7, 8))
-            # fused: one hop launch per time step covers the rows above the threshold only, and a projection per pass gathers the rest
-            assert (full, long_only) == ((q * (K - 2), q) if fuse else (q * (K - 1), 0)), (fuse, full, long_only)
-            assert gathered == ((q + q_chunk - 1) // q_chunk if fuse else 0)
+        _lib.profile_start(256)
+        out = F.cheb_forward_compact(plan, x, W2, bias, bias_kind, K, q_chunk=q_chunk)
+        prof = _lib.profile_stop(256)
+        full, kind7, kind8 = (sum(1 for kind, _ in prof if kind == k) for k in (0, 7, 8))
+        # one hop launch per hop and time step covers every row; the retired kinds 7 / 8 are never recorded
+        assert (full, kind7, kind8) == (q * (K - 1), 0, 0), (full, kind7, kind8)
     finally:
         L.tgcn_reset_tuning()
-    assert torch.equal(outs[0], outs[1])
     Ls = op.to_scipy()
     P = [x.cpu().numpy()]
     for _ in range(1, K):
@@ -440,4 +430,4 @@ def test_last_hop_fused_into_the_projection_is_bitwise_the_unfused_forward(q, C,
     ref = sum(P[k].astype(np.float64) @ W[k].cpu().numpy().astype(np.float64) for k in range(K))
     if bias is not None:
         ref = ref + bias.cpu().numpy()
-    assert rel_err(outs[0].cpu().numpy(), ref) <= TOL
+    assert rel_err(out.cpu().numpy(), ref) <= TOL

@@ -44,7 +44,7 @@ class _Plan:
     def __init__(self, n, n_c, n_empty):
         self.n, self.n_c, self.n_empty = n, n_c, n_empty
         self.first, self.rest = _Op(n_c, 4 * n_c, n_cols=n), _Op(n_c, 4 * n_c, n_cols=n_c + 1)
-        self.rows = self.cid = torch.zeros(n_c, dtype=torch.int32)
+        self.rows = torch.zeros(n_c, dtype=torch.int32)
         self.empty = torch.zeros(n_empty, dtype=torch.int32)
         self.q_chunk_cache = {}
 

@@ -80,10 +80,9 @@ def test_stream_kernel_is_the_shipped_choice_for_the_compact_forward_shapes(gpu_
     assert rel_err(out.cpu().numpy(), ref) <= TOL
 
 
-def test_stream_kernel_with_the_map_on_the_terms_only(gpu_device, monkeypatch):
-    """tgcn_set_tuning("compact_proj", 1): ONE projection launch over all vertices in order -- output and bias rows are the tile rows, the
-    hop tensors are read through the vertex -> compact-id map (empty vertices point at the zero row): the kProjMapTermsOnly form of the row map,
-    which the streaming kernel takes from 32768 rows.  Against the two-launch default and against float64."""
+def test_compact_forward_is_two_row_mapped_launches_through_the_streaming_kernel(gpu_device, monkeypatch):
+    """The compacted forward of a pass projects in two row-mapped launches -- the compact rows with all K terms, the empty rows with x alone --
+    which the streaming kernel takes from 32768 rows.  Against float64."""
     import scipy.sparse as sp
     from tgcn_amd import functional as F, graph, _lib
     monkeypatch.setattr(graph, "COMPACT_MIN_ROWS", 1)
@@ -106,12 +105,8 @@ def test_stream_kernel_with_the_map_on_the_terms_only(gpu_device, monkeypatch):
         P.append(np.stack([Ls @ P[-1][b] for b in range(q)]))
     ref = sum(P[k] @ W[k].astype(np.float64) for k in range(K)) + bias
     W2 = _dev(W.reshape(K * C, N))
-    outs = {}
-    for mode in (0, 1):
-        _lib.check(_lib.lib().tgcn_set_tuning(b"compact_proj", mode))
-        _lib.profile_start(256)
-        outs[mode] = F.cheb_forward_compact(plan, _dev(x), W2, _dev(bias), 2, K, q_chunk=q).cpu().numpy()
-        prof = _lib.profile_stop(256)
-        assert sum(1 for kind, _ in prof if kind == 2) == (1 if mode else 2)
-        assert rel_err(outs[mode], ref) <= TOL
-    assert rel_err(outs[1], outs[0]) <= 2e-6
+    _lib.profile_start(256)
+    out = F.cheb_forward_compact(plan, _dev(x), W2, _dev(bias), 2, K, q_chunk=q).cpu().numpy()
+    prof = _lib.profile_stop(256)
+    assert sum(1 for kind, _ in prof if kind == 2) == 2
+    assert rel_err(out, ref) <= TOL

@@ -110,11 +110,11 @@ SIGNATURES = {
     "tgcn_cheb_forward_compact_workspace_bytes": (C.c_size_t, [C.POINTER(SchedStruct), C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64]),
     "tgcn_cheb_forward_compact_f32": (C.c_int, [_P, C.POINTER(CsrStruct), C.POINTER(CsrStruct), C.POINTER(SchedStruct), C.c_int32,
                                                 C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, _P,
-                                                C.c_int64, _P, C.c_int64, _P, C.c_size_t]),
+                                                C.c_int64, C.c_int64, _P, C.c_size_t]),
     "tgcn_cheb_compact_layer_workspace_bytes": (C.c_size_t, [C.POINTER(SchedStruct), C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32]),
     "tgcn_cheb_compact_layer_f32": (C.c_int, [_P, C.POINTER(CsrStruct), C.POINTER(CsrStruct), C.POINTER(SchedStruct), C.c_int32, C.c_int32,
                                               C.c_int64, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, _P,
-                                              C.c_int64, _P, C.c_int64, _P, _P, C.c_size_t]),
+                                              C.c_int64, C.c_int64, _P, _P, C.c_size_t]),
     "tgcn_cheb_forward_small_supported": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "tgcn_cheb_basis_small_supported": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "tgcn_cheb_forward_small_pool_supported": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
@@ -138,7 +138,7 @@ SIGNATURES = {
 }
 
 _lib = None
-ABI_VERSION = 7      # include/tgcn_hip.h: TGCN_ABI_VERSION
+ABI_VERSION = 8      # include/tgcn_hip.h: TGCN_ABI_VERSION
 DTYPE_F32, DTYPE_BF16 = 0, 1     # TGCN_DTYPE_* of the bf16 entries' dtype flags
 
 

@@ -98,39 +98,10 @@ thread_local TuneInt g_hop_mix{0};          // hop_kernel: row blocks dealt even
 thread_local TuneInt g_hop_stream{1};       // hop_kernel: non-temporal entries / stores / partial rows when the output exceeds the Infinity Cache (0: never)
 thread_local TuneInt g_hop_lds_pad{0};      // hop_kernel: bytes of unused dynamic LDS per workgroup (occupancy limiter, developer A/B)
 thread_local TuneInt g_proj_variant{0};     // 1: force the streaming-W kernel
-thread_local TuneInt g_overlap{0};          // layer driver: projection of pass i on a side stream under the hops of pass i+1
 thread_local TuneInt g_x3_form{2};          // bf16x3 projection, aligned operands, >= 96 output columns: 2 = A fragments from registers (+20 %), 1 = both operands through LDS
-thread_local TuneInt g_compact_proj{0};     // compacted forward: 0 two row-mapped projections (compact rows, empty rows), 1 one projection over all vertices in order
-thread_local TuneInt g_fuse_last{0};        // compacted forward: 1 = last hop's short rows gathered inside the projection (project_x3_gather_kernel), bitwise the same
-                                            // result; measured SLOWER (cfg5 290 -> 329 ms: the gathers want the hop kernel's occupancy), so 0 = hop + projection ships
 thread_local TuneInt g_x3_tail{1};          // project_x3v2_kernel: rows of a thinly filled last round as 128-row tiles (0: 256-row tiles throughout)
 thread_local TuneInt g_small_narrow{1};     // C <= 4 inputs of the one-launch path: input-side recursion (0: output-side kernel)
 thread_local TuneInt g_small_dense{2};      // small dense operands: 2 bf16x3 matrix pipe, 1 fp32 matrix pipe, 0 vector-ALU kernels only
-
-struct SideStream { hipStream_t st = nullptr; hipEvent_t hops_done[2] = {nullptr, nullptr}; hipEvent_t proj_done[2] = {nullptr, nullptr}; };
-std::mutex g_side_mu;
-SideStream g_side[16];
-
-// One helper stream + 4 events per device, created on first use and kept for the life of the process.
-SideStream* side_stream() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  std::lock_guard<std::mutex> lk(g_side_mu);
-  SideStream& s = g_side[dev];
-  if (!s.st) {
-    if (hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking) != hipSuccess) { s.st = nullptr; return nullptr; }
-    for (int i = 0; i < 2; ++i) {
-      if (hipEventCreateWithFlags(&s.hops_done[i], hipEventDisableTiming) != hipSuccess ||
-          hipEventCreateWithFlags(&s.proj_done[i], hipEventDisableTiming) != hipSuccess) {
-        (void)hipStreamDestroy(s.st);
-        s.st = nullptr;
-        return nullptr;
-      }
-    }
-  }
-  return &s;
-}
-
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

@@ -54,8 +54,7 @@ int tgcn_abi_version(void) { return TGCN_ABI_VERSION; }
 
 void tgcn_reset_tuning(void) {
   g_hop_variant.store(0); g_hop_remap.store(1); g_hop_seg_remap.store(0); g_hop_mix.store(0); g_hop_stream.store(1); g_hop_lds_pad.store(0);
-  g_proj_variant.store(0); g_small_dense.store(2); g_small_narrow.store(1); g_x3_form.store(2); g_compact_proj.store(0); g_x3_tail.store(1); g_fuse_last.store(0);
-  g_overlap.store(0);
+  g_proj_variant.store(0); g_small_dense.store(2); g_small_narrow.store(1); g_x3_form.store(2); g_x3_tail.store(1);
 }
 
 int tgcn_set_tuning(const char* key, int32_t value) {
@@ -69,10 +68,7 @@ int tgcn_set_tuning(const char* key, int32_t value) {
   if (key && strcmp(key, "small_dense") == 0) { g_small_dense.store(value); return TGCN_OK; }
   if (key && strcmp(key, "small_narrow") == 0) { g_small_narrow.store(value); return TGCN_OK; }
   if (key && strcmp(key, "x3_form") == 0) { g_x3_form.store(value); return TGCN_OK; }
-  if (key && strcmp(key, "compact_proj") == 0) { g_compact_proj.store(value); return TGCN_OK; }
   if (key && strcmp(key, "x3_tail") == 0) { g_x3_tail.store(value != 0); return TGCN_OK; }
-  if (key && strcmp(key, "fuse_last_hop") == 0) { g_fuse_last.store(value != 0); return TGCN_OK; }
-  if (key && strcmp(key, "overlap") == 0) { g_overlap.store(value); return TGCN_OK; }
   TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: unknown key");
 }
 
@@ -117,20 +113,18 @@ int tgcn_csr_hop_f32(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, i
 
 static int hop_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
                     const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
-                    const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes, int long_rows_only, int bf16 = 0);
+                    const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes, int bf16 = 0);
 
 int tgcn_csr_hop2_f32(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
                       const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
                       const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes) {
-  return hop_impl(stream, A, S, nb, C, X, Z, alpha, beta, Z2, gamma, Y, P, workspace, workspace_bytes, 0);
+  return hop_impl(stream, A, S, nb, C, X, Z, alpha, beta, Z2, gamma, Y, P, workspace, workspace_bytes);
 }
 
-// long_rows_only: the rows of more than row_thresh entries only (whole-row wave segments, lane-group segments + fix-up) -- the others are
-// left to the caller (the projection with the fused last hop gathers them itself); the rows it skips are not written.
 // bf16: rows of bf16 elements (tgcn_csr_hop_bf16; strides in elements, hop_geom_bf16), fp32 sums and partial rows.
 static int hop_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
                     const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
-                    const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes, int long_rows_only, int bf16) {
+                    const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes, int bf16) {
   if (!A || !S || !X || !X->ptr) TGCN_FAIL(TGCN_ERR_INVALID, "hop: null operand");
   if (int drc = check_pointer_device(X->ptr, (hipStream_t)stream, "hop")) return drc;
   if ((!Y || !Y->ptr) && (!P || !P->ptr)) TGCN_FAIL(TGCN_ERR_INVALID, "hop: no output");
@@ -177,12 +171,6 @@ static int hop_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, in
     p.mix_period = (mix == 1 || (mix == 0 && S->row_mix)) ? 1 : (mix == 2 ? -1 : 0);
   }
   p.stream_out = !bf16 && ((int64_t)A->n * C * (int64_t)sizeof(float) * nb > ((int64_t)256 << 20)) && g_hop_stream.load();
-  if (long_rows_only) {
-    if (S->nseg == 0) return TGCN_OK;       // no row above the threshold: nothing to do
-    p.nblk = 0;                             // no row blocks: every workgroup of the launch is a segment block
-    p.mix_period = 0;
-    p.long_rows_only = 1;                   // (a FULL hop on a schedule without row blocks is still a TGCN_PROF_HOP record: ADVICE r04)
-  }
   const int gpb = kBlock / g.lpr;
   const int seg_blocks = (S->nseg + gpb - 1) / gpb;
   const dim3 grid((unsigned)(S->nblk + seg_blocks), (unsigned)(nb * g.nchunks));
@@ -201,29 +189,20 @@ size_t tgcn_csr_hop_bf16_workspace_bytes(const tgcn_csr_sched* sched, int32_t nb
 int tgcn_csr_hop_bf16(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
                       const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Y,
                       const tgcn_dense* P, void* workspace, size_t workspace_bytes) {
-  return hop_impl(stream, A, S, nb, C, X, Z, alpha, beta, nullptr, 0.f, Y, P, workspace, workspace_bytes, 0, 1);
+  return hop_impl(stream, A, S, nb, C, X, Z, alpha, beta, nullptr, 0.f, Y, P, workspace, workspace_bytes, 1);
 }
 
 int tgcn_csr_hop2_bf16(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S, int32_t nb, int32_t C,
                        const tgcn_dense* X, const tgcn_dense* Z, float alpha, float beta, const tgcn_dense* Z2, float gamma,
                        const tgcn_dense* Y, const tgcn_dense* P, void* workspace, size_t workspace_bytes) {
-  return hop_impl(stream, A, S, nb, C, X, Z, alpha, beta, Z2, gamma, Y, P, workspace, workspace_bytes, 0, 1);
+  return hop_impl(stream, A, S, nb, C, X, Z, alpha, beta, Z2, gamma, Y, P, workspace, workspace_bytes, 1);
 }
 
 static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const float* const* a,
                         const int64_t* lda, const float* W, const float* bias, int32_t bias_kind,
                         int64_t n_vertices, int64_t interleave, int32_t accumulate, float* out, int64_t ldo,
                         int32_t win_n, int32_t win_t, int32_t bias_cols = -1, const int32_t* rowmap = nullptr, uint32_t mapped = 0,
-                        int32_t nbatch = 1, const int64_t* a_bs = nullptr, int64_t out_bs = 0, int32_t pool = 0, uint8_t* pool_idx = nullptr,
-                        const struct ProjGather* gather = nullptr);
-
-// The last hop fused into the projection (ProjParams.g_*): operand, gather source and the term it produces.
-struct ProjGather {
-  const tgcn_csr* A;      // rows = the projection's tile rows (compact rows), columns index rows of X
-  const float* X;         // the previous hop tensor (row stride = the row length Kc), sample stride xbs floats
-  int64_t xbs;
-  int32_t term, thresh;   // term whose tiles are gathered for rows of at most `thresh` entries
-};
+                        int32_t nbatch = 1, const int64_t* a_bs = nullptr, int64_t out_bs = 0, int32_t pool = 0, uint8_t* pool_idx = nullptr);
 
 // THE dispatch of the projection: which kernel a shape takes.  project_impl launches what this returns and project_pool_fusable asks the
 // same function, so the fused relu + pool epilogue can never be requested from a kernel that does not have it.
@@ -243,8 +222,8 @@ struct ProjChoice {
   bool pool_epilogue;   // the kernel can end in relu + max over consecutive rows (through its vector epilogue)
   int pool_max;         // ... over groups whose size divides this: 16 (rows of a wave's tile in LDS scratch), 4 in the wide bf16x3 kernel (a lane's four accumulator rows)
 };
-// stream_ok: the call has nothing the streaming kernel lacks (pool epilogue, fused last hop, accumulate, interleave, windows) -- project_impl knows,
-// the shape-only queries (pool / gather fusability) pass false: those forms live in project_x3_kernel.
+// stream_ok: the call has nothing the streaming kernel lacks (pool epilogue, accumulate, interleave, windows) -- project_impl knows,
+// the shape-only query (pool fusability) passes false: that form lives in project_x3_kernel.
 static ProjChoice project_choose(int64_t M, int32_t Kc, int32_t N, int32_t nterms, bool vec4, bool vec_epilogue, bool has_rowmap, bool windows,
                                  bool stream_ok = false, int32_t nbatch = 1) {
   ProjChoice c;
@@ -291,13 +270,6 @@ static ProjChoice project_choose(int64_t M, int32_t Kc, int32_t N, int32_t nterm
   return c;
 }
 
-// Whether the projection of this shape (aligned operands) takes the kernel that has the gathering form (fused last hop).
-static bool project_gather_fusable(int64_t M, int32_t Kc, int32_t N, int32_t nterms, bool has_rowmap) {
-  if (Kc % 4 != 0 || nterms > kMaxTerms) return false;
-  const ProjChoice c = project_choose(M, Kc, N, nterms, true, N % 4 == 0, has_rowmap, false);
-  return c.kernel == kProjX3 && c.nts <= 4;
-}
-
 // Whether the projection of this shape (aligned operands, no row map) ends in a kernel with the fused relu + pool epilogue.
 static bool project_pool_fusable(int64_t M, int32_t Kc, int32_t N, int32_t nterms, int32_t pool) {
   if (pool < 2 || 16 % pool != 0 || M % pool != 0 || N % 4 != 0 || nterms > kMaxTerms) return false;
@@ -314,7 +286,7 @@ int tgcn_cheb_project_f32(void* stream, int64_t M, int32_t Kc, int32_t N, int32_
 int tgcn_cheb_project_mapped_f32(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const float* const* a, const int64_t* lda,
                                  const float* W, const float* bias, int32_t bias_kind, int64_t n_vertices, int64_t interleave, const int32_t* rowmap,
                                  uint32_t mapped_terms, int32_t nbatch, const int64_t* a_bs, int64_t out_bs, float* out, int64_t ldo) {
-  if (!rowmap || nbatch < 1 || (nbatch > 1 && !a_bs) || (mapped_terms & kProjMapTermsOnly) || interleave < 1)
+  if (!rowmap || nbatch < 1 || (nbatch > 1 && !a_bs) || interleave < 1)
     TGCN_FAIL(TGCN_ERR_INVALID, "project_mapped: bad argument");
   int64_t zero_bs[kMaxTerms] = {0};
   return project_impl(stream, M, Kc, N, nterms, a, lda, W, bias, bias_kind, n_vertices, interleave, 0, out, ldo, 0, 0, -1, rowmap, mapped_terms, nbatch,
@@ -335,7 +307,7 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
                         const int64_t* lda, const float* W, const float* bias, int32_t bias_kind,
                         int64_t n_vertices, int64_t interleave, int32_t accumulate, float* out, int64_t ldo,
                         int32_t win_n, int32_t win_t, int32_t bias_cols, const int32_t* rowmap, uint32_t mapped,
-                        int32_t nbatch, const int64_t* a_bs, int64_t out_bs, int32_t pool, uint8_t* pool_idx, const ProjGather* gather) {
+                        int32_t nbatch, const int64_t* a_bs, int64_t out_bs, int32_t pool, uint8_t* pool_idx) {
   if (nbatch < 1 || (nbatch > 1 && !a_bs)) TGCN_FAIL(TGCN_ERR_INVALID, "project: nbatch %d", nbatch);
   if (M <= 0 || Kc <= 0 || N <= 0 || nterms <= 0 || !a || !lda || !W || !out) TGCN_FAIL(TGCN_ERR_INVALID, "project: bad argument");
   if (int drc = check_pointer_device(out, (hipStream_t)stream, "project")) return drc;
@@ -344,7 +316,7 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
   if (interleave < 1 || n_vertices < 1) TGCN_FAIL(TGCN_ERR_INVALID, "project: interleave/n_vertices");
   if (interleave > 1 && !rowmap && M != interleave * n_vertices) TGCN_FAIL(TGCN_ERR_INVALID, "project: M != interleave*n_vertices");
   if (rowmap && win_n != 0) TGCN_FAIL(TGCN_ERR_INVALID, "project: a row map excludes windows");
-  if (rowmap && interleave != 1 && (M % interleave != 0 || (mapped & kProjMapTermsOnly) || nbatch != 1))
+  if (rowmap && interleave != 1 && (M % interleave != 0 || nbatch != 1))
     TGCN_FAIL(TGCN_ERR_INVALID, "project: row map with interleave %lld: M must be mapped vertices x interleave, one sample batch", (long long)interleave);
   ProjParams p;
   memset(&p, 0, sizeof(p));
@@ -365,7 +337,7 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
                    (p.bias_cols % 4 == 0);
   bool strides4 = (out_bs % 4 == 0);
   if (nbatch > 1) for (int t = 0; t < nterms; ++t) strides4 = strides4 && (a_bs[t] % 4 == 0);
-  const bool stream_ok = pool <= 1 && !gather && !accumulate && interleave == 1 && win_n == 0 && strides4 && bias_cols < 0 && n_vertices < (int64_t)INT32_MAX;
+  const bool stream_ok = pool <= 1 && !accumulate && interleave == 1 && win_n == 0 && strides4 && bias_cols < 0 && n_vertices < (int64_t)INT32_MAX;
   const ProjChoice choice = project_choose(M, Kc, N, nterms, vec4, p.vec_epilogue != 0, rowmap != nullptr, win_n != 0, stream_ok, nbatch);
   if (rowmap && interleave != 1 && choice.kernel != kProjNarrow)
     TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project: a row map together with interleave is the vector-ALU kernel's form (nterms*Kc <= %d, N %% 4 == 0, M >= 4096)", kNarrowMaxK);
@@ -374,16 +346,6 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
         n_vertices % pool != 0)
       TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project: no fused pool epilogue for this shape (M=%lld Kc=%d N=%d terms=%d pool=%d)", (long long)M, Kc, N, nterms, pool);
     p.pool = pool; p.pool_idx = pool_idx;
-  }
-  if (gather) {       // fused last hop: only the bf16x3 kernel with at most 4 column tiles has the gathering form
-    if (choice.kernel != kProjX3 || !vec4 || choice.nts > 4 || pool > 1 || accumulate || interleave != 1 || win_n != 0 || !gather->A || !gather->X ||
-        gather->term < 0 || gather->term >= nterms || gather->A->n != M || ((uintptr_t)gather->X & 15) || (gather->xbs % 4) != 0 ||
-        (rowmap && ((mapped >> gather->term) & 1u)))
-      TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project: no gathering form for this shape (M=%lld Kc=%d N=%d terms=%d)", (long long)M, Kc, N, nterms);
-    p.g_rowptr = gather->A->rowptr; p.g_edges = gather->A->edges; p.g_X = gather->X; p.g_xbs = gather->xbs;
-    p.g_term = gather->term; p.g_thresh = gather->thresh;
-  } else {
-    p.g_term = -1;
   }
   p.nbatch = 1;
   if (nbatch > 1) {
@@ -473,7 +435,7 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
   if (mb > (int64_t)INT32_MAX) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project: M too large");
   const int tiles = (N + 15) / 16, nts = choice.nts;
   const dim3 grid((unsigned)mb, (unsigned)((tiles + nts - 1) / nts));
-  ProfScope ps(gather ? TGCN_PROF_PROJECT_GATHER : TGCN_PROF_PROJECT, st);
+  ProfScope ps(TGCN_PROF_PROJECT, st);
 #define TGCN_PROJ(NTV)                                                                               \
   if (vec4) hipLaunchKernelGGL((project_kernel<NTV, true>), grid, dim3(kBlock), 0, st, p);             \
   else hipLaunchKernelGGL((project_kernel<NTV, false>), grid, dim3(kBlock), 0, st, p);
@@ -490,15 +452,6 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
       tail_blocks = (M - main_blocks * 256 + 127) / 128;
     }
     const dim3 grid3v2((unsigned)(main_blocks + tail_blocks), grid.y);
-    if (gather) {
-      switch (nts) {
-        case 1: hipLaunchKernelGGL((project_x3_gather_kernel<1>), grid3, dim3(512), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((project_x3_gather_kernel<2>), grid3, dim3(512), 0, st, p); break;
-        default: hipLaunchKernelGGL((project_x3_gather_kernel<4>), grid3, dim3(512), 0, st, p); break;
-      }
-      TGCN_CHECK_LAUNCH("tgcn_cheb_project_f32 (bf16x3 + fused last hop)");
-      return TGCN_OK;
-    }
 #define TGCN_PROJ3(NTV)                                                                              \
   if (NTV >= 6 && choice.kernel == kProjX3Wide) hipLaunchKernelGGL((project_x3v2_kernel<NTV>), grid3v2, dim3(512), 0, st, p, (int)main_blocks); /* wide outputs: compute-bound */ \
   else if (vec4) hipLaunchKernelGGL((project_x3_kernel<NTV, true>), grid3, dim3(512), 0, st, p);      \
@@ -669,12 +622,6 @@ int tgcn_relayout_qnc_to_nqc_f32(void* stream, const float* in, float* out, int6
 //   [xt]        n*q*C floats           (layout 1 only: re-laid input)
 //   [hop 1..K-1] (K-1) * qc*n*C floats
 //   [partial]   long-row segment scratch for one hop
-static int fwd_nsets(int64_t q, int64_t qc, int32_t layout) {
-  // two sets of hop tensors when there are several passes: the projection of pass i (side stream, MFMA-bound)
-  // overlaps the hops of pass i+1 (memory-bound)
-  return (layout == 0 && q > qc && g_overlap.load() != 0) ? 2 : 1;
-}
-
 static void fwd_ws_layout(const tgcn_csr_sched* S, int32_t K, int64_t q, int64_t n, int32_t C, int32_t layout,
                           int64_t qc, size_t* off_xt, size_t* off_hops, size_t* hop_bytes, size_t* off_part, size_t* total) {
   size_t o = 0;
@@ -684,7 +631,7 @@ static void fwd_ws_layout(const tgcn_csr_sched* S, int32_t K, int64_t q, int64_t
   // consecutive hop tensors are staggered by an odd multiple of 256 B on top of their size: the projection streams
   // all K of them at once and equally aligned streams collide on the same DRAM channels (measured: -6 %)
   *hop_bytes = align_up((size_t)qc * n * C * sizeof(float), 256) + 65 * 256;
-  o += (size_t)fwd_nsets(q, qc, layout) * (size_t)(K > 1 ? K - 1 : 0) * *hop_bytes;
+  o += (size_t)(K > 1 ? K - 1 : 0) * *hop_bytes;
   *off_part = o;
   const int32_t nb = layout == 1 ? 1 : (int32_t)qc;
   const int32_t Crow = layout == 1 ? (int32_t)(q * C) : C;
@@ -941,14 +888,8 @@ static int forward_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S
   int64_t ldas[kMaxTerms];
   int rc;
 
-  const int nsets = fwd_nsets(q, qc, layout);
-  SideStream* side = nsets == 2 ? side_stream() : nullptr;
-  hipStream_t main_st = (hipStream_t)stream;
-  const size_t set_bytes = (size_t)(K > 1 ? K - 1 : 0) * hop_bytes;
-  int pass = 0;
-  for (int64_t q0 = 0; q0 < q; q0 += qc, ++pass) {
+  for (int64_t q0 = 0; q0 < q; q0 += qc) {
     const int64_t qn = (q - q0 < qc) ? (q - q0) : qc;
-    const int set = side ? (pass & 1) : 0;
     // operand view of this pass
     int32_t nb, Crow;
     const float* x0;
@@ -961,10 +902,8 @@ static int forward_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S
     }
     const int64_t bs = (int64_t)n * Crow;
     auto hop_ptr = [&](int k) -> float* {
-      return k == 0 ? const_cast<float*>(x0) : (float*)(ws + off_hops + (size_t)set * set_bytes + (size_t)(k - 1) * hop_bytes);
+      return k == 0 ? const_cast<float*>(x0) : (float*)(ws + off_hops + (size_t)(k - 1) * hop_bytes);
     };
-    // this set was last read by the projection of pass-2: wait for it before overwriting
-    if (side && pass >= 2 && hipStreamWaitEvent(main_st, side->proj_done[set], 0) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "forward: stream wait failed");
     for (int k = 1; k < K; ++k) {
       tgcn_dense X = {hop_ptr(k - 1), bs, Crow};
       tgcn_dense Y = {hop_ptr(k), bs, Crow};
@@ -976,12 +915,6 @@ static int forward_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S
       }
       if (rc != TGCN_OK) return rc;
     }
-    void* proj_stream = stream;
-    if (side) {
-      if (hipEventRecord(side->hops_done[set], main_st) != hipSuccess || hipStreamWaitEvent(side->st, side->hops_done[set], 0) != hipSuccess)
-        TGCN_FAIL(TGCN_ERR_LAUNCH, "forward: stream fork failed");
-      proj_stream = side->st;
-    }
     // projection, in chunks of <= 32 terms
     const int64_t M = (layout == 1) ? n * q : qn * n;
     const int pl = pool > 1 ? pool : 1;              // pooled epilogue (layout 0, K <= 32 terms): output rows shrink by the pool
@@ -990,16 +923,11 @@ static int forward_impl(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S
       const int nt = (K - k0 < kMaxTerms) ? K - k0 : kMaxTerms;
       for (int t = 0; t < nt; ++t) { terms[t] = hop_ptr(k0 + t); ldas[t] = C; }
       const bool last = (k0 + nt >= K);
-      rc = project_impl(proj_stream, M, C, N, nt, terms, ldas, W + (size_t)k0 * C * N, last ? bias : nullptr,
+      rc = project_impl(stream, M, C, N, nt, terms, ldas, W + (size_t)k0 * C * N, last ? bias : nullptr,
                         last ? bias_kind : 0, n, layout == 1 ? q : 1, k0 > 0 ? 1 : 0, o0, N, 0, 0, -1, nullptr, 0, 1, nullptr, 0,
                         pool > 1 ? pool : 0, pool_idx ? pool_idx + q0 * (n / pl) * N : nullptr);
       if (rc != TGCN_OK) return rc;
     }
-    if (side && hipEventRecord(side->proj_done[set], side->st) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "forward: event record failed");
-  }
-  if (side) {  // join: everything the side stream did is ordered before whatever the caller enqueues next
-    for (int i = 0; i < 2 && i < pass; ++i)
-      if (hipStreamWaitEvent(main_st, side->proj_done[i], 0) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "forward: stream join failed");
   }
   return TGCN_OK;
 }
@@ -1032,15 +960,15 @@ size_t tgcn_cheb_forward_compact_workspace_bytes(const tgcn_csr_sched* S, int32_
 int tgcn_cheb_forward_compact_f32(void* stream, const tgcn_csr* A_first, const tgcn_csr* A_rest, const tgcn_csr_sched* S, int32_t K,
                                   int64_t q, int64_t n, int32_t C, int32_t N, const float* x, const float* W, const float* bias,
                                   int32_t bias_kind, float* out, const int32_t* rows, const int32_t* empty_rows, int64_t n_empty,
-                                  const int32_t* compact_id, int64_t q_chunk, void* workspace, size_t workspace_bytes) {
+                                  int64_t q_chunk, void* workspace, size_t workspace_bytes) {
   return tgcn_cheb_compact_layer_f32(stream, A_first, A_rest, S, 0, K, q, n, C, N, x, W, nullptr, bias, bias_kind, out, rows, empty_rows, n_empty,
-                                     compact_id, q_chunk, nullptr, workspace, workspace_bytes);
+                                     q_chunk, nullptr, workspace, workspace_bytes);
 }
 
 int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgcn_csr* A_rest, const tgcn_csr_sched* S, int32_t mode, int32_t K,
                                 int64_t q, int64_t n, int32_t C, int32_t N, const float* x, const float* W, const float* W_left, const float* bias,
                                 int32_t bias_kind, float* out, const int32_t* rows, const int32_t* empty_rows, int64_t n_empty,
-                                const int32_t* compact_id, int64_t q_chunk, float* keep_terms, void* workspace, size_t workspace_bytes) {
+                                int64_t q_chunk, float* keep_terms, void* workspace, size_t workspace_bytes) {
   if (!A_first || !A_rest || !S || !x || !W || !out || !rows) TGCN_FAIL(TGCN_ERR_INVALID, "compact_layer: null operand");
   if (int drc = check_pointer_device(x, (hipStream_t)stream, "compact_layer")) return drc;
   const int64_t n_c = A_first->n;
@@ -1067,8 +995,7 @@ int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgc
     return keep_terms ? keep_terms + (int64_t)i * q * bs_c : (float*)(ws + (size_t)i * hop_bytes);
   };
   hipStream_t st = (hipStream_t)stream;
-  // the zero row of every hop tensor (gathered from by the next hop and, with compact_id, by the projection for the left-out
-  // vertices); no hop writes it, so once per call
+  // the zero row of every hop tensor (gathered from by the next hop); no hop writes it, so once per call
   for (int k = k_first; k < K; ++k)
     if (hipMemset2DAsync(hop_ptr(k) + n_c * (int64_t)C, (size_t)bs_c * sizeof(float), 0, (size_t)C * sizeof(float), (size_t)qc, st) != hipSuccess)
       TGCN_FAIL(TGCN_ERR_LAUNCH, "compact_layer: memset failed");
@@ -1079,13 +1006,6 @@ int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgc
   int64_t a_bs[kMaxTerms];
   a_bs[0] = mode == 1 ? bs_c : n * (int64_t)C;
   for (int k = 1; k < K; ++k) a_bs[k] = bs_c;
-  // tgcn_set_tuning("fuse_last_hop", 1): last hop fused into the projection of the compact rows, where that projection is the bf16x3 kernel
-  // with <= 64 output columns (with compact_proj = 1 the projection runs over all vertices instead).  Bitwise the unfused result; OFF by
-  // default: measured slower on cfg5 (docs/EXPERIMENTS.md A.4).  Mode 0 only.
-  const bool one_proj = mode == 0 && compact_id && g_compact_proj.load() == 1;
-  const bool fuse_last = mode == 0 && g_fuse_last.load() && !one_proj && ((uintptr_t)x & 15) == 0 &&
-                         project_gather_fusable(n_c, C, N, K, true) && (N % 4 == 0) && (((uintptr_t)out & 15) == 0) &&
-                         (!bias || ((uintptr_t)bias & 15) == 0);
   const bool vec_rows = (C % 4 == 0) && (((uintptr_t)x & 15) == 0);
   for (int64_t q0 = 0; q0 < q; q0 += qc) {
     const int64_t qn = (q - q0 < qc) ? (q - q0) : qc;
@@ -1093,8 +1013,6 @@ int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgc
     // hops: one launch per hop and time step (a launch's gather working set stays one (n_c, C) slab).
     // mode 0 (monomials of the folded weight): P_1 = A_first x (columns in the caller's labels), P_k = A_rest P_{k-1}.
     // mode 1 (Chebyshev): T_0 = the kept rows of x, T_1 = A_rest T_0, T_k = 2 A_rest T_{k-1} - T_{k-2}.
-    // fuse_last: the rows of at most row_thresh entries of the LAST hop are gathered inside the projection (project_x3_gather_kernel); the
-    // hop launch then covers the longer rows only, and the last hop tensor is neither written nor read for the others.
     for (int64_t b = 0; b < qn; ++b) {
       if (mode == 1) {
         const int64_t units = vec_rows ? n_c * (C / 4) : n_c * (int64_t)C;
@@ -1107,10 +1025,9 @@ int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgc
         tgcn_dense Y = {hop_ptr(k) + b * bs_c, 0, C};
         if (mode == 1 && k >= 2) {
           tgcn_dense Zd = {hop_ptr(k - 2) + b * bs_c, 0, C};
-          rc = hop_impl(stream, A_rest, S, 1, C, &X, &Zd, 2.f, -1.f, nullptr, 0.f, &Y, nullptr, part, part_bytes, 0);
+          rc = hop_impl(stream, A_rest, S, 1, C, &X, &Zd, 2.f, -1.f, nullptr, 0.f, &Y, nullptr, part, part_bytes);
         } else {
-          rc = hop_impl(stream, (mode == 0 && k == 1) ? A_first : A_rest, S, 1, C, &X, nullptr, 1.f, 0.f, nullptr, 0.f, &Y, nullptr, part, part_bytes,
-                        (fuse_last && k == K - 1) ? 1 : 0);
+          rc = hop_impl(stream, (mode == 0 && k == 1) ? A_first : A_rest, S, 1, C, &X, nullptr, 1.f, 0.f, nullptr, 0.f, &Y, nullptr, part, part_bytes);
         }
         if (rc != TGCN_OK) return rc;
       }
@@ -1119,23 +1036,9 @@ int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgc
     terms[0] = mode == 1 ? hop_ptr(0) : x0;
     for (int k = 1; k < K; ++k) terms[k] = hop_ptr(k);
     float* o = out + q0 * n * N;
-    if (one_proj) {
-      // ONE launch over all vertices in order: x, bias and out stream contiguously; terms 1..K-1 are read through the vertex ->
-      // compact id map (empty vertices read the zero row): twice the tile work of the split form, every byte in whole DRAM pages
-      uint32_t bits = kProjMapTermsOnly;
-      for (int k = 1; k < K; ++k) bits |= (1u << k);
-      rc = project_impl(stream, n, C, N, K, terms, ldas, W, bias, bias_kind, n, 1, 0, o, N, 0, 0, -1, compact_id, bits, (int32_t)qn, a_bs, n * (int64_t)N);
-      if (rc != TGCN_OK) return rc;
-      continue;
-    }
     // kept vertices: all K terms (mode 0: x through the row map, hop tensors in compact rows; mode 1: every term in compact rows)
-    ProjGather gat;
-    gat.A = (K == 2) ? A_first : A_rest;                                // the last hop's operand and its gather source (hop K-2, or x for K = 2)
-    gat.X = (K == 2) ? x0 : hop_ptr(K - 2);
-    gat.xbs = (K == 2) ? n * (int64_t)C : bs_c;
-    gat.term = K - 1; gat.thresh = S->row_thresh;
     rc = project_impl(stream, n_c, C, N, K, terms, ldas, W, bias, bias_kind, n, 1, 0, o, N, 0, 0, -1, rows, mode == 1 ? 0u : 1u, (int32_t)qn, a_bs,
-                      n * (int64_t)N, 0, nullptr, fuse_last ? &gat : nullptr);
+                      n * (int64_t)N);
     if (rc != TGCN_OK) return rc;
     // the others.  mode 0: P_k = 0 for k >= 1, so out = x W'_0 + bias.  mode 1: the left-out vertices are ISOLATED (no entries, never pointed at):
     // T_k = x, 0, -x, 0, ... so out = x (W_0 - W_2 + W_4 - ...) + bias = x W_left + bias.

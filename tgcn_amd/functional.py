@@ -510,7 +510,7 @@ def cheb_forward_compact(plan, x3, Wt, bias, bias_kind, K, q_chunk=None, mode=MO
             q_chunk = plan.q_chunk_cache[(K, Crow, q)] = max(1, q_chunk // 2)        # the cached choice no longer fits: fewer time steps per pass from now on
     _lib.check(L.tgcn_cheb_compact_layer_f32(_lib.stream_ptr(), C.byref(plan.first.struct), C.byref(plan.rest.struct), C.byref(sched.struct), mode, K, q, n,
                                              Crow, N, _lib.ptr(x3), _lib.ptr(Wt), _lib.ptr(W_left), _lib.ptr(bias), bias_kind, _lib.ptr(out),
-                                             _lib.ptr(plan.rows), _lib.ptr(plan.empty), plan.n_empty, _lib.ptr(plan.cid), q_chunk, _lib.ptr(kept),
+                                             _lib.ptr(plan.rows), _lib.ptr(plan.empty), plan.n_empty, q_chunk, _lib.ptr(kept),
                                              _lib.ptr(ws), ws.numel()))
     if not keep:
         return out

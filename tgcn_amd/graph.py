@@ -226,12 +226,11 @@ class CompactPlan:
         self.empty = _as_i32((~keep).nonzero().flatten())
         self.n_empty = int(self.empty.numel())
         rowptr_c = torch.cat([op.rowptr[:-1][keep], op.rowptr[-1:]]).contiguous()
-        cid = torch.full((op.n,), self.n_c, dtype=torch.int32, device=dev)
+        cid = torch.full((op.n,), self.n_c, dtype=torch.int32, device=dev)      # compact id of every vertex, n_c for the empty ones
         cid[rows] = torch.arange(self.n_c, dtype=torch.int32, device=dev)
         edges_c = op.edges.clone()
         if op.nnz:
             edges_c[:, 0] = cid[op.edges[:, 0].long()]
-        self.cid = cid                              # compact id of every vertex, n_c for the empty ones
         self.first = GraphOperand._from_packed(self.n_c, rowptr_c, op.edges, op.nnz, n_cols=op.n)
         self.rest = GraphOperand._from_packed(self.n_c, rowptr_c, edges_c, op.nnz, n_cols=self.n_c + 1)
         self.q_chunk_cache = {}                     # functional.cheb_forward_compact: time steps per pass, chosen once per shape
