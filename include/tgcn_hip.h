@@ -305,6 +305,24 @@ int tgcn_cheb_windows_backward_f32(void* stream, int64_t S, int64_t n_vertices, 
                                    const float* stack, const float* g, const float* W, float* G, float* dW, void* workspace,
                                    size_t workspace_bytes);
 
+/* Streaming time windows of MULTI-CHANNEL series: stack (K, S, n_vertices, T*f) are the hop tensors of S recordings whose
+ * time rows hold f contiguous channels; window w of vertex i is the H*f floats from float offset w*f of its row.  W: (K, H*f, N).
+ *   out[(s, w, i), :] = sum_k stack[k, s, i, w*f : (w+H)*f] . W[k] + bias       one launch for all S recordings
+ * as_series = 0: out is (S*(T-H+1), n_vertices, N), the order of tgcn_cheb_project_windows_f32; 1: (S, n_vertices, T-H+1, N), a series of
+ * N channels that the next time layer streams over.  fp32 MFMA; bias_kind as in tgcn_cheb_project_f32 (2: [n_vertices*N]). */
+int tgcn_cheb_project_series_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                 const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out);
+
+/* Backward of tgcn_cheb_project_series_f32; g is the gradient of its output in the layout g_as_series names (read in place).
+ *   G  (nullable, (K, S, n_vertices, T*f)):  G[k, s, i, t*f + c] = sum_h sum_m g[(s, t-h), i, m] W[k, h*f + c, m]  -- per-term input
+ *      gradients for the hops on L^T, by the forward's kernel on the time-flipped transposed weight (built in the workspace)
+ *   dW (nullable, (K, H*f, N)):  dW[k, h*f + c, m] = sum_{s,w,i} stack[k, s, i, (w+h)*f + c] g[(s, w), i, m]; fp32 MFMA, partial sums per
+ *      row block folded in block order (deterministic).  The workspace must be 16-byte aligned. */
+size_t tgcn_cheb_series_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K);
+int tgcn_cheb_series_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                  const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
+                                  void* workspace, size_t workspace_bytes);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

@@ -9,6 +9,7 @@
 //   wgrad.h          dW_t = A_t^T G, two deterministic stages on the fp32 MFMA
 //   small_graph.h    graphs that fit in LDS: whole layer / basis in ONE launch (sparse, first-layer, dense matrix-pipe)
 //   pool_relayout.h  (Q,n,C) -> (n,Q,C), gcn_pool / gcn_pool_4, relu + pool pass
+//   windows.h        streaming time windows of multi-channel series: sliding-window fp32 MFMA GEMM (forward, input gradient), weight gradient
 //   device_build.h   operand / schedule construction on the device: prefix sums, stable radix sort, CSR build, schedule kernels
 //   graph_build.h    tgcn_graph_* / tgcn_sched_* / tgcn_csr_build_f32: host-side orchestration of device_build.h (one-off per operand)
 // This file: the extern "C" entry points (argument checks, workspace carving, launches) declared in tgcn_hip.h.
@@ -39,6 +40,7 @@ namespace {
 #include "wgrad.h"
 #include "small_graph.h"
 #include "pool_relayout.h"
+#include "windows.h"
 #include "device_build.h"
 #include "graph_build.h"
 
@@ -1175,6 +1177,136 @@ int tgcn_cheb_windows_backward_f32(void* stream, int64_t S, int64_t n_vertices, 
     hipLaunchKernelGGL(windows_wgrad_reduce_kernel, dim3(grid_1d(count)), dim3(kBlock), 0, st, (const float*)workspace, dW, count, nchunks);
   }
   TGCN_CHECK_LAUNCH("tgcn_cheb_windows_backward_f32");
+  return TGCN_OK;
+}
+
+// ---- streaming time windows of multi-channel series (windows.h)
+// Chooses HC (weight time rows per staged span) and the dynamic LDS of series_gemm_kernel: the whole horizon when four spans and the weight
+// tile fit 64 KB, else the largest chunk that does, else the largest that fits the device's opt-in limit; 0 when even one row does not.
+static int series_gemm_lds(int H, int f, int NT, bool vec, int* hc_out) {
+  const int ws = kSgKT * series_ws_stride(NT);
+  auto bytes = [&](int hc) { return (size_t)(ws + 4 * series_span_floats(hc, f, vec)) * sizeof(float); };
+  const size_t limits[2] = {64 * 1024, (size_t)lds_optin_limit()};
+  for (size_t lim : limits)
+    for (int hc = H; hc >= 1; --hc)
+      if (bytes(hc) <= lim) { *hc_out = hc; return (int)bytes(hc); }
+  return 0;
+}
+
+static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who) {
+  p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
+  p.ntiles = S * p.n * p.tpv;
+  const int64_t gx = (p.ntiles + 3) / 4;
+  const int NT = p.N <= 16 ? 1 : (p.N <= 32 ? 2 : 4);
+  const int64_t gy = (p.N + NT * 16 - 1) / (NT * 16);
+  if (gx > (int64_t)INT32_MAX || gy > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
+  int hc = 0;
+  const int lds = series_gemm_lds(p.H, p.f, NT, vec, &hc);
+  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, p.f);
+  p.HC = hc;
+  const dim3 grid((unsigned)gx, (unsigned)gy);
+  ProfScope ps(TGCN_PROF_PROJECT, st);
+#define TGCN_SERIES_GEMM(NT_, VEC_)                                                                   \
+  do {                                                                                                \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_kernel<NT_, VEC_>, lds);            \
+    hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_>), grid, dim3(kBlock), lds, st, p);              \
+  } while (0)
+  if (vec) { if (NT == 1) TGCN_SERIES_GEMM(1, true); else if (NT == 2) TGCN_SERIES_GEMM(2, true); else TGCN_SERIES_GEMM(4, true); }
+  else { if (NT == 1) TGCN_SERIES_GEMM(1, false); else if (NT == 2) TGCN_SERIES_GEMM(2, false); else TGCN_SERIES_GEMM(4, false); }
+#undef TGCN_SERIES_GEMM
+  return TGCN_OK;
+}
+
+static bool series_shape_ok(int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K) {
+  return S >= 1 && n >= 1 && n < (int64_t)INT32_MAX && f >= 1 && H >= 1 && T >= H && N >= 1 && K >= 1 && (int64_t)T * f < (int64_t)INT32_MAX &&
+         (int64_t)H * f < (int64_t)INT32_MAX / 2 && (int64_t)H * N < (int64_t)INT32_MAX / 2 && (int64_t)K * f < (int64_t)INT32_MAX;
+}
+
+int tgcn_cheb_project_series_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                 const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out) {
+  if (!series_shape_ok(S, n_vertices, T, f, H, N, K) || !stack || !W || !out) TGCN_FAIL(TGCN_ERR_INVALID, "project_series: bad argument");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series: bias_kind %d", bias_kind);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series")) return drc;
+  const int64_t n = n_vertices, Tf = (int64_t)T * f, nwin = T - H + 1;
+  SeriesGemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.src = stack; p.W = W; p.bias = bias; p.out = out;
+  p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
+  if (as_series) { p.o_ss = n * nwin * N; p.o_is = nwin * N; p.o_ws = N; }      // (S, n, nwin, N)
+  else { p.o_ss = nwin * n * N; p.o_is = N; p.o_ws = n * N; }                     // (S, nwin, n, N)
+  p.o_gs = 0; p.ocg = N;
+  p.n = n; p.Tin = T; p.padl = 0; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
+  const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0);
+  if (int rc = series_gemm_launch((hipStream_t)stream, p, S, vec, "project_series")) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_f32");
+  return TGCN_OK;
+}
+
+// Row blocks of the series weight gradient: wgrad_rows_per_block's rule, with the partials held to 256 MB (each is a whole (K, H*f, N) weight)
+static int64_t series_wgrad_rows_per_block(int64_t M, int64_t weight_floats) {
+  int64_t rpb = wgrad_rows_per_block(M);
+  int64_t most = ((int64_t)256 << 20) / (weight_floats * (int64_t)sizeof(float));
+  if (most < 1) most = 1;
+  if ((M + rpb - 1) / rpb > most) rpb = ((M + most - 1) / most + 15) / 16 * 16;
+  return rpb;
+}
+
+size_t tgcn_cheb_series_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K) {
+  if (!series_shape_ok(S, n_vertices, T, f, H, N, K)) return 0;
+  const int64_t wf = (int64_t)K * H * f * N, M = S * n_vertices * (T - H + 1);
+  const int64_t rpb = series_wgrad_rows_per_block(M, wf);
+  return align_up((size_t)wf * sizeof(float), 256) + (size_t)((M + rpb - 1) / rpb) * wf * sizeof(float);
+}
+
+int tgcn_cheb_series_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                  const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
+                                  void* workspace, size_t workspace_bytes) {
+  if (!series_shape_ok(S, n_vertices, T, f, H, N, K) || !g) TGCN_FAIL(TGCN_ERR_INVALID, "series_backward: bad argument");
+  if (int drc = check_pointer_device(g, (hipStream_t)stream, "series_backward")) return drc;
+  const size_t need = tgcn_cheb_series_backward_workspace_bytes(S, n_vertices, T, f, H, N, K);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) TGCN_FAIL(TGCN_ERR_WORKSPACE, "series_backward: workspace %zu < %zu", workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = n_vertices, Tf = (int64_t)T * f, nwin = T - H + 1, wf = (int64_t)K * H * f * N;
+  int64_t g_ss, g_is, g_ws;
+  if (g_as_series) { g_ss = n * nwin * N; g_is = nwin * N; g_ws = N; }
+  else { g_ss = nwin * n * N; g_is = N; g_ws = n * N; }
+  if (G) {      // the forward's kernel over g as a series of N channels: T output "windows" reaching H - 1 rows back, columns (k, c)
+    if (!W) TGCN_FAIL(TGCN_ERR_INVALID, "series_backward: the input gradient needs W");
+    float* Wd = (float*)workspace;
+    { ProfScope ps(TGCN_PROF_RELAYOUT, st);
+      hipLaunchKernelGGL(series_flip_weight_kernel, dim3(grid_1d(wf)), dim3(kBlock), 0, st, W, Wd, (int)K, (int)H, (int)f, (int)N); }
+    SeriesGemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.src = g; p.W = Wd; p.bias = nullptr; p.out = G;
+    p.src_ks = 0; p.src_ss = g_ss; p.src_is = g_is; p.src_ts = g_ws;
+    p.o_ss = n * Tf; p.o_is = Tf; p.o_ws = f; p.o_gs = S * n * Tf; p.ocg = f;
+    p.n = n; p.Tin = (int32_t)nwin; p.padl = H - 1; p.nwin = T; p.H = H; p.f = N; p.N = K * f; p.nterms = 1; p.bias_kind = 0;
+    const bool vec = (N % 4 == 0) && (((uintptr_t)g & 15) == 0);
+    if (int rc = series_gemm_launch(st, p, S, vec, "series_backward")) return rc;
+  }
+  if (dW) {
+    if (!stack) TGCN_FAIL(TGCN_ERR_INVALID, "series_backward: the weight gradient needs the hop tensors");
+    const int64_t M = S * n * nwin;
+    SeriesWgradParams q;
+    memset(&q, 0, sizeof(q));
+    q.stack = stack; q.g = g; q.partial = (float*)((char*)workspace + align_up((size_t)wf * sizeof(float), 256));
+    q.st_ks = S * n * Tf; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
+    q.M = M; q.rows_per_block = series_wgrad_rows_per_block(M, wf); q.n = n;
+    q.Tf = (int32_t)Tf; q.f = f; q.nwin = (int32_t)nwin; q.J = H * f; q.N = N; q.K = K;
+    const int64_t nblocks = (M + q.rows_per_block - 1) / q.rows_per_block;
+    const int64_t jtiles = (q.J + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
+    if (q.rows_per_block + nwin >= (int64_t)INT32_MAX || q.rows_per_block / nwin + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX ||
+        (N + 63) / 64 > 65535 || jtiles * tgroups > 65535)
+      TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_backward: weight gradient shape too large");
+    { ProfScope ps(TGCN_PROF_WGRAD, st);
+      hipLaunchKernelGGL(series_wgrad_partial_kernel, dim3((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups)), dim3(64), 0, st, q); }
+    WgradParams r;
+    memset(&r, 0, sizeof(r));
+    r.partial = q.partial; r.dW = dW; r.Kc = q.J; r.N = N; r.nterms = K; r.nblocks = (int32_t)nblocks;
+    { ProfScope ps(TGCN_PROF_WGRAD, st);
+      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
+  }
+  TGCN_CHECK_LAUNCH("tgcn_cheb_series_backward_f32");
   return TGCN_OK;
 }
 

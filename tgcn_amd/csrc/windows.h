@@ -1,0 +1,229 @@
+// windows.h -- streaming time windows of MULTI-CHANNEL series (tgcn_cheb_project_series_f32 / tgcn_cheb_series_backward_f32)
+// Part of the single translation unit tgcn_hip.hip (included once, inside its anonymous namespace).
+#pragma once
+
+// --------------------------------------------------------------------------------------------------
+// sliding-window GEMM:  out[(s, i, w), col] = sum_term sum_{j < H*f} src_term[s, i, w - padl + j / f, j % f] * W[term][j][col]  (+ bias)
+// --------------------------------------------------------------------------------------------------
+// A series is addressed as src + term * src_ks + s * src_ss + i * src_is + t * src_ts + c with f contiguous channels per time row and
+// zeros outside 0 <= t < Tin, so ONE kernel serves
+//   the forward       (src = hop stack (K, S, n, T*f), padl = 0, nwin = T - H + 1 windows, columns = output channels) and
+//   the input gradient (src = g read as a series of N channels over the windows, in either output layout, padl = H - 1, T "windows",
+//                       one term, W = the time-flipped transposed weight, columns = (k, c) written into the (K, S, n, T*f) layout).
+// Workgroup = 4 waves; wave v owns 32 consecutive windows of one vertex (two 16-row tiles of v_mfma_f32_16x16x4_f32 sharing their B
+// fragments, layouts as in project.h) x NT*16 columns.  Per term (and per chunk of HC weight time rows when the span would not fit) the
+// wave stages the (31 + HC) time rows its windows cover ONCE into its own LDS span -- 16-byte loads when VEC -- and feeds the A fragments
+// from it at sliding offsets: window w, weight row (h, c) reads span row w + h, so a staged float serves up to HC windows.  The weight
+// streams through one 32 x NT*16 LDS tile shared by the four waves.
+// LDS banks: VEC spans keep f + 2 floats per time row (f % 4 == 0: (f + 2) / 2 is odd, the 16 windows x 2 k of a half wave fall into 32
+// different banks); otherwise the span is the plain float sequence (window stride f).  Ws as in project_kernel.
+struct SeriesGemmParams {
+  const float* src;
+  const float* W;       // (nterms, H*f, N) row-major
+  const float* bias;    // bias_kind 1: [N]; 2: [n][N]
+  float* out;
+  int64_t src_ks, src_ss, src_is, src_ts;
+  int64_t o_ss, o_is, o_ws, o_gs;   // output strides: recording, vertex, window, column group (column col lives at (col / ocg) * o_gs + col % ocg)
+  int64_t n, ntiles;                // vertices per recording; wave tiles = S * n * tpv
+  int32_t Tin, padl, nwin, H, f, N, nterms, ocg, bias_kind, tpv, HC;
+};
+
+constexpr int kSgWin = 32;    // windows per wave
+constexpr int kSgKT = 32;     // weight rows per staged tile
+
+__host__ __device__ inline int series_span_floats(int hc, int f, bool vec) {
+  return vec ? (kSgWin - 1 + hc) * (f + 2) : ((kSgWin - 1 + hc) * f + 4 + 3) / 4 * 4;
+}
+__host__ __device__ constexpr int series_ws_stride(int NT) { return (NT * 16) % 32 == 0 ? NT * 16 + 16 : NT * 16; }
+
+template <int NT, bool VEC>
+__global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmParams p) {
+  constexpr int NW = NT * 16, NS = series_ws_stride(NT), WREG = (kSgKT * NW) / kBlock;
+  extern __shared__ __attribute__((aligned(16))) float sg_lds[];
+  float* Ws = sg_lds;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, kq = lane >> 4;
+  const int fp = VEC ? p.f + 2 : p.f;
+  float* span = sg_lds + kSgKT * NS + wave * series_span_floats(p.HC, p.f, VEC);
+  const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+  const bool live = tile < p.ntiles;
+  const int64_t si = live ? tile / p.tpv : 0;
+  const int w0 = live ? (int)(tile % p.tpv) * kSgWin : 0;
+  const int64_t s = si / p.n, iv = si % p.n;
+  const int n0 = blockIdx.y * NW;
+  const int J = p.H * p.f;
+  f32x4 acc[2][NT];
+#pragma unroll
+  for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) acc[rt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int term = 0; term < p.nterms; ++term) {
+    const float* __restrict__ base = p.src + term * p.src_ks + s * p.src_ss + iv * p.src_is;
+    const float* __restrict__ Wt = p.W + (int64_t)term * J * p.N;
+    for (int hc0 = 0; hc0 < p.H; hc0 += p.HC) {
+      const int hcn = min(p.HC, p.H - hc0);
+      const int rows = kSgWin - 1 + hcn, t0 = w0 + hc0 - p.padl;
+      // ---- this wave's span: time rows t0 .. t0 + rows - 1 (zeros outside the series, and for a wave without a tile)
+      if constexpr (VEC) {
+        const int f4 = p.f >> 2, total4 = rows * f4;
+        for (int e = lane; e < total4; e += 64) {
+          const int tr = e / f4, c = (e - tr * f4) * 4, t = t0 + tr;
+          float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (live && t >= 0 && t < p.Tin) v = *reinterpret_cast<const float4*>(base + (int64_t)t * p.src_ts + c);
+          float2* d = reinterpret_cast<float2*>(span + tr * fp + c);
+          d[0] = make_float2(v.x, v.y);
+          d[1] = make_float2(v.z, v.w);
+        }
+      } else {
+        const int total = series_span_floats(hcn, p.f, false);
+        for (int e = lane; e < total; e += 64) {
+          const int tr = e / p.f, c = e - tr * p.f, t = t0 + tr;
+          span[e] = (live && tr < rows && t >= 0 && t < p.Tin) ? base[(int64_t)t * p.src_ts + c] : 0.f;
+        }
+      }
+      const int jn = hcn * p.f;                 // weight rows of this chunk: W rows hc0 * f + [0, jn)
+      int hh = 0, cc = 0;                       // VEC: (time row, channel) of the current k step, kept without a division
+      for (int j0 = 0; j0 < jn; j0 += kSgKT) {
+        __syncthreads();                        // the previous weight tile has been read by every wave
+#pragma unroll
+        for (int h = 0; h < WREG; ++h) {
+          const int idx = tid + h * kBlock;
+          const int kk = idx / NW, col = idx % NW;
+          const bool ok = (j0 + kk < jn) && (n0 + col < p.N);
+          Ws[kk * NS + col] = ok ? Wt[(int64_t)(hc0 * p.f + j0 + kk) * p.N + n0 + col] : 0.f;
+        }
+        __syncthreads();                        // weight tile (and, first time round, the span) visible
+        const int ksteps = min(kSgKT, jn - j0 + 3) >> 2;
+        for (int ks = 0; ks < ksteps; ++ks) {
+          int aoff;
+          if constexpr (VEC) {
+            aoff = (r + hh) * fp + cc + kq;
+            cc += 4;
+            if (cc >= p.f) { cc = 0; ++hh; }
+          } else {
+            aoff = r * p.f + j0 + ks * 4 + kq;  // < 31 * f + jn + 3: inside the zero-tailed span
+          }
+          const float a0 = span[aoff];
+          const float a1 = span[aoff + 16 * fp];
+#pragma unroll
+          for (int nt = 0; nt < NT; ++nt) {
+            const float bv = Ws[(ks * 4 + kq) * NS + nt * 16 + r];
+            acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv, acc[0][nt], 0, 0, 0);
+            acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bv, acc[1][nt], 0, 0, 0);
+          }
+        }
+      }
+      __syncthreads();                          // span and weight tile are free again
+    }
+  }
+  if (!live) return;
+  // ---- epilogue (D: col = lane & 15, row = (lane >> 4) * 4 + reg): bias, column-group addressing, store
+  float* orow0 = p.out + s * p.o_ss + iv * p.o_is;
+#pragma unroll
+  for (int nt = 0; nt < NT; ++nt) {
+    const int col = n0 + nt * 16 + r;
+    if (col >= p.N) continue;
+    const int64_t coff = (int64_t)(col / p.ocg) * p.o_gs + col % p.ocg;
+    float b = 0.f;
+    if (p.bias_kind == 1) b = p.bias[col];
+    else if (p.bias_kind == 2) b = p.bias[iv * p.N + col];
+#pragma unroll
+    for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int w = w0 + rt * 16 + kq * 4 + i;
+        if (w < p.nwin) orow0[(int64_t)w * p.o_ws + coff] = acc[rt][nt][i] + b;
+      }
+  }
+}
+
+// Wd[(h', nn), (k, c)] = W[k, H - 1 - h', c, nn]: the weight of the input gradient as a sliding-window GEMM over g
+__global__ __launch_bounds__(kBlock) void series_flip_weight_kernel(const float* __restrict__ W, float* __restrict__ Wd, int K, int H, int f, int N) {
+  const int64_t total = (int64_t)K * H * f * N;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {   // index into W: (k, h, c, nn)
+    const int nn = (int)(i % N), c = (int)((i / N) % f), h = (int)((i / ((int64_t)N * f)) % H), k = (int)(i / ((int64_t)N * f * H));
+    Wd[((int64_t)(H - 1 - h) * N + nn) * ((int64_t)K * f) + (int64_t)k * f + c] = W[i];
+  }
+}
+
+// --------------------------------------------------------------------------------------------------
+// weight gradient: dW[k][j][nn] = sum_{s, i, w} stack[k, s, i, w*f + j] * g[(s, i, w), nn]         (j = h*f + c < H*f)
+// --------------------------------------------------------------------------------------------------
+// wgrad_partial_kernel's scheme on window rows: rows m = (s, i, w) in vertex-major order (consecutive rows are consecutive windows of one
+// vertex, f floats apart, so the H-fold overlap is served by the caches), one wave per (row block, 64 columns of g, 16 rows j of the
+// weight, group of kWgTerms terms), fp32 MFMA with k = 4 rows per instruction; g is addressed by strides, so either output layout is read
+// in place.  Partials per row block, folded in block order by wgrad_reduce_kernel: deterministic.
+struct SeriesWgradParams {
+  const float* stack;
+  const float* g;
+  float* partial;                 // [nblocks][K*J][N]
+  int64_t st_ks, g_ss, g_is, g_ws;
+  int64_t M, rows_per_block, n;
+  int32_t Tf, f, nwin, J, N, K;
+};
+
+__global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWgradParams p) {
+  const int lane = threadIdx.x;
+  const int r = lane & 15, kq = lane >> 4;
+  const int64_t m_lo = (int64_t)blockIdx.x * p.rows_per_block;
+  const int64_t m_hi = min(p.M, m_lo + p.rows_per_block);
+  const int n0 = blockIdx.y * 64;
+  const int tgroups = (p.K + kWgTerms - 1) / kWgTerms;
+  const int jt = blockIdx.z / tgroups, tg = blockIdx.z % tgroups;
+  const int t0 = tg * kWgTerms;
+  const int j = jt * 16 + r;
+  float* part = p.partial + (size_t)blockIdx.x * p.K * p.J * p.N;
+  // (vertex row, window) of the block's first row once in 64 bits; rows inside the block by 32-bit arithmetic from there
+  const int64_t si_lo = m_lo / p.nwin;
+  const uint32_t w_lo = (uint32_t)(m_lo % p.nwin);
+  const int64_t s_lo = si_lo / p.n;
+  const uint32_t i_lo = (uint32_t)(si_lo % p.n);
+  const uint32_t nwin = (uint32_t)p.nwin, nv = (uint32_t)p.n;
+  f32x4 acc[kWgTerms][4];
+#pragma unroll
+  for (int t = 0; t < kWgTerms; ++t)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[t][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int64_t m0 = m_lo; m0 < m_hi; m0 += 4 * kWgUnroll) {
+    float gv[kWgUnroll][4], av[kWgUnroll][kWgTerms];
+#pragma unroll
+    for (int u = 0; u < kWgUnroll; ++u) {
+      const int64_t m = m0 + u * 4 + kq;
+      const bool mok = m < m_hi;
+      const uint32_t d = w_lo + (uint32_t)((mok ? m : m_lo) - m_lo);
+      const uint32_t dv = d / nwin, w = d - dv * nwin;
+      const uint32_t ii = i_lo + dv, ds = ii / nv, i = ii - ds * nv;
+      const int64_t s = s_lo + ds;
+      const float* grow = p.g + s * p.g_ss + (int64_t)i * p.g_is + (int64_t)w * p.g_ws;
+      const float* arow = p.stack + (s * p.n + i) * (int64_t)p.Tf + (int64_t)w * p.f;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int nn = n0 + q * 16 + r;
+        gv[u][q] = (mok && nn < p.N) ? grow[nn] : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < kWgTerms; ++t)
+        av[u][t] = (mok && j < p.J && t0 + t < p.K) ? arow[(int64_t)(t0 + t) * p.st_ks + j] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < kWgUnroll; ++u)
+#pragma unroll
+      for (int t = 0; t < kWgTerms; ++t) {
+        if (t0 + t >= p.K) break;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[t][q] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[u][t], gv[u][q], acc[t][q], 0, 0, 0);
+      }
+  }
+#pragma unroll
+  for (int t = 0; t < kWgTerms; ++t) {
+    if (t0 + t >= p.K) break;
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int jj = jt * 16 + kq * 4 + i, nn = n0 + q * 16 + r;
+        if (jj < p.J && nn < p.N) part[((size_t)(t0 + t) * p.J + jj) * p.N + nn] = acc[t][q][i];
+      }
+  }
+}

@@ -385,18 +385,97 @@ class ChebWindowsFn(torch.autograd.Function):
         return gx, dW, gb, None, None, None
 
 
-def cheb_time_windows(op, series, weight_khg, bias, bias_kind, mode=MODE_POWER):
-    """Streaming form of TGCNCheb_H / ChebTimeConv on sliding windows (f = 1): series (S, n, T) raw recordings,
-    weight (K, H, N) in the reference basis.  Returns (S * (T-H+1), n, N), identical to running the layer on the
-    windowed batch x[s*(T-H+1) + w, i, h] = series[s, i, w + h] (load/data_hcp.py:146-152), but the K-1 hops run
-    once on the T columns of each recording -- in the backward too (ChebWindowsFn), so the windows it replaces can be
-    trained through."""
-    if param_dtype(weight_khg, bias, "cheb_time_windows") == BF16:
+class ChebSeriesFn(torch.autograd.Function):
+    """Streaming time-window layer on a multi-channel series (S, n, T, f), weight (K, H, f, N): the hops run once on rows of T*f floats in
+    both directions, the window projection and its two gradients are the sliding-window MFMA kernels of csrc/windows.h
+    (tgcn_cheb_project_series_f32 / tgcn_cheb_series_backward_f32), one launch each for all S recordings.  as_series picks the output
+    layout, (S*nwin, n, N) or (S, n, nwin, N); the backward reads its gradient in that layout in place."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series):
+        L = _lib.lib()
+        S, n, T, f = series.shape
+        K, H, _, N = weight_khfg.shape
+        nwin = T - H + 1
+        x3 = _aligned_input(series.float().contiguous().view(S, n, T * f))
+        W = weight_khfg.float().contiguous().view(K, H * f, N)
+        fold = _power_fold(mode, W)
+        Wt = _working_weight(fold, W)
+        # the series is in the operand's labels already (cheb_time_windows relabelled it)
+        stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)   # (K, S, n, T*f)
+        out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=torch.float32, device=x3.device)
+        b = bias.contiguous() if bias is not None else None
+        _lib.check(L.tgcn_cheb_project_series_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind,
+                                                  1 if as_series else 0, _lib.ptr(out)))
+        ctx.save_for_backward(Wt)
+        ctx.stack = stack if ctx.needs_input_grad[1] else None       # the basis the weight gradient contracts with g
+        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
+        ctx.dims = (S, n, T, f, H, N, K)
+        ctx.bias_shape = None if bias is None else bias.shape
+        return out
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, g):
+        Wt, = ctx.saved_tensors
+        S, n, T, f, H, N, K = ctx.dims
+        L = _lib.lib()
+        g = _aligned_input(g.float().contiguous())
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx = dW = None
+        if need_x or need_w:
+            G = torch.empty((K, S, n, T * f), dtype=torch.float32, device=g.device) if need_x else None
+            dW = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
+            ws = _workspace(L.tgcn_cheb_series_backward_workspace_bytes(S, n, T, f, H, N, K), g.device, floor=16)
+            _lib.check(L.tgcn_cheb_series_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
+                                                       1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel()))
+            ctx.stack = None
+            if need_x:
+                gx = _adjoint_hops(ctx.op.transpose(), G, ctx.mode).reshape(S, n, T, f)
+            if need_w:
+                if ctx.fold is not None:
+                    dW = fold_weight(ctx.fold, dW, transpose=True)
+                dW = dW.view(K, H, f, N)
+        gb = None
+        if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
+            if ctx.as_series:
+                gb = (g.sum(dim=(0, 1, 2)) if ctx.bias_kind == BIAS_CHANNEL else g.sum(dim=(0, 2))).reshape(ctx.bias_shape)
+            else:
+                gb = _bias_grad(g, ctx.bias_kind, ctx.bias_shape, True)
+        return gx, dW, gb, None, None, None, None
+
+
+def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_series=False):
+    """Streaming form of TGCNCheb_H / ChebTimeConv on sliding windows: series (S, n, T) raw recordings with weight (K, H, N), or
+    (S, n, T, f) with weight (K, H, f, N), in the reference basis.  Returns (S * (T-H+1), n, N), identical to running the layer on the
+    windowed batch x[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c] (load/data_hcp.py:146-152), but the K-1 hops run once on the T time
+    rows of each recording -- in the backward too, so the windows it replaces can be trained through.
+    as_series=True returns the same numbers as (S, n, T-H+1, N), contiguous: itself a series, which the next time layer streams over.
+    A single-channel series with as_series=False takes the scalar-load form (ChebWindowsFn, one projection launch per recording); every
+    other call the sliding-window MFMA kernels (ChebSeriesFn, one launch for all recordings)."""
+    if param_dtype(weight, bias, "cheb_time_windows") == BF16:
         raise _lib.TgcnError("forward_series / cheb_time_windows: bfloat16 parameters are not supported")
-    _lib.require_device(series, weight_khg, bias)
+    if series.dim() not in (3, 4) or weight.dim() != series.dim():
+        raise _lib.TgcnError("cheb_time_windows: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
+                             "(got %s and %s)" % (tuple(series.shape), tuple(weight.shape)))
+    f = series.shape[3] if series.dim() == 4 else 1
+    if series.dim() == 4 and weight.shape[2] != f:
+        raise _lib.TgcnError("cheb_time_windows: the series has %d channels, the weight %d" % (f, weight.shape[2]))
+    if series.shape[2] < weight.shape[1]:
+        raise _lib.TgcnError("cheb_time_windows: %d time steps are fewer than one window of %d" % (series.shape[2], weight.shape[1]))
+    _lib.require_device(series, weight, bias)
+    if f == 1 and not as_series:
+        if series.dim() == 4:
+            series, weight = series.reshape(series.shape[:3]), weight.reshape(weight.shape[0], weight.shape[1], weight.shape[3])
+        series, bias = _to_operand_labels(op, series, bias, bias_kind)
+        out = ChebWindowsFn.apply(series, weight, bias, op, mode, bias_kind)
+        return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)
+    if series.dim() == 3:
+        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
     series, bias = _to_operand_labels(op, series, bias, bias_kind)
-    out = ChebWindowsFn.apply(series, weight_khg, bias, op, mode, bias_kind)
-    return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)
+    out = ChebSeriesFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series))
+    return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)      # the vertex axis is dim 1 in both layouts
 
 
 @_on_device

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""forward_series on multi-channel series against the only thing the modules offered for those shapes before: the same module's forward on
+the materialised windowed batch xw[s*nwin + w, i, h, c] = series[s, i, w + h, c] (built once, outside the timed region).  Events around the
+call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + backward.  Developer tool; bench.py's headline is untouched.
+
+    python tools/series_bench.py [--steps 5] [--warmup 2] [--out profiles/r08_series_channels.json]
+
+Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
+32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
+streaming passes the first layer's output on as a series (as_series=True), the baseline cuts the second layer's windows out of the first
+layer's output inside the timed region (it has to: they do not exist before)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+import tgcn_amd  # noqa: E402
+from tgcn_amd import _lib  # noqa: E402
+from tgcn_amd.graph import GraphOperand  # noqa: E402
+from tools import synth  # noqa: E402
+from tools.precision_bench import measure  # noqa: E402
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
+
+
+def dti148(dev):
+    z = np.load(os.path.join(GOLDEN, "TGCNChebH_dti148_q4_f1_g32_K10_H15.npz"))
+    n = int(z["n"])
+    rowptr = torch.as_tensor(z["rowptr"]).long()
+    row = torch.repeat_interleave(torch.arange(n), rowptr[1:] - rowptr[:-1])
+    return GraphOperand.from_coo(n, row.to(dev), torch.as_tensor(z["col"]).long().to(dev), torch.as_tensor(z["val"]).float().to(dev))
+
+
+def windows(series, H):
+    """(S, n, T, f) -> (S*nwin, n, H, f), contiguous"""
+    S, n, T, f = series.shape
+    nwin = T - H + 1
+    return series.unfold(2, H, 1).permute(0, 2, 1, 4, 3).reshape(S * nwin, n, H, f).contiguous()
+
+
+def timed(fn, train, steps, warmup):
+    def call():
+        if train:
+            out = fn()
+            out.backward(torch.ones_like(out))
+        else:
+            with torch.no_grad():
+                fn()
+    r, _ = measure(call, steps, warmup)
+    if train:
+        r["note"] = "kernel times cover the forward only: the backward runs on autograd's thread, which the thread-local launch record does not see"
+    return r
+
+
+def compare(stream, batch, steps, warmup):
+    out = {}
+    for train in (False, True):
+        s, b = timed(stream, train, steps, warmup), timed(batch, train, steps, warmup)
+        out["forward_backward" if train else "forward"] = dict(streaming=s, materialised=b,
+                                                                materialised_over_streaming=round(b["ms_per_call"] / s["ms_per_call"], 3))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, cases={})
+    torch.manual_seed(0)
+
+    def case(name, desc, layer, series, H):
+        series = series.requires_grad_(True)
+        xw = windows(series.detach(), H).requires_grad_(True)
+        entry = dict(desc=desc, **compare(lambda: layer.forward_series(series), lambda: layer(xw), args.steps, args.warmup))
+        res["cases"][name] = entry
+        print(json.dumps({name: entry}), flush=True)
+        del xw
+        torch.cuda.empty_cache()
+
+    op = dti148(dev)
+    S, T, H, K = 8, 284, 15, 10
+    l1 = tgcn_amd.TGCNCheb_H(op, 1, 32, K, H).to(dev)
+    l2 = tgcn_amd.TGCNCheb_H(op, 32, 64, K, H).to(dev)
+    case("a_dti148_1to32", "dti148 S=8 T=284 H=15 K=10 f=1 -> g=32", l1, torch.randn(S, op.n, T, 1, device=dev), H)
+    case("a_dti148_32to64", "dti148 S=8 T=284 H=15 K=10 f=32 -> g=64", l2, torch.randn(S, op.n, T, 32, device=dev), H)
+
+    n, row, col, val = synth.sheet_mesh(300, device=dev)
+    opm = GraphOperand.from_coo(n, row, col, val, dev)
+    lm = tgcn_amd.TGCNCheb_H(opm, 4, 32, 5, 15).to(dev)
+    case("b_mesh90k_4to32", "sheet_mesh(300) n=%d S=1 T=75 H=15 K=5 f=4 -> g=32" % n, lm, torch.randn(1, n, 75, 4, device=dev), 15)
+    del lm, opm
+    torch.cuda.empty_cache()
+
+    series = torch.randn(S, op.n, T, 1, device=dev).requires_grad_(True)
+    xw1 = windows(series.detach(), H).requires_grad_(True)
+    T1 = T - H + 1
+
+    def chain_stream():
+        return l2.forward_series(torch.relu(l1.forward_series(series, as_series=True)))
+
+    def chain_batch():
+        h = torch.relu(l1(xw1))                                           # (S*T1, n, 32)
+        return l2(windows(h.view(S, T1, op.n, 32).permute(0, 2, 1, 3), H))
+    entry = dict(desc="dti148 S=8 T=284: TGCNCheb_H(1,32,10,15) -> relu -> TGCNCheb_H(32,64,10,15)", **compare(chain_stream, chain_batch, args.steps, args.warmup))
+    res["cases"]["c_dti148_chain"] = entry
+    print(json.dumps({"c_dti148_chain": entry}), flush=True)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
