@@ -323,6 +323,13 @@ int tgcn_cheb_series_backward_f32(void* stream, int64_t S, int64_t n_vertices, i
                                   const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
                                   void* workspace, size_t workspace_bytes);
 
+/* Host-only query of the launch tgcn_cheb_project_series_f32 / the input gradient of tgcn_cheb_series_backward_f32 make for H time rows of f
+ * channels and N columns (forward: (H, f, N); input gradient: (H, N, K*f)); vec = 16-byte loads (f % 4 == 0 and an aligned source).
+ *   hc: weight time rows per staged LDS span (hc == H: the whole horizon at once; less: the horizon in chunks); lds_bytes: dynamic LDS of
+ *   the launch (above 65536: the device's opt-in limit is used; without a device that limit is 65536).
+ * TGCN_ERR_UNSUPPORTED when one time row does not fit the limit: the launch would be refused with the same code. */
+int tgcn_series_gemm_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t* hc, int32_t* lds_bytes);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

@@ -19,6 +19,7 @@ SCALARS = (ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32, ctypes
 class _Recorder:
     def __init__(self, small):
         self.calls, self.small = [], small
+        self.nulls = []           # per logged call: the positions of its void* arguments that were null
 
     def __getattr__(self, name):
         if name.endswith("_supported"):
@@ -32,6 +33,7 @@ class _Recorder:
             types = _lib.SIGNATURES[name][1]
             nums = [("%g" % a if isinstance(a, float) else str(a)) for a, t in zip(args, types) if t in SCALARS]
             self.calls.append(" ".join([name[len("tgcn_"):].replace("_f32", "")] + nums))
+            self.nulls.append(tuple(i for i, (a, t) in enumerate(zip(args, types)) if t is ctypes.c_void_p and not getattr(a, "value", a)))
             return 0
         return launch
 

@@ -55,6 +55,36 @@ def test_multi_channel_series_launches_the_series_entries_once(mode, as_series, 
     assert back == (["cheb_series_backward %d %d %d %d %d %d %d %d 1024" % (S, N_V, T, f, H, N, K, int(as_series))] if train else [])
 
 
+# positions of the nullable pointers in tgcn_cheb_series_backward_f32(stream, S, n, T, f, H, N, K, stack, g, g_as_series, W, G, dW, ws, bytes)
+_STACK, _G, _DW = 8, 12, 13
+
+
+@pytest.mark.parametrize("as_series", [False, True], ids=["window-major", "series"])
+@pytest.mark.parametrize("need_series,need_params", [(True, True), (False, True), (True, False), (False, False)],
+                         ids=["both", "first-layer", "frozen", "nothing"])
+def test_one_sided_backwards_pass_null_pointers(need_series, need_params, as_series, recorder):
+    """G is null when the series needs no gradient, dW (and the hop stack it contracts) when the parameters are frozen; when nothing needs
+    a gradient there is no backward call at all"""
+    rec = recorder({})
+    S, T, H, f, N, K = 2, T_WIN, 5, 4, 8, 3
+    torch.manual_seed(0)
+    series = torch.randn(S, N_V, T, f, requires_grad=need_series)
+    W, bias = torch.randn(K, H, f, N, requires_grad=need_params), torch.randn(N, requires_grad=need_params)
+    out = F.cheb_time_windows(_op("plain"), series, W, bias, F.BIAS_CHANNEL, 0, as_series=as_series)
+    assert out.requires_grad == (need_series or need_params)
+    if out.requires_grad:
+        out.backward(torch.ones_like(out))
+    assert (series.grad is not None) == need_series and (W.grad is not None) == need_params and (bias.grad is not None) == need_params
+    back = [i for i, c in enumerate(rec.calls) if c.startswith("cheb_series_backward ")]
+    assert len(back) == (1 if need_series or need_params else 0)
+    for i in back:
+        assert rec.calls[i] == "cheb_series_backward %d %d %d %d %d %d %d %d 1024" % (S, N_V, T, f, H, N, K, int(as_series))
+        nulls = set(rec.nulls[i]) - {0}            # the recorder's stream is null
+        assert nulls == ({_G} if not need_series else set()) | ({_STACK, _DW} if not need_params else set()), nulls
+    # the adjoint hops run only for a series that needs its gradient
+    assert len([c for c in rec.calls if c.startswith("csr_hop2 ")]) == (K - 1) * (2 if need_series else 1)
+
+
 @pytest.mark.parametrize("train", [False, True], ids=["inference", "training"])
 def test_single_channel_in_the_series_layout_launches_the_series_entries(train, recorder):
     rec = recorder({})

@@ -43,15 +43,19 @@ struct ProfScope {
 };
 
 // Kernels that take more than 64 KB of dynamic LDS.  The attribute belongs to the calling thread's current device
-// (nn.DataParallel drives several devices from one process), so it is set once per (device, kernel).
+// (nn.DataParallel drives several devices from one process), so it is kept per (device, kernel): set on the first request and raised
+// when a later launch of the same kernel asks for more (series_gemm_launch and hop_kernel's pad pass the launch's own size).
 inline void allow_large_lds(const void* fn, int bytes) {
   static std::mutex mu;
-  static std::set<std::pair<int, const void*>> done;
+  static std::map<std::pair<int, const void*>, int> largest;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return;
   std::lock_guard<std::mutex> lk(mu);
-  if (done.insert(std::make_pair(dev, fn)).second)
+  int& have = largest[std::make_pair(dev, fn)];
+  if (bytes > have) {
     (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);   // a refusal surfaces as a launch error
+    have = bytes;
+  }
 }
 
 // Compute units of the calling thread's current device (256 on MI355X), read once per device: round sizes of one-workgroup-per-CU

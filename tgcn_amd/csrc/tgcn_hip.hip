@@ -22,6 +22,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <map>
 #include <new>
 #include <numeric>
 #include <mutex>
@@ -1193,11 +1194,22 @@ static int series_gemm_lds(int H, int f, int NT, bool vec, int* hc_out) {
   return 0;
 }
 
+static int series_gemm_nt(int N) { return N <= 16 ? 1 : (N <= 32 ? 2 : 4); }
+
+int tgcn_series_gemm_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t* hc, int32_t* lds_bytes) {
+  if (H < 1 || f < 1 || N < 1 || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_gemm_plan: bad argument");
+  int h = 0;
+  const int lds = series_gemm_lds(H, f, series_gemm_nt(N), vec != 0, &h);
+  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_gemm_plan: %d channels per time row do not fit the LDS span", f);
+  *hc = h; *lds_bytes = lds;
+  return TGCN_OK;
+}
+
 static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who) {
   p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
   p.ntiles = S * p.n * p.tpv;
   const int64_t gx = (p.ntiles + 3) / 4;
-  const int NT = p.N <= 16 ? 1 : (p.N <= 32 ? 2 : 4);
+  const int NT = series_gemm_nt(p.N);
   const int64_t gy = (p.N + NT * 16 - 1) / (NT * 16);
   if (gx > (int64_t)INT32_MAX || gy > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
   int hc = 0;
