@@ -330,6 +330,30 @@ int tgcn_cheb_series_backward_f32(void* stream, int64_t S, int64_t n_vertices, i
  * TGCN_ERR_UNSUPPORTED when one time row does not fit the limit: the launch would be refused with the same code. */
 int tgcn_series_gemm_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t* hc, int32_t* lds_bytes);
 
+/* The two entries above as a convolution over time with a window step and zero padding ("stride and padding"):
+ * 0 <= pad_left, pad_right <= H-1 zero time rows in front of / behind every recording, Tp = T + pad_left + pad_right >= H,
+ * nwin = (Tp - H) / stride + 1 windows, window w covering the time rows w*stride - pad_left ... + H - 1 (zeros outside 0 <= t < T):
+ *   out[(s, w, i), :] = sum_k sum_{h, c} stack[k, s, i, (w*stride - pad_left + h)*f + c] . W[k, h*f + c, :] + bias
+ * with out (S*nwin, n_vertices, N) or, as_series, (S, n_vertices, nwin, N).  stack stays (K, S, n_vertices, T*f): nothing is padded in memory.
+ * Backward: G (nullable, (K, S, n_vertices, T*f)) is written whole -- time rows that no window covers get exact zeros, gradient that falls
+ * into the padding is dropped -- by one step-1 launch of the forward's kernel per phase (t + pad_left) % stride, each over the weight time
+ * rows of its phase; dW (nullable) as above, a (w, h) pair outside the recording contributing nothing.  A stride above Tp (one window) is
+ * taken as Tp.  (stride, pad_left, pad_right) = (1, 0, 0) makes the launches of the entries above: bit-identical results. */
+int tgcn_cheb_project_series_conv_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
+                                      int32_t stride, int32_t pad_left, int32_t pad_right);
+size_t tgcn_cheb_series_conv_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                      int32_t stride, int32_t pad_left, int32_t pad_right);
+int tgcn_cheb_series_conv_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                       const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
+                                       void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right);
+
+/* tgcn_series_gemm_plan for a window step: the span of hc weight time rows holds 31 * min(stride, hc) + hc time rows (from stride >= hc on
+ * only the rows that are read are staged), so a step moves ordinary shapes out of the whole-horizon regime earlier.  The padding does not
+ * enter.  The forward asks with (H, f, N, stride).  The input gradient runs its phases at step 1 on g as a series of N channels; phase 0 has
+ * the most weight time rows and asks with (ceil(H / stride), N, K*f, 1), the other phases with that or one row less. */
+int tgcn_series_conv_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

@@ -1184,28 +1184,39 @@ int tgcn_cheb_windows_backward_f32(void* stream, int64_t S, int64_t n_vertices, 
 // ---- streaming time windows of multi-channel series (windows.h)
 // Chooses HC (weight time rows per staged span) and the dynamic LDS of series_gemm_kernel: the whole horizon when four spans and the weight
 // tile fit 64 KB, else the largest chunk that does, else the largest that fits the device's opt-in limit; 0 when even one row does not.
-static int series_gemm_lds(int H, int f, int NT, bool vec, int* hc_out) {
+// stride: the window step (the span of hc rows then holds 31 * min(stride, hc) + hc time rows, series_span_floats).
+static int series_gemm_lds(int H, int f, int NT, bool vec, int stride, int* hc_out) {
   const int ws = kSgKT * series_ws_stride(NT);
-  auto bytes = [&](int hc) { return (size_t)(ws + 4 * series_span_floats(hc, f, vec)) * sizeof(float); };
+  auto bytes = [&](int hc) { return (size_t)(ws + 4 * (size_t)series_span_floats(hc, f, vec, stride)) * sizeof(float); };      // 64-bit
   const size_t limits[2] = {64 * 1024, (size_t)lds_optin_limit()};
   for (size_t lim : limits)
     for (int hc = H; hc >= 1; --hc)
-      if (bytes(hc) <= lim) { *hc_out = hc; return (int)bytes(hc); }
+      if (bytes(hc) <= lim) { *hc_out = hc; return (int)bytes(hc); }      // <= the limit: the kernel's 32-bit span arithmetic is safe
   return 0;
 }
 
 static int series_gemm_nt(int N) { return N <= 16 ? 1 : (N <= 32 ? 2 : 4); }
 
+int tgcn_series_conv_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes) {
+  if (H < 1 || f < 1 || N < 1 || stride < 1 || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_conv_plan: bad argument");
+  int h = 0;
+  const int lds = series_gemm_lds(H, f, series_gemm_nt(N), vec != 0, stride, &h);
+  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_conv_plan: %d channels per time row do not fit the LDS span", f);
+  *hc = h; *lds_bytes = lds;
+  return TGCN_OK;
+}
+
 int tgcn_series_gemm_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t* hc, int32_t* lds_bytes) {
   if (H < 1 || f < 1 || N < 1 || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_gemm_plan: bad argument");
   int h = 0;
-  const int lds = series_gemm_lds(H, f, series_gemm_nt(N), vec != 0, &h);
+  const int lds = series_gemm_lds(H, f, series_gemm_nt(N), vec != 0, 1, &h);
   if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_gemm_plan: %d channels per time row do not fit the LDS span", f);
   *hc = h; *lds_bytes = lds;
   return TGCN_OK;
 }
 
-static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who) {
+// stride >= 2 takes the STRIDED instantiations; stride 1 (the input gradient's phases included) the ones without a step
+static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1) {
   p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
   p.ntiles = S * p.n * p.tpv;
   const int64_t gx = (p.ntiles + 3) / 4;
@@ -1213,18 +1224,22 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
   const int64_t gy = (p.N + NT * 16 - 1) / (NT * 16);
   if (gx > (int64_t)INT32_MAX || gy > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
   int hc = 0;
-  const int lds = series_gemm_lds(p.H, p.f, NT, vec, &hc);
+  const int lds = series_gemm_lds(p.H, p.f, NT, vec, stride, &hc);
   if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, p.f);
   p.HC = hc;
+  p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = series_row_floats(hc, p.f, vec, stride);
   const dim3 grid((unsigned)gx, (unsigned)gy);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_GEMM(NT_, VEC_)                                                                   \
-  do {                                                                                                \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_kernel<NT_, VEC_>, lds);            \
-    hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_>), grid, dim3(kBlock), lds, st, p);              \
+#define TGCN_SERIES_GEMM(NT_, VEC_, STR_)                                                                   \
+  do {                                                                                                      \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_kernel<NT_, VEC_, STR_>, lds);            \
+    hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_, STR_>), grid, dim3(kBlock), lds, st, p);              \
   } while (0)
-  if (vec) { if (NT == 1) TGCN_SERIES_GEMM(1, true); else if (NT == 2) TGCN_SERIES_GEMM(2, true); else TGCN_SERIES_GEMM(4, true); }
-  else { if (NT == 1) TGCN_SERIES_GEMM(1, false); else if (NT == 2) TGCN_SERIES_GEMM(2, false); else TGCN_SERIES_GEMM(4, false); }
+#define TGCN_SERIES_GEMM_NT(VEC_, STR_)                                                                     \
+  do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_); else TGCN_SERIES_GEMM(4, VEC_, STR_); } while (0)
+  if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false); else TGCN_SERIES_GEMM_NT(false, false); }
+  else { if (vec) TGCN_SERIES_GEMM_NT(true, true); else TGCN_SERIES_GEMM_NT(false, true); }
+#undef TGCN_SERIES_GEMM_NT
 #undef TGCN_SERIES_GEMM
   return TGCN_OK;
 }
@@ -1234,12 +1249,21 @@ static bool series_shape_ok(int64_t S, int64_t n, int32_t T, int32_t f, int32_t 
          (int64_t)H * f < (int64_t)INT32_MAX / 2 && (int64_t)H * N < (int64_t)INT32_MAX / 2 && (int64_t)K * f < (int64_t)INT32_MAX;
 }
 
-int tgcn_cheb_project_series_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                 const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out) {
-  if (!series_shape_ok(S, n_vertices, T, f, H, N, K) || !stack || !W || !out) TGCN_FAIL(TGCN_ERR_INVALID, "project_series: bad argument");
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series: bias_kind %d", bias_kind);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series")) return drc;
-  const int64_t n = n_vertices, Tf = (int64_t)T * f, nwin = T - H + 1;
+// The geometry of the strided, zero-padded entries: pads within a window (every window touches a real row), the padded series holds a window,
+// and 64 padded series stay inside 32-bit time arithmetic (a wave addresses 32 windows of it)
+static bool series_conv_shape_ok(int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, int32_t stride, int32_t pl, int32_t pr) {
+  if (!(H >= 1 && T >= 1 && stride >= 1 && pl >= 0 && pr >= 0 && pl < H && pr < H)) return false;
+  const int64_t Tp = (int64_t)T + pl + pr;
+  return Tp >= H && Tp * 64 < (int64_t)INT32_MAX && Tp * f < (int64_t)INT32_MAX && series_shape_ok(S, n, (int32_t)Tp, f, H, N, K);
+}
+// A step beyond the padded series leaves one window, as every step above Tp - H does: clamped, so that 32 * stride stays a 32-bit number
+static int32_t series_conv_stride(int32_t T, int32_t stride, int32_t pl, int32_t pr) { return stride < T + pl + pr ? stride : T + pl + pr; }
+static int64_t series_conv_nwin(int32_t T, int32_t H, int32_t stride, int32_t pl, int32_t pr) { return ((int64_t)T + pl + pr - H) / stride + 1; }
+
+static int project_series_impl(hipStream_t st, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, const float* stack,
+                               const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out, int32_t stride, int32_t pl,
+                               int32_t pr, const char* who) {
+  const int64_t Tf = (int64_t)T * f, nwin = series_conv_nwin(T, H, stride, pl, pr);
   SeriesGemmParams p;
   memset(&p, 0, sizeof(p));
   p.src = stack; p.W = W; p.bias = bias; p.out = out;
@@ -1247,10 +1271,33 @@ int tgcn_cheb_project_series_f32(void* stream, int64_t S, int64_t n_vertices, in
   if (as_series) { p.o_ss = n * nwin * N; p.o_is = nwin * N; p.o_ws = N; }      // (S, n, nwin, N)
   else { p.o_ss = nwin * n * N; p.o_is = N; p.o_ws = n * N; }                     // (S, nwin, n, N)
   p.o_gs = 0; p.ocg = N;
-  p.n = n; p.Tin = T; p.padl = 0; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
+  p.n = n; p.Tin = T; p.padl = pl; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
   const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0);
-  if (int rc = series_gemm_launch((hipStream_t)stream, p, S, vec, "project_series")) return rc;
+  return series_gemm_launch(st, p, S, vec, who, stride);
+}
+
+int tgcn_cheb_project_series_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                 const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out) {
+  if (!series_shape_ok(S, n_vertices, T, f, H, N, K) || !stack || !W || !out) TGCN_FAIL(TGCN_ERR_INVALID, "project_series: bad argument");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series: bias_kind %d", bias_kind);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series")) return drc;
+  if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, 1, 0, 0,
+                                   "project_series")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_f32");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_series_conv_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
+                                      int32_t stride, int32_t pad_left, int32_t pad_right) {
+  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right) || !stack || !W || !out)
+    TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv: bad argument");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv: bias_kind %d", bias_kind);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_conv")) return drc;
+  stride = series_conv_stride(T, stride, pad_left, pad_right);
+  if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, stride, pad_left,
+                                   pad_right, "project_series_conv")) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_conv_f32");
   return TGCN_OK;
 }
 
@@ -1263,11 +1310,85 @@ static int64_t series_wgrad_rows_per_block(int64_t M, int64_t weight_floats) {
   return rpb;
 }
 
-size_t tgcn_cheb_series_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K) {
-  if (!series_shape_ok(S, n_vertices, T, f, H, N, K)) return 0;
-  const int64_t wf = (int64_t)K * H * f * N, M = S * n_vertices * (T - H + 1);
+static size_t series_backward_workspace(int64_t M, int64_t wf) {
   const int64_t rpb = series_wgrad_rows_per_block(M, wf);
   return align_up((size_t)wf * sizeof(float), 256) + (size_t)((M + rpb - 1) / rpb) * wf * sizeof(float);
+}
+
+size_t tgcn_cheb_series_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K) {
+  if (!series_shape_ok(S, n_vertices, T, f, H, N, K)) return 0;
+  return series_backward_workspace(S * n_vertices * (T - H + 1), (int64_t)K * H * f * N);
+}
+
+size_t tgcn_cheb_series_conv_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                      int32_t stride, int32_t pad_left, int32_t pad_right) {
+  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right)) return 0;
+  stride = series_conv_stride(T, stride, pad_left, pad_right);
+  return series_backward_workspace(S * n_vertices * series_conv_nwin(T, H, stride, pad_left, pad_right), (int64_t)K * H * f * N);
+}
+
+// Both gradients for a window step and zero padding; (1, 0, 0) is tgcn_cheb_series_backward_f32's launch sequence, launch for launch.
+static int series_backward_impl(hipStream_t st, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, const float* stack,
+                                const float* g, int32_t g_as_series, const float* W, float* G, float* dW, void* workspace, int32_t stride,
+                                int32_t pl, int32_t pr, const char* who) {
+  const int64_t Tf = (int64_t)T * f, nwin = series_conv_nwin(T, H, stride, pl, pr), wf = (int64_t)K * H * f * N;
+  const bool conv = stride != 1 || pl != 0 || pr != 0;
+  int64_t g_ss, g_is, g_ws;
+  if (g_as_series) { g_ss = n * nwin * N; g_is = nwin * N; g_ws = N; }
+  else { g_ss = nwin * n * N; g_is = N; g_ws = n * N; }
+  if (G) {      // the forward's kernel over g as a series of N channels, columns (k, c); per phase of the window step, each at step 1
+    if (!W) TGCN_FAIL(TGCN_ERR_INVALID, "%s: the input gradient needs W", who);
+    float* Wd = (float*)workspace;
+    { ProfScope ps(TGCN_PROF_RELAYOUT, st);
+      hipLaunchKernelGGL(series_flip_weight_kernel, dim3(grid_1d(wf)), dim3(kBlock), 0, st, W, Wd, (int)K, (int)H, (int)f, (int)N, (int)stride); }
+    // the time rows of the phases ph >= H (a step longer than the window) lie between the windows: exact zeros
+    if (stride > H && hipMemsetAsync(G, 0, (size_t)K * S * n * Tf * sizeof(float), st) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "%s: memset failed", who);
+    const bool vec = (N % 4 == 0) && (((uintptr_t)g & 15) == 0);
+    for (int ph = 0; ph < stride && ph < H; ++ph) {
+      // time rows t = u * stride + ph - pl, u0 <= u <= u1; row u sums g[u - m] W[ph + m * stride]^T over m < Hp: "window" u - u0 of the
+      // Hp-row kernel reaching Hp - 1 - u0 rows back
+      const int Hp = series_phase_rows(H, stride, ph);
+      // (a recording shorter than the phase, T + pl <= ph, has no time row of it: what its windows send there falls into the right padding)
+      if ((int64_t)T - 1 + pl - ph < 0) continue;
+      const int64_t u0 = ph >= pl ? 0 : (pl - ph + stride - 1) / stride, u1 = ((int64_t)T - 1 + pl - ph) / stride;
+      if (u1 < u0) continue;
+      SeriesGemmParams p;
+      memset(&p, 0, sizeof(p));
+      p.src = g; p.W = Wd + (int64_t)series_phase_row0(H, stride, ph) * N * K * f; p.bias = nullptr;
+      p.out = G + (u0 * stride + ph - pl) * f;
+      p.src_ks = 0; p.src_ss = g_ss; p.src_is = g_is; p.src_ts = g_ws;
+      p.o_ss = n * Tf; p.o_is = Tf; p.o_ws = (int64_t)stride * f; p.o_gs = S * n * Tf; p.ocg = f;
+      p.n = n; p.Tin = (int32_t)nwin; p.padl = (int32_t)(Hp - 1 - u0); p.nwin = (int32_t)(u1 - u0 + 1); p.H = Hp; p.f = N; p.N = K * f; p.nterms = 1;
+      p.bias_kind = 0;
+      if (int rc = series_gemm_launch(st, p, S, vec, who)) return rc;
+    }
+  }
+  if (dW) {
+    if (!stack) TGCN_FAIL(TGCN_ERR_INVALID, "%s: the weight gradient needs the hop tensors", who);
+    const int64_t M = S * n * nwin;
+    SeriesWgradParams q;
+    memset(&q, 0, sizeof(q));
+    q.stack = stack; q.g = g; q.partial = (float*)((char*)workspace + align_up((size_t)wf * sizeof(float), 256));
+    q.st_ks = S * n * Tf; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
+    q.M = M; q.rows_per_block = series_wgrad_rows_per_block(M, wf); q.n = n;
+    q.Tf = (int32_t)Tf; q.f = f; q.nwin = (int32_t)nwin; q.J = H * f; q.N = N; q.K = K;
+    q.stride = stride; q.padl = pl; q.T = T;
+    const int64_t nblocks = (M + q.rows_per_block - 1) / q.rows_per_block;
+    const int64_t jtiles = (q.J + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
+    if (q.rows_per_block + nwin >= (int64_t)INT32_MAX || q.rows_per_block / nwin + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX ||
+        (N + 63) / 64 > 65535 || jtiles * tgroups > 65535)
+      TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: weight gradient shape too large", who);
+    { ProfScope ps(TGCN_PROF_WGRAD, st);
+      const dim3 grid((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups));
+      if (conv) hipLaunchKernelGGL(series_wgrad_partial_kernel<true>, grid, dim3(64), 0, st, q);
+      else hipLaunchKernelGGL(series_wgrad_partial_kernel<false>, grid, dim3(64), 0, st, q); }
+    WgradParams r;
+    memset(&r, 0, sizeof(r));
+    r.partial = q.partial; r.dW = dW; r.Kc = q.J; r.N = N; r.nterms = K; r.nblocks = (int32_t)nblocks;
+    { ProfScope ps(TGCN_PROF_WGRAD, st);
+      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
+  }
+  return TGCN_OK;
 }
 
 int tgcn_cheb_series_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
@@ -1277,48 +1398,24 @@ int tgcn_cheb_series_backward_f32(void* stream, int64_t S, int64_t n_vertices, i
   if (int drc = check_pointer_device(g, (hipStream_t)stream, "series_backward")) return drc;
   const size_t need = tgcn_cheb_series_backward_workspace_bytes(S, n_vertices, T, f, H, N, K);
   if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) TGCN_FAIL(TGCN_ERR_WORKSPACE, "series_backward: workspace %zu < %zu", workspace_bytes, need);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t n = n_vertices, Tf = (int64_t)T * f, nwin = T - H + 1, wf = (int64_t)K * H * f * N;
-  int64_t g_ss, g_is, g_ws;
-  if (g_as_series) { g_ss = n * nwin * N; g_is = nwin * N; g_ws = N; }
-  else { g_ss = nwin * n * N; g_is = N; g_ws = n * N; }
-  if (G) {      // the forward's kernel over g as a series of N channels: T output "windows" reaching H - 1 rows back, columns (k, c)
-    if (!W) TGCN_FAIL(TGCN_ERR_INVALID, "series_backward: the input gradient needs W");
-    float* Wd = (float*)workspace;
-    { ProfScope ps(TGCN_PROF_RELAYOUT, st);
-      hipLaunchKernelGGL(series_flip_weight_kernel, dim3(grid_1d(wf)), dim3(kBlock), 0, st, W, Wd, (int)K, (int)H, (int)f, (int)N); }
-    SeriesGemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.src = g; p.W = Wd; p.bias = nullptr; p.out = G;
-    p.src_ks = 0; p.src_ss = g_ss; p.src_is = g_is; p.src_ts = g_ws;
-    p.o_ss = n * Tf; p.o_is = Tf; p.o_ws = f; p.o_gs = S * n * Tf; p.ocg = f;
-    p.n = n; p.Tin = (int32_t)nwin; p.padl = H - 1; p.nwin = T; p.H = H; p.f = N; p.N = K * f; p.nterms = 1; p.bias_kind = 0;
-    const bool vec = (N % 4 == 0) && (((uintptr_t)g & 15) == 0);
-    if (int rc = series_gemm_launch(st, p, S, vec, "series_backward")) return rc;
-  }
-  if (dW) {
-    if (!stack) TGCN_FAIL(TGCN_ERR_INVALID, "series_backward: the weight gradient needs the hop tensors");
-    const int64_t M = S * n * nwin;
-    SeriesWgradParams q;
-    memset(&q, 0, sizeof(q));
-    q.stack = stack; q.g = g; q.partial = (float*)((char*)workspace + align_up((size_t)wf * sizeof(float), 256));
-    q.st_ks = S * n * Tf; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
-    q.M = M; q.rows_per_block = series_wgrad_rows_per_block(M, wf); q.n = n;
-    q.Tf = (int32_t)Tf; q.f = f; q.nwin = (int32_t)nwin; q.J = H * f; q.N = N; q.K = K;
-    const int64_t nblocks = (M + q.rows_per_block - 1) / q.rows_per_block;
-    const int64_t jtiles = (q.J + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
-    if (q.rows_per_block + nwin >= (int64_t)INT32_MAX || q.rows_per_block / nwin + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX ||
-        (N + 63) / 64 > 65535 || jtiles * tgroups > 65535)
-      TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_backward: weight gradient shape too large");
-    { ProfScope ps(TGCN_PROF_WGRAD, st);
-      hipLaunchKernelGGL(series_wgrad_partial_kernel, dim3((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups)), dim3(64), 0, st, q); }
-    WgradParams r;
-    memset(&r, 0, sizeof(r));
-    r.partial = q.partial; r.dW = dW; r.Kc = q.J; r.N = N; r.nterms = K; r.nblocks = (int32_t)nblocks;
-    { ProfScope ps(TGCN_PROF_WGRAD, st);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
-  }
+  if (int rc = series_backward_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, 1, 0, 0,
+                                    "series_backward")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_series_backward_f32");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_series_conv_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                       const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
+                                       void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right) {
+  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right) || !g) TGCN_FAIL(TGCN_ERR_INVALID, "series_conv_backward: bad argument");
+  if (int drc = check_pointer_device(g, (hipStream_t)stream, "series_conv_backward")) return drc;
+  const size_t need = tgcn_cheb_series_conv_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))
+    TGCN_FAIL(TGCN_ERR_WORKSPACE, "series_conv_backward: workspace %zu < %zu", workspace_bytes, need);
+  stride = series_conv_stride(T, stride, pad_left, pad_right);
+  if (int rc = series_backward_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, stride, pad_left,
+                                    pad_right, "series_conv_backward")) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_series_conv_backward_f32");
   return TGCN_OK;
 }
 

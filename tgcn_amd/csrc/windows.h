@@ -26,25 +26,44 @@ struct SeriesGemmParams {
   int64_t o_ss, o_is, o_ws, o_gs;   // output strides: recording, vertex, window, column group (column col lives at (col / ocg) * o_gs + col % ocg)
   int64_t n, ntiles;                // vertices per recording; wave tiles = S * n * tpv
   int32_t Tin, padl, nwin, H, f, N, nterms, ocg, bias_kind, tpv, HC;
+  int32_t stride, lst, fp;          // STRIDED only: window step in time rows, window distance in span rows, floats per span row
 };
 
 constexpr int kSgWin = 32;    // windows per wave
 constexpr int kSgKT = 32;     // weight rows per staged tile
 
-__host__ __device__ inline int series_span_floats(int hc, int f, bool vec) {
-  return vec ? (kSgWin - 1 + hc) * (f + 2) : ((kSgWin - 1 + hc) * f + 4 + 3) / 4 * 4;
+// With a window step (STRIDED, stride >= 2) window r of the wave starts stride time rows after window r - 1.  The span keeps the rows that
+// are READ: lst = min(stride, hc) span rows per window, span row r * lst + hh <-> time row t0 + r * stride + hh (hh < hc), so from
+// stride >= hc on (no two windows of a chunk share a row) it holds the 32 windows back to back, 31 * hc + hc rows, and never the rows
+// between them: a larger step costs no LDS and no loads beyond the no-overlap case.
+// Bank rule: the 16 windows x 2 k of a half wave (ds_read_b32: 32 banks, lanes (r, kq) at r * D + kq, D = lst * row floats) are
+// conflict-free exactly when D / 2 is odd.  VEC rows keep f + 2 floats for an odd lst (stride 1 included: today's layout) and f + 1 for
+// an even one -- odd rows make D / 2 odd for lst = 2 (mod 4); they are staged with 4-byte stores instead of 8-byte ones.  Cost: one
+// float per time row LESS than the odd case, and on the WRITE side four ds_write_b32 per staged float4 whose lanes sit 4 words apart
+// (32 banks, 8 of them hit by a half wave: about 4-way conflicted) -- paid once per staged float, which the conflict-free reads then
+// use about HC / lst times for each of the NT column tiles.  Residual: lst = 0 (mod 4) leaves D = 0 (mod 4) whatever the padding, 2^(e-1)-way for
+// lst = 2^e * odd (lst 4: 2-way, 8: 4-way).  Scalar-load spans (f % 4 != 0) stay the plain float sequence, D = lst * f, unpadded as at step 1.
+__host__ __device__ inline int series_span_lst(int hc, int stride) { return stride < hc ? stride : hc; }
+__host__ __device__ inline int series_row_floats(int hc, int f, bool vec, int stride) {
+  return !vec ? f : ((series_span_lst(hc, stride) & 1) ? f + 2 : f + 1);
+}
+// 64-bit: the host tries every hc <= H, and 32 * hc rows of f floats leave 32 bits for shapes the entries admit; what is launched fits the LDS
+__host__ __device__ inline int64_t series_span_floats(int hc, int f, bool vec, int stride = 1) {
+  const int64_t rows = (int64_t)(kSgWin - 1) * series_span_lst(hc, stride) + hc;
+  return vec ? rows * series_row_floats(hc, f, vec, stride) : (rows * f + 4 + 3) / 4 * 4;
 }
 __host__ __device__ constexpr int series_ws_stride(int NT) { return (NT * 16) % 32 == 0 ? NT * 16 + 16 : NT * 16; }
 
-template <int NT, bool VEC>
+template <int NT, bool VEC, bool STRIDED = false>
 __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmParams p) {
   constexpr int NW = NT * 16, NS = series_ws_stride(NT), WREG = (kSgKT * NW) / kBlock;
   extern __shared__ __attribute__((aligned(16))) float sg_lds[];
   float* Ws = sg_lds;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r = lane & 15, kq = lane >> 4;
-  const int fp = VEC ? p.f + 2 : p.f;
-  float* span = sg_lds + kSgKT * NS + wave * series_span_floats(p.HC, p.f, VEC);
+  const int fp = STRIDED ? p.fp : (VEC ? p.f + 2 : p.f);
+  const int lst = STRIDED ? p.lst : 1;          // span rows between consecutive windows
+  float* span = sg_lds + kSgKT * NS + wave * (int)(STRIDED ? series_span_floats(p.HC, p.f, VEC, p.stride) : series_span_floats(p.HC, p.f, VEC));
   const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
   const bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
@@ -63,9 +82,31 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
     const float* __restrict__ Wt = p.W + (int64_t)term * J * p.N;
     for (int hc0 = 0; hc0 < p.H; hc0 += p.HC) {
       const int hcn = min(p.HC, p.H - hc0);
-      const int rows = kSgWin - 1 + hcn, t0 = w0 + hc0 - p.padl;
+      const int rows = (kSgWin - 1) * lst + hcn, t0 = (STRIDED ? w0 * p.stride : w0) + hc0 - p.padl;
       // ---- this wave's span: time rows t0 .. t0 + rows - 1 (zeros outside the series, and for a wave without a tile)
-      if constexpr (VEC) {
+      if constexpr (STRIDED) {
+        // span row tr = wr * lst + hh holds time row t0 + wr * stride + hh; rows hh >= hcn lie between two windows (lst == HC > hcn): zeros
+        const int fq = VEC ? p.f >> 2 : p.f;                      // staged units (float4 / float) per time row
+        const int total = VEC ? rows * fq : ((rows * p.f + 4 + 3) / 4 * 4);
+        for (int e = lane; e < total; e += 64) {
+          const int tr = e / fq, cu = e - tr * fq;
+          const int wr = tr / lst, hh = tr - wr * lst;
+          const int t = t0 + wr * p.stride + hh;
+          const bool ok = live && tr < rows && hh < hcn && t >= 0 && t < p.Tin;
+          if constexpr (VEC) {
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (ok) v = *reinterpret_cast<const float4*>(base + (int64_t)t * p.src_ts + cu * 4);
+            float* d = span + tr * fp + cu * 4;
+            if (fp & 1) { d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }      // odd rows: 4-byte aligned only
+            else {
+              reinterpret_cast<float2*>(d)[0] = make_float2(v.x, v.y);
+              reinterpret_cast<float2*>(d)[1] = make_float2(v.z, v.w);
+            }
+          } else {
+            span[e] = ok ? base[(int64_t)t * p.src_ts + cu] : 0.f;
+          }
+        }
+      } else if constexpr (VEC) {
         const int f4 = p.f >> 2, total4 = rows * f4;
         for (int e = lane; e < total4; e += 64) {
           const int tr = e / f4, c = (e - tr * f4) * 4, t = t0 + tr;
@@ -76,7 +117,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
           d[1] = make_float2(v.z, v.w);
         }
       } else {
-        const int total = series_span_floats(hcn, p.f, false);
+        const int total = (int)series_span_floats(hcn, p.f, false);
         for (int e = lane; e < total; e += 64) {
           const int tr = e / p.f, c = e - tr * p.f, t = t0 + tr;
           span[e] = (live && tr < rows && t >= 0 && t < p.Tin) ? base[(int64_t)t * p.src_ts + c] : 0.f;
@@ -98,14 +139,14 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
         for (int ks = 0; ks < ksteps; ++ks) {
           int aoff;
           if constexpr (VEC) {
-            aoff = (r + hh) * fp + cc + kq;
+            aoff = ((STRIDED ? r * lst : r) + hh) * fp + cc + kq;
             cc += 4;
             if (cc >= p.f) { cc = 0; ++hh; }
           } else {
-            aoff = r * p.f + j0 + ks * 4 + kq;  // < 31 * f + jn + 3: inside the zero-tailed span
+            aoff = (STRIDED ? r * lst : r) * p.f + j0 + ks * 4 + kq;  // < 31 * lst * f + jn + 3: inside the zero-tailed span
           }
           const float a0 = span[aoff];
-          const float a1 = span[aoff + 16 * fp];
+          const float a1 = span[aoff + (STRIDED ? 16 * lst : 16) * fp];
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt) {
             const float bv = Ws[(ks * 4 + kq) * NS + nt * 16 + r];
@@ -138,12 +179,21 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
   }
 }
 
-// Wd[(h', nn), (k, c)] = W[k, H - 1 - h', c, nn]: the weight of the input gradient as a sliding-window GEMM over g
-__global__ __launch_bounds__(kBlock) void series_flip_weight_kernel(const float* __restrict__ W, float* __restrict__ Wd, int K, int H, int f, int N) {
+// Wd[(h', nn), (k, c)] = W[k, H - 1 - h', c, nn]: the weight of the input gradient as a sliding-window GEMM over g.
+// With a window step the input gradient is one such GEMM per phase ph = (t + pad_left) % stride over the weight time rows h = ph + m * stride,
+// m < Hp = ceil((H - ph) / stride): the phases' weights lie one after the other, phase ph from row series_phase_row0(H, stride, ph) on,
+//   Wd_ph[(h', nn), (k, c)] = W[k, ph + (Hp - 1 - h') * stride, c, nn]        (stride 1: the one phase, the line above)
+__host__ __device__ inline int series_phase_rows(int H, int stride, int ph) { return ph < H ? (H - ph + stride - 1) / stride : 0; }
+__host__ __device__ inline int series_phase_row0(int H, int stride, int ph) { return ph * (H / stride) + (ph < H % stride ? ph : H % stride); }   // ph <= stride
+
+__global__ __launch_bounds__(kBlock) void series_flip_weight_kernel(const float* __restrict__ W, float* __restrict__ Wd, int K, int H, int f, int N,
+                                                                    int stride) {
   const int64_t total = (int64_t)K * H * f * N;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {   // index into W: (k, h, c, nn)
     const int nn = (int)(i % N), c = (int)((i / N) % f), h = (int)((i / ((int64_t)N * f)) % H), k = (int)(i / ((int64_t)N * f * H));
-    Wd[((int64_t)(H - 1 - h) * N + nn) * ((int64_t)K * f) + (int64_t)k * f + c] = W[i];
+    const int ph = h % stride, m = h / stride;
+    const int row = series_phase_row0(H, stride, ph) + series_phase_rows(H, stride, ph) - 1 - m;
+    Wd[((int64_t)row * N + nn) * ((int64_t)K * f) + (int64_t)k * f + c] = W[i];
   }
 }
 
@@ -154,6 +204,8 @@ __global__ __launch_bounds__(kBlock) void series_flip_weight_kernel(const float*
 // vertex, f floats apart, so the H-fold overlap is served by the caches), one wave per (row block, 64 columns of g, 16 rows j of the
 // weight, group of kWgTerms terms), fp32 MFMA with k = 4 rows per instruction; g is addressed by strides, so either output layout is read
 // in place.  Partials per row block, folded in block order by wgrad_reduce_kernel: deterministic.
+// CONV (a window step and / or zero padding): row (s, i, w) starts at time row w * stride - padl, and weight row j = h*f + c contributes only
+// where its OWN time row w * stride - padl + h lies inside 0 <= t < T -- the floats before and after a vertex's row are its neighbours'.
 struct SeriesWgradParams {
   const float* stack;
   const float* g;
@@ -161,8 +213,10 @@ struct SeriesWgradParams {
   int64_t st_ks, g_ss, g_is, g_ws;
   int64_t M, rows_per_block, n;
   int32_t Tf, f, nwin, J, N, K;
+  int32_t stride, padl, T;        // CONV only
 };
 
+template <bool CONV>
 __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWgradParams p) {
   const int lane = threadIdx.x;
   const int r = lane & 15, kq = lane >> 4;
@@ -180,6 +234,7 @@ __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWg
   const int64_t s_lo = si_lo / p.n;
   const uint32_t i_lo = (uint32_t)(si_lo % p.n);
   const uint32_t nwin = (uint32_t)p.nwin, nv = (uint32_t)p.n;
+  const int hj = CONV ? j / p.f : 0;        // the weight time row of this lane's j
   f32x4 acc[kWgTerms][4];
 #pragma unroll
   for (int t = 0; t < kWgTerms; ++t)
@@ -196,7 +251,9 @@ __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWg
       const uint32_t ii = i_lo + dv, ds = ii / nv, i = ii - ds * nv;
       const int64_t s = s_lo + ds;
       const float* grow = p.g + s * p.g_ss + (int64_t)i * p.g_is + (int64_t)w * p.g_ws;
-      const float* arow = p.stack + (s * p.n + i) * (int64_t)p.Tf + (int64_t)w * p.f;
+      const int tw = CONV ? (int)w * p.stride - p.padl : (int)w;      // first time row of the window
+      const float* arow = p.stack + (s * p.n + i) * (int64_t)p.Tf;
+      const bool tok = !CONV || (tw + hj >= 0 && tw + hj < p.T);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int nn = n0 + q * 16 + r;
@@ -204,7 +261,7 @@ __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWg
       }
 #pragma unroll
       for (int t = 0; t < kWgTerms; ++t)
-        av[u][t] = (mok && j < p.J && t0 + t < p.K) ? arow[(int64_t)(t0 + t) * p.st_ks + j] : 0.f;
+        av[u][t] = (mok && tok && j < p.J && t0 + t < p.K) ? arow[(int64_t)(t0 + t) * p.st_ks + (int64_t)tw * p.f + j] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < kWgUnroll; ++u)

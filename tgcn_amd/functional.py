@@ -6,6 +6,7 @@ memory, the stream and autograd bookkeeping.  There is no CPU fallback.
 import ctypes as C
 import dataclasses
 import functools
+import numbers
 import threading
 
 import torch
@@ -385,19 +386,51 @@ class ChebWindowsFn(torch.autograd.Function):
         return gx, dW, gb, None, None, None
 
 
+def series_geometry(T, H, stride=1, padding=0, who="cheb_time_windows"):
+    """(stride, left, right, nwin) of a streaming call on T time steps with windows of H: padding an int p = (p, p), a pair (left, right) or
+    "causal" = (H-1, 0), 0 <= left, right <= H-1 (every window touches a real row); nwin = (T + left + right - H) // stride + 1.
+    TgcnError for anything else -- checked before an operand is built or anything launches."""
+    def integer(v):
+        return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if isinstance(padding, str):
+        if padding != "causal":
+            raise _lib.TgcnError('%s: padding is an int, a pair (left, right) or "causal", got %r' % (who, padding))
+        left, right = H - 1, 0
+    elif integer(padding):
+        left = right = int(padding)
+    elif isinstance(padding, (tuple, list)) and len(padding) == 2 and all(integer(v) for v in padding):
+        left, right = int(padding[0]), int(padding[1])
+    else:
+        raise _lib.TgcnError('%s: padding is an int, a pair (left, right) or "causal", got %r' % (who, padding))
+    if not integer(stride) or stride < 1:
+        raise _lib.TgcnError("%s: stride is an integer >= 1, got %r" % (who, stride))
+    if not (0 <= left <= H - 1 and 0 <= right <= H - 1):
+        raise _lib.TgcnError("%s: padding (%d, %d) outside 0 .. H - 1 = %d" % (who, left, right, H - 1))
+    if T + left + right < H:
+        raise _lib.TgcnError("%s: %d time steps with padding (%d, %d) are fewer than one window of %d" % (who, T, left, right, H))
+    return int(stride), left, right, (T + left + right - H) // int(stride) + 1
+
+
 class ChebSeriesFn(torch.autograd.Function):
     """Streaming time-window layer on a multi-channel series (S, n, T, f), weight (K, H, f, N): the hops run once on rows of T*f floats in
     both directions, the window projection and its two gradients are the sliding-window MFMA kernels of csrc/windows.h
     (tgcn_cheb_project_series_f32 / tgcn_cheb_series_backward_f32), one launch each for all S recordings.  as_series picks the output
-    layout, (S*nwin, n, N) or (S, n, nwin, N); the backward reads its gradient in that layout in place."""
+    layout, (S*nwin, n, N) or (S, n, nwin, N); the backward reads its gradient in that layout in place.
+    geom = (stride, left, right): a window step and zero padding in time.  (1, 0, 0) calls the entries above; anything else their _conv
+    forms (the hops do not depend on it), after asking tgcn_series_conv_plan whether the forward's span fits -- before the hops run."""
 
     @staticmethod
     @_on_device
-    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series):
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom=(1, 0, 0)):
         L = _lib.lib()
         S, n, T, f = series.shape
         K, H, _, N = weight_khfg.shape
-        nwin = T - H + 1
+        stride, left, right = geom
+        conv = tuple(geom) != (1, 0, 0)
+        nwin = (T + left + right - H) // stride + 1
+        if conv:
+            hc, lds = C.c_int32(0), C.c_int32(0)
+            _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), stride, C.byref(hc), C.byref(lds)))
         x3 = _aligned_input(series.float().contiguous().view(S, n, T * f))
         W = weight_khfg.float().contiguous().view(K, H * f, N)
         fold = _power_fold(mode, W)
@@ -406,8 +439,12 @@ class ChebSeriesFn(torch.autograd.Function):
         stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)   # (K, S, n, T*f)
         out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=torch.float32, device=x3.device)
         b = bias.contiguous() if bias is not None else None
-        _lib.check(L.tgcn_cheb_project_series_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind,
-                                                  1 if as_series else 0, _lib.ptr(out)))
+        args = (_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(out))
+        if conv:
+            _lib.check(L.tgcn_cheb_project_series_conv_f32(*args, stride, left, right))
+        else:
+            _lib.check(L.tgcn_cheb_project_series_f32(*args))
+        ctx.geom = (stride, left, right) if conv else None
         ctx.save_for_backward(Wt)
         ctx.stack = stack if ctx.needs_input_grad[1] else None       # the basis the weight gradient contracts with g
         ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
@@ -427,9 +464,15 @@ class ChebSeriesFn(torch.autograd.Function):
         if need_x or need_w:
             G = torch.empty((K, S, n, T * f), dtype=torch.float32, device=g.device) if need_x else None
             dW = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
-            ws = _workspace(L.tgcn_cheb_series_backward_workspace_bytes(S, n, T, f, H, N, K), g.device, floor=16)
-            _lib.check(L.tgcn_cheb_series_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
-                                                       1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel()))
+            if ctx.geom is None:
+                ws = _workspace(L.tgcn_cheb_series_backward_workspace_bytes(S, n, T, f, H, N, K), g.device, floor=16)
+                _lib.check(L.tgcn_cheb_series_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
+                                                           1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel()))
+            else:
+                ws = _workspace(L.tgcn_cheb_series_conv_backward_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
+                _lib.check(L.tgcn_cheb_series_conv_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
+                                                                1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
+                                                                ws.numel(), *ctx.geom))
             ctx.stack = None
             if need_x:
                 gx = _adjoint_hops(ctx.op.transpose(), G, ctx.mode).reshape(S, n, T, f)
@@ -443,17 +486,21 @@ class ChebSeriesFn(torch.autograd.Function):
                 gb = (g.sum(dim=(0, 1, 2)) if ctx.bias_kind == BIAS_CHANNEL else g.sum(dim=(0, 2))).reshape(ctx.bias_shape)
             else:
                 gb = _bias_grad(g, ctx.bias_kind, ctx.bias_shape, True)
-        return gx, dW, gb, None, None, None, None
+        return gx, dW, gb, None, None, None, None, None
 
 
-def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_series=False):
+def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_series=False, stride=1, padding=0):
     """Streaming form of TGCNCheb_H / ChebTimeConv on sliding windows: series (S, n, T) raw recordings with weight (K, H, N), or
     (S, n, T, f) with weight (K, H, f, N), in the reference basis.  Returns (S * (T-H+1), n, N), identical to running the layer on the
     windowed batch x[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c] (load/data_hcp.py:146-152), but the K-1 hops run once on the T time
     rows of each recording -- in the backward too, so the windows it replaces can be trained through.
     as_series=True returns the same numbers as (S, n, T-H+1, N), contiguous: itself a series, which the next time layer streams over.
     A single-channel series with as_series=False takes the scalar-load form (ChebWindowsFn, one projection launch per recording); every
-    other call the sliding-window MFMA kernels (ChebSeriesFn, one launch for all recordings)."""
+    other call the sliding-window MFMA kernels (ChebSeriesFn, one launch for all recordings).
+    stride, padding: the layer as a convolution over time.  padding = p, (left, right) or "causal" (= (H-1, 0)) puts that many zero time rows
+    (at most H-1 each) around every recording, stride keeps every stride-th window: nwin = (T + left + right - H) // stride + 1 windows,
+    xw[s*nwin + w, i, h, c] = padded_series[s, i, w*stride + h, c], out (S*nwin, n, N) or (S, n, nwin, N).  The hops do not depend on either;
+    the projection and its gradients shrink with the stride.  Anything but stride=1, padding=0 runs the MFMA kernels, f == 1 included."""
     if param_dtype(weight, bias, "cheb_time_windows") == BF16:
         raise _lib.TgcnError("forward_series / cheb_time_windows: bfloat16 parameters are not supported")
     if series.dim() not in (3, 4) or weight.dim() != series.dim():
@@ -462,10 +509,9 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     f = series.shape[3] if series.dim() == 4 else 1
     if series.dim() == 4 and weight.shape[2] != f:
         raise _lib.TgcnError("cheb_time_windows: the series has %d channels, the weight %d" % (f, weight.shape[2]))
-    if series.shape[2] < weight.shape[1]:
-        raise _lib.TgcnError("cheb_time_windows: %d time steps are fewer than one window of %d" % (series.shape[2], weight.shape[1]))
+    geom = series_geometry(series.shape[2], weight.shape[1], stride, padding)[:3]
     _lib.require_device(series, weight, bias)
-    if f == 1 and not as_series:
+    if f == 1 and not as_series and geom == (1, 0, 0):
         if series.dim() == 4:
             series, weight = series.reshape(series.shape[:3]), weight.reshape(weight.shape[0], weight.shape[1], weight.shape[3])
         series, bias = _to_operand_labels(op, series, bias, bias_kind)
@@ -474,7 +520,7 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     if series.dim() == 3:
         series, weight = series.unsqueeze(3), weight.unsqueeze(2)
     series, bias = _to_operand_labels(op, series, bias, bias_kind)
-    out = ChebSeriesFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series))
+    out = ChebSeriesFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom)
     return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)      # the vertex axis is dim 1 in both layouts
 
 

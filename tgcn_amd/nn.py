@@ -180,24 +180,28 @@ class TGCNCheb_H(_DenseLBase):
             X = X.unsqueeze(3)
         return self._stack(X)
 
-    def forward_series(self, series, as_series=False):
+    def forward_series(self, series, as_series=False, stride=1, padding=0):
         """Additive API (not in the reference): series (S, n, T) or (S, n, T, f) raw recordings, f == in_channels -> the layer's output
         for all T-H+1 sliding windows of every recording without materialising the windows (load/data_hcp.py:116-154 builds them on
         the host and the hops then run H times too often): layer(xw) for xw[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c].
         as_series=False returns (S*(T-H+1), n, g), the order of that batch; as_series=True the same numbers as (S, n, T-H+1, g),
         contiguous -- a series again, so layer2.forward_series(act(layer1.forward_series(x, as_series=True))) chains two time layers with
-        no transpose and no windows.  Differentiable: the backward runs the hops once per call too."""
+        no transpose and no windows.  Differentiable: the backward runs the hops once per call too.
+        stride, padding: the layer as a convolution over time (F.cheb_time_windows): padding = p, (left, right) or "causal" (H-1 zero time
+        rows in front, so a chain keeps its outputs aligned with the input's time axis), each side at most H-1; stride keeps every
+        stride-th window.  nwin = (T + left + right - H) // stride + 1 replaces T-H+1 above."""
         if _compute_dtype(self) != torch.float32:
             raise _lib.TgcnError("TGCNCheb_H.forward_series: bfloat16 parameters are not supported")
-        series, W = _series_args(self, series)
+        series, W, geom = _series_args(self, series, stride, padding)
         return F.cheb_time_windows(self._operand(series.device), series, W,
                                    None if self.bias is None else self.bias.reshape(-1),
-                                   F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series)
+                                   F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series,
+                                   stride=geom[0], padding=geom[1:])
 
 
-def _series_args(module, series):
-    """(series, weight) of a forward_series call as F.cheb_time_windows takes them -- a 3-D series with the (K, H, g) weight, a 4-D one with
-    (K, H, f, g) -- after the shape checks: TgcnError before anything is built or launched."""
+def _series_args(module, series, stride=1, padding=0):
+    """(series, weight, (stride, left, right)) of a forward_series call as F.cheb_time_windows takes them -- a 3-D series with the (K, H, g) weight, a 4-D one with
+    (K, H, f, g) -- after the shape and geometry checks: TgcnError before anything is built or launched."""
     name = type(module).__name__
     K, H, f, g = module.weight.shape
     if series.dim() not in (3, 4):
@@ -205,9 +209,8 @@ def _series_args(module, series):
     if (series.shape[3] if series.dim() == 4 else 1) != f:
         raise _lib.TgcnError("%s.forward_series: the series has %d channel(s), the layer in_channels = %d"
                              % (name, series.shape[3] if series.dim() == 4 else 1, f))
-    if series.shape[2] < H:
-        raise _lib.TgcnError("%s.forward_series: %d time steps are fewer than one window of H = %d" % (name, series.shape[2], H))
-    return series, (module.weight.reshape(K, H, g) if series.dim() == 3 else module.weight)
+    stride, left, right, _ = F.series_geometry(series.shape[2], H, stride, padding, "%s.forward_series" % name)
+    return series, (module.weight.reshape(K, H, g) if series.dim() == 3 else module.weight), (stride, left, right)
 
 
 class GCNCheb(_DenseLBase):
@@ -435,21 +438,23 @@ class ChebTimeConv(_EdgeBase):
         return F.cheb_layer(*args, values=self._values(x, edge_index, edge_weight, args[0]))
 
 
-    def forward_series(self, series, edge_index, edge_weight=None, as_series=False):
+    def forward_series(self, series, edge_index, edge_weight=None, as_series=False, stride=1, padding=0):
         """Additive API: TGCNCheb_H.forward_series' contract for this class -- series (S, n, T) or (S, n, T, f), f == in_channels, ->
         forward(xw, edge_index, edge_weight) on the windowed batch xw[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c], as
         (S*(T-H+1), n, g) or, as_series=True, (S, n, T-H+1, g); true recurrence, per-channel bias.  The operand is the one forward builds
         and caches.  A learnable edge_weight (requires_grad) raises TgcnError: its gradient needs the basis of every window, which
-        this entry exists not to form -- call forward on materialised windows to train edge weights."""
+        this entry exists not to form -- call forward on materialised windows to train edge weights.
+        stride, padding as in TGCNCheb_H.forward_series."""
         if edge_weight is not None and edge_weight.requires_grad:
             raise _lib.TgcnError("ChebTimeConv.forward_series: learnable edge weights (edge_weight.requires_grad) are not supported -- "
                                  "use forward on the windowed batch")
         if _compute_dtype(self, edge_weight) != torch.float32:
             raise _lib.TgcnError("ChebTimeConv.forward_series: bfloat16 parameters are not supported")
-        series, W = _series_args(self, series)
+        series, W, geom = _series_args(self, series, stride, padding)
         op = self._operand(series, edge_index, edge_weight)
         return F.cheb_time_windows(op, series, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
-                                   as_series=as_series)
+                                   as_series=as_series,
+                                   stride=geom[0], padding=geom[1:])
 
 
 # ------------------------------------------------------------------------------------ fused caller pattern

@@ -3,12 +3,16 @@
 the materialised windowed batch xw[s*nwin + w, i, h, c] = series[s, i, w + h, c] (built once, outside the timed region).  Events around the
 call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + backward.  Developer tool; bench.py's headline is untouched.
 
-    python tools/series_bench.py [--steps 5] [--warmup 2] [--out profiles/r08_series_channels.json]
+    python tools/series_bench.py [--steps 5] [--warmup 2] [--stride 1] [--padding 0] [--conv] [--out profiles/r08_series_channels.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
 streaming passes the first layer's output on as a series (as_series=True), the baseline cuts the second layer's windows out of the first
-layer's output inside the timed region (it has to: they do not exist before)."""
+layer's output inside the timed region (it has to: they do not exist before).
+--stride / --padding (an int, "left,right" or "causal") run (a) and (b) with that geometry (the baseline's windows are cut with it too, outside
+the timed region); --conv adds the cases of profiles/r09_series_conv.json: (a) 32 -> 64 and (b) at stride 4, and chain (c) with
+padding="causal" in both layers (284 time steps in, 284 out).  --include LABEL=FILE (repeatable) embeds the --out file of another run --
+the parent commit's tool on the default cases, a repeat of this one for the run-to-run spread -- with its times relative to this run's."""
 import argparse
 import json
 import os
@@ -20,6 +24,7 @@ import torch  # noqa: E402
 
 import tgcn_amd  # noqa: E402
 from tgcn_amd import _lib  # noqa: E402
+from tgcn_amd import functional as F  # noqa: E402
 from tgcn_amd.graph import GraphOperand  # noqa: E402
 from tools import synth  # noqa: E402
 from tools.precision_bench import measure  # noqa: E402
@@ -35,11 +40,21 @@ def dti148(dev):
     return GraphOperand.from_coo(n, row.to(dev), torch.as_tensor(z["col"]).long().to(dev), torch.as_tensor(z["val"]).float().to(dev))
 
 
-def windows(series, H):
-    """(S, n, T, f) -> (S*nwin, n, H, f), contiguous"""
+def windows(series, H, stride=1, padding=0):
+    """(S, n, T, f) -> (S*nwin, n, H, f), contiguous: every stride-th window of the zero-padded series"""
     S, n, T, f = series.shape
-    nwin = T - H + 1
-    return series.unfold(2, H, 1).permute(0, 2, 1, 4, 3).reshape(S * nwin, n, H, f).contiguous()
+    left, right = F.series_geometry(T, H, stride, padding)[1:3]
+    if left or right:
+        series = torch.nn.functional.pad(series, (0, 0, left, right))
+    w = series.unfold(2, H, stride)                                        # (S, n, nwin, f, H)
+    return w.permute(0, 2, 1, 4, 3).reshape(S * w.shape[2], n, H, f).contiguous()
+
+
+def padding_arg(text):
+    if text == "causal":
+        return text
+    parts = [int(v) for v in text.split(",")]
+    return parts[0] if len(parts) == 1 else tuple(parts)
 
 
 def timed(fn, train, steps, warmup):
@@ -69,16 +84,26 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--stride", type=int, default=1)
+    ap.add_argument("--padding", type=padding_arg, default=0)
+    ap.add_argument("--conv", action="store_true", help="add the stride-4 and causal-chain cases")
+    ap.add_argument("--include", action="append", default=[], metavar="LABEL=FILE",
+                    help="put another run's --out file (the parent commit's, a repeat of this one) into this one under runs[LABEL], with "
+                         "each shared case's ms per call relative to this run")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
-    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, cases={})
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, stride=args.stride,
+               padding=args.padding, cases={})
     torch.manual_seed(0)
 
-    def case(name, desc, layer, series, H):
+    def case(name, desc, layer, series, H, stride=args.stride, padding=args.padding):
         series = series.requires_grad_(True)
-        xw = windows(series.detach(), H).requires_grad_(True)
-        entry = dict(desc=desc, **compare(lambda: layer.forward_series(series), lambda: layer(xw), args.steps, args.warmup))
+        xw = windows(series.detach(), H, stride, padding).requires_grad_(True)
+        geo = {} if (stride, padding) == (1, 0) else dict(stride=stride, padding=padding)      # the default call exactly as it was
+        if geo:
+            desc += " stride=%s padding=%s" % (stride, padding)
+        entry = dict(desc=desc, **compare(lambda: layer.forward_series(series, **geo), lambda: layer(xw), args.steps, args.warmup))
         res["cases"][name] = entry
         print(json.dumps({name: entry}), flush=True)
         del xw
@@ -90,11 +115,15 @@ def main():
     l2 = tgcn_amd.TGCNCheb_H(op, 32, 64, K, H).to(dev)
     case("a_dti148_1to32", "dti148 S=8 T=284 H=15 K=10 f=1 -> g=32", l1, torch.randn(S, op.n, T, 1, device=dev), H)
     case("a_dti148_32to64", "dti148 S=8 T=284 H=15 K=10 f=32 -> g=64", l2, torch.randn(S, op.n, T, 32, device=dev), H)
+    if args.conv:
+        case("a_dti148_32to64_stride4", "dti148 S=8 T=284 H=15 K=10 f=32 -> g=64", l2, torch.randn(S, op.n, T, 32, device=dev), H, 4, 0)
 
     n, row, col, val = synth.sheet_mesh(300, device=dev)
     opm = GraphOperand.from_coo(n, row, col, val, dev)
     lm = tgcn_amd.TGCNCheb_H(opm, 4, 32, 5, 15).to(dev)
     case("b_mesh90k_4to32", "sheet_mesh(300) n=%d S=1 T=75 H=15 K=5 f=4 -> g=32" % n, lm, torch.randn(1, n, 75, 4, device=dev), 15)
+    if args.conv:
+        case("b_mesh90k_4to32_stride4", "sheet_mesh(300) n=%d S=1 T=75 H=15 K=5 f=4 -> g=32" % n, lm, torch.randn(1, n, 75, 4, device=dev), 15, 4, 0)
     del lm, opm
     torch.cuda.empty_cache()
 
@@ -111,6 +140,31 @@ def main():
     entry = dict(desc="dti148 S=8 T=284: TGCNCheb_H(1,32,10,15) -> relu -> TGCNCheb_H(32,64,10,15)", **compare(chain_stream, chain_batch, args.steps, args.warmup))
     res["cases"]["c_dti148_chain"] = entry
     print(json.dumps({"c_dti148_chain": entry}), flush=True)
+    if args.conv:
+        del xw1
+        torch.cuda.empty_cache()
+        xc1 = windows(series.detach(), H, 1, "causal").requires_grad_(True)              # (S*T, n, H, 1)
+
+        def causal_stream():
+            return l2.forward_series(torch.relu(l1.forward_series(series, as_series=True, padding="causal")), padding="causal")
+
+        def causal_batch():
+            h = torch.relu(l1(xc1))                                       # (S*T, n, 32)
+            return l2(windows(h.view(S, T, op.n, 32).permute(0, 2, 1, 3), H, 1, "causal"))
+        entry = dict(desc='dti148 S=8 T=284: the chain with padding="causal" in both layers, 284 windows out',
+                     **compare(causal_stream, causal_batch, args.steps, args.warmup))
+        res["cases"]["c_dti148_chain_causal"] = entry
+        print(json.dumps({"c_dti148_chain_causal": entry}), flush=True)
+    for item in args.include:
+        label, path = item.split("=", 1)
+        with open(path) as f:
+            other = json.load(f)
+        rel = {}
+        for name, entry in other["cases"].items():
+            if name in res["cases"]:
+                rel[name] = {d: {k: round(entry[d][k]["ms_per_call"] / res["cases"][name][d][k]["ms_per_call"], 3) for k in ("streaming", "materialised")}
+                             for d in ("forward", "forward_backward")}
+        res.setdefault("runs", {})[label] = dict(run=other, ms_over_this_run=rel)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
