@@ -354,6 +354,31 @@ int tgcn_cheb_series_conv_backward_f32(void* stream, int64_t S, int64_t n_vertic
  * the most weight time rows and asks with (ceil(H / stride), N, K*f, 1), the other phases with that or one row less. */
 int tgcn_series_conv_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes);
 
+/* The streaming time windows on bf16 tensors (DESIGN.md 3.10 "bf16"): ONE entry family, the strided, zero-padded geometry of the _conv
+ * entries above; (stride, pad_left, pad_right) = (1, 0, 0) is the plain sliding window.
+ *   stack: bf16 (K, S, n_vertices, .) with stack_ld >= T*f ELEMENTS per vertex row (the rows may carry trailing padding, e.g. up to a
+ *          multiple of 8 for the 16-byte hop form; the time rows inside stay f contiguous elements); W: bf16 (K, H*f, N) in the working basis;
+ *          bias: fp32 or bf16 (bias_dtype = TGCN_DTYPE_*), added in fp32; out: bf16, (S*nwin, n_vertices, N) or, as_series, (S, n_vertices,
+ *          nwin, N), each element rounded once from its fp32 sum.
+ * Products run on v_mfma_f32_16x16x32_bf16 with fp32 accumulators.  16-byte loads when f % 8 == 0, stack_ld % 8 == 0 and stack is 16-byte
+ * aligned; element loads otherwise.
+ * Backward: g bf16 in the layout g_as_series names, read in place; G (nullable) fp32 (K, S, n_vertices, T*f), written whole, one launch per
+ * phase of the window step over the time-flipped transposed bf16 weight (16-byte loads of g when N % 8 == 0 and g is 16-byte aligned); dW
+ * (nullable) fp32 (K, H*f, N), fp32 partials folded in block order (bit-equal across runs); W may be null when G is, stack when dW is.
+ * The workspace (16-byte aligned) has the fp32 entries' size, partials capped at 256 MB.
+ * tgcn_series_conv_plan_bf16: tgcn_series_conv_plan's three regimes and refusal on the bf16 span's bytes (vec: the 16-byte form, taken only
+ * when f % 8 == 0); the forward asks with (H, f, N, stride), the input gradient with (ceil(H / stride), N, K*f, 1).
+ * A shape the plan refuses returns TGCN_ERR_UNSUPPORTED with nothing launched. */
+int tgcn_cheb_project_series_conv_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                       const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                       int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right);
+size_t tgcn_cheb_series_conv_backward_bf16_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                           int32_t stride, int32_t pad_left, int32_t pad_right);
+int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                        const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
+                                        float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right);
+int tgcn_series_conv_plan_bf16(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

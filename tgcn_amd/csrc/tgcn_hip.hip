@@ -10,6 +10,7 @@
 //   small_graph.h    graphs that fit in LDS: whole layer / basis in ONE launch (sparse, first-layer, dense matrix-pipe)
 //   pool_relayout.h  (Q,n,C) -> (n,Q,C), gcn_pool / gcn_pool_4, relu + pool pass
 //   windows.h        streaming time windows of multi-channel series: sliding-window fp32 MFMA GEMM (forward, input gradient), weight gradient
+//   windows_bf16.h   the same on bf16 tensors: sliding-window bf16 MFMA GEMM, flipped bf16 weight, weight gradient (fp32 sums)
 //   device_build.h   operand / schedule construction on the device: prefix sums, stable radix sort, CSR build, schedule kernels
 //   graph_build.h    tgcn_graph_* / tgcn_sched_* / tgcn_csr_build_f32: host-side orchestration of device_build.h (one-off per operand)
 // This file: the extern "C" entry points (argument checks, workspace carving, launches) declared in tgcn_hip.h.
@@ -42,6 +43,7 @@ namespace {
 #include "small_graph.h"
 #include "pool_relayout.h"
 #include "windows.h"
+#include "windows_bf16.h"
 #include "device_build.h"
 #include "graph_build.h"
 
@@ -1416,6 +1418,166 @@ int tgcn_cheb_series_conv_backward_f32(void* stream, int64_t S, int64_t n_vertic
   if (int rc = series_backward_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, stride, pad_left,
                                     pad_right, "series_conv_backward")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_series_conv_backward_f32");
+  return TGCN_OK;
+}
+
+// ---- streaming time windows on bf16 tensors (windows_bf16.h): one entry family, the general geometry; (1, 0, 0) is its default
+// series_gemm_lds's three regimes on bf16 span bytes: the weight tile is NT*16 columns of kPbLd bf16
+static int series_gemm_bf16_lds(int H, int f, int NT, bool vec, int stride, int* hc_out) {
+  auto bytes = [&](int hc) { return ((size_t)NT * 16 * kPbLd + 4 * (size_t)series_bf16_span_elems(hc, f, vec, stride)) * sizeof(hbf16); };   // 64-bit
+  const size_t limits[2] = {64 * 1024, (size_t)lds_optin_limit()};
+  for (size_t lim : limits)
+    for (int hc = H; hc >= 1; --hc)
+      if (bytes(hc) <= lim) { *hc_out = hc; return (int)bytes(hc); }
+  return 0;
+}
+
+int tgcn_series_conv_plan_bf16(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes) {
+  if (H < 1 || f < 1 || N < 1 || stride < 1 || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_conv_plan_bf16: bad argument");
+  int h = 0;
+  const int lds = series_gemm_bf16_lds(H, f, series_gemm_nt(N), vec != 0 && f % 8 == 0, stride, &h);
+  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_conv_plan_bf16: %d channels per time row do not fit the LDS span", f);
+  *hc = h; *lds_bytes = lds;
+  return TGCN_OK;
+}
+
+// out_f32: the input gradient's fp32 columns; otherwise bf16 output.  stride >= 2 takes the STRIDED instantiations.
+static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride = 1) {
+  p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
+  p.ntiles = S * p.n * p.tpv;
+  const int64_t gx = (p.ntiles + 3) / 4;
+  const int NT = series_gemm_nt(p.N);
+  const int64_t gy = (p.N + NT * 16 - 1) / (NT * 16);
+  if (gx > (int64_t)INT32_MAX || gy > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
+  int hc = 0;
+  const int lds = series_gemm_bf16_lds(p.H, p.f, NT, vec, stride, &hc);
+  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, p.f);
+  p.HC = hc;
+  p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = vec ? series_bf16_row_elems(p.f, p.lst) : p.f;
+  const dim3 grid((unsigned)gx, (unsigned)gy);
+  ProfScope ps(TGCN_PROF_PROJECT, st);
+#define TGCN_SERIES_GEMM_B(NT_, VEC_, STR_, OUT_)                                                                 \
+  do {                                                                                                            \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_>, lds);       \
+    hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_>), grid, dim3(kBlock), lds, st, p);         \
+  } while (0)
+#define TGCN_SERIES_GEMM_B_NT(VEC_, STR_, OUT_)                                                                   \
+  do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_); else if (NT == 2) TGCN_SERIES_GEMM_B(2, VEC_, STR_, OUT_);   \
+       else TGCN_SERIES_GEMM_B(4, VEC_, STR_, OUT_); } while (0)
+  if (out_f32) {        // the input gradient: one launch per phase, each at step 1
+    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float); else TGCN_SERIES_GEMM_B_NT(false, false, float);
+  } else if (stride == 1) {
+    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16);
+  } else {
+    if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16);
+  }
+#undef TGCN_SERIES_GEMM_B_NT
+#undef TGCN_SERIES_GEMM_B
+  return TGCN_OK;
+}
+
+static bool series_stack_ld_ok(int32_t T, int32_t f, int64_t stack_ld) { return stack_ld >= (int64_t)T * f && stack_ld < (int64_t)INT32_MAX; }
+
+int tgcn_cheb_project_series_conv_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                       const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                       int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right) {
+  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right) || !stack || !W || !out || !series_stack_ld_ok(T, f, stack_ld))
+    TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv_bf16: bad argument");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv_bf16: bias_kind %d", bias_kind);
+  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv_bf16: dtype code %d", bias_dtype);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_conv_bf16")) return drc;
+  stride = series_conv_stride(T, stride, pad_left, pad_right);
+  const int64_t n = n_vertices, nwin = series_conv_nwin(T, H, stride, pad_left, pad_right);
+  SeriesGemmBf16Params p;
+  memset(&p, 0, sizeof(p));
+  p.src = (const hbf16*)stack; p.W = (const hbf16*)W; p.bias = bias; p.out = out;
+  p.src_ks = S * n * stack_ld; p.src_ss = n * stack_ld; p.src_is = stack_ld; p.src_ts = f;
+  if (as_series) { p.o_ss = n * nwin * N; p.o_is = nwin * N; p.o_ws = N; }      // (S, n, nwin, N)
+  else { p.o_ss = nwin * n * N; p.o_is = N; p.o_ws = n * N; }                     // (S, nwin, n, N)
+  p.o_gs = 0; p.ocg = N;
+  p.n = n; p.Tin = T; p.padl = pad_left; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
+  p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
+  const bool vec = (f % 8 == 0) && (stack_ld % 8 == 0) && (((uintptr_t)stack & 15) == 0);
+  if (int rc = series_gemm_bf16_launch((hipStream_t)stream, p, S, vec, false, "project_series_conv_bf16", stride)) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_conv_bf16");
+  return TGCN_OK;
+}
+
+size_t tgcn_cheb_series_conv_backward_bf16_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                           int32_t stride, int32_t pad_left, int32_t pad_right) {
+  // the flipped weight (bf16, in the fp32 entries' slot) and the fp32 partials: the fp32 entries' size and 256 MB cap
+  return tgcn_cheb_series_conv_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
+}
+
+int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                        const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
+                                        float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right) {
+  const char* who = "series_conv_backward_bf16";
+  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right) || !g) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (int drc = check_pointer_device(g, (hipStream_t)stream, who)) return drc;
+  const size_t need = tgcn_cheb_series_conv_backward_bf16_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) TGCN_FAIL(TGCN_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+  stride = series_conv_stride(T, stride, pad_left, pad_right);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = n_vertices, Tf = (int64_t)T * f, nwin = series_conv_nwin(T, H, stride, pad_left, pad_right), wf = (int64_t)K * H * f * N;
+  const int32_t pl = pad_left;
+  const bool conv = stride != 1 || pad_left != 0 || pad_right != 0;
+  int64_t g_ss, g_is, g_ws;
+  if (g_as_series) { g_ss = n * nwin * N; g_is = nwin * N; g_ws = N; }
+  else { g_ss = nwin * n * N; g_is = N; g_ws = n * N; }
+  if (G) {      // the forward's kernel over g as a series of N channels, columns (k, c), fp32 out; per phase of the window step, each at step 1
+    if (!W) TGCN_FAIL(TGCN_ERR_INVALID, "%s: the input gradient needs W", who);
+    hbf16* Wd = (hbf16*)workspace;
+    { ProfScope ps(TGCN_PROF_RELAYOUT, st);
+      hipLaunchKernelGGL(series_flip_weight_bf16_kernel, dim3(grid_1d(wf)), dim3(kBlock), 0, st, (const hbf16*)W, Wd, (int)K, (int)H, (int)f, (int)N,
+                         (int)stride); }
+    // the time rows of the phases ph >= H (a step longer than the window) lie between the windows: exact zeros
+    if (stride > H && hipMemsetAsync(G, 0, (size_t)K * S * n * Tf * sizeof(float), st) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "%s: memset failed", who);
+    // 16-byte loads of g's time rows: N % 8 makes every stride of either layout a multiple of 8 elements.  The phases' weights start at
+    // rows of N*K*f elements: any alignment, the weight tile is loaded element by element.
+    const bool vec = (N % 8 == 0) && (((uintptr_t)g & 15) == 0);
+    for (int ph = 0; ph < stride && ph < H; ++ph) {
+      const int Hp = series_phase_rows(H, stride, ph);
+      if ((int64_t)T - 1 + pl - ph < 0) continue;
+      const int64_t u0 = ph >= pl ? 0 : (pl - ph + stride - 1) / stride, u1 = ((int64_t)T - 1 + pl - ph) / stride;
+      if (u1 < u0) continue;
+      SeriesGemmBf16Params p;
+      memset(&p, 0, sizeof(p));
+      p.src = (const hbf16*)g; p.W = Wd + (int64_t)series_phase_row0(H, stride, ph) * N * K * f; p.bias = nullptr;
+      p.out = G + (u0 * stride + ph - pl) * f;
+      p.src_ks = 0; p.src_ss = g_ss; p.src_is = g_is; p.src_ts = g_ws;
+      p.o_ss = n * Tf; p.o_is = Tf; p.o_ws = (int64_t)stride * f; p.o_gs = S * n * Tf; p.ocg = f;
+      p.n = n; p.Tin = (int32_t)nwin; p.padl = (int32_t)(Hp - 1 - u0); p.nwin = (int32_t)(u1 - u0 + 1); p.H = Hp; p.f = N; p.N = K * f; p.nterms = 1;
+      p.bias_kind = 0;
+      if (int rc = series_gemm_bf16_launch(st, p, S, vec, true, who)) return rc;
+    }
+  }
+  if (dW) {
+    if (!stack || !series_stack_ld_ok(T, f, stack_ld)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: the weight gradient needs the hop tensors", who);
+    const int64_t M = S * n * nwin;
+    SeriesWgradBf16Params q;
+    memset(&q, 0, sizeof(q));
+    q.stack = (const hbf16*)stack; q.g = (const hbf16*)g; q.partial = (float*)((char*)workspace + align_up((size_t)wf * sizeof(float), 256));
+    q.st_ks = S * n * stack_ld; q.st_is = stack_ld; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
+    q.M = M; q.rows_per_block = series_wgrad_rows_per_block(M, wf); q.n = n;
+    q.f = f; q.nwin = (int32_t)nwin; q.J = H * f; q.N = N; q.K = K;
+    q.stride = stride; q.padl = pl; q.T = T;
+    const int64_t nblocks = (M + q.rows_per_block - 1) / q.rows_per_block;
+    const int64_t jtiles = (q.J + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
+    if (q.rows_per_block + nwin >= (int64_t)INT32_MAX || q.rows_per_block / nwin + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX ||
+        (N + 63) / 64 > 65535 || jtiles * tgroups > 65535)
+      TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: weight gradient shape too large", who);
+    { ProfScope ps(TGCN_PROF_WGRAD, st);
+      const dim3 grid((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups));
+      if (conv) hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<true>, grid, dim3(64), 0, st, q);
+      else hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<false>, grid, dim3(64), 0, st, q); }
+    WgradParams r;
+    memset(&r, 0, sizeof(r));
+    r.partial = q.partial; r.dW = dW; r.Kc = q.J; r.N = N; r.nterms = K; r.nblocks = (int32_t)nblocks;
+    { ProfScope ps(TGCN_PROF_WGRAD, st);
+      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
+  }
+  TGCN_CHECK_LAUNCH("tgcn_cheb_series_conv_backward_bf16");
   return TGCN_OK;
 }
 

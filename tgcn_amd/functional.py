@@ -411,6 +411,19 @@ def series_geometry(T, H, stride=1, padding=0, who="cheb_time_windows"):
     return int(stride), left, right, (T + left + right - H) // int(stride) + 1
 
 
+def check_series_bf16(f, as_series, geom, series_dtype):
+    """what a streaming call with bfloat16 parameters needs, checked before an operand is built: not the scalar-load form (ChebWindowsFn: one
+    channel, window-major, default geometry), and a series that is bfloat16 already -- a streaming chain is bf16 from end to end (an
+    as_series=True output feeds the next layer as it is), so the recording is cast once by its owner, not once per call here; a series of
+    another dtype with bf16 parameters is refused like a weight and a bias of two dtypes (param_dtype)."""
+    if f == 1 and not as_series and tuple(geom) == (1, 0, 0):
+        raise _lib.TgcnError("forward_series / cheb_time_windows: bfloat16 parameters are not supported on a single-channel series with "
+                             "as_series=False at stride=1, padding=0 (the scalar-load form); as_series=True or any stride / padding runs")
+    if series_dtype != BF16:
+        raise _lib.TgcnError("forward_series / cheb_time_windows: the parameters are bfloat16 but the series is %s -- cast it once "
+                             "(series.to(torch.bfloat16))" % series_dtype)
+
+
 class ChebSeriesFn(torch.autograd.Function):
     """Streaming time-window layer on a multi-channel series (S, n, T, f), weight (K, H, f, N): the hops run once on rows of T*f floats in
     both directions, the window projection and its two gradients are the sliding-window MFMA kernels of csrc/windows.h
@@ -500,9 +513,10 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     stride, padding: the layer as a convolution over time.  padding = p, (left, right) or "causal" (= (H-1, 0)) puts that many zero time rows
     (at most H-1 each) around every recording, stride keeps every stride-th window: nwin = (T + left + right - H) // stride + 1 windows,
     xw[s*nwin + w, i, h, c] = padded_series[s, i, w*stride + h, c], out (S*nwin, n, N) or (S, n, nwin, N).  The hops do not depend on either;
-    the projection and its gradients shrink with the stride.  Anything but stride=1, padding=0 runs the MFMA kernels, f == 1 included."""
-    if param_dtype(weight, bias, "cheb_time_windows") == BF16:
-        raise _lib.TgcnError("forward_series / cheb_time_windows: bfloat16 parameters are not supported")
+    the projection and its gradients shrink with the stride.  Anything but stride=1, padding=0 runs the MFMA kernels, f == 1 included.
+    bfloat16 parameters take ChebSeriesBf16Fn (bf16 series, stack and output, fp32 sums) for every call but the scalar-load form; that one, and
+    a series that is not bfloat16 itself, raise TgcnError before anything is built (check_series_bf16)."""
+    bf16 = param_dtype(weight, bias, "cheb_time_windows") == BF16
     if series.dim() not in (3, 4) or weight.dim() != series.dim():
         raise _lib.TgcnError("cheb_time_windows: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
                              "(got %s and %s)" % (tuple(series.shape), tuple(weight.shape)))
@@ -510,7 +524,15 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     if series.dim() == 4 and weight.shape[2] != f:
         raise _lib.TgcnError("cheb_time_windows: the series has %d channels, the weight %d" % (f, weight.shape[2]))
     geom = series_geometry(series.shape[2], weight.shape[1], stride, padding)[:3]
+    if bf16:
+        check_series_bf16(f, as_series, geom, series.dtype)
     _lib.require_device(series, weight, bias)
+    if bf16:
+        if series.dim() == 3:
+            series, weight = series.unsqueeze(3), weight.unsqueeze(2)
+        series, bias = _to_operand_labels(op, series, bias, bias_kind)      # (the relabelling kernel is fp32: bf16 values pass through it exactly)
+        out = ChebSeriesBf16Fn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom)
+        return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm).to(BF16)
     if f == 1 and not as_series and geom == (1, 0, 0):
         if series.dim() == 4:
             series, weight = series.reshape(series.shape[:3]), weight.reshape(weight.shape[0], weight.shape[1], weight.shape[3])
@@ -1443,15 +1465,19 @@ def _working_weight_bf16(fold, W):
     return fold_weight(fold, W.float()).to(BF16) if fold is not None else W
 
 
-def _basis_bf16(op, x3, K, mode):
+def _basis_bf16(op, x3, K, mode, out=None):
     """the K terms of the layer's basis on bf16 rows, one bf16 hop each: monomials L^k x (MODE_POWER: the basis of the folded weight),
-    Chebyshev T_k x (MODE_CHEBYSHEV); term 0 is x3"""
-    terms = [x3]
+    Chebyshev T_k x (MODE_CHEBYSHEV); term 0 is x3.  out: a (K,) + x3.shape bf16 tensor whose slices the terms are written into (term 0 is
+    copied there)"""
+    if out is not None:
+        out[0].copy_(x3)
+    terms = [x3 if out is None else out[0]]
     for k in range(1, K):
+        dst = None if out is None else out[k]
         if mode == MODE_POWER or k == 1:
-            terms.append(csr_hop_bf16(op, terms[k - 1]))
+            terms.append(csr_hop_bf16(op, terms[k - 1], out=dst))
         else:
-            terms.append(csr_hop_bf16(op, terms[k - 1], z=terms[k - 2], alpha=2.0, beta=-1.0))
+            terms.append(csr_hop_bf16(op, terms[k - 1], z=terms[k - 2], alpha=2.0, beta=-1.0, out=dst))
     return terms
 
 
@@ -1549,3 +1575,83 @@ def cheb_layer_bf16(op, x3, weight_kcn, bias, bias_kind, mode, values=None):
     x3, bias = _to_operand_labels(op, x3, bias, bias_kind)        # (the relabelling kernel is fp32: bf16 values pass through it exactly)
     out = ChebLayerBf16Fn.apply(x3, weight_kcn, bias, op, mode, bias_kind, torch.is_grad_enabled())
     return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm).to(BF16)
+
+
+class ChebSeriesBf16Fn(torch.autograd.Function):
+    """ChebSeriesFn with bfloat16 parameters, at the rounding points of the bf16 layers (DESIGN.md 3.9 / 3.10 "bf16"): the series is bf16 (the
+    caller's: check_series_bf16), the stack (K, S, n, ld) comes from the bf16 hops on rows of T*f elements (_basis_bf16: every hop rounds once), the
+    weight is folded in fp32 and rounded once (_working_weight_bf16), the sliding-window projection (tgcn_cheb_project_series_conv_bf16) sums in
+    fp32, adds the bias in fp32 and rounds once; out is bf16 in either layout.  Rows of T*f >= 7 elements that are no multiple of 8 are padded
+    with trailing zeros up to one (ld, the 16-byte hop form) -- never by channels: a time row stays f contiguous elements.
+    The plan queries -- the forward's and, when the series needs a gradient, the input gradient's -- are asked before the hops.  Backward (tgcn_cheb_series_conv_backward_bf16): dW fp32 from the bf16 stack (kept at 2 B per
+    element) and the bf16 g, fold transposed in fp32, rounded; d series = the fp32 G through the fp32 adjoint hops on L^T, rounded once; the
+    bias gradient is reduced in fp32 and rounded."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom=(1, 0, 0)):
+        L = _lib.lib()
+        S, n, T, f = series.shape
+        K, H, _, N = weight_khfg.shape
+        stride, left, right = geom
+        nwin = (T + left + right - H) // stride + 1
+        hc, lds = C.c_int32(0), C.c_int32(0)
+        _lib.check(L.tgcn_series_conv_plan_bf16(H, f, N, int(f % 8 == 0), stride, C.byref(hc), C.byref(lds)))
+        if ctx.needs_input_grad[0]:       # the input gradient's own span (phase 0 at step 1 over g as a series of N channels): refused here, not in the backward
+            st = min(stride, T + left + right)
+            _lib.check(L.tgcn_series_conv_plan_bf16(-(-H // st), N, K * f, int(N % 8 == 0), 1, C.byref(hc), C.byref(lds)))
+        Tf = T * f
+        ld = Tf if (Tf % 8 == 0 or Tf < 7) else Tf + (-Tf) % 8
+        x3 = series.to(BF16).contiguous().view(S, n, Tf)      # bf16 already, or its bf16 values in fp32 behind a reordered operand's relabelling
+        if ld != Tf:
+            x3 = torch.nn.functional.pad(x3, (0, ld - Tf))
+        W = weight_khfg.to(BF16).contiguous().view(K, H * f, N)
+        fold = _power_fold(mode, W)
+        Wt = _working_weight_bf16(fold, W)
+        # the series is in the operand's labels already (cheb_time_windows relabelled it)
+        stack = torch.empty((K, S, n, ld), dtype=BF16, device=x3.device)
+        _basis_bf16(op, x3, K, mode, out=stack)
+        out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=BF16, device=x3.device)
+        b = bias.to(BF16).contiguous() if bias is not None else None
+        _lib.check(L.tgcn_cheb_project_series_conv_bf16(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), ld, _lib.ptr(Wt), _lib.ptr(b),
+                                                        _lib.DTYPE_BF16, bias_kind, 1 if as_series else 0, _lib.ptr(out), stride, left, right))
+        ctx.save_for_backward(Wt)
+        ctx.stack = stack if ctx.needs_input_grad[1] else None       # the basis the weight gradient contracts with g, 2 B per element
+        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
+        ctx.dims, ctx.ld, ctx.geom = (S, n, T, f, H, N, K), ld, (stride, left, right)
+        ctx.bias_shape = None if bias is None else bias.shape
+        ctx.dtypes = (series.dtype, weight_khfg.dtype, None if bias is None else bias.dtype)
+        return out
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, g):
+        Wt, = ctx.saved_tensors
+        S, n, T, f, H, N, K = ctx.dims
+        L = _lib.lib()
+        g = _aligned_input(g.to(BF16).contiguous())
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx = dW = None
+        if need_x or need_w:
+            G = torch.empty((K, S, n, T * f), dtype=torch.float32, device=g.device) if need_x else None
+            dW = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
+            ws = _workspace(L.tgcn_cheb_series_conv_backward_bf16_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
+            _lib.check(L.tgcn_cheb_series_conv_backward_bf16(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), ctx.ld, _lib.ptr(g),
+                                                             1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
+                                                             ws.numel(), *ctx.geom))
+            ctx.stack = None
+            if need_x:
+                gx = _adjoint_hops(ctx.op.transpose(), G, ctx.mode).reshape(S, n, T, f).to(ctx.dtypes[0])      # bf16 (fp32 behind a relabelling)
+            if need_w:
+                if ctx.fold is not None:
+                    dW = fold_weight(ctx.fold, dW, transpose=True)
+                dW = dW.view(K, H, f, N).to(ctx.dtypes[1])
+        gb = None
+        if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
+            g32 = g.float()
+            if ctx.as_series:
+                gb = (g32.sum(dim=(0, 1, 2)) if ctx.bias_kind == BIAS_CHANNEL else g32.sum(dim=(0, 2))).reshape(ctx.bias_shape)
+            else:
+                gb = _bias_grad(g32, ctx.bias_kind, ctx.bias_shape, True)
+            gb = gb.to(ctx.dtypes[2])
+        return gx, dW, gb, None, None, None, None, None

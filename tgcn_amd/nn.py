@@ -190,9 +190,10 @@ class TGCNCheb_H(_DenseLBase):
         stride, padding: the layer as a convolution over time (F.cheb_time_windows): padding = p, (left, right) or "causal" (H-1 zero time
         rows in front, so a chain keeps its outputs aligned with the input's time axis), each side at most H-1; stride keeps every
         stride-th window.  nwin = (T + left + right - H) // stride + 1 replaces T-H+1 above."""
-        if _compute_dtype(self) != torch.float32:
-            raise _lib.TgcnError("TGCNCheb_H.forward_series: bfloat16 parameters are not supported")
+        bf16 = _compute_dtype(self) == torch.bfloat16      # F.cheb_time_windows routes it: every call but the scalar-load form
         series, W, geom = _series_args(self, series, stride, padding)
+        if bf16:
+            F.check_series_bf16(self.weight.shape[2], as_series, geom, series.dtype)
         return F.cheb_time_windows(self._operand(series.device), series, W,
                                    None if self.bias is None else self.bias.reshape(-1),
                                    F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series,
@@ -448,9 +449,10 @@ class ChebTimeConv(_EdgeBase):
         if edge_weight is not None and edge_weight.requires_grad:
             raise _lib.TgcnError("ChebTimeConv.forward_series: learnable edge weights (edge_weight.requires_grad) are not supported -- "
                                  "use forward on the windowed batch")
-        if _compute_dtype(self, edge_weight) != torch.float32:
-            raise _lib.TgcnError("ChebTimeConv.forward_series: bfloat16 parameters are not supported")
+        bf16 = _compute_dtype(self, edge_weight) == torch.bfloat16      # as in TGCNCheb_H.forward_series
         series, W, geom = _series_args(self, series, stride, padding)
+        if bf16:
+            F.check_series_bf16(self.weight.shape[2], as_series, geom, series.dtype)
         op = self._operand(series, edge_index, edge_weight)
         return F.cheb_time_windows(op, series, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
                                    as_series=as_series,

@@ -4,6 +4,7 @@ the materialised windowed batch xw[s*nwin + w, i, h, c] = series[s, i, w + h, c]
 call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + backward.  Developer tool; bench.py's headline is untouched.
 
     python tools/series_bench.py [--steps 5] [--warmup 2] [--stride 1] [--padding 0] [--conv] [--out profiles/r08_series_channels.json]
+    python tools/series_bench.py --dtype bf16 [--out profiles/r10_series_bf16.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -12,7 +13,9 @@ layer's output inside the timed region (it has to: they do not exist before).
 --stride / --padding (an int, "left,right" or "causal") run (a) and (b) with that geometry (the baseline's windows are cut with it too, outside
 the timed region); --conv adds the cases of profiles/r09_series_conv.json: (a) 32 -> 64 and (b) at stride 4, and chain (c) with
 padding="causal" in both layers (284 time steps in, 284 out).  --include LABEL=FILE (repeatable) embeds the --out file of another run --
-the parent commit's tool on the default cases, a repeat of this one for the run-to-run spread -- with its times relative to this run's."""
+the parent commit's tool on the default cases, a repeat of this one for the run-to-run spread -- with its times relative to this run's.
+--dtype bf16 runs cases (a) 32 -> 64, (b) and (c) with bfloat16 layers (forward_series on bf16 tensors, DESIGN.md 3.10 "bf16") and, on the same
+commit, the fp32 streaming call and the bf16 module's forward on the materialised windows; default --out profiles/r10_series_bf16.json."""
 import argparse
 import json
 import os
@@ -80,8 +83,69 @@ def compare(stream, batch, steps, warmup):
     return out
 
 
+def compare_bf16(stream_bf16, stream_fp32, batch_bf16, steps, warmup):
+    out = {}
+    for train in (False, True):
+        s, f32, b = (timed(fn, train, steps, warmup) for fn in (stream_bf16, stream_fp32, batch_bf16))
+        out["forward_backward" if train else "forward"] = dict(streaming_bf16=s, streaming_fp32=f32, materialised_bf16=b,
+                                                                fp32_over_bf16=round(f32["ms_per_call"] / s["ms_per_call"], 3),
+                                                                materialised_over_streaming=round(b["ms_per_call"] / s["ms_per_call"], 3))
+    return out
+
+
+def main_bf16(args):
+    import copy
+    BF = torch.bfloat16
+    dev = torch.device("cuda:0")
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, dtype="bf16", cases={})
+    torch.manual_seed(0)
+
+    def record(name, entry):
+        res["cases"][name] = entry
+        print(json.dumps({name: entry}), flush=True)
+        torch.cuda.empty_cache()
+
+    def case(name, desc, layer, series, H):
+        lb = copy.deepcopy(layer).to(BF)
+        s32, sb = series.requires_grad_(True), series.detach().to(BF).requires_grad_(True)
+        xw = windows(series.detach(), H).to(BF).requires_grad_(True)
+        record(name, dict(desc=desc, **compare_bf16(lambda: lb.forward_series(sb), lambda: layer.forward_series(s32), lambda: lb(xw),
+                                                    args.steps, args.warmup)))
+
+    op = dti148(dev)
+    S, T, H, K = 8, 284, 15, 10
+    l1 = tgcn_amd.TGCNCheb_H(op, 1, 32, K, H).to(dev)
+    l2 = tgcn_amd.TGCNCheb_H(op, 32, 64, K, H).to(dev)
+    case("a_dti148_32to64", "dti148 S=8 T=284 H=15 K=10 f=32 -> g=64", l2, torch.randn(S, op.n, T, 32, device=dev), H)
+    n, row, col, val = synth.sheet_mesh(300, device=dev)
+    opm = GraphOperand.from_coo(n, row, col, val, dev)
+    lm = tgcn_amd.TGCNCheb_H(opm, 4, 32, 5, 15).to(dev)
+    case("b_mesh90k_4to32", "sheet_mesh(300) n=%d S=1 T=75 H=15 K=5 f=4 -> g=32" % n, lm, torch.randn(1, n, 75, 4, device=dev), 15)
+    del lm, opm
+    torch.cuda.empty_cache()
+
+    l1b, l2b = copy.deepcopy(l1).to(BF), copy.deepcopy(l2).to(BF)
+    series = torch.randn(S, op.n, T, 1, device=dev).requires_grad_(True)
+    sb = series.detach().to(BF).requires_grad_(True)
+    xw1 = windows(series.detach(), H).to(BF).requires_grad_(True)
+    T1 = T - H + 1
+
+    def chain_batch():
+        h = torch.relu(l1b(xw1))                                          # (S*T1, n, 32)
+        return l2b(windows(h.view(S, T1, op.n, 32).permute(0, 2, 1, 3), H))
+    record("c_dti148_chain", dict(desc="dti148 S=8 T=284: TGCNCheb_H(1,32,10,15) -> relu -> TGCNCheb_H(32,64,10,15)",
+                                  **compare_bf16(lambda: l2b.forward_series(torch.relu(l1b.forward_series(sb, as_series=True))),
+                                                 lambda: l2.forward_series(torch.relu(l1.forward_series(series, as_series=True))),
+                                                 chain_batch, args.steps, args.warmup)))
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r10_series_bf16.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32", help="bf16: the bfloat16 streaming cases (profiles/r10_series_bf16.json)")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--stride", type=int, default=1)
@@ -92,6 +156,8 @@ def main():
                          "each shared case's ms per call relative to this run")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.dtype == "bf16":
+        return main_bf16(args)
     dev = torch.device("cuda:0")
     res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, stride=args.stride,
                padding=args.padding, cases={})
