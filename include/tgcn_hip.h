@@ -379,6 +379,36 @@ int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_verti
                                         float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right);
 int tgcn_series_conv_plan_bf16(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes);
 
+/* The _conv entries (fp32 and bf16) with dilated taps ("Dilation"): tap h of a window lies h*dilation time rows after its
+ * first, the window spans He = (H-1)*dilation + 1 time rows, and He takes H's place in the geometry: 0 <= pad_left, pad_right <= He-1,
+ * Tp = T + pad_left + pad_right >= He, nwin = (Tp - He) / stride + 1,
+ *   out[(s, w, i), :] = sum_k sum_{h, c} stack[k, s, i, (w*stride - pad_left + h*dilation)*f + c] . W[k, h*f + c, :] + bias
+ * W stays (K, H*f, N), every other argument is the _conv entry's.  dilation == 1 makes the _conv entry's launches: bit-identical results;
+ * so does H == 1 at any dilation >= 1 and stride == 1 (one tap has nothing to dilate, and no span would bound the dilation).
+ * dilation > 1 runs at stride == 1 only (TGCN_ERR_UNSUPPORTED otherwise; dilation < 1: TGCN_ERR_INVALID): a wave owns 32 windows of one
+ * phase w % dilation, which are step-1 windows of every dilation-th time row, so the launch is planned as step 1 --
+ * tgcn_series_conv_plan(H, f, N, vec, 1) for the forward, (H, N, K*f, vec, 1) for the input gradient (one launch over the time-flipped weight,
+ * G written whole), and the _bf16 query for the bf16 entries. */
+int tgcn_cheb_project_series_dilated_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                         const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
+                                         int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation);
+size_t tgcn_cheb_series_dilated_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                         int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation);
+int tgcn_cheb_series_dilated_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                          const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
+                                          void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right,
+                                          int32_t dilation);
+int tgcn_cheb_project_series_dilated_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                          const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                          int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right,
+                                          int32_t dilation);
+size_t tgcn_cheb_series_dilated_backward_bf16_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                              int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation);
+int tgcn_cheb_series_dilated_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                           const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
+                                           float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right,
+                                           int32_t dilation);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

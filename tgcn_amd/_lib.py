@@ -149,6 +149,18 @@ SIGNATURES = {
     "tgcn_cheb_series_conv_backward_bf16": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64,
                                                       _P, C.c_int32, _P, _P, _P, _P, C.c_size_t, C.c_int32, C.c_int32, C.c_int32]),
     "tgcn_series_conv_plan_bf16": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tgcn_cheb_project_series_dilated_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                                       C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tgcn_cheb_series_dilated_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                       C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tgcn_cheb_series_dilated_backward_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                                        C.c_int32, _P, _P, _P, _P, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tgcn_cheb_project_series_dilated_bf16": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64,
+                                                        _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tgcn_cheb_series_dilated_backward_bf16_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                            C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tgcn_cheb_series_dilated_backward_bf16": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64,
+                                                         _P, C.c_int32, _P, _P, _P, _P, C.c_size_t, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "tgcn_fold_weight_f32": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32]),
     "tgcn_weight_layout_f32": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "tgcn_csr_hop_f64": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, C.c_double, C.c_double, _P, _P]),

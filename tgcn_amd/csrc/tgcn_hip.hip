@@ -1217,9 +1217,20 @@ int tgcn_series_gemm_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t*
   return TGCN_OK;
 }
 
-// stride >= 2 takes the STRIDED instantiations; stride 1 (the input gradient's phases included) the ones without a step
-static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1) {
+// Phase-major tiles of the DILATED kernels: min(dil, nwin) phases hold a window, the longest ceil(nwin / dil) of them.
+// 2 <= dil < the padded series (series_dilated_check), so nothing here leaves 32 bits.
+static void series_dilated_tiles(int32_t nwin, int32_t dil, int32_t* tpp, int32_t* tpv) {
+  const int32_t nph = dil < nwin ? dil : nwin;
+  *tpp = ((nwin - 1) / dil + 1 + kSgWin - 1) / kSgWin;
+  *tpv = nph * *tpp;
+}
+
+// stride >= 2 takes the STRIDED instantiations; stride 1 (the input gradient's phases included) the ones without a step; dil >= 2 (at step 1)
+// the DILATED ones, planned as step 1
+static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1, int dil = 1) {
   p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
+  p.dil = dil;
+  if (dil > 1) series_dilated_tiles(p.nwin, dil, &p.tpp, &p.tpv);
   p.ntiles = S * p.n * p.tpv;
   const int64_t gx = (p.ntiles + 3) / 4;
   const int NT = series_gemm_nt(p.N);
@@ -1232,15 +1243,17 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = series_row_floats(hc, p.f, vec, stride);
   const dim3 grid((unsigned)gx, (unsigned)gy);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_GEMM(NT_, VEC_, STR_)                                                                   \
+#define TGCN_SERIES_GEMM(NT_, VEC_, STR_, DIL_)                                                             \
   do {                                                                                                      \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_kernel<NT_, VEC_, STR_>, lds);            \
-    hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_, STR_>), grid, dim3(kBlock), lds, st, p);              \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_kernel<NT_, VEC_, STR_, DIL_>, lds);      \
+    hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_, STR_, DIL_>), grid, dim3(kBlock), lds, st, p);        \
   } while (0)
-#define TGCN_SERIES_GEMM_NT(VEC_, STR_)                                                                     \
-  do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_); else TGCN_SERIES_GEMM(4, VEC_, STR_); } while (0)
-  if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false); else TGCN_SERIES_GEMM_NT(false, false); }
-  else { if (vec) TGCN_SERIES_GEMM_NT(true, true); else TGCN_SERIES_GEMM_NT(false, true); }
+#define TGCN_SERIES_GEMM_NT(VEC_, STR_, DIL_)                                                               \
+  do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_, DIL_); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_, DIL_);   \
+       else TGCN_SERIES_GEMM(4, VEC_, STR_, DIL_); } while (0)
+  if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true); else TGCN_SERIES_GEMM_NT(false, false, true); }
+  else if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, false); else TGCN_SERIES_GEMM_NT(false, false, false); }
+  else { if (vec) TGCN_SERIES_GEMM_NT(true, true, false); else TGCN_SERIES_GEMM_NT(false, true, false); }
 #undef TGCN_SERIES_GEMM_NT
 #undef TGCN_SERIES_GEMM
   return TGCN_OK;
@@ -1262,10 +1275,31 @@ static bool series_conv_shape_ok(int64_t S, int64_t n, int32_t T, int32_t f, int
 static int32_t series_conv_stride(int32_t T, int32_t stride, int32_t pl, int32_t pr) { return stride < T + pl + pr ? stride : T + pl + pr; }
 static int64_t series_conv_nwin(int32_t T, int32_t H, int32_t stride, int32_t pl, int32_t pr) { return ((int64_t)T + pl + pr - H) / stride + 1; }
 
+// One tap has nothing to dilate: H == 1 at any dilation >= 1 is the undilated window, and the _dilated entries hand it to the _conv entries
+// (at stride 1; with a step the combination stays refused like every dilation > 1), so no dilation without a bound reaches a kernel.
+static bool series_dilation_is_one(int32_t H, int32_t stride, int32_t dil) { return dil == 1 || (H == 1 && dil > 1 && stride == 1); }
+
+// Dilated taps: the window spans He = (H - 1) * dilation + 1 time rows, and He takes H's place in the geometry rules of the _conv entries.
+// TGCN_OK, TGCN_ERR_INVALID for a bad value, TGCN_ERR_UNSUPPORTED for dilation > 1 with stride > 1 (not built).  *He_out: the span.
+// For H >= 2 the span bounds the dilation, dil < He <= Tp < 2^25: the 32 windows of a wave, dil time rows apart, stay inside 32 bits.
+static int series_dilated_check(int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, int32_t stride, int32_t pl, int32_t pr,
+                                int32_t dil, int32_t* He_out) {
+  if (dil < 1 || H < 1 || T < 1) return TGCN_ERR_INVALID;
+  const int64_t He = ((int64_t)H - 1) * dil + 1;
+  if (He > (int64_t)T + (pl > 0 ? pl : 0) + (pr > 0 ? pr : 0) || He >= (int64_t)INT32_MAX / 64) return TGCN_ERR_INVALID;
+  // the He-row window in the _conv rules (pads below He, the padded series holds a window, 32-bit time arithmetic); the weight's own H for the rest
+  if (!series_conv_shape_ok(S, n, T, f, (int32_t)He, N, K, stride, pl, pr) || !series_shape_ok(S, n, (int32_t)((int64_t)T + pl + pr), f, H, N, K))
+    return TGCN_ERR_INVALID;
+  if (dil > 1 && stride > 1) return TGCN_ERR_UNSUPPORTED;
+  if (dil > 1 && dil >= He) return TGCN_ERR_INVALID;   // H == 1: no span bounds the dilation (the entries take series_dilation_is_one's way)
+  *He_out = (int32_t)He;
+  return TGCN_OK;
+}
+
 static int project_series_impl(hipStream_t st, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, const float* stack,
                                const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out, int32_t stride, int32_t pl,
-                               int32_t pr, const char* who) {
-  const int64_t Tf = (int64_t)T * f, nwin = series_conv_nwin(T, H, stride, pl, pr);
+                               int32_t pr, const char* who, int32_t dil = 1) {
+  const int64_t Tf = (int64_t)T * f, nwin = series_conv_nwin(T, (H - 1) * dil + 1, stride, pl, pr);
   SeriesGemmParams p;
   memset(&p, 0, sizeof(p));
   p.src = stack; p.W = W; p.bias = bias; p.out = out;
@@ -1275,7 +1309,7 @@ static int project_series_impl(hipStream_t st, int64_t S, int64_t n, int32_t T, 
   p.o_gs = 0; p.ocg = N;
   p.n = n; p.Tin = T; p.padl = pl; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
   const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0);
-  return series_gemm_launch(st, p, S, vec, who, stride);
+  return series_gemm_launch(st, p, S, vec, who, stride, dil);
 }
 
 int tgcn_cheb_project_series_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
@@ -1300,6 +1334,23 @@ int tgcn_cheb_project_series_conv_f32(void* stream, int64_t S, int64_t n_vertice
   if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, stride, pad_left,
                                    pad_right, "project_series_conv")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_conv_f32");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_series_dilated_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                         const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
+                                         int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
+  if (series_dilation_is_one(H, stride, dilation))
+    return tgcn_cheb_project_series_conv_f32(stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, stride, pad_left, pad_right);
+  int32_t He = 0;
+  const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
+  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "project_series_dilated: dilation %d with stride %d is not built", dilation, stride);
+  if (grc || !stack || !W || !out) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_dilated: bad argument");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_dilated: bias_kind %d", bias_kind);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_dilated")) return drc;
+  if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, 1, pad_left,
+                                   pad_right, "project_series_dilated", dilation)) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_dilated_f32");
   return TGCN_OK;
 }
 
@@ -1332,8 +1383,8 @@ size_t tgcn_cheb_series_conv_backward_workspace_bytes(int64_t S, int64_t n_verti
 // Both gradients for a window step and zero padding; (1, 0, 0) is tgcn_cheb_series_backward_f32's launch sequence, launch for launch.
 static int series_backward_impl(hipStream_t st, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, const float* stack,
                                 const float* g, int32_t g_as_series, const float* W, float* G, float* dW, void* workspace, int32_t stride,
-                                int32_t pl, int32_t pr, const char* who) {
-  const int64_t Tf = (int64_t)T * f, nwin = series_conv_nwin(T, H, stride, pl, pr), wf = (int64_t)K * H * f * N;
+                                int32_t pl, int32_t pr, const char* who, int32_t dil = 1) {
+  const int64_t Tf = (int64_t)T * f, nwin = series_conv_nwin(T, (H - 1) * dil + 1, stride, pl, pr), wf = (int64_t)K * H * f * N;
   const bool conv = stride != 1 || pl != 0 || pr != 0;
   int64_t g_ss, g_is, g_ws;
   if (g_as_series) { g_ss = n * nwin * N; g_is = nwin * N; g_ws = N; }
@@ -1346,23 +1397,34 @@ static int series_backward_impl(hipStream_t st, int64_t S, int64_t n, int32_t T,
     // the time rows of the phases ph >= H (a step longer than the window) lie between the windows: exact zeros
     if (stride > H && hipMemsetAsync(G, 0, (size_t)K * S * n * Tf * sizeof(float), st) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "%s: memset failed", who);
     const bool vec = (N % 4 == 0) && (((uintptr_t)g & 15) == 0);
-    for (int ph = 0; ph < stride && ph < H; ++ph) {
-      // time rows t = u * stride + ph - pl, u0 <= u <= u1; row u sums g[u - m] W[ph + m * stride]^T over m < Hp: "window" u - u0 of the
-      // Hp-row kernel reaching Hp - 1 - u0 rows back
-      const int Hp = series_phase_rows(H, stride, ph);
-      // (a recording shorter than the phase, T + pl <= ph, has no time row of it: what its windows send there falls into the right padding)
-      if ((int64_t)T - 1 + pl - ph < 0) continue;
-      const int64_t u0 = ph >= pl ? 0 : (pl - ph + stride - 1) / stride, u1 = ((int64_t)T - 1 + pl - ph) / stride;
-      if (u1 < u0) continue;
-      SeriesGemmParams p;
-      memset(&p, 0, sizeof(p));
-      p.src = g; p.W = Wd + (int64_t)series_phase_row0(H, stride, ph) * N * K * f; p.bias = nullptr;
-      p.out = G + (u0 * stride + ph - pl) * f;
-      p.src_ks = 0; p.src_ss = g_ss; p.src_is = g_is; p.src_ts = g_ws;
-      p.o_ss = n * Tf; p.o_is = Tf; p.o_ws = (int64_t)stride * f; p.o_gs = S * n * Tf; p.ocg = f;
-      p.n = n; p.Tin = (int32_t)nwin; p.padl = (int32_t)(Hp - 1 - u0); p.nwin = (int32_t)(u1 - u0 + 1); p.H = Hp; p.f = N; p.N = K * f; p.nterms = 1;
-      p.bias_kind = 0;
-      if (int rc = series_gemm_launch(st, p, S, vec, who)) return rc;
+    SeriesGemmParams over_g;      // what every launch over g shares: g as a series of N channels, columns (k, c) into (K, S, n, T*f)
+    memset(&over_g, 0, sizeof(over_g));
+    over_g.src = g; over_g.bias = nullptr; over_g.bias_kind = 0;
+    over_g.src_ks = 0; over_g.src_ss = g_ss; over_g.src_is = g_is; over_g.src_ts = g_ws;
+    over_g.o_ss = n * Tf; over_g.o_is = Tf; over_g.o_gs = S * n * Tf; over_g.ocg = f;
+    over_g.n = n; over_g.Tin = (int32_t)nwin; over_g.f = N; over_g.N = K * f; over_g.nterms = 1;
+    if (dil > 1) {
+      // dilated taps (step 1): time row t sums g[t + pl - h * dil] W[h]^T -- "window" t of the DILATED kernel over g with the flipped weight,
+      // reaching (H - 1) * dil - pl rows back; all T rows in one launch
+      SeriesGemmParams p = over_g;
+      p.W = Wd; p.out = G; p.o_ws = f;
+      p.padl = (H - 1) * dil - pl; p.nwin = T; p.H = H;
+      if (int rc = series_gemm_launch(st, p, S, vec, who, 1, dil)) return rc;
+    } else {
+      for (int ph = 0; ph < stride && ph < H; ++ph) {
+        // time rows t = u * stride + ph - pl, u0 <= u <= u1; row u sums g[u - m] W[ph + m * stride]^T over m < Hp: "window" u - u0 of the
+        // Hp-row kernel reaching Hp - 1 - u0 rows back
+        const int Hp = series_phase_rows(H, stride, ph);
+        // (a recording shorter than the phase, T + pl <= ph, has no time row of it: what its windows send there falls into the right padding)
+        if ((int64_t)T - 1 + pl - ph < 0) continue;
+        const int64_t u0 = ph >= pl ? 0 : (pl - ph + stride - 1) / stride, u1 = ((int64_t)T - 1 + pl - ph) / stride;
+        if (u1 < u0) continue;
+        SeriesGemmParams p = over_g;
+        p.W = Wd + (int64_t)series_phase_row0(H, stride, ph) * N * K * f;
+        p.out = G + (u0 * stride + ph - pl) * f; p.o_ws = (int64_t)stride * f;
+        p.padl = (int32_t)(Hp - 1 - u0); p.nwin = (int32_t)(u1 - u0 + 1); p.H = Hp;
+        if (int rc = series_gemm_launch(st, p, S, vec, who)) return rc;
+      }
     }
   }
   if (dW) {
@@ -1374,7 +1436,7 @@ static int series_backward_impl(hipStream_t st, int64_t S, int64_t n, int32_t T,
     q.st_ks = S * n * Tf; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
     q.M = M; q.rows_per_block = series_wgrad_rows_per_block(M, wf); q.n = n;
     q.Tf = (int32_t)Tf; q.f = f; q.nwin = (int32_t)nwin; q.J = H * f; q.N = N; q.K = K;
-    q.stride = stride; q.padl = pl; q.T = T;
+    q.stride = stride; q.padl = pl; q.T = T; q.dil = dil;
     const int64_t nblocks = (M + q.rows_per_block - 1) / q.rows_per_block;
     const int64_t jtiles = (q.J + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
     if (q.rows_per_block + nwin >= (int64_t)INT32_MAX || q.rows_per_block / nwin + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX ||
@@ -1382,7 +1444,8 @@ static int series_backward_impl(hipStream_t st, int64_t S, int64_t n, int32_t T,
       TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: weight gradient shape too large", who);
     { ProfScope ps(TGCN_PROF_WGRAD, st);
       const dim3 grid((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups));
-      if (conv) hipLaunchKernelGGL(series_wgrad_partial_kernel<true>, grid, dim3(64), 0, st, q);
+      if (dil > 1) hipLaunchKernelGGL((series_wgrad_partial_kernel<true, true>), grid, dim3(64), 0, st, q);
+      else if (conv) hipLaunchKernelGGL(series_wgrad_partial_kernel<true>, grid, dim3(64), 0, st, q);
       else hipLaunchKernelGGL(series_wgrad_partial_kernel<false>, grid, dim3(64), 0, st, q); }
     WgradParams r;
     memset(&r, 0, sizeof(r));
@@ -1421,6 +1484,35 @@ int tgcn_cheb_series_conv_backward_f32(void* stream, int64_t S, int64_t n_vertic
   return TGCN_OK;
 }
 
+size_t tgcn_cheb_series_dilated_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                         int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
+  if (series_dilation_is_one(H, stride, dilation)) return tgcn_cheb_series_conv_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
+  int32_t He = 0;
+  if (series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He)) return 0;
+  return series_backward_workspace(S * n_vertices * series_conv_nwin(T, He, 1, pad_left, pad_right), (int64_t)K * H * f * N);
+}
+
+int tgcn_cheb_series_dilated_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                          const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
+                                          void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right,
+                                          int32_t dilation) {
+  if (series_dilation_is_one(H, stride, dilation))
+    return tgcn_cheb_series_conv_backward_f32(stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, workspace_bytes,
+                                              stride, pad_left, pad_right);
+  int32_t He = 0;
+  const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
+  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "series_dilated_backward: dilation %d with stride %d is not built", dilation, stride);
+  if (grc || !g) TGCN_FAIL(TGCN_ERR_INVALID, "series_dilated_backward: bad argument");
+  if (int drc = check_pointer_device(g, (hipStream_t)stream, "series_dilated_backward")) return drc;
+  const size_t need = tgcn_cheb_series_dilated_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))
+    TGCN_FAIL(TGCN_ERR_WORKSPACE, "series_dilated_backward: workspace %zu < %zu", workspace_bytes, need);
+  if (int rc = series_backward_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, 1, pad_left,
+                                    pad_right, "series_dilated_backward", dilation)) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_series_dilated_backward_f32");
+  return TGCN_OK;
+}
+
 // ---- streaming time windows on bf16 tensors (windows_bf16.h): one entry family, the general geometry; (1, 0, 0) is its default
 // series_gemm_lds's three regimes on bf16 span bytes: the weight tile is NT*16 columns of kPbLd bf16
 static int series_gemm_bf16_lds(int H, int f, int NT, bool vec, int stride, int* hc_out) {
@@ -1441,9 +1533,13 @@ int tgcn_series_conv_plan_bf16(int32_t H, int32_t f, int32_t N, int32_t vec, int
   return TGCN_OK;
 }
 
-// out_f32: the input gradient's fp32 columns; otherwise bf16 output.  stride >= 2 takes the STRIDED instantiations.
-static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride = 1) {
+// out_f32: the input gradient's fp32 columns; otherwise bf16 output.  stride >= 2 takes the STRIDED instantiations, dil >= 2 (at step 1) the
+// DILATED ones, planned as step 1.
+static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride = 1,
+                                   int dil = 1) {
   p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
+  p.dil = dil;
+  if (dil > 1) series_dilated_tiles(p.nwin, dil, &p.tpp, &p.tpv);
   p.ntiles = S * p.n * p.tpv;
   const int64_t gx = (p.ntiles + 3) / 4;
   const int NT = series_gemm_nt(p.N);
@@ -1456,20 +1552,23 @@ static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int6
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = vec ? series_bf16_row_elems(p.f, p.lst) : p.f;
   const dim3 grid((unsigned)gx, (unsigned)gy);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_GEMM_B(NT_, VEC_, STR_, OUT_)                                                                 \
-  do {                                                                                                            \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_>, lds);       \
-    hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_>), grid, dim3(kBlock), lds, st, p);         \
+#define TGCN_SERIES_GEMM_B(NT_, VEC_, STR_, OUT_, DIL_)                                                                 \
+  do {                                                                                                                  \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_>, lds);       \
+    hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_>), grid, dim3(kBlock), lds, st, p);         \
   } while (0)
-#define TGCN_SERIES_GEMM_B_NT(VEC_, STR_, OUT_)                                                                   \
-  do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_); else if (NT == 2) TGCN_SERIES_GEMM_B(2, VEC_, STR_, OUT_);   \
-       else TGCN_SERIES_GEMM_B(4, VEC_, STR_, OUT_); } while (0)
-  if (out_f32) {        // the input gradient: one launch per phase, each at step 1
-    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float); else TGCN_SERIES_GEMM_B_NT(false, false, float);
+#define TGCN_SERIES_GEMM_B_NT(VEC_, STR_, OUT_, DIL_)                                                                   \
+  do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_, DIL_); else if (NT == 2) TGCN_SERIES_GEMM_B(2, VEC_, STR_, OUT_, DIL_);   \
+       else TGCN_SERIES_GEMM_B(4, VEC_, STR_, OUT_, DIL_); } while (0)
+  if (dil > 1) {        // dilated taps at step 1: the forward, and the input gradient in one launch
+    if (out_f32) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, true); else TGCN_SERIES_GEMM_B_NT(false, false, float, true); }
+    else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true); }
+  } else if (out_f32) {        // the input gradient: one launch per phase, each at step 1
+    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, false); else TGCN_SERIES_GEMM_B_NT(false, false, float, false);
   } else if (stride == 1) {
-    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16);
+    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, false); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, false);
   } else {
-    if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16);
+    if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16, false); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16, false);
   }
 #undef TGCN_SERIES_GEMM_B_NT
 #undef TGCN_SERIES_GEMM_B
@@ -1478,16 +1577,16 @@ static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int6
 
 static bool series_stack_ld_ok(int32_t T, int32_t f, int64_t stack_ld) { return stack_ld >= (int64_t)T * f && stack_ld < (int64_t)INT32_MAX; }
 
-int tgcn_cheb_project_series_conv_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                       const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
-                                       int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right) {
-  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right) || !stack || !W || !out || !series_stack_ld_ok(T, f, stack_ld))
-    TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv_bf16: bad argument");
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv_bf16: bias_kind %d", bias_kind);
-  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv_bf16: dtype code %d", bias_dtype);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_conv_bf16")) return drc;
+// The bf16 forward after the geometry check (dil > 1: stride == 1); who names the entry in messages
+static int project_series_bf16_impl(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                    const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype, int32_t bias_kind,
+                                    int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dil, const char* who) {
+  if (!stack || !W || !out || !series_stack_ld_ok(T, f, stack_ld)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
+  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "%s: dtype code %d", who, bias_dtype);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
   stride = series_conv_stride(T, stride, pad_left, pad_right);
-  const int64_t n = n_vertices, nwin = series_conv_nwin(T, H, stride, pad_left, pad_right);
+  const int64_t n = n_vertices, nwin = series_conv_nwin(T, (H - 1) * dil + 1, stride, pad_left, pad_right);
   SeriesGemmBf16Params p;
   memset(&p, 0, sizeof(p));
   p.src = (const hbf16*)stack; p.W = (const hbf16*)W; p.bias = bias; p.out = out;
@@ -1498,8 +1597,33 @@ int tgcn_cheb_project_series_conv_bf16(void* stream, int64_t S, int64_t n_vertic
   p.n = n; p.Tin = T; p.padl = pad_left; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
   p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
   const bool vec = (f % 8 == 0) && (stack_ld % 8 == 0) && (((uintptr_t)stack & 15) == 0);
-  if (int rc = series_gemm_bf16_launch((hipStream_t)stream, p, S, vec, false, "project_series_conv_bf16", stride)) return rc;
+  return series_gemm_bf16_launch((hipStream_t)stream, p, S, vec, false, who, stride, dil);
+}
+
+int tgcn_cheb_project_series_conv_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                       const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                       int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right) {
+  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv_bf16: bad argument");
+  if (int rc = project_series_bf16_impl(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, as_series, out, stride,
+                                        pad_left, pad_right, 1, "project_series_conv_bf16")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_conv_bf16");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_series_dilated_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                          const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                          int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right,
+                                          int32_t dilation) {
+  if (series_dilation_is_one(H, stride, dilation))
+    return tgcn_cheb_project_series_conv_bf16(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, as_series, out,
+                                              stride, pad_left, pad_right);
+  int32_t He = 0;
+  const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
+  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "project_series_dilated_bf16: dilation %d with stride %d is not built", dilation, stride);
+  if (grc) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_dilated_bf16: bad argument");
+  if (int rc = project_series_bf16_impl(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, as_series, out, 1,
+                                        pad_left, pad_right, dilation, "project_series_dilated_bf16")) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_dilated_bf16");
   return TGCN_OK;
 }
 
@@ -1509,17 +1633,18 @@ size_t tgcn_cheb_series_conv_backward_bf16_workspace_bytes(int64_t S, int64_t n_
   return tgcn_cheb_series_conv_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
 }
 
-int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                        const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
-                                        float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right) {
-  const char* who = "series_conv_backward_bf16";
-  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right) || !g) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+// Both bf16 gradients after the geometry check (dil > 1: stride == 1); need: the entry's own workspace size
+static int series_backward_bf16_impl(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                     const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G, float* dW,
+                                     void* workspace, size_t workspace_bytes, size_t need, int32_t stride, int32_t pad_left, int32_t pad_right,
+                                     int32_t dil, const char* who) {
+  if (!g) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
   if (int drc = check_pointer_device(g, (hipStream_t)stream, who)) return drc;
-  const size_t need = tgcn_cheb_series_conv_backward_bf16_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
   if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) TGCN_FAIL(TGCN_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
   stride = series_conv_stride(T, stride, pad_left, pad_right);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t n = n_vertices, Tf = (int64_t)T * f, nwin = series_conv_nwin(T, H, stride, pad_left, pad_right), wf = (int64_t)K * H * f * N;
+  const int64_t n = n_vertices, Tf = (int64_t)T * f, nwin = series_conv_nwin(T, (H - 1) * dil + 1, stride, pad_left, pad_right),
+                wf = (int64_t)K * H * f * N;
   const int32_t pl = pad_left;
   const bool conv = stride != 1 || pad_left != 0 || pad_right != 0;
   int64_t g_ss, g_is, g_ws;
@@ -1536,20 +1661,29 @@ int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_verti
     // 16-byte loads of g's time rows: N % 8 makes every stride of either layout a multiple of 8 elements.  The phases' weights start at
     // rows of N*K*f elements: any alignment, the weight tile is loaded element by element.
     const bool vec = (N % 8 == 0) && (((uintptr_t)g & 15) == 0);
-    for (int ph = 0; ph < stride && ph < H; ++ph) {
-      const int Hp = series_phase_rows(H, stride, ph);
-      if ((int64_t)T - 1 + pl - ph < 0) continue;
-      const int64_t u0 = ph >= pl ? 0 : (pl - ph + stride - 1) / stride, u1 = ((int64_t)T - 1 + pl - ph) / stride;
-      if (u1 < u0) continue;
-      SeriesGemmBf16Params p;
-      memset(&p, 0, sizeof(p));
-      p.src = (const hbf16*)g; p.W = Wd + (int64_t)series_phase_row0(H, stride, ph) * N * K * f; p.bias = nullptr;
-      p.out = G + (u0 * stride + ph - pl) * f;
-      p.src_ks = 0; p.src_ss = g_ss; p.src_is = g_is; p.src_ts = g_ws;
-      p.o_ss = n * Tf; p.o_is = Tf; p.o_ws = (int64_t)stride * f; p.o_gs = S * n * Tf; p.ocg = f;
-      p.n = n; p.Tin = (int32_t)nwin; p.padl = (int32_t)(Hp - 1 - u0); p.nwin = (int32_t)(u1 - u0 + 1); p.H = Hp; p.f = N; p.N = K * f; p.nterms = 1;
-      p.bias_kind = 0;
-      if (int rc = series_gemm_bf16_launch(st, p, S, vec, true, who)) return rc;
+    SeriesGemmBf16Params over_g;      // what every launch over g shares (as in series_backward_impl)
+    memset(&over_g, 0, sizeof(over_g));
+    over_g.src = (const hbf16*)g; over_g.bias = nullptr; over_g.bias_kind = 0;
+    over_g.src_ks = 0; over_g.src_ss = g_ss; over_g.src_is = g_is; over_g.src_ts = g_ws;
+    over_g.o_ss = n * Tf; over_g.o_is = Tf; over_g.o_gs = S * n * Tf; over_g.ocg = f;
+    over_g.n = n; over_g.Tin = (int32_t)nwin; over_g.f = N; over_g.N = K * f; over_g.nterms = 1;
+    if (dil > 1) {      // dilated taps (step 1): all T time rows in one launch of the DILATED kernel over g, reaching (H - 1) * dil - pl rows back
+      SeriesGemmBf16Params p = over_g;
+      p.W = Wd; p.out = G; p.o_ws = f;
+      p.padl = (H - 1) * dil - pl; p.nwin = T; p.H = H;
+      if (int rc = series_gemm_bf16_launch(st, p, S, vec, true, who, 1, dil)) return rc;
+    } else {
+      for (int ph = 0; ph < stride && ph < H; ++ph) {
+        const int Hp = series_phase_rows(H, stride, ph);
+        if ((int64_t)T - 1 + pl - ph < 0) continue;
+        const int64_t u0 = ph >= pl ? 0 : (pl - ph + stride - 1) / stride, u1 = ((int64_t)T - 1 + pl - ph) / stride;
+        if (u1 < u0) continue;
+        SeriesGemmBf16Params p = over_g;
+        p.W = Wd + (int64_t)series_phase_row0(H, stride, ph) * N * K * f;
+        p.out = G + (u0 * stride + ph - pl) * f; p.o_ws = (int64_t)stride * f;
+        p.padl = (int32_t)(Hp - 1 - u0); p.nwin = (int32_t)(u1 - u0 + 1); p.H = Hp;
+        if (int rc = series_gemm_bf16_launch(st, p, S, vec, true, who)) return rc;
+      }
     }
   }
   if (dW) {
@@ -1561,7 +1695,7 @@ int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_verti
     q.st_ks = S * n * stack_ld; q.st_is = stack_ld; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
     q.M = M; q.rows_per_block = series_wgrad_rows_per_block(M, wf); q.n = n;
     q.f = f; q.nwin = (int32_t)nwin; q.J = H * f; q.N = N; q.K = K;
-    q.stride = stride; q.padl = pl; q.T = T;
+    q.stride = stride; q.padl = pl; q.T = T; q.dil = dil;
     const int64_t nblocks = (M + q.rows_per_block - 1) / q.rows_per_block;
     const int64_t jtiles = (q.J + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
     if (q.rows_per_block + nwin >= (int64_t)INT32_MAX || q.rows_per_block / nwin + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX ||
@@ -1569,7 +1703,8 @@ int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_verti
       TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: weight gradient shape too large", who);
     { ProfScope ps(TGCN_PROF_WGRAD, st);
       const dim3 grid((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups));
-      if (conv) hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<true>, grid, dim3(64), 0, st, q);
+      if (dil > 1) hipLaunchKernelGGL((series_wgrad_bf16_partial_kernel<true, true>), grid, dim3(64), 0, st, q);
+      else if (conv) hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<true>, grid, dim3(64), 0, st, q);
       else hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<false>, grid, dim3(64), 0, st, q); }
     WgradParams r;
     memset(&r, 0, sizeof(r));
@@ -1577,7 +1712,40 @@ int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_verti
     { ProfScope ps(TGCN_PROF_WGRAD, st);
       hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
   }
+  return TGCN_OK;
+}
+
+int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                        const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
+                                        float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right) {
+  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right)) TGCN_FAIL(TGCN_ERR_INVALID, "series_conv_backward_bf16: bad argument");
+  const size_t need = tgcn_cheb_series_conv_backward_bf16_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
+  if (int rc = series_backward_bf16_impl(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, g, g_as_series, W, G, dW, workspace, workspace_bytes,
+                                         need, stride, pad_left, pad_right, 1, "series_conv_backward_bf16")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_series_conv_backward_bf16");
+  return TGCN_OK;
+}
+
+size_t tgcn_cheb_series_dilated_backward_bf16_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                              int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
+  return tgcn_cheb_series_dilated_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation);
+}
+
+int tgcn_cheb_series_dilated_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                           const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
+                                           float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right,
+                                           int32_t dilation) {
+  if (series_dilation_is_one(H, stride, dilation))
+    return tgcn_cheb_series_conv_backward_bf16(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, g, g_as_series, W, G, dW, workspace,
+                                               workspace_bytes, stride, pad_left, pad_right);
+  int32_t He = 0;
+  const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
+  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "series_dilated_backward_bf16: dilation %d with stride %d is not built", dilation, stride);
+  if (grc) TGCN_FAIL(TGCN_ERR_INVALID, "series_dilated_backward_bf16: bad argument");
+  const size_t need = tgcn_cheb_series_dilated_backward_bf16_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation);
+  if (int rc = series_backward_bf16_impl(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, g, g_as_series, W, G, dW, workspace, workspace_bytes,
+                                         need, 1, pad_left, pad_right, dilation, "series_dilated_backward_bf16")) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_series_dilated_backward_bf16");
   return TGCN_OK;
 }
 

@@ -27,6 +27,7 @@ struct SeriesGemmParams {
   int64_t n, ntiles;                // vertices per recording; wave tiles = S * n * tpv
   int32_t Tin, padl, nwin, H, f, N, nterms, ocg, bias_kind, tpv, HC;
   int32_t stride, lst, fp;          // STRIDED only: window step in time rows, window distance in span rows, floats per span row
+  int32_t dil, tpp;                 // DILATED only: time rows between two taps, tiles of 32 windows per phase
 };
 
 constexpr int kSgWin = 32;    // windows per wave
@@ -54,7 +55,14 @@ __host__ __device__ inline int64_t series_span_floats(int hc, int f, bool vec, i
 }
 __host__ __device__ constexpr int series_ws_stride(int NT) { return (NT * 16) % 32 == 0 ? NT * 16 + 16 : NT * 16; }
 
-template <int NT, bool VEC, bool STRIDED = false>
+// DILATED (taps dil >= 2 time rows apart, window step 1): window w reads the time rows w - padl + h * dil, so the windows of one phase
+// q = w % dil, w = q + v * dil, are the UNDILATED step-1 windows v of the sub-series t = (q - padl) + u * dil.  A wave owns 32 consecutive
+// windows v of one phase; tiles are phase-major inside a vertex: tile -> (recording * vertex, phase q < min(dil, nwin), block of 32
+// inside the phase), tpv = min(dil, nwin) * tpp.  Span row tr <-> time row (q - padl) + (v0 + hc0 + tr) * dil -- the phase is taken from the window
+// index, which is never negative, so the left padding needs no signed division -- and everything after the staging (span of 31 + HC rows,
+// bank layout, sliding A offsets, regimes) is the step-1 kernel's.  Phase q holds ceil((nwin - q) / dil) windows: a wave whose block starts
+// past its phase's last window stages zeros, reaches every barrier and writes nothing.
+template <int NT, bool VEC, bool STRIDED = false, bool DILATED = false>
 __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmParams p) {
   constexpr int NW = NT * 16, NS = series_ws_stride(NT), WREG = (kSgKT * NW) / kBlock;
   extern __shared__ __attribute__((aligned(16))) float sg_lds[];
@@ -64,10 +72,19 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
   const int fp = STRIDED ? p.fp : (VEC ? p.f + 2 : p.f);
   const int lst = STRIDED ? p.lst : 1;          // span rows between consecutive windows
   float* span = sg_lds + kSgKT * NS + wave * (int)(STRIDED ? series_span_floats(p.HC, p.f, VEC, p.stride) : series_span_floats(p.HC, p.f, VEC));
+  static_assert(!(STRIDED && DILATED), "a window step with dilated taps is not built");
   const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-  const bool live = tile < p.ntiles;
+  bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
-  const int w0 = live ? (int)(tile % p.tpv) * kSgWin : 0;
+  int w0 = live ? (int)(tile % p.tpv) * kSgWin : 0;      // DILATED: the first window's index v0 inside its phase
+  int ph = 0;                                             // DILATED: the phase q
+  if constexpr (DILATED) {
+    const int rem = live ? (int)(tile % p.tpv) : 0;
+    ph = rem / p.tpp;
+    w0 = (rem - ph * p.tpp) * kSgWin;
+    live = live && ph + w0 * p.dil < p.nwin;
+  }
+  const int tstep = DILATED ? p.dil : 1;                  // time rows between two span rows
   const int64_t s = si / p.n, iv = si % p.n;
   const int n0 = blockIdx.y * NW;
   const int J = p.H * p.f;
@@ -82,7 +99,8 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
     const float* __restrict__ Wt = p.W + (int64_t)term * J * p.N;
     for (int hc0 = 0; hc0 < p.H; hc0 += p.HC) {
       const int hcn = min(p.HC, p.H - hc0);
-      const int rows = (kSgWin - 1) * lst + hcn, t0 = (STRIDED ? w0 * p.stride : w0) + hc0 - p.padl;
+      const int rows = (kSgWin - 1) * lst + hcn,
+                t0 = DILATED ? ph - p.padl + (w0 + hc0) * p.dil : (STRIDED ? w0 * p.stride : w0) + hc0 - p.padl;
       // ---- this wave's span: time rows t0 .. t0 + rows - 1 (zeros outside the series, and for a wave without a tile)
       if constexpr (STRIDED) {
         // span row tr = wr * lst + hh holds time row t0 + wr * stride + hh; rows hh >= hcn lie between two windows (lst == HC > hcn): zeros
@@ -109,7 +127,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
       } else if constexpr (VEC) {
         const int f4 = p.f >> 2, total4 = rows * f4;
         for (int e = lane; e < total4; e += 64) {
-          const int tr = e / f4, c = (e - tr * f4) * 4, t = t0 + tr;
+          const int tr = e / f4, c = (e - tr * f4) * 4, t = t0 + tr * tstep;
           float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
           if (live && t >= 0 && t < p.Tin) v = *reinterpret_cast<const float4*>(base + (int64_t)t * p.src_ts + c);
           float2* d = reinterpret_cast<float2*>(span + tr * fp + c);
@@ -119,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
       } else {
         const int total = (int)series_span_floats(hcn, p.f, false);
         for (int e = lane; e < total; e += 64) {
-          const int tr = e / p.f, c = e - tr * p.f, t = t0 + tr;
+          const int tr = e / p.f, c = e - tr * p.f, t = t0 + tr * tstep;
           span[e] = (live && tr < rows && t >= 0 && t < p.Tin) ? base[(int64_t)t * p.src_ts + c] : 0.f;
         }
       }
@@ -173,7 +191,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int w = w0 + rt * 16 + kq * 4 + i;
+        const int w = DILATED ? ph + (w0 + rt * 16 + kq * 4 + i) * p.dil : w0 + rt * 16 + kq * 4 + i;
         if (w < p.nwin) orow0[(int64_t)w * p.o_ws + coff] = acc[rt][nt][i] + b;
       }
   }
@@ -214,9 +232,11 @@ struct SeriesWgradParams {
   int64_t M, rows_per_block, n;
   int32_t Tf, f, nwin, J, N, K;
   int32_t stride, padl, T;        // CONV only
+  int32_t dil;                    // DIL only
 };
 
-template <bool CONV>
+// DIL (with CONV, step 1): weight row j = h*f + c of window w reads element (tw + h * dil) * f + c, tw = w - padl, where that time row exists.
+template <bool CONV, bool DIL = false>
 __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWgradParams p) {
   const int lane = threadIdx.x;
   const int r = lane & 15, kq = lane >> 4;
@@ -235,6 +255,8 @@ __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWg
   const uint32_t i_lo = (uint32_t)(si_lo % p.n);
   const uint32_t nwin = (uint32_t)p.nwin, nv = (uint32_t)p.n;
   const int hj = CONV ? j / p.f : 0;        // the weight time row of this lane's j
+  const int hd = DIL ? hj * p.dil : hj;     // its distance from the window's first time row
+  const int jd = DIL ? j + (hd - hj) * p.f : j;
   f32x4 acc[kWgTerms][4];
 #pragma unroll
   for (int t = 0; t < kWgTerms; ++t)
@@ -253,7 +275,7 @@ __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWg
       const float* grow = p.g + s * p.g_ss + (int64_t)i * p.g_is + (int64_t)w * p.g_ws;
       const int tw = CONV ? (int)w * p.stride - p.padl : (int)w;      // first time row of the window
       const float* arow = p.stack + (s * p.n + i) * (int64_t)p.Tf;
-      const bool tok = !CONV || (tw + hj >= 0 && tw + hj < p.T);
+      const bool tok = !CONV || (tw + hd >= 0 && tw + hd < p.T);
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int nn = n0 + q * 16 + r;
@@ -261,7 +283,7 @@ __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWg
       }
 #pragma unroll
       for (int t = 0; t < kWgTerms; ++t)
-        av[u][t] = (mok && tok && j < p.J && t0 + t < p.K) ? arow[(int64_t)(t0 + t) * p.st_ks + (int64_t)tw * p.f + j] : 0.f;
+        av[u][t] = (mok && tok && j < p.J && t0 + t < p.K) ? arow[(int64_t)(t0 + t) * p.st_ks + (int64_t)tw * p.f + jd] : 0.f;
     }
 #pragma unroll
     for (int u = 0; u < kWgUnroll; ++u)

@@ -40,6 +40,7 @@ struct SeriesGemmBf16Params {
   int64_t n, ntiles;
   int32_t Tin, padl, nwin, H, f, N, nterms, ocg, bias_kind, bias_bf16, tpv, HC;
   int32_t stride, lst, fp;
+  int32_t dil, tpp;                 // DILATED only (windows.h)
 };
 
 __host__ __device__ inline int series_bf16_row_elems(int f, int lst) {
@@ -55,7 +56,9 @@ __host__ __device__ inline int64_t series_bf16_span_elems(int hc, int f, bool ve
   return vec ? rows * series_bf16_row_elems(f, lst) : (rows * f + 7) / 8 * 8;
 }
 
-template <int NT, bool VEC8, bool STRIDED, typename OutT>
+// DILATED: series_gemm_kernel's phase-major tiles (windows.h) -- 32 windows of one phase q = w % dil, staged from the sub-series
+// t = (q - padl) + u * dil; span, bank rule and A reads are the step-1 form's.
+template <int NT, bool VEC8, bool STRIDED, typename OutT, bool DILATED = false>
 __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGemmBf16Params p) {
   constexpr int NW = NT * 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char sgb_lds[];
@@ -66,10 +69,19 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
   const int fp = VEC8 ? p.fp : p.f;
   hbf16* span = Ws + NW * kPbLd + wave * (int)series_bf16_span_elems(p.HC, p.f, VEC8, stride);
   const uint16_t* span16 = reinterpret_cast<const uint16_t*>(span);
+  static_assert(!(STRIDED && DILATED), "a window step with dilated taps is not built");
   const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-  const bool live = tile < p.ntiles;
+  bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
-  const int w0 = live ? (int)(tile % p.tpv) * kSgWin : 0;
+  int w0 = live ? (int)(tile % p.tpv) * kSgWin : 0;      // DILATED: the first window's index v0 inside its phase
+  int ph = 0;                                             // DILATED: the phase q
+  if constexpr (DILATED) {
+    const int rem = live ? (int)(tile % p.tpv) : 0;
+    ph = rem / p.tpp;
+    w0 = (rem - ph * p.tpp) * kSgWin;
+    live = live && ph + w0 * p.dil < p.nwin;
+  }
+  const int tstep = DILATED ? p.dil : stride;             // time rows between two windows' first span rows
   const int64_t s = si / p.n, iv = si % p.n;
   const int n0 = blockIdx.y * NW;
   const int J = p.H * p.f;
@@ -85,7 +97,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
     const hbf16* __restrict__ Wt = p.W + (int64_t)term * J * p.N;
     for (int hc0 = 0; hc0 < p.H; hc0 += p.HC) {
       const int hcn = min(p.HC, p.H - hc0);
-      const int rows = (kSgWin - 1) * lst + hcn, t0 = w0 * stride + hc0 - p.padl;
+      const int rows = (kSgWin - 1) * lst + hcn, t0 = DILATED ? ph - p.padl + (w0 + hc0) * p.dil : w0 * stride + hc0 - p.padl;
       // ---- this wave's span: span row tr = wr * lst + hh holds time row t0 + wr * stride + hh; rows hh >= hcn lie between two windows
       // (lst == HC > hcn), rows outside the series and the span of a wave without a tile are zeros
       const int fq = VEC8 ? p.f >> 3 : p.f;                  // staged units (8 elements / 1 element) per time row
@@ -93,7 +105,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
       for (int e = lane; e < total; e += 64) {
         const int tr = e / fq, cu = e - tr * fq;
         const int wr = tr / lst, hh = tr - wr * lst;
-        const int t = t0 + wr * stride + hh;
+        const int t = t0 + wr * tstep + hh;
         const bool ok = live && hh < hcn && t >= 0 && t < p.Tin;
         if constexpr (VEC8) {
           uint4 v = make_uint4(0u, 0u, 0u, 0u);
@@ -172,7 +184,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
     for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const int w = w0 + rt * 16 + kq * 4 + i;
+        const int w = DILATED ? ph + (w0 + rt * 16 + kq * 4 + i) * p.dil : w0 + rt * 16 + kq * 4 + i;
         if (w < p.nwin) orow0[(int64_t)w * p.o_ws + coff] = (OutT)(acc[rt][nt][i] + b);
       }
   }
@@ -206,9 +218,11 @@ struct SeriesWgradBf16Params {
   int64_t M, rows_per_block, n;
   int32_t f, nwin, J, N, K;
   int32_t stride, padl, T;        // CONV only
+  int32_t dil;                    // DIL only
 };
 
-template <bool CONV>
+// DIL (with CONV, step 1): weight row j = h*f + c of window w reads element (tw + h * dil) * f + c, where that time row exists.
+template <bool CONV, bool DIL = false>
 __global__ __launch_bounds__(64) void series_wgrad_bf16_partial_kernel(const SeriesWgradBf16Params p) {
   const int lane = threadIdx.x;
   const int r = lane & 15, kq = lane >> 4;
@@ -226,6 +240,8 @@ __global__ __launch_bounds__(64) void series_wgrad_bf16_partial_kernel(const Ser
   const uint32_t i_lo = (uint32_t)(si_lo % p.n);
   const uint32_t nwin = (uint32_t)p.nwin, nv = (uint32_t)p.n;
   const int hj = CONV ? j / p.f : 0;        // the weight time row of this lane's j
+  const int hd = DIL ? hj * p.dil : hj;     // its distance from the window's first time row
+  const int jd = DIL ? j + (hd - hj) * p.f : j;
   const hbf16 zero = (hbf16)0.f;
   f32x4 acc[kWgTerms][4];
 #pragma unroll
@@ -247,8 +263,8 @@ __global__ __launch_bounds__(64) void series_wgrad_bf16_partial_kernel(const Ser
       const bool mok = mf + e < m_hi;
       const hbf16* grow = p.g + s * p.g_ss + (int64_t)i * p.g_is + (int64_t)w * p.g_ws;
       const int tw = CONV ? (int)w * p.stride - p.padl : (int)w;      // first time row of the window
-      const hbf16* arow = p.stack + (s * p.n + i) * p.st_is + (int64_t)tw * p.f + j;
-      const bool aok = mok && j < p.J && (!CONV || (tw + hj >= 0 && tw + hj < p.T));
+      const hbf16* arow = p.stack + (s * p.n + i) * p.st_is + (int64_t)tw * p.f + jd;
+      const bool aok = mok && j < p.J && (!CONV || (tw + hd >= 0 && tw + hd < p.T));
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int nn = n0 + q * 16 + r;

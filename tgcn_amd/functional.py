@@ -386,12 +386,17 @@ class ChebWindowsFn(torch.autograd.Function):
         return gx, dW, gb, None, None, None
 
 
-def series_geometry(T, H, stride=1, padding=0, who="cheb_time_windows"):
+def series_geometry(T, H, stride=1, padding=0, who="cheb_time_windows", dilation=1):
     """(stride, left, right, nwin) of a streaming call on T time steps with windows of H: padding an int p = (p, p), a pair (left, right) or
     "causal" = (H-1, 0), 0 <= left, right <= H-1 (every window touches a real row); nwin = (T + left + right - H) // stride + 1.
+    dilation (an integer >= 1) puts the H taps that many time rows apart: the window then spans He = (H-1)*dilation + 1 rows and He takes H's
+    place in all of the above; dilation > 1 runs at stride 1 only.  (H == 1: He == 1, the undilated window -- series_dilation.)
     TgcnError for anything else -- checked before an operand is built or anything launches."""
     def integer(v):
         return isinstance(v, numbers.Integral) and not isinstance(v, bool)
+    if not integer(dilation) or dilation < 1:
+        raise _lib.TgcnError("%s: dilation is an integer >= 1, got %r" % (who, dilation))
+    taps, H = H, (H - 1) * int(dilation) + 1      # from here on H is the span He
     if isinstance(padding, str):
         if padding != "causal":
             raise _lib.TgcnError('%s: padding is an int, a pair (left, right) or "causal", got %r' % (who, padding))
@@ -404,11 +409,25 @@ def series_geometry(T, H, stride=1, padding=0, who="cheb_time_windows"):
         raise _lib.TgcnError('%s: padding is an int, a pair (left, right) or "causal", got %r' % (who, padding))
     if not integer(stride) or stride < 1:
         raise _lib.TgcnError("%s: stride is an integer >= 1, got %r" % (who, stride))
+    if dilation > 1 and stride > 1:
+        raise _lib.TgcnError("%s: dilation=%d together with stride=%d is not supported (a dilated window runs at stride 1)" % (who, dilation, stride))
     if not (0 <= left <= H - 1 and 0 <= right <= H - 1):
-        raise _lib.TgcnError("%s: padding (%d, %d) outside 0 .. H - 1 = %d" % (who, left, right, H - 1))
+        raise _lib.TgcnError("%s: padding (%d, %d) outside 0 .. %s - 1 = %d" % (who, left, right, "H" if dilation == 1 else "(H - 1) * dilation + 1", H - 1))
     if T + left + right < H:
-        raise _lib.TgcnError("%s: %d time steps with padding (%d, %d) are fewer than one window of %d" % (who, T, left, right, H))
+        raise _lib.TgcnError("%s: %d time steps with padding (%d, %d) are fewer than one window of %d%s"
+                             % (who, T, left, right, H, "" if dilation == 1 else " (%d taps, dilation %d)" % (taps, dilation)))
     return int(stride), left, right, (T + left + right - H) // int(stride) + 1
+
+
+def series_dilation(H, dilation):
+    """the dilation a call with H taps runs at, after series_geometry has checked it: one tap has nothing to dilate, so H == 1 runs as
+    dilation 1 (the same windows, the same calls) whatever the value -- no dilation that a span does not bound reaches a kernel"""
+    return 1 if H == 1 else int(dilation)
+
+
+def _geom4(geom):
+    """(stride, left, right, dilation) of a geom given with or without its dilation"""
+    return (tuple(geom) + (1,))[:4]
 
 
 def check_series_bf16(f, as_series, geom, series_dtype):
@@ -416,9 +435,10 @@ def check_series_bf16(f, as_series, geom, series_dtype):
     channel, window-major, default geometry), and a series that is bfloat16 already -- a streaming chain is bf16 from end to end (an
     as_series=True output feeds the next layer as it is), so the recording is cast once by its owner, not once per call here; a series of
     another dtype with bf16 parameters is refused like a weight and a bias of two dtypes (param_dtype)."""
-    if f == 1 and not as_series and tuple(geom) == (1, 0, 0):
+    if f == 1 and not as_series and _geom4(geom) == (1, 0, 0, 1):
         raise _lib.TgcnError("forward_series / cheb_time_windows: bfloat16 parameters are not supported on a single-channel series with "
-                             "as_series=False at stride=1, padding=0 (the scalar-load form); as_series=True or any stride / padding runs")
+                             "as_series=False at stride=1, padding=0, dilation=1 (the scalar-load form); as_series=True or any stride / padding "
+                             "/ dilation runs")
     if series_dtype != BF16:
         raise _lib.TgcnError("forward_series / cheb_time_windows: the parameters are bfloat16 but the series is %s -- cast it once "
                              "(series.to(torch.bfloat16))" % series_dtype)
@@ -429,8 +449,9 @@ class ChebSeriesFn(torch.autograd.Function):
     both directions, the window projection and its two gradients are the sliding-window MFMA kernels of csrc/windows.h
     (tgcn_cheb_project_series_f32 / tgcn_cheb_series_backward_f32), one launch each for all S recordings.  as_series picks the output
     layout, (S*nwin, n, N) or (S, n, nwin, N); the backward reads its gradient in that layout in place.
-    geom = (stride, left, right): a window step and zero padding in time.  (1, 0, 0) calls the entries above; anything else their _conv
-    forms (the hops do not depend on it), after asking tgcn_series_conv_plan whether the forward's span fits -- before the hops run."""
+    geom = (stride, left, right[, dilation]): a window step, zero padding and tap distance in time.  (1, 0, 0) calls the entries above; anything
+    else their _conv forms (the hops do not depend on it), after asking tgcn_series_conv_plan whether the forward's span fits -- before the hops
+    run.  dilation > 1 (at stride 1) calls the _dilated entries, planned as step 1: their span does not grow with the dilation."""
 
     @staticmethod
     @_on_device
@@ -438,10 +459,10 @@ class ChebSeriesFn(torch.autograd.Function):
         L = _lib.lib()
         S, n, T, f = series.shape
         K, H, _, N = weight_khfg.shape
-        stride, left, right = geom
-        conv = tuple(geom) != (1, 0, 0)
-        nwin = (T + left + right - H) // stride + 1
-        if conv:
+        stride, left, right, dil = _geom4(geom)
+        conv = (stride, left, right) != (1, 0, 0)
+        nwin = (T + left + right - (H - 1) * dil - 1) // stride + 1
+        if conv or dil > 1:
             hc, lds = C.c_int32(0), C.c_int32(0)
             _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), stride, C.byref(hc), C.byref(lds)))
         x3 = _aligned_input(series.float().contiguous().view(S, n, T * f))
@@ -453,11 +474,13 @@ class ChebSeriesFn(torch.autograd.Function):
         out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=torch.float32, device=x3.device)
         b = bias.contiguous() if bias is not None else None
         args = (_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(out))
-        if conv:
+        if dil > 1:
+            _lib.check(L.tgcn_cheb_project_series_dilated_f32(*args, stride, left, right, dil))
+        elif conv:
             _lib.check(L.tgcn_cheb_project_series_conv_f32(*args, stride, left, right))
         else:
             _lib.check(L.tgcn_cheb_project_series_f32(*args))
-        ctx.geom = (stride, left, right) if conv else None
+        ctx.geom = (stride, left, right, dil) if dil > 1 else ((stride, left, right) if conv else None)
         ctx.save_for_backward(Wt)
         ctx.stack = stack if ctx.needs_input_grad[1] else None       # the basis the weight gradient contracts with g
         ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
@@ -481,6 +504,11 @@ class ChebSeriesFn(torch.autograd.Function):
                 ws = _workspace(L.tgcn_cheb_series_backward_workspace_bytes(S, n, T, f, H, N, K), g.device, floor=16)
                 _lib.check(L.tgcn_cheb_series_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
                                                            1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel()))
+            elif len(ctx.geom) == 4:
+                ws = _workspace(L.tgcn_cheb_series_dilated_backward_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
+                _lib.check(L.tgcn_cheb_series_dilated_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
+                                                                   1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
+                                                                   ws.numel(), *ctx.geom))
             else:
                 ws = _workspace(L.tgcn_cheb_series_conv_backward_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
                 _lib.check(L.tgcn_cheb_series_conv_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
@@ -502,7 +530,7 @@ class ChebSeriesFn(torch.autograd.Function):
         return gx, dW, gb, None, None, None, None, None
 
 
-def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_series=False, stride=1, padding=0):
+def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_series=False, stride=1, padding=0, dilation=1):
     """Streaming form of TGCNCheb_H / ChebTimeConv on sliding windows: series (S, n, T) raw recordings with weight (K, H, N), or
     (S, n, T, f) with weight (K, H, f, N), in the reference basis.  Returns (S * (T-H+1), n, N), identical to running the layer on the
     windowed batch x[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c] (load/data_hcp.py:146-152), but the K-1 hops run once on the T time
@@ -514,6 +542,10 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     (at most H-1 each) around every recording, stride keeps every stride-th window: nwin = (T + left + right - H) // stride + 1 windows,
     xw[s*nwin + w, i, h, c] = padded_series[s, i, w*stride + h, c], out (S*nwin, n, N) or (S, n, nwin, N).  The hops do not depend on either;
     the projection and its gradients shrink with the stride.  Anything but stride=1, padding=0 runs the MFMA kernels, f == 1 included.
+    dilation: the H taps of a window lie that many time rows apart, xw[s*nwin + w, i, h, c] = padded_series[s, i, w*stride + h*dilation, c];
+    the window spans He = (H-1)*dilation + 1 rows, and He replaces H in the padding rules ("causal" = (He-1, 0)) and in nwin.  dilation > 1
+    runs at stride 1 only (TgcnError otherwise) through the _dilated entries, f == 1 included; a chain with dilations 1, 2, 4, ... sees
+    exponentially many time steps with a few taps per layer.  A one-tap layer (H == 1) has nothing to dilate and makes the calls of dilation 1.
     bfloat16 parameters take ChebSeriesBf16Fn (bf16 series, stack and output, fp32 sums) for every call but the scalar-load form; that one, and
     a series that is not bfloat16 itself, raise TgcnError before anything is built (check_series_bf16)."""
     bf16 = param_dtype(weight, bias, "cheb_time_windows") == BF16
@@ -523,7 +555,7 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     f = series.shape[3] if series.dim() == 4 else 1
     if series.dim() == 4 and weight.shape[2] != f:
         raise _lib.TgcnError("cheb_time_windows: the series has %d channels, the weight %d" % (f, weight.shape[2]))
-    geom = series_geometry(series.shape[2], weight.shape[1], stride, padding)[:3]
+    geom = series_geometry(series.shape[2], weight.shape[1], stride, padding, dilation=dilation)[:3] + (series_dilation(weight.shape[1], dilation),)
     if bf16:
         check_series_bf16(f, as_series, geom, series.dtype)
     _lib.require_device(series, weight, bias)
@@ -533,7 +565,7 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
         series, bias = _to_operand_labels(op, series, bias, bias_kind)      # (the relabelling kernel is fp32: bf16 values pass through it exactly)
         out = ChebSeriesBf16Fn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom)
         return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm).to(BF16)
-    if f == 1 and not as_series and geom == (1, 0, 0):
+    if f == 1 and not as_series and geom == (1, 0, 0, 1):
         if series.dim() == 4:
             series, weight = series.reshape(series.shape[:3]), weight.reshape(weight.shape[0], weight.shape[1], weight.shape[3])
         series, bias = _to_operand_labels(op, series, bias, bias_kind)
@@ -1583,9 +1615,11 @@ class ChebSeriesBf16Fn(torch.autograd.Function):
     weight is folded in fp32 and rounded once (_working_weight_bf16), the sliding-window projection (tgcn_cheb_project_series_conv_bf16) sums in
     fp32, adds the bias in fp32 and rounds once; out is bf16 in either layout.  Rows of T*f >= 7 elements that are no multiple of 8 are padded
     with trailing zeros up to one (ld, the 16-byte hop form) -- never by channels: a time row stays f contiguous elements.
-    The plan queries -- the forward's and, when the series needs a gradient, the input gradient's -- are asked before the hops.  Backward (tgcn_cheb_series_conv_backward_bf16): dW fp32 from the bf16 stack (kept at 2 B per
-    element) and the bf16 g, fold transposed in fp32, rounded; d series = the fp32 G through the fp32 adjoint hops on L^T, rounded once; the
-    bias gradient is reduced in fp32 and rounded."""
+    The plan queries -- the forward's and, when the series needs a gradient, the input gradient's -- are asked before the hops.  A geom with a
+    dilation > 1 (at stride 1) takes the _dilated_bf16 entries, planned as step 1.
+    Backward (tgcn_cheb_series_conv_backward_bf16): dW fp32 from the bf16 stack (kept at 2 B per element) and the bf16 g, fold transposed in
+    fp32, rounded; d series = the fp32 G through the fp32 adjoint hops on L^T, rounded once; the bias gradient is reduced in fp32 and
+    rounded."""
 
     @staticmethod
     @_on_device
@@ -1593,12 +1627,12 @@ class ChebSeriesBf16Fn(torch.autograd.Function):
         L = _lib.lib()
         S, n, T, f = series.shape
         K, H, _, N = weight_khfg.shape
-        stride, left, right = geom
-        nwin = (T + left + right - H) // stride + 1
+        stride, left, right, dil = _geom4(geom)
+        nwin = (T + left + right - (H - 1) * dil - 1) // stride + 1
         hc, lds = C.c_int32(0), C.c_int32(0)
         _lib.check(L.tgcn_series_conv_plan_bf16(H, f, N, int(f % 8 == 0), stride, C.byref(hc), C.byref(lds)))
         if ctx.needs_input_grad[0]:       # the input gradient's own span (phase 0 at step 1 over g as a series of N channels): refused here, not in the backward
-            st = min(stride, T + left + right)
+            st = min(stride, T + left + right)      # (dilated: stride 1, all H weight time rows in the one launch)
             _lib.check(L.tgcn_series_conv_plan_bf16(-(-H // st), N, K * f, int(N % 8 == 0), 1, C.byref(hc), C.byref(lds)))
         Tf = T * f
         ld = Tf if (Tf % 8 == 0 or Tf < 7) else Tf + (-Tf) % 8
@@ -1613,12 +1647,16 @@ class ChebSeriesBf16Fn(torch.autograd.Function):
         _basis_bf16(op, x3, K, mode, out=stack)
         out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=BF16, device=x3.device)
         b = bias.to(BF16).contiguous() if bias is not None else None
-        _lib.check(L.tgcn_cheb_project_series_conv_bf16(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), ld, _lib.ptr(Wt), _lib.ptr(b),
-                                                        _lib.DTYPE_BF16, bias_kind, 1 if as_series else 0, _lib.ptr(out), stride, left, right))
+        args = (_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), ld, _lib.ptr(Wt), _lib.ptr(b), _lib.DTYPE_BF16, bias_kind,
+                1 if as_series else 0, _lib.ptr(out), stride, left, right)
+        if dil > 1:
+            _lib.check(L.tgcn_cheb_project_series_dilated_bf16(*args, dil))
+        else:
+            _lib.check(L.tgcn_cheb_project_series_conv_bf16(*args))
         ctx.save_for_backward(Wt)
         ctx.stack = stack if ctx.needs_input_grad[1] else None       # the basis the weight gradient contracts with g, 2 B per element
         ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
-        ctx.dims, ctx.ld, ctx.geom = (S, n, T, f, H, N, K), ld, (stride, left, right)
+        ctx.dims, ctx.ld, ctx.geom = (S, n, T, f, H, N, K), ld, ((stride, left, right, dil) if dil > 1 else (stride, left, right))
         ctx.bias_shape = None if bias is None else bias.shape
         ctx.dtypes = (series.dtype, weight_khfg.dtype, None if bias is None else bias.dtype)
         return out
@@ -1635,10 +1673,11 @@ class ChebSeriesBf16Fn(torch.autograd.Function):
         if need_x or need_w:
             G = torch.empty((K, S, n, T * f), dtype=torch.float32, device=g.device) if need_x else None
             dW = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
-            ws = _workspace(L.tgcn_cheb_series_conv_backward_bf16_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
-            _lib.check(L.tgcn_cheb_series_conv_backward_bf16(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), ctx.ld, _lib.ptr(g),
-                                                             1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
-                                                             ws.numel(), *ctx.geom))
+            query, entry = ((L.tgcn_cheb_series_dilated_backward_bf16_workspace_bytes, L.tgcn_cheb_series_dilated_backward_bf16)
+                            if len(ctx.geom) == 4 else (L.tgcn_cheb_series_conv_backward_bf16_workspace_bytes, L.tgcn_cheb_series_conv_backward_bf16))
+            ws = _workspace(query(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
+            _lib.check(entry(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), ctx.ld, _lib.ptr(g), 1 if ctx.as_series else 0,
+                             _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel(), *ctx.geom))
             ctx.stack = None
             if need_x:
                 gx = _adjoint_hops(ctx.op.transpose(), G, ctx.mode).reshape(S, n, T, f).to(ctx.dtypes[0])      # bf16 (fp32 behind a relabelling)

@@ -180,7 +180,7 @@ class TGCNCheb_H(_DenseLBase):
             X = X.unsqueeze(3)
         return self._stack(X)
 
-    def forward_series(self, series, as_series=False, stride=1, padding=0):
+    def forward_series(self, series, as_series=False, stride=1, padding=0, dilation=1):
         """Additive API (not in the reference): series (S, n, T) or (S, n, T, f) raw recordings, f == in_channels -> the layer's output
         for all T-H+1 sliding windows of every recording without materialising the windows (load/data_hcp.py:116-154 builds them on
         the host and the hops then run H times too often): layer(xw) for xw[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c].
@@ -189,19 +189,22 @@ class TGCNCheb_H(_DenseLBase):
         no transpose and no windows.  Differentiable: the backward runs the hops once per call too.
         stride, padding: the layer as a convolution over time (F.cheb_time_windows): padding = p, (left, right) or "causal" (H-1 zero time
         rows in front, so a chain keeps its outputs aligned with the input's time axis), each side at most H-1; stride keeps every
-        stride-th window.  nwin = (T + left + right - H) // stride + 1 replaces T-H+1 above."""
+        stride-th window.  nwin = (T + left + right - H) // stride + 1 replaces T-H+1 above.
+        dilation: the taps of a window lie that many time rows apart, xw[., i, h, c] = padded_series[s, i, w*stride + h*dilation, c]; the
+        window spans He = (H-1)*dilation + 1 rows and He replaces H in the padding rules and in nwin ("causal" = He-1 rows in front).
+        dilation > 1 needs stride=1.  A causal chain with dilations 1, 2, 4, ... sees hundreds of time steps with a few taps per layer."""
         bf16 = _compute_dtype(self) == torch.bfloat16      # F.cheb_time_windows routes it: every call but the scalar-load form
-        series, W, geom = _series_args(self, series, stride, padding)
+        series, W, geom = _series_args(self, series, stride, padding, dilation)
         if bf16:
             F.check_series_bf16(self.weight.shape[2], as_series, geom, series.dtype)
         return F.cheb_time_windows(self._operand(series.device), series, W,
                                    None if self.bias is None else self.bias.reshape(-1),
                                    F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series,
-                                   stride=geom[0], padding=geom[1:])
+                                   stride=geom[0], padding=geom[1:3], dilation=geom[3])
 
 
-def _series_args(module, series, stride=1, padding=0):
-    """(series, weight, (stride, left, right)) of a forward_series call as F.cheb_time_windows takes them -- a 3-D series with the (K, H, g) weight, a 4-D one with
+def _series_args(module, series, stride=1, padding=0, dilation=1):
+    """(series, weight, (stride, left, right, dilation)) of a forward_series call as F.cheb_time_windows takes them -- a 3-D series with the (K, H, g) weight, a 4-D one with
     (K, H, f, g) -- after the shape and geometry checks: TgcnError before anything is built or launched."""
     name = type(module).__name__
     K, H, f, g = module.weight.shape
@@ -210,8 +213,8 @@ def _series_args(module, series, stride=1, padding=0):
     if (series.shape[3] if series.dim() == 4 else 1) != f:
         raise _lib.TgcnError("%s.forward_series: the series has %d channel(s), the layer in_channels = %d"
                              % (name, series.shape[3] if series.dim() == 4 else 1, f))
-    stride, left, right, _ = F.series_geometry(series.shape[2], H, stride, padding, "%s.forward_series" % name)
-    return series, (module.weight.reshape(K, H, g) if series.dim() == 3 else module.weight), (stride, left, right)
+    stride, left, right, _ = F.series_geometry(series.shape[2], H, stride, padding, "%s.forward_series" % name, dilation)
+    return series, (module.weight.reshape(K, H, g) if series.dim() == 3 else module.weight), (stride, left, right, F.series_dilation(H, dilation))
 
 
 class GCNCheb(_DenseLBase):
@@ -439,24 +442,24 @@ class ChebTimeConv(_EdgeBase):
         return F.cheb_layer(*args, values=self._values(x, edge_index, edge_weight, args[0]))
 
 
-    def forward_series(self, series, edge_index, edge_weight=None, as_series=False, stride=1, padding=0):
+    def forward_series(self, series, edge_index, edge_weight=None, as_series=False, stride=1, padding=0, dilation=1):
         """Additive API: TGCNCheb_H.forward_series' contract for this class -- series (S, n, T) or (S, n, T, f), f == in_channels, ->
         forward(xw, edge_index, edge_weight) on the windowed batch xw[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c], as
         (S*(T-H+1), n, g) or, as_series=True, (S, n, T-H+1, g); true recurrence, per-channel bias.  The operand is the one forward builds
         and caches.  A learnable edge_weight (requires_grad) raises TgcnError: its gradient needs the basis of every window, which
         this entry exists not to form -- call forward on materialised windows to train edge weights.
-        stride, padding as in TGCNCheb_H.forward_series."""
+        stride, padding, dilation as in TGCNCheb_H.forward_series."""
         if edge_weight is not None and edge_weight.requires_grad:
             raise _lib.TgcnError("ChebTimeConv.forward_series: learnable edge weights (edge_weight.requires_grad) are not supported -- "
                                  "use forward on the windowed batch")
         bf16 = _compute_dtype(self, edge_weight) == torch.bfloat16      # as in TGCNCheb_H.forward_series
-        series, W, geom = _series_args(self, series, stride, padding)
+        series, W, geom = _series_args(self, series, stride, padding, dilation)
         if bf16:
             F.check_series_bf16(self.weight.shape[2], as_series, geom, series.dtype)
         op = self._operand(series, edge_index, edge_weight)
         return F.cheb_time_windows(op, series, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
                                    as_series=as_series,
-                                   stride=geom[0], padding=geom[1:])
+                                   stride=geom[0], padding=geom[1:3], dilation=geom[3])
 
 
 # ------------------------------------------------------------------------------------ fused caller pattern

@@ -5,6 +5,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
 
     python tools/series_bench.py [--steps 5] [--warmup 2] [--stride 1] [--padding 0] [--conv] [--out profiles/r08_series_channels.json]
     python tools/series_bench.py --dtype bf16 [--out profiles/r10_series_bf16.json]
+    python tools/series_bench.py --dilation [--out profiles/r11_series_dilation.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -15,7 +16,10 @@ the timed region); --conv adds the cases of profiles/r09_series_conv.json: (a) 3
 padding="causal" in both layers (284 time steps in, 284 out).  --include LABEL=FILE (repeatable) embeds the --out file of another run --
 the parent commit's tool on the default cases, a repeat of this one for the run-to-run spread -- with its times relative to this run's.
 --dtype bf16 runs cases (a) 32 -> 64, (b) and (c) with bfloat16 layers (forward_series on bf16 tensors, DESIGN.md 3.10 "bf16") and, on the same
-commit, the fp32 streaming call and the bf16 module's forward on the materialised windows; default --out profiles/r10_series_bf16.json."""
+commit, the fp32 streaming call and the bf16 module's forward on the materialised windows; default --out profiles/r10_series_bf16.json.
+--dilation runs the dilated cases (DESIGN.md 3.10 "Dilation"): (a) 32 -> 64 and (b) at dilation 4, and a three-layer causal chain of H = 5
+layers with dilations 1, 2, 4 (1 -> 32 -> 32 -> 64 channels, 284 steps in, 284 out, receptive field 29 steps), each next to the module's forward on
+the materialised dilated windows on the same commit; default --out profiles/r11_series_dilation.json."""
 import argparse
 import json
 import os
@@ -51,6 +55,16 @@ def windows(series, H, stride=1, padding=0):
         series = torch.nn.functional.pad(series, (0, 0, left, right))
     w = series.unfold(2, H, stride)                                        # (S, n, nwin, f, H)
     return w.permute(0, 2, 1, 4, 3).reshape(S * w.shape[2], n, H, f).contiguous()
+
+
+def windows_dilated(series, H, dilation, padding=0):
+    """(S, n, T, f) -> (S*nwin, n, H, f), contiguous: the windows of the zero-padded series whose taps lie `dilation` time rows apart"""
+    S, n, T, f = series.shape
+    left, right, nwin = F.series_geometry(T, H, 1, padding, dilation=dilation)[1:]
+    if left or right:
+        series = torch.nn.functional.pad(series, (0, 0, left, right))
+    idx = torch.arange(nwin, device=series.device)[:, None] + torch.arange(H, device=series.device)[None, :] * dilation
+    return series[:, :, idx].permute(0, 2, 1, 3, 4).reshape(S * nwin, n, H, f).contiguous()
 
 
 def padding_arg(text):
@@ -143,6 +157,62 @@ def main_bf16(args):
         json.dump(res, f, indent=1)
 
 
+def main_dilation(args):
+    dev = torch.device("cuda:0")
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, cases={})
+    torch.manual_seed(0)
+
+    def record(name, entry):
+        res["cases"][name] = entry
+        print(json.dumps({name: entry}), flush=True)
+        torch.cuda.empty_cache()
+
+    def case(name, desc, layer, series, H, d):
+        series = series.requires_grad_(True)
+        xw = windows_dilated(series.detach(), H, d).requires_grad_(True)
+        record(name, dict(desc=desc + " dilation=%d" % d, **compare(lambda: layer.forward_series(series, dilation=d), lambda: layer(xw),
+                                                                   args.steps, args.warmup)))
+
+    op = dti148(dev)
+    S, T, H, K = 8, 284, 15, 10
+    l2 = tgcn_amd.TGCNCheb_H(op, 32, 64, K, H).to(dev)
+    case("a_dti148_32to64_dilation4", "dti148 S=8 T=284 H=15 K=10 f=32 -> g=64", l2, torch.randn(S, op.n, T, 32, device=dev), H, 4)
+    del l2
+    n, row, col, val = synth.sheet_mesh(300, device=dev)
+    opm = GraphOperand.from_coo(n, row, col, val, dev)
+    lm = tgcn_amd.TGCNCheb_H(opm, 4, 32, 5, 15).to(dev)
+    case("b_mesh90k_4to32_dilation4", "sheet_mesh(300) n=%d S=1 T=75 H=15 K=5 f=4 -> g=32" % n, lm, torch.randn(1, n, 75, 4, device=dev), 15, 4)
+    del lm, opm
+    torch.cuda.empty_cache()
+
+    Hc, dils, chans = 5, (1, 2, 4), (1, 32, 32, 64)
+    layers = [tgcn_amd.TGCNCheb_H(op, chans[i], chans[i + 1], K, Hc).to(dev) for i in range(3)]
+    series = torch.randn(S, op.n, T, 1, device=dev).requires_grad_(True)
+
+    def chain_stream():
+        h = series
+        for i, (layer, d) in enumerate(zip(layers, dils)):
+            h = layer.forward_series(h, as_series=True, padding="causal", dilation=d)
+            if i < 2:
+                h = torch.relu(h)
+        return h
+
+    def chain_batch():          # every layer's windows are cut from the previous layer's output inside the timed region: they do not exist before
+        h = series
+        for i, (layer, d) in enumerate(zip(layers, dils)):
+            y = layer(windows_dilated(h, Hc, d, "causal"))               # (S*T, n, g)
+            h = y.view(S, T, op.n, -1).permute(0, 2, 1, 3)
+            if i < 2:
+                h = torch.relu(h)
+        return h
+    record("c_dti148_chain_dilated", dict(desc="dti148 S=8 T=284: three causal TGCNCheb_H(., ., 10, 5) layers 1 -> 32 -> 32 -> 64 with dilations 1, 2, 4",
+                                          **compare(chain_stream, chain_batch, args.steps, args.warmup)))
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r11_series_dilation.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32", help="bf16: the bfloat16 streaming cases (profiles/r10_series_bf16.json)")
@@ -151,6 +221,7 @@ def main():
     ap.add_argument("--stride", type=int, default=1)
     ap.add_argument("--padding", type=padding_arg, default=0)
     ap.add_argument("--conv", action="store_true", help="add the stride-4 and causal-chain cases")
+    ap.add_argument("--dilation", action="store_true", help="the dilated cases (profiles/r11_series_dilation.json)")
     ap.add_argument("--include", action="append", default=[], metavar="LABEL=FILE",
                     help="put another run's --out file (the parent commit's, a repeat of this one) into this one under runs[LABEL], with "
                          "each shared case's ms per call relative to this run")
@@ -158,6 +229,8 @@ def main():
     args = ap.parse_args()
     if args.dtype == "bf16":
         return main_bf16(args)
+    if args.dilation:
+        return main_dilation(args)
     dev = torch.device("cuda:0")
     res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, stride=args.stride,
                padding=args.padding, cases={})
