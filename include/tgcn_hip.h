@@ -409,6 +409,25 @@ int tgcn_cheb_series_dilated_backward_bf16(void* stream, int64_t S, int64_t n_ve
                                            float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right,
                                            int32_t dilation);
 
+/* Streaming state ("Streaming state"): the causal forward of the _dilated entries on one CHUNK of a longer series.  stack
+ * (K, S, n, Tc*f) (bf16: rows stack_ld elements apart) holds the hop tensors of the next Tc >= 1 time rows; ring (K, S, n, ring_ld),
+ * ring_ld >= C*f, C = (H-1)*dilation, holds the C time rows before them -- slot j (elements j*f ..) the row whose absolute index is
+ * j (mod C), head (0 <= head < C) the slot of the oldest; time row t < 0 of the chunk is slot (head + t + C) mod C.  out (S, n, Tc, N):
+ *   out[(s, i, t), :] = sum_k sum_{h, c} row[k, s, i, t - C + h*dilation][c] . W[k, h*f + c, :] + bias
+ * i.e. windows [seen, seen + Tc) of the _dilated entry on the whole series at stride 1, pads (C, 0), as_series = 1 -- bit-identical to
+ * them; a zeroed ring is the causal zero padding.  Two launches on the stream: the GEMM, then the ring update, which writes rows
+ * j in [max(0, Tc - C), Tc) of the stack to the slots (head + j) mod C in place; the caller then sets head = (head + Tc) mod C.
+ * 16-byte accesses when the stack allows them and ring_ld is a multiple of 4 (bf16: 8) elements on a 16-byte aligned ring.
+ * Planned as step 1: tgcn_series_conv_plan(H, f, N, vec, 1) / _bf16 (TGCN_ERR_UNSUPPORTED where it refuses, nothing launched).
+ * TGCN_ERR_INVALID: head outside [0, C) (H == 1 keeps no ring: call the _conv entry), Tc < 1, dilation < 1, ring_ld < C*f or
+ * ring_ld >= INT32_MAX, and every shape the _dilated entry refuses for a chunk of Tc rows behind C rows of padding. */
+int tgcn_cheb_project_series_stream_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                        const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                                        int64_t ring_ld, int32_t head, int32_t dilation);
+int tgcn_cheb_project_series_stream_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                         const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                         int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int32_t dilation);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

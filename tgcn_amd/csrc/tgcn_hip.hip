@@ -1227,7 +1227,9 @@ static void series_dilated_tiles(int32_t nwin, int32_t dil, int32_t* tpp, int32_
 
 // stride >= 2 takes the STRIDED instantiations; stride 1 (the input gradient's phases included) the ones without a step; dil >= 2 (at step 1)
 // the DILATED ones, planned as step 1
-static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1, int dil = 1) {
+// carry (step 1, the stream entries): the CARRY instantiations, which stage the time rows before the chunk from p.ring
+static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1, int dil = 1,
+                              bool carry = false) {
   p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
   p.dil = dil;
   if (dil > 1) series_dilated_tiles(p.nwin, dil, &p.tpp, &p.tpv);
@@ -1243,15 +1245,18 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = series_row_floats(hc, p.f, vec, stride);
   const dim3 grid((unsigned)gx, (unsigned)gy);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_GEMM(NT_, VEC_, STR_, DIL_)                                                             \
-  do {                                                                                                      \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_kernel<NT_, VEC_, STR_, DIL_>, lds);      \
-    hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_, STR_, DIL_>), grid, dim3(kBlock), lds, st, p);        \
+#define TGCN_SERIES_GEMM(NT_, VEC_, STR_, DIL_, ...)                                                                      \
+  do {                                                                                                                    \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_kernel<NT_, VEC_, STR_, DIL_, ##__VA_ARGS__>, lds);     \
+    hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_, STR_, DIL_, ##__VA_ARGS__>), grid, dim3(kBlock), lds, st, p);       \
   } while (0)
-#define TGCN_SERIES_GEMM_NT(VEC_, STR_, DIL_)                                                               \
-  do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_, DIL_); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_, DIL_);   \
-       else TGCN_SERIES_GEMM(4, VEC_, STR_, DIL_); } while (0)
-  if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true); else TGCN_SERIES_GEMM_NT(false, false, true); }
+#define TGCN_SERIES_GEMM_NT(VEC_, STR_, DIL_, ...)                                                                        \
+  do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_, DIL_, ##__VA_ARGS__); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_, DIL_, ##__VA_ARGS__);   \
+       else TGCN_SERIES_GEMM(4, VEC_, STR_, DIL_, ##__VA_ARGS__); } while (0)
+  if (carry) {
+    if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, true); else TGCN_SERIES_GEMM_NT(false, false, true, true); }
+    else { if (vec) TGCN_SERIES_GEMM_NT(true, false, false, true); else TGCN_SERIES_GEMM_NT(false, false, false, true); }
+  } else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true); else TGCN_SERIES_GEMM_NT(false, false, true); }
   else if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, false); else TGCN_SERIES_GEMM_NT(false, false, false); }
   else { if (vec) TGCN_SERIES_GEMM_NT(true, true, false); else TGCN_SERIES_GEMM_NT(false, true, false); }
 #undef TGCN_SERIES_GEMM_NT
@@ -1351,6 +1356,63 @@ int tgcn_cheb_project_series_dilated_f32(void* stream, int64_t S, int64_t n_vert
   if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, 1, pad_left,
                                    pad_right, "project_series_dilated", dilation)) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_dilated_f32");
+  return TGCN_OK;
+}
+
+// ---- streaming state ("Streaming state"): one chunk of Tc time rows, the C = (H - 1) * dilation rows before it in a ring
+// What both stream entries check before anything is launched: TGCN_OK and *C_out, or TGCN_ERR_INVALID.  The chunk behind C zero rows is a
+// geometry of the _dilated entries (Tp = Tc + C >= He, pad_left = C = He - 1), so their rules bound every number the kernels form.
+static int series_stream_check(int64_t S, int64_t n, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K, int32_t dil, int64_t ring_ld,
+                               int32_t head, int32_t* C_out) {
+  if (dil < 1 || Tc < 1 || H < 2) return TGCN_ERR_INVALID;       // one tap keeps no ring: the _conv entry runs it
+  const int64_t C = ((int64_t)H - 1) * dil;
+  if (C >= (int64_t)INT32_MAX / 64) return TGCN_ERR_INVALID;
+  int32_t He = 0;
+  if (dil > 1 ? series_dilated_check(S, n, Tc, f, H, N, K, 1, (int32_t)C, 0, dil, &He) != TGCN_OK
+              : !series_conv_shape_ok(S, n, Tc, f, H, N, K, 1, (int32_t)C, 0)) return TGCN_ERR_INVALID;
+  if (head < 0 || head >= C || ring_ld < C * f || ring_ld >= (int64_t)INT32_MAX) return TGCN_ERR_INVALID;
+  *C_out = (int32_t)C;
+  return TGCN_OK;
+}
+
+// The ring update launch: rows = K * S * n rows of the stack (ld elements apart) and of the ring; esize: bytes per element (4 / 2);
+// vec: 16-byte accesses (4 floats / 8 bf16 per unit), else one element
+static void series_ring_update_launch(hipStream_t st, const void* stack, void* ring, int64_t rows, int64_t stack_ld, int64_t ring_ld, int32_t f,
+                                      int esize, bool vec, int32_t Tc, int32_t C, int32_t head) {
+  const int unit = vec ? 16 / esize : 1, m = Tc < C ? Tc : C, fu = f / unit;
+  const dim3 grid(grid_1d(rows * m * fu));
+  ProfScope ps(TGCN_PROF_RELAYOUT, st);
+#define TGCN_RING_UPDATE(U_)                                                                                                        \
+  hipLaunchKernelGGL(series_ring_update_kernel<U_>, grid, dim3(kBlock), 0, st, (const U_*)stack, (U_*)ring, rows, stack_ld / unit, \
+                     ring_ld / unit, fu, Tc - m, m, C, head)
+  if (vec) TGCN_RING_UPDATE(uint4);
+  else if (esize == 4) TGCN_RING_UPDATE(uint32_t);
+  else TGCN_RING_UPDATE(uint16_t);
+#undef TGCN_RING_UPDATE
+}
+
+int tgcn_cheb_project_series_stream_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                        const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                                        int64_t ring_ld, int32_t head, int32_t dilation) {
+  int32_t C = 0;
+  if (series_stream_check(S, n_vertices, Tc, f, H, N, K, dilation, ring_ld, head, &C) || !stack || !W || !out || !ring)
+    TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream: bad argument");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream: bias_kind %d", bias_kind);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_stream")) return drc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = n_vertices, Tf = (int64_t)Tc * f;
+  SeriesGemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.src = stack; p.W = W; p.bias = bias; p.out = out;
+  p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
+  p.o_ss = n * Tc * N; p.o_is = (int64_t)Tc * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, Tc, N)
+  p.n = n; p.Tin = Tc; p.padl = C; p.nwin = Tc; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
+  p.ring = ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head;
+  // 16-byte staging and copies: the stack's rule, and a ring that keeps it
+  const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0) && (ring_ld % 4 == 0) && (((uintptr_t)ring & 15) == 0);
+  if (int rc = series_gemm_launch(st, p, S, vec, "project_series_stream", 1, dilation, true)) return rc;
+  series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, vec, Tc, C, head);
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_f32");
   return TGCN_OK;
 }
 
@@ -1536,7 +1598,7 @@ int tgcn_series_conv_plan_bf16(int32_t H, int32_t f, int32_t N, int32_t vec, int
 // out_f32: the input gradient's fp32 columns; otherwise bf16 output.  stride >= 2 takes the STRIDED instantiations, dil >= 2 (at step 1) the
 // DILATED ones, planned as step 1.
 static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride = 1,
-                                   int dil = 1) {
+                                   int dil = 1, bool carry = false) {
   p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
   p.dil = dil;
   if (dil > 1) series_dilated_tiles(p.nwin, dil, &p.tpp, &p.tpv);
@@ -1552,15 +1614,19 @@ static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int6
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = vec ? series_bf16_row_elems(p.f, p.lst) : p.f;
   const dim3 grid((unsigned)gx, (unsigned)gy);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_GEMM_B(NT_, VEC_, STR_, OUT_, DIL_)                                                                 \
-  do {                                                                                                                  \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_>, lds);       \
-    hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_>), grid, dim3(kBlock), lds, st, p);         \
+#define TGCN_SERIES_GEMM_B(NT_, VEC_, STR_, OUT_, DIL_, ...)                                                                      \
+  do {                                                                                                                            \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>, lds);  \
+    hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>), grid, dim3(kBlock), lds, st, p);    \
   } while (0)
-#define TGCN_SERIES_GEMM_B_NT(VEC_, STR_, OUT_, DIL_)                                                                   \
-  do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_, DIL_); else if (NT == 2) TGCN_SERIES_GEMM_B(2, VEC_, STR_, OUT_, DIL_);   \
-       else TGCN_SERIES_GEMM_B(4, VEC_, STR_, OUT_, DIL_); } while (0)
-  if (dil > 1) {        // dilated taps at step 1: the forward, and the input gradient in one launch
+#define TGCN_SERIES_GEMM_B_NT(VEC_, STR_, OUT_, DIL_, ...)                                                                        \
+  do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                                 \
+       else if (NT == 2) TGCN_SERIES_GEMM_B(2, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                            \
+       else TGCN_SERIES_GEMM_B(4, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__); } while (0)
+  if (carry) {          // the stream entries: bf16 out, step 1, the time rows before the chunk from p.ring
+    if (dil > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true, true); }
+    else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, false, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, false, true); }
+  } else if (dil > 1) {        // dilated taps at step 1: the forward, and the input gradient in one launch
     if (out_f32) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, true); else TGCN_SERIES_GEMM_B_NT(false, false, float, true); }
     else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true); }
   } else if (out_f32) {        // the input gradient: one launch per phase, each at step 1
@@ -1624,6 +1690,33 @@ int tgcn_cheb_project_series_dilated_bf16(void* stream, int64_t S, int64_t n_ver
   if (int rc = project_series_bf16_impl(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, as_series, out, 1,
                                         pad_left, pad_right, dilation, "project_series_dilated_bf16")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_dilated_bf16");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_series_stream_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                         const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                         int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int32_t dilation) {
+  int32_t C = 0;
+  if (series_stream_check(S, n_vertices, Tc, f, H, N, K, dilation, ring_ld, head, &C) || !stack || !W || !out || !ring ||
+      !series_stack_ld_ok(Tc, f, stack_ld))
+    TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_bf16: bad argument");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_bf16: bias_kind %d", bias_kind);
+  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_bf16: dtype code %d", bias_dtype);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_stream_bf16")) return drc;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = n_vertices;
+  SeriesGemmBf16Params p;
+  memset(&p, 0, sizeof(p));
+  p.src = (const hbf16*)stack; p.W = (const hbf16*)W; p.bias = bias; p.out = out;
+  p.src_ks = S * n * stack_ld; p.src_ss = n * stack_ld; p.src_is = stack_ld; p.src_ts = f;
+  p.o_ss = n * Tc * N; p.o_is = (int64_t)Tc * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, Tc, N)
+  p.n = n; p.Tin = Tc; p.padl = C; p.nwin = Tc; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
+  p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
+  p.ring = (const hbf16*)ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head;
+  const bool vec = (f % 8 == 0) && (stack_ld % 8 == 0) && (((uintptr_t)stack & 15) == 0) && (ring_ld % 8 == 0) && (((uintptr_t)ring & 15) == 0);
+  if (int rc = series_gemm_bf16_launch(st, p, S, vec, false, "project_series_stream_bf16", 1, dilation, true)) return rc;
+  series_ring_update_launch(st, stack, ring, K * S * n, stack_ld, ring_ld, f, 2, vec, Tc, C, head);
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_bf16");
   return TGCN_OK;
 }
 

@@ -28,6 +28,9 @@ struct SeriesGemmParams {
   int32_t Tin, padl, nwin, H, f, N, nterms, ocg, bias_kind, tpv, HC;
   int32_t stride, lst, fp;          // STRIDED only: window step in time rows, window distance in span rows, floats per span row
   int32_t dil, tpp;                 // DILATED only: time rows between two taps, tiles of 32 windows per phase
+  const float* ring;                // CARRY only: the C = padl time rows before the chunk, (nterms, S, n, ring_ld), slot j at j * f
+  int64_t ring_ks, ring_ss, ring_is;
+  int32_t C, head;                  // CARRY only: slots of the ring, slot of its oldest row
 };
 
 constexpr int kSgWin = 32;    // windows per wave
@@ -62,7 +65,11 @@ __host__ __device__ constexpr int series_ws_stride(int NT) { return (NT * 16) % 
 // index, which is never negative, so the left padding needs no signed division -- and everything after the staging (span of 31 + HC rows,
 // bank layout, sliding A offsets, regimes) is the step-1 kernel's.  Phase q holds ceil((nwin - q) / dil) windows: a wave whose block starts
 // past its phase's last window stages zeros, reaches every barrier and writes nothing.
-template <int NT, bool VEC, bool STRIDED = false, bool DILATED = false>
+// CARRY (step 1, padl == C, DILATED or not): the src is one CHUNK of a longer series and the C time rows before it live in a ring buffer --
+// slot j holds the row whose absolute index is j (mod C), head is the slot of the oldest.  Only the staging differs: a time row t < 0
+// (t >= -C always: t0 >= -padl) is loaded from slot head + t + C (mod C; the sum lies in [0, 2C), one conditional subtraction) with the
+// ring's own strides, a zeroed ring being the causal zero padding.  Span, banks, A offsets, regimes, tile decode and epilogue are untouched.
+template <int NT, bool VEC, bool STRIDED = false, bool DILATED = false, bool CARRY = false>
 __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmParams p) {
   constexpr int NW = NT * 16, NS = series_ws_stride(NT), WREG = (kSgKT * NW) / kBlock;
   extern __shared__ __attribute__((aligned(16))) float sg_lds[];
@@ -73,6 +80,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
   const int lst = STRIDED ? p.lst : 1;          // span rows between consecutive windows
   float* span = sg_lds + kSgKT * NS + wave * (int)(STRIDED ? series_span_floats(p.HC, p.f, VEC, p.stride) : series_span_floats(p.HC, p.f, VEC));
   static_assert(!(STRIDED && DILATED), "a window step with dilated taps is not built");
+  static_assert(!(STRIDED && CARRY), "a carried ring with a window step is not built");
   const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
   bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
@@ -97,6 +105,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
   for (int term = 0; term < p.nterms; ++term) {
     const float* __restrict__ base = p.src + term * p.src_ks + s * p.src_ss + iv * p.src_is;
     const float* __restrict__ Wt = p.W + (int64_t)term * J * p.N;
+    const float* __restrict__ rbase = CARRY ? p.ring + term * p.ring_ks + s * p.ring_ss + iv * p.ring_is : nullptr;
     for (int hc0 = 0; hc0 < p.H; hc0 += p.HC) {
       const int hcn = min(p.HC, p.H - hc0);
       const int rows = (kSgWin - 1) * lst + hcn,
@@ -130,6 +139,13 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
           const int tr = e / f4, c = (e - tr * f4) * 4, t = t0 + tr * tstep;
           float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
           if (live && t >= 0 && t < p.Tin) v = *reinterpret_cast<const float4*>(base + (int64_t)t * p.src_ts + c);
+          if constexpr (CARRY) {
+            if (live && t < 0 && t >= -p.C) {
+              int slot = p.head + t + p.C;
+              if (slot >= p.C) slot -= p.C;
+              v = *reinterpret_cast<const float4*>(rbase + (int64_t)slot * p.f + c);
+            }
+          }
           float2* d = reinterpret_cast<float2*>(span + tr * fp + c);
           d[0] = make_float2(v.x, v.y);
           d[1] = make_float2(v.z, v.w);
@@ -138,7 +154,15 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
         const int total = (int)series_span_floats(hcn, p.f, false);
         for (int e = lane; e < total; e += 64) {
           const int tr = e / p.f, c = e - tr * p.f, t = t0 + tr * tstep;
-          span[e] = (live && tr < rows && t >= 0 && t < p.Tin) ? base[(int64_t)t * p.src_ts + c] : 0.f;
+          float v = (live && tr < rows && t >= 0 && t < p.Tin) ? base[(int64_t)t * p.src_ts + c] : 0.f;
+          if constexpr (CARRY) {
+            if (live && tr < rows && t < 0 && t >= -p.C) {
+              int slot = p.head + t + p.C;
+              if (slot >= p.C) slot -= p.C;
+              v = rbase[(int64_t)slot * p.f + c];
+            }
+          }
+          span[e] = v;
         }
       }
       const int jn = hcn * p.f;                 // weight rows of this chunk: W rows hc0 * f + [0, jn)
@@ -194,6 +218,25 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
         const int w = DILATED ? ph + (w0 + rt * 16 + kq * 4 + i) * p.dil : w0 + rt * 16 + kq * 4 + i;
         if (w < p.nwin) orow0[(int64_t)w * p.o_ws + coff] = acc[rt][nt][i] + b;
       }
+  }
+}
+
+// Ring update of the CARRY form, after the projection: the m = min(Tc, C) newest time rows j0 .. j0 + m - 1 (j0 = Tc - m) of every (term,
+// recording, vertex) row of the chunk's stack go to the slots (head + j) mod C of the ring's row; the host then moves head by Tc (mod C).
+// A grid-stride copy in units U of the widest access f and the two alignments allow (16 bytes: float4 / 8 bf16; else one element); fu units
+// per time row, leading dimensions in units.  The slots of one call are m <= C different ones and the source is the stack: in place, and
+// values move unchanged in either dtype.
+template <typename U>
+__global__ __launch_bounds__(kBlock) void series_ring_update_kernel(const U* __restrict__ stack, U* __restrict__ ring, int64_t nrows, int64_t stack_ld,
+                                                                    int64_t ring_ld, int fu, int j0, int m, int C, int head) {
+  const int64_t per_row = (int64_t)m * fu, total = nrows * per_row;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
+    const int64_t row = i / per_row;
+    const int e = (int)(i - row * per_row);
+    const int jj = e / fu, cu = e - jj * fu;
+    const int j = j0 + jj;
+    const int slot = (int)(((int64_t)head + j) % C);
+    ring[row * ring_ld + (int64_t)slot * fu + cu] = stack[row * stack_ld + (int64_t)j * fu + cu];
   }
 }
 

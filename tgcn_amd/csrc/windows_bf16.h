@@ -41,6 +41,9 @@ struct SeriesGemmBf16Params {
   int32_t Tin, padl, nwin, H, f, N, nterms, ocg, bias_kind, bias_bf16, tpv, HC;
   int32_t stride, lst, fp;
   int32_t dil, tpp;                 // DILATED only (windows.h)
+  const hbf16* ring;                // CARRY only (windows.h): (nterms, S, n, ring_ld), slot j at j * f
+  int64_t ring_ks, ring_ss, ring_is;
+  int32_t C, head;
 };
 
 __host__ __device__ inline int series_bf16_row_elems(int f, int lst) {
@@ -58,7 +61,9 @@ __host__ __device__ inline int64_t series_bf16_span_elems(int hc, int f, bool ve
 
 // DILATED: series_gemm_kernel's phase-major tiles (windows.h) -- 32 windows of one phase q = w % dil, staged from the sub-series
 // t = (q - padl) + u * dil; span, bank rule and A reads are the step-1 form's.
-template <int NT, bool VEC8, bool STRIDED, typename OutT, bool DILATED = false>
+// CARRY: series_gemm_kernel's ring staging (windows.h) -- a time row t < 0 comes from slot head + t + C (mod C) of the ring; a pure load,
+// the bf16 values of the ring reach the span as they are.
+template <int NT, bool VEC8, bool STRIDED, typename OutT, bool DILATED = false, bool CARRY = false>
 __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGemmBf16Params p) {
   constexpr int NW = NT * 16;
   extern __shared__ __attribute__((aligned(16))) unsigned char sgb_lds[];
@@ -70,6 +75,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
   hbf16* span = Ws + NW * kPbLd + wave * (int)series_bf16_span_elems(p.HC, p.f, VEC8, stride);
   const uint16_t* span16 = reinterpret_cast<const uint16_t*>(span);
   static_assert(!(STRIDED && DILATED), "a window step with dilated taps is not built");
+  static_assert(!(STRIDED && CARRY), "a carried ring with a window step is not built");
   const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
   bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
@@ -95,6 +101,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
   for (int term = 0; term < p.nterms; ++term) {
     const hbf16* __restrict__ base = p.src + term * p.src_ks + s * p.src_ss + iv * p.src_is;
     const hbf16* __restrict__ Wt = p.W + (int64_t)term * J * p.N;
+    const hbf16* __restrict__ rbase = CARRY ? p.ring + term * p.ring_ks + s * p.ring_ss + iv * p.ring_is : nullptr;
     for (int hc0 = 0; hc0 < p.H; hc0 += p.HC) {
       const int hcn = min(p.HC, p.H - hc0);
       const int rows = (kSgWin - 1) * lst + hcn, t0 = DILATED ? ph - p.padl + (w0 + hc0) * p.dil : w0 * stride + hc0 - p.padl;
@@ -107,12 +114,22 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
         const int wr = tr / lst, hh = tr - wr * lst;
         const int t = t0 + wr * tstep + hh;
         const bool ok = live && hh < hcn && t >= 0 && t < p.Tin;
+        bool carried = false;
+        int slot = 0;
+        if constexpr (CARRY) {
+          carried = live && hh < hcn && t < 0 && t >= -p.C;
+          slot = p.head + t + p.C;
+          if (slot >= p.C) slot -= p.C;
+        }
         if constexpr (VEC8) {
           uint4 v = make_uint4(0u, 0u, 0u, 0u);
           if (ok) v = *reinterpret_cast<const uint4*>(base + (int64_t)t * p.src_ts + cu * 8);
+          if constexpr (CARRY) { if (carried) v = *reinterpret_cast<const uint4*>(rbase + (int64_t)slot * p.f + cu * 8); }
           *reinterpret_cast<uint4*>(span + tr * fp + cu * 8) = v;
         } else {
-          span[e] = ok ? base[(int64_t)t * p.src_ts + cu] : (hbf16)0.f;
+          hbf16 v = ok ? base[(int64_t)t * p.src_ts + cu] : (hbf16)0.f;
+          if constexpr (CARRY) { if (carried) v = rbase[(int64_t)slot * p.f + cu]; }
+          span[e] = v;
         }
       }
       const int jn = hcn * p.f;                   // weight rows of this chunk: W rows hc0 * f + [0, jn)

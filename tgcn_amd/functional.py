@@ -1694,3 +1694,144 @@ class ChebSeriesBf16Fn(torch.autograd.Function):
                 gb = _bias_grad(g32, ctx.bias_kind, ctx.bias_shape, True)
             gb = gb.to(ctx.dtypes[2])
         return gx, dW, gb, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------------------- streaming state
+class SeriesStreamState:
+    """What a causal time layer keeps between two chunks of a recording (cheb_time_stream, DESIGN.md 3.10 "Streaming state"): the last
+    C = (H-1)*dilation time rows of its own hop stack in a ring (K, S, n, ring_ld), in the operand's vertex labels and the layer's dtype --
+    slot j (elements j*f ..) holds the row whose absolute index is j (mod C), head = seen mod C is the slot of the oldest row kept, seen
+    the number of time rows passed through.  A zero ring is the causal zero padding, so a fresh state starts a recording.  Made for one
+    operand, dtype, (S, n, f, K, H) and dilation; updated in place by every call.  H == 1 keeps no ring (C == 0, ring None)."""
+
+    def __init__(self, op, dtype, S, n, f, K, H, dilation, device):
+        self.op, self.dtype, self.dilation = op, dtype, int(dilation)
+        self.S, self.n, self.f, self.K, self.H = int(S), int(n), int(f), int(K), int(H)
+        self.C = (self.H - 1) * self.dilation
+        self.ring_ld = self.C * self.f      # f % 4 == 0 (bf16: 8) makes it a multiple of the 16-byte staging unit; any other f stages narrow
+        self.ring = torch.zeros((self.K, self.S, self.n, self.ring_ld), dtype=dtype, device=device) if self.C else None
+        self.head = self.seen = 0
+
+    def reset(self):
+        """start a new recording: zero ring, head = seen = 0"""
+        if self.ring is not None:
+            self.ring.zero_()
+        self.head = self.seen = 0
+        return self
+
+    def mismatch(self, dtype, S, n, f, K, H, dilation):
+        """None when the state was made for this call's dtype, shape and dilation, else what differs (the operand is cheb_time_stream's check)"""
+        if self.dtype != dtype:
+            return "dtype %s, the call is %s" % (self.dtype, dtype)
+        if self.dilation != dilation:
+            return "dilation %d, the call has %d" % (self.dilation, dilation)
+        if (self.S, self.n, self.f, self.K, self.H) != (S, n, f, K, H):
+            return "(S, n, f, K, H) = %s, the call has %s" % ((self.S, self.n, self.f, self.K, self.H), (S, n, f, K, H))
+        return None
+
+    def advance(self, Tc):
+        self.seen += Tc
+        if self.C:
+            self.head = (self.head + Tc) % self.C
+
+
+@_on_device
+def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state):
+    """one chunk (S, n, Tc, f) in the operand's labels through the ring of `state`: plan query, K-1 hops on rows of Tc*f, the stream entry (the
+    projection and the ring update), head and seen moved; H == 1: the _conv entry on the chunk"""
+    L = _lib.lib()
+    S, n, Tc, f = chunk.shape
+    K, H, _, N = weight_khfg.shape
+    bf16 = state.dtype == BF16
+    hc, lds = C.c_int32(0), C.c_int32(0)
+    if bf16:
+        _lib.check(L.tgcn_series_conv_plan_bf16(H, f, N, int(f % 8 == 0), 1, C.byref(hc), C.byref(lds)))
+    else:
+        _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), 1, C.byref(hc), C.byref(lds)))
+    W = weight_khfg.to(state.dtype).contiguous().view(K, H * f, N)
+    fold = _power_fold(mode, W)
+    Wt = _working_weight_bf16(fold, W) if bf16 else _working_weight(fold, W)      # folded on every call, as forward_series does
+    Tf = Tc * f
+    if bf16:
+        ld = Tf if (Tf % 8 == 0 or Tf < 7) else Tf + (-Tf) % 8      # ChebSeriesBf16Fn's trailing-element row padding
+        x3 = chunk.to(BF16).contiguous().view(S, n, Tf)
+        if ld != Tf:
+            x3 = torch.nn.functional.pad(x3, (0, ld - Tf))
+        stack = torch.empty((K, S, n, ld), dtype=BF16, device=x3.device)
+        _basis_bf16(op, x3, K, mode, out=stack)
+    else:
+        x3 = _aligned_input(chunk.float().contiguous().view(S, n, Tf))
+        stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)
+    out = torch.empty((S, n, Tc, N), dtype=state.dtype, device=x3.device)
+    b = bias.to(state.dtype).contiguous() if bias is not None else None
+    head = (_lib.stream_ptr(), S, n, Tc, f, H, N, K, _lib.ptr(stack))
+    if bf16:
+        mid = (ld, _lib.ptr(Wt), _lib.ptr(b), _lib.DTYPE_BF16, bias_kind)
+        if state.C:
+            _lib.check(L.tgcn_cheb_project_series_stream_bf16(*head, *mid, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld, state.head, state.dilation))
+        else:
+            _lib.check(L.tgcn_cheb_project_series_conv_bf16(*head, *mid, 1, _lib.ptr(out), 1, 0, 0))
+    else:
+        mid = (_lib.ptr(Wt), _lib.ptr(b), bias_kind)
+        if state.C:
+            _lib.check(L.tgcn_cheb_project_series_stream_f32(*head, *mid, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld, state.head, state.dilation))
+        else:
+            _lib.check(L.tgcn_cheb_project_series_conv_f32(*head, *mid, 1, _lib.ptr(out), 1, 0, 0))
+    state.advance(Tc)
+    return out
+
+
+def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream"):
+    """Everything cheb_time_stream refuses that does not need the operand -- the modules run it before they build one.
+    -> (dtype, (S, n, f, K, H), the dilation the call runs at)"""
+    dt = param_dtype(weight, bias, who)
+    if chunk.dim() not in (3, 4) or weight.dim() != chunk.dim():
+        raise _lib.TgcnError("%s: a (S, n, Tc) chunk takes a (K, H, N) weight and a (S, n, Tc, f) chunk a (K, H, f, N) weight (got %s and %s)"
+                             % (who, tuple(chunk.shape), tuple(weight.shape)))
+    f = chunk.shape[3] if chunk.dim() == 4 else 1
+    if chunk.dim() == 4 and weight.shape[2] != f:
+        raise _lib.TgcnError("%s: the chunk has %d channels, the weight %d" % (who, f, weight.shape[2]))
+    S, n, Tc = chunk.shape[:3]
+    K, H, N = weight.shape[0], weight.shape[1], weight.shape[-1]
+    if Tc < 1:
+        raise _lib.TgcnError("%s: a chunk holds at least one time row, got %s" % (who, tuple(chunk.shape)))
+    series_geometry(Tc, H, 1, "causal", who, dilation)       # the dilation's rule; stride 1 and causal padding are the only geometry
+    dilation = series_dilation(H, dilation)
+    if dt == BF16 and chunk.dtype != BF16:
+        raise _lib.TgcnError("%s: the parameters are bfloat16 but the chunk is %s -- cast it once (chunk.to(torch.bfloat16))" % (who, chunk.dtype))
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (chunk, weight, bias)):
+        raise _lib.TgcnError("%s: streaming has no backward -- call it under torch.no_grad() (training stays with forward_series / "
+                             "cheb_time_windows)" % who)
+    if state is not None:
+        if not isinstance(state, SeriesStreamState):
+            raise _lib.TgcnError("%s: state is a SeriesStreamState or None, got %s" % (who, type(state).__name__))
+        bad = state.mismatch(dt, S, n, f, K, H, dilation)
+        if bad:
+            raise _lib.TgcnError("%s: the state was made for %s -- one state per layer and recording batch" % (who, bad))
+    return dt, (S, n, f, K, H), dilation
+
+
+def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=None, dilation=1):
+    """The causal streaming layer on the NEXT Tc time rows of S recordings (inference only): chunk (S, n, Tc) with weight (K, H, N), or
+    (S, n, Tc, f) with weight (K, H, f, N) -> (out (S, n, Tc, N) contiguous, state).  out equals rows [state.seen, state.seen + Tc) of
+    cheb_time_windows(op, whole, ..., as_series=True, padding="causal", dilation=dilation) on the whole series: the layer keeps the last
+    (H-1)*dilation time rows of its hop stack in state's ring (SeriesStreamState), the projection reads each window from the ring and the
+    chunk's stack, and every time row is hopped once.  state=None starts a recording (a zero ring = the causal padding); the state is updated
+    in place and returned.  The series layout is the only one: a chain is l2(relu(o1), s2) with one state per layer.
+    TgcnError before an operand is relabelled or anything launches: a state made for another operand, dtype, shape or dilation; grad mode with
+    a chunk or a parameter that requires grad (there is no backward: torch.no_grad(); training stays with cheb_time_windows); bfloat16
+    parameters with a chunk of another dtype; dilation < 1.  H == 1 keeps no ring and runs the _conv entry on the chunk."""
+    dt, (S, n, f, K, H), dilation = stream_precheck(chunk, weight, bias, state, dilation)
+    if state is not None and state.op is not op:
+        raise _lib.TgcnError("cheb_time_stream: the state was made for another operand -- one state per layer and graph")
+    _lib.require_device(chunk, weight, bias)
+    if state is None:
+        state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device)
+    with torch.no_grad():
+        if chunk.dim() == 3:
+            chunk, weight = chunk.unsqueeze(3), weight.unsqueeze(2)
+        chunk, bias = _to_operand_labels(op, chunk, bias, bias_kind)      # the ring lives in the operand's labels
+        out = _stream_chunk(chunk, weight, bias, op, mode, bias_kind, state)
+        if op.perm is not None:
+            out = relabel_rows(out, op.inv_perm, op.perm).to(dt)
+    return out, state

@@ -56,6 +56,12 @@ class _OperandCache:
         self._d = collections.OrderedDict()
         self._lock = threading.Lock()
 
+    def peek(self, key):
+        """the cached object of `key` or None; builds nothing and leaves the order of use alone"""
+        with self._lock:
+            hit = self._d.get(key)
+            return None if hit is None else hit[0]
+
     def get(self, key, build, sources=()):
         with self._lock:
             hit = self._d.get(key)
@@ -91,12 +97,15 @@ def _tensor_key(t):
 class _DenseLBase(torch.nn.Module):
     """Shared plumbing of the three classes that take L in the constructor."""
 
-    def _operand(self, device):
+    def _operand_key(self, device):
         L = self.L
         dense = isinstance(L, torch.Tensor) and L.layout == torch.strided
-        key = (id(L), L.data_ptr() if dense else None, getattr(L, "_version", 0), tuple(L.shape) if hasattr(L, "shape") else None,
-               str(device), None if isinstance(L, torch.Tensor) else _np_fingerprint(L))
-        return self._ops.get(key, lambda: GraphOperand.from_any(L, device), sources=(L,))
+        return (id(L), L.data_ptr() if dense else None, getattr(L, "_version", 0), tuple(L.shape) if hasattr(L, "shape") else None,
+                str(device), None if isinstance(L, torch.Tensor) else _np_fingerprint(L))
+
+    def _operand(self, device):
+        L = self.L
+        return self._ops.get(self._operand_key(device), lambda: GraphOperand.from_any(L, device), sources=(L,))
 
     def _num_vertices(self):
         return self.L.shape[0] if hasattr(self.L, "shape") else self.L[0].shape[0]
@@ -201,6 +210,42 @@ class TGCNCheb_H(_DenseLBase):
                                    None if self.bias is None else self.bias.reshape(-1),
                                    F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series,
                                    stride=geom[0], padding=geom[1:3], dilation=geom[3])
+
+    def forward_stream(self, chunk, state=None, dilation=1):
+        """Additive API, inference only: the causal layer on the next Tc time rows of S recordings.  chunk (S, n, Tc) or (S, n, Tc, f) ->
+        (out (S, n, Tc, g) contiguous, state); out equals rows [seen, seen + Tc) of forward_series(whole, as_series=True, padding="causal",
+        dilation=dilation), seen = the time rows already passed through state (F.SeriesStreamState: the last (H-1)*dilation rows of the hop
+        stack in a ring, updated in place; None starts a recording, state.reset() another one).  Every time row is hopped once and memory
+        follows the chunk, not the recording.  A chain keeps one state per layer: l2.forward_stream(relu(o1), s2, dilation=2).
+        No autograd (TgcnError in grad mode when the chunk or a parameter requires grad: use torch.no_grad()); training stays with
+        forward_series.  A state of another shape, dtype, dilation or layer raises TgcnError before anything launches."""
+        _compute_dtype(self)
+        chunk, W = _stream_args(self, chunk)
+        F.stream_precheck(chunk, W, self.bias, state, dilation, "TGCNCheb_H.forward_stream")      # refusals come before the operand is built
+        _state_operand_check(self, state, self._operand_key(chunk.device))
+        return F.cheb_time_stream(self._operand(chunk.device), chunk, W, None if self.bias is None else self.bias.reshape(-1),
+                                  F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, state=state, dilation=dilation)
+
+
+def _state_operand_check(module, state, key):
+    """A state belongs to the operand object it was made with, and that operand is still in the module's cache under this call's key when the
+    call continues its recording.  Anything else -- another layer's state, another graph, a graph the cache has evicted since -- is refused
+    here, by a look into the cache, so that no operand is built for a call that is refused."""
+    if state is not None and module._ops.peek(key) is not state.op:
+        raise _lib.TgcnError("%s.forward_stream: the state was made for another operand -- one state per layer and graph (a graph this "
+                             "layer's operand cache no longer holds starts a new recording: state=None)" % type(module).__name__)
+
+
+def _stream_args(module, chunk):
+    """(chunk, weight) of a forward_stream call as F.cheb_time_stream takes them, after the shape checks (_series_args' rules)"""
+    name = type(module).__name__
+    K, H, f, g = module.weight.shape
+    if chunk.dim() not in (3, 4):
+        raise _lib.TgcnError("%s.forward_stream: the chunk is (S, n, Tc) or (S, n, Tc, f), got %s" % (name, tuple(chunk.shape)))
+    if (chunk.shape[3] if chunk.dim() == 4 else 1) != f:
+        raise _lib.TgcnError("%s.forward_stream: the chunk has %d channel(s), the layer in_channels = %d"
+                             % (name, chunk.shape[3] if chunk.dim() == 4 else 1, f))
+    return chunk, (module.weight.reshape(K, H, g) if chunk.dim() == 3 else module.weight)
 
 
 def _series_args(module, series, stride=1, padding=0, dilation=1):
@@ -351,8 +396,13 @@ class _EdgeBase(torch.nn.Module):
             # (the first build's values are re-packed by the same formula as every later refresh, so that equal weights give bit-equal
             # operands whatever the history of the module: the builder rounds -d^-1/2 w d^-1/2 in another order)
             return _refresh_values(op, edge_weight, vals)
-        key = (_tensor_key(edge_index), _tensor_key(edge_weight), n, str(x.device))
+        key = self._operand_key(x, edge_index, edge_weight)
         return self._ops.get(key, lambda: GraphOperand.from_edge_index(edge_index, w, n, x.device), sources=(edge_index, w))
+
+    @staticmethod
+    def _operand_key(x, edge_index, edge_weight):
+        """the cache key of a graph with fixed weights"""
+        return (_tensor_key(edge_index), _tensor_key(edge_weight), x.size(1), str(x.device))
 
     def _links(self, edge_index, n, dev):
         """(source edge of every stored entry, its constant coefficient -deg^-1/2[row] deg^-1/2[col]) in the operand's CSR order, once per edge_index"""
@@ -460,6 +510,22 @@ class ChebTimeConv(_EdgeBase):
         return F.cheb_time_windows(op, series, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
                                    as_series=as_series,
                                    stride=geom[0], padding=geom[1:3], dilation=geom[3])
+
+    def forward_stream(self, chunk, edge_index, edge_weight=None, state=None, dilation=1):
+        """Additive API, inference only: TGCNCheb_H.forward_stream's contract for this class -- chunk (S, n, Tc[, f]) -> (out (S, n, Tc, g),
+        state), the rows [seen, seen + Tc) of forward_series(whole, edge_index, edge_weight, as_series=True, padding="causal",
+        dilation=dilation); true recurrence, per-channel bias.  The state belongs to the operand of (edge_index, edge_weight): another graph
+        needs its own.  A learnable edge_weight raises TgcnError, as in forward_series."""
+        if edge_weight is not None and edge_weight.requires_grad:
+            raise _lib.TgcnError("ChebTimeConv.forward_stream: learnable edge weights (edge_weight.requires_grad) are not supported -- "
+                                 "streaming is inference only; detach() the weight")
+        _compute_dtype(self, edge_weight)
+        chunk, W = _stream_args(self, chunk)
+        F.stream_precheck(chunk, W, self.bias, state, dilation, "ChebTimeConv.forward_stream")      # refusals come before the operand is built
+        _state_operand_check(self, state, self._operand_key(chunk, edge_index, edge_weight))
+        op = self._operand(chunk, edge_index, edge_weight)
+        return F.cheb_time_stream(op, chunk, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
+                                  state=state, dilation=dilation)
 
 
 # ------------------------------------------------------------------------------------ fused caller pattern

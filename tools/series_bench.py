@@ -6,6 +6,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py [--steps 5] [--warmup 2] [--stride 1] [--padding 0] [--conv] [--out profiles/r08_series_channels.json]
     python tools/series_bench.py --dtype bf16 [--out profiles/r10_series_bf16.json]
     python tools/series_bench.py --dilation [--out profiles/r11_series_dilation.json]
+    python tools/series_bench.py --stream [--out profiles/r12_series_stream.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -19,7 +20,10 @@ the parent commit's tool on the default cases, a repeat of this one for the run-
 commit, the fp32 streaming call and the bf16 module's forward on the materialised windows; default --out profiles/r10_series_bf16.json.
 --dilation runs the dilated cases (DESIGN.md 3.10 "Dilation"): (a) 32 -> 64 and (b) at dilation 4, and a three-layer causal chain of H = 5
 layers with dilations 1, 2, 4 (1 -> 32 -> 32 -> 64 channels, 284 steps in, 284 out, receptive field 29 steps), each next to the module's forward on
-the materialised dilated windows on the same commit; default --out profiles/r11_series_dilation.json."""
+the materialised dilated windows on the same commit; default --out profiles/r11_series_dilation.json.
+--stream times the streaming state (DESIGN.md 3.10 "Streaming state"): ms per chunk of that three-layer causal chain through forward_stream at
+chunk sizes 1, 8 and 64 (states warmed by 64 time rows), next to what a caller has to do without it on the same commit -- keep the trailing
+He - 1 + Tc input rows of every layer and run forward_series on them; default --out profiles/r12_series_stream.json."""
 import argparse
 import json
 import os
@@ -213,6 +217,54 @@ def main_dilation(args):
         json.dump(res, f, indent=1)
 
 
+def main_stream(args):
+    dev = torch.device("cuda:0")
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, cases={})
+    torch.manual_seed(0)
+    op = dti148(dev)
+    S, K, Hc, dils, chans = 8, 10, 5, (1, 2, 4), (1, 32, 32, 64)
+    layers = [tgcn_amd.TGCNCheb_H(op, chans[i], chans[i + 1], K, Hc).to(dev) for i in range(3)]
+    for Tc in (1, 8, 64):
+        chunk = torch.randn(S, op.n, Tc, 1, device=dev)
+        states = [None] * 3
+
+        def stream_step(x=chunk):
+            h = x
+            for i, (layer, d) in enumerate(zip(layers, dils)):
+                h, states[i] = layer.forward_stream(h, states[i], dilation=d)
+                if i < 2:
+                    h = torch.relu(h)
+            return h
+
+        # without the state: every layer's caller keeps the last He - 1 + Tc rows of that layer's input and runs forward_series on them
+        tails = [torch.zeros(S, op.n, (Hc - 1) * d + Tc, chans[i], device=dev) for i, d in enumerate(dils)]
+
+        def trailing_step(x=chunk):
+            h = x
+            for i, (layer, d) in enumerate(zip(layers, dils)):
+                tails[i] = torch.cat((tails[i][:, :, h.shape[2]:], h), dim=2)
+                h = layer.forward_series(tails[i], as_series=True, dilation=d)          # the Tc newest outputs
+                if i < 2:
+                    h = torch.relu(h)
+            return h
+
+        with torch.no_grad():
+            for _ in range(-(-64 // Tc)):
+                a, b = stream_step(), trailing_step()
+            assert a.shape == b.shape == (S, op.n, Tc, chans[-1])
+            err = float((a - b).abs().max() / b.abs().max())
+        st, tr = timed(stream_step, False, args.steps, args.warmup), timed(trailing_step, False, args.steps, args.warmup)
+        entry = dict(desc="dti148 S=8: three causal TGCNCheb_H(., ., 10, 5) layers 1 -> 32 -> 32 -> 64 with dilations 1, 2, 4, chunks of %d time rows" % Tc,
+                     forward_stream=st, forward_series_on_trailing_rows=tr, max_rel_difference=err,
+                     trailing_over_stream=round(tr["ms_per_call"] / st["ms_per_call"], 3))
+        res["cases"]["chain_chunk%d" % Tc] = entry
+        print(json.dumps({"chain_chunk%d" % Tc: entry}), flush=True)
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r12_series_stream.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32", help="bf16: the bfloat16 streaming cases (profiles/r10_series_bf16.json)")
@@ -222,6 +274,7 @@ def main():
     ap.add_argument("--padding", type=padding_arg, default=0)
     ap.add_argument("--conv", action="store_true", help="add the stride-4 and causal-chain cases")
     ap.add_argument("--dilation", action="store_true", help="the dilated cases (profiles/r11_series_dilation.json)")
+    ap.add_argument("--stream", action="store_true", help="the streaming-state cases (profiles/r12_series_stream.json)")
     ap.add_argument("--include", action="append", default=[], metavar="LABEL=FILE",
                     help="put another run's --out file (the parent commit's, a repeat of this one) into this one under runs[LABEL], with "
                          "each shared case's ms per call relative to this run")
@@ -231,6 +284,8 @@ def main():
         return main_bf16(args)
     if args.dilation:
         return main_dilation(args)
+    if args.stream:
+        return main_stream(args)
     dev = torch.device("cuda:0")
     res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, stride=args.stride,
                padding=args.padding, cases={})
