@@ -428,6 +428,26 @@ int tgcn_cheb_project_series_stream_bf16(void* stream, int64_t S, int64_t n_vert
                                          const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
                                          int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int32_t dilation);
 
+/* The stream entries with the ring's position in DEVICE memory, so that one step captured into a hipGraph can be replayed for a whole
+ * recording: int64_t pos[2] = {head, seen}, owned by the caller's state next to the ring; the arguments are the entries' above with pos in
+ * head's place.  Three launches, sequential on the stream (a captured step has no parallel branches): the GEMM and the ring update, which
+ * both read pos[0] (one wave-uniform load per workgroup), then tgcn_series_stream_advance's kernel, pos[0] = (pos[0] + Tc) mod C and
+ * pos[1] += Tc -- a launch of its own because every workgroup of the first two must have read the old head before it moves.
+ * Defensive read: the host cannot check a device value without a synchronisation, so the kernels use pos[0] as head only if
+ * 0 <= pos[0] < C and take 0 otherwise (one compare); no value in that memory sends a ring access out of bounds.  With a valid pos[0] the
+ * results are bit-identical to the entries above at head = pos[0].
+ * TGCN_ERR_INVALID: pos == NULL and everything the entries above refuse (the head rule aside); TGCN_ERR_UNSUPPORTED where the plan
+ * refuses; nothing is launched in either case.
+ * tgcn_series_stream_advance is the third launch alone -- for the one-tap layer, which keeps no ring (C = 0: head stays 0) and runs the
+ * _conv entry, but still counts seen.  TGCN_ERR_INVALID: pos == NULL, Tc < 1, C < 0. */
+int tgcn_cheb_project_series_stream_pos_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                            const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                                            int64_t ring_ld, int64_t* pos, int32_t dilation);
+int tgcn_cheb_project_series_stream_pos_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                             const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                             int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int64_t* pos, int32_t dilation);
+int tgcn_series_stream_advance(void* stream, int64_t* pos, int32_t Tc, int32_t C);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

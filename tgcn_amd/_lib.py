@@ -165,6 +165,11 @@ SIGNATURES = {
                                                       C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32]),
     "tgcn_cheb_project_series_stream_bf16": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64,
                                                        _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, C.c_int32]),
+    "tgcn_cheb_project_series_stream_pos_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                                          C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),
+    "tgcn_cheb_project_series_stream_pos_bf16": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64,
+                                                           _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),
+    "tgcn_series_stream_advance": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
     "tgcn_fold_weight_f32": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32]),
     "tgcn_weight_layout_f32": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "tgcn_csr_hop_f64": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, C.c_double, C.c_double, _P, _P]),

@@ -1376,29 +1376,44 @@ static int series_stream_check(int64_t S, int64_t n, int32_t Tc, int32_t f, int3
 }
 
 // The ring update launch: rows = K * S * n rows of the stack (ld elements apart) and of the ring; esize: bytes per element (4 / 2);
-// vec: 16-byte accesses (4 floats / 8 bf16 per unit), else one element
+// vec: 16-byte accesses (4 floats / 8 bf16 per unit), else one element; pos non-null: head is read on the device (the _pos entries)
 static void series_ring_update_launch(hipStream_t st, const void* stack, void* ring, int64_t rows, int64_t stack_ld, int64_t ring_ld, int32_t f,
-                                      int esize, bool vec, int32_t Tc, int32_t C, int32_t head) {
+                                      int esize, bool vec, int32_t Tc, int32_t C, int32_t head, const int64_t* pos) {
   const int unit = vec ? 16 / esize : 1, m = Tc < C ? Tc : C, fu = f / unit;
   const dim3 grid(grid_1d(rows * m * fu));
   ProfScope ps(TGCN_PROF_RELAYOUT, st);
 #define TGCN_RING_UPDATE(U_)                                                                                                        \
   hipLaunchKernelGGL(series_ring_update_kernel<U_>, grid, dim3(kBlock), 0, st, (const U_*)stack, (U_*)ring, rows, stack_ld / unit, \
-                     ring_ld / unit, fu, Tc - m, m, C, head)
+                     ring_ld / unit, fu, Tc - m, m, C, head, pos)
   if (vec) TGCN_RING_UPDATE(uint4);
   else if (esize == 4) TGCN_RING_UPDATE(uint32_t);
   else TGCN_RING_UPDATE(uint16_t);
 #undef TGCN_RING_UPDATE
 }
 
-int tgcn_cheb_project_series_stream_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
-                                        const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
-                                        int64_t ring_ld, int32_t head, int32_t dilation) {
+// The position of a ring kept in device memory (the _pos entries) moves behind the ring update, in a launch of its own
+static void series_stream_advance_launch(hipStream_t st, int64_t* pos, int32_t Tc, int32_t C) {
+  ProfScope ps(TGCN_PROF_RELAYOUT, st);
+  hipLaunchKernelGGL(series_stream_advance_kernel, dim3(1), dim3(1), 0, st, pos, Tc, C);
+}
+
+int tgcn_series_stream_advance(void* stream, int64_t* pos, int32_t Tc, int32_t C) {
+  if (!pos || Tc < 1 || C < 0) TGCN_FAIL(TGCN_ERR_INVALID, "series_stream_advance: bad argument");
+  series_stream_advance_launch((hipStream_t)stream, pos, Tc, C);
+  TGCN_CHECK_LAUNCH("tgcn_series_stream_advance");
+  return TGCN_OK;
+}
+
+// Both fp32 stream entries: pos null -> the host's head and two launches; pos non-null -> head read on the device (the head argument is
+// unused and passes the check as 0) and the advance as a third launch
+static int project_series_stream_impl(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                                      int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation, const char* who) {
   int32_t C = 0;
   if (series_stream_check(S, n_vertices, Tc, f, H, N, K, dilation, ring_ld, head, &C) || !stack || !W || !out || !ring)
-    TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream: bad argument");
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream: bias_kind %d", bias_kind);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_stream")) return drc;
+    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = n_vertices, Tf = (int64_t)Tc * f;
   SeriesGemmParams p;
@@ -1407,12 +1422,31 @@ int tgcn_cheb_project_series_stream_f32(void* stream, int64_t S, int64_t n_verti
   p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
   p.o_ss = n * Tc * N; p.o_is = (int64_t)Tc * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, Tc, N)
   p.n = n; p.Tin = Tc; p.padl = C; p.nwin = Tc; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
-  p.ring = ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head;
+  p.ring = ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
   // 16-byte staging and copies: the stack's rule, and a ring that keeps it
   const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0) && (ring_ld % 4 == 0) && (((uintptr_t)ring & 15) == 0);
-  if (int rc = series_gemm_launch(st, p, S, vec, "project_series_stream", 1, dilation, true)) return rc;
-  series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, vec, Tc, C, head);
+  if (int rc = series_gemm_launch(st, p, S, vec, who, 1, dilation, true)) return rc;
+  series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, vec, Tc, C, head, pos);
+  if (pos) series_stream_advance_launch(st, pos, Tc, C);
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_series_stream_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                        const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                                        int64_t ring_ld, int32_t head, int32_t dilation) {
+  if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, head, nullptr,
+                                          dilation, "project_series_stream")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_f32");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_series_stream_pos_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                            const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                                            int64_t ring_ld, int64_t* pos, int32_t dilation) {
+  if (!pos) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_pos: bad argument");
+  if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, 0, pos,
+                                          dilation, "project_series_stream_pos")) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pos_f32");
   return TGCN_OK;
 }
 
@@ -1693,16 +1727,18 @@ int tgcn_cheb_project_series_dilated_bf16(void* stream, int64_t S, int64_t n_ver
   return TGCN_OK;
 }
 
-int tgcn_cheb_project_series_stream_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
-                                         const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
-                                         int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int32_t dilation) {
+// Both bf16 stream entries (project_series_stream_impl's rule for head and pos)
+static int project_series_stream_bf16_impl(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                           const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                           int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation,
+                                           const char* who) {
   int32_t C = 0;
   if (series_stream_check(S, n_vertices, Tc, f, H, N, K, dilation, ring_ld, head, &C) || !stack || !W || !out || !ring ||
       !series_stack_ld_ok(Tc, f, stack_ld))
-    TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_bf16: bad argument");
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_bf16: bias_kind %d", bias_kind);
-  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_bf16: dtype code %d", bias_dtype);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_stream_bf16")) return drc;
+    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
+  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "%s: dtype code %d", who, bias_dtype);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t n = n_vertices;
   SeriesGemmBf16Params p;
@@ -1712,11 +1748,30 @@ int tgcn_cheb_project_series_stream_bf16(void* stream, int64_t S, int64_t n_vert
   p.o_ss = n * Tc * N; p.o_is = (int64_t)Tc * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, Tc, N)
   p.n = n; p.Tin = Tc; p.padl = C; p.nwin = Tc; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
   p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
-  p.ring = (const hbf16*)ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head;
+  p.ring = (const hbf16*)ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
   const bool vec = (f % 8 == 0) && (stack_ld % 8 == 0) && (((uintptr_t)stack & 15) == 0) && (ring_ld % 8 == 0) && (((uintptr_t)ring & 15) == 0);
-  if (int rc = series_gemm_bf16_launch(st, p, S, vec, false, "project_series_stream_bf16", 1, dilation, true)) return rc;
-  series_ring_update_launch(st, stack, ring, K * S * n, stack_ld, ring_ld, f, 2, vec, Tc, C, head);
+  if (int rc = series_gemm_bf16_launch(st, p, S, vec, false, who, 1, dilation, true)) return rc;
+  series_ring_update_launch(st, stack, ring, K * S * n, stack_ld, ring_ld, f, 2, vec, Tc, C, head, pos);
+  if (pos) series_stream_advance_launch(st, pos, Tc, C);
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_series_stream_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                         const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                         int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int32_t dilation) {
+  if (int rc = project_series_stream_bf16_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, out, ring,
+                                               ring_ld, head, nullptr, dilation, "project_series_stream_bf16")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_bf16");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_series_stream_pos_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                             const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                             int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int64_t* pos, int32_t dilation) {
+  if (!pos) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_pos_bf16: bad argument");
+  if (int rc = project_series_stream_bf16_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, out, ring,
+                                               ring_ld, 0, pos, dilation, "project_series_stream_pos_bf16")) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pos_bf16");
   return TGCN_OK;
 }
 

@@ -31,6 +31,7 @@ struct SeriesGemmParams {
   const float* ring;                // CARRY only: the C = padl time rows before the chunk, (nterms, S, n, ring_ld), slot j at j * f
   int64_t ring_ks, ring_ss, ring_is;
   int32_t C, head;                  // CARRY only: slots of the ring, slot of its oldest row
+  const int64_t* pos;               // CARRY only: non-null -> the slot of the oldest row is read from pos[0] in device memory (head is ignored)
 };
 
 constexpr int kSgWin = 32;    // windows per wave
@@ -69,6 +70,15 @@ __host__ __device__ constexpr int series_ws_stride(int NT) { return (NT * 16) % 
 // slot j holds the row whose absolute index is j (mod C), head is the slot of the oldest.  Only the staging differs: a time row t < 0
 // (t >= -C always: t0 >= -padl) is loaded from slot head + t + C (mod C; the sum lies in [0, 2C), one conditional subtraction) with the
 // ring's own strides, a zeroed ring being the causal zero padding.  Span, banks, A offsets, regimes, tile decode and epilogue are untouched.
+// head comes from the parameter struct, or -- p.pos non-null, the form a captured hipGraph step replays -- from device memory: one
+// wave-uniform load per workgroup, before any store.  The host cannot check a device value without a synchronisation, so the loaded value is
+// used only if 0 <= value < C and 0 is taken otherwise (one compare): whatever that memory holds, head + t + C stays in [0, 2C) and no ring
+// access leaves the ring.  Only the source of head differs between the two forms.
+__device__ __forceinline__ int series_ring_head(const int64_t* pos, int head, int C) {
+  if (!pos) return head;
+  const int64_t v = pos[0];
+  return (v >= 0 && v < (int64_t)C) ? (int)v : 0;
+}
 template <int NT, bool VEC, bool STRIDED = false, bool DILATED = false, bool CARRY = false>
 __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmParams p) {
   constexpr int NW = NT * 16, NS = series_ws_stride(NT), WREG = (kSgKT * NW) / kBlock;
@@ -93,6 +103,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
     live = live && ph + w0 * p.dil < p.nwin;
   }
   const int tstep = DILATED ? p.dil : 1;                  // time rows between two span rows
+  const int head = CARRY ? series_ring_head(p.pos, p.head, p.C) : 0;
   const int64_t s = si / p.n, iv = si % p.n;
   const int n0 = blockIdx.y * NW;
   const int J = p.H * p.f;
@@ -141,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
           if (live && t >= 0 && t < p.Tin) v = *reinterpret_cast<const float4*>(base + (int64_t)t * p.src_ts + c);
           if constexpr (CARRY) {
             if (live && t < 0 && t >= -p.C) {
-              int slot = p.head + t + p.C;
+              int slot = head + t + p.C;
               if (slot >= p.C) slot -= p.C;
               v = *reinterpret_cast<const float4*>(rbase + (int64_t)slot * p.f + c);
             }
@@ -157,7 +168,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
           float v = (live && tr < rows && t >= 0 && t < p.Tin) ? base[(int64_t)t * p.src_ts + c] : 0.f;
           if constexpr (CARRY) {
             if (live && tr < rows && t < 0 && t >= -p.C) {
-              int slot = p.head + t + p.C;
+              int slot = head + t + p.C;
               if (slot >= p.C) slot -= p.C;
               v = rbase[(int64_t)slot * p.f + c];
             }
@@ -225,10 +236,13 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
 // recording, vertex) row of the chunk's stack go to the slots (head + j) mod C of the ring's row; the host then moves head by Tc (mod C).
 // A grid-stride copy in units U of the widest access f and the two alignments allow (16 bytes: float4 / 8 bf16; else one element); fu units
 // per time row, leading dimensions in units.  The slots of one call are m <= C different ones and the source is the stack: in place, and
-// values move unchanged in either dtype.
+// values move unchanged in either dtype.  pos non-null: head is read from pos[0] by series_ring_head's rule (0 unless 0 <= pos[0] < C), so
+// (head + j) mod C is a slot of the ring whatever that memory holds; the kernel never writes pos.
 template <typename U>
 __global__ __launch_bounds__(kBlock) void series_ring_update_kernel(const U* __restrict__ stack, U* __restrict__ ring, int64_t nrows, int64_t stack_ld,
-                                                                    int64_t ring_ld, int fu, int j0, int m, int C, int head) {
+                                                                    int64_t ring_ld, int fu, int j0, int m, int C, int head_arg,
+                                                                    const int64_t* __restrict__ pos) {
+  const int head = series_ring_head(pos, head_arg, C);
   const int64_t per_row = (int64_t)m * fu, total = nrows * per_row;
   for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
     const int64_t row = i / per_row;
@@ -238,6 +252,16 @@ __global__ __launch_bounds__(kBlock) void series_ring_update_kernel(const U* __r
     const int slot = (int)(((int64_t)head + j) % C);
     ring[row * ring_ld + (int64_t)slot * fu + cu] = stack[row * stack_ld + (int64_t)j * fu + cu];
   }
+}
+
+// The position {head, seen} of a ring kept in device memory moves by one chunk: head = (head + Tc) mod C from the value the two kernels above
+// used (series_ring_head's rule), seen += Tc; C == 0 (a one-tap layer keeps no ring) leaves head at 0.  One thread, and a launch of its own
+// behind the ring update on the same stream: every workgroup of the GEMM and of the update has read the old head before it moves.
+__global__ void series_stream_advance_kernel(int64_t* __restrict__ pos, int Tc, int C) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  const int64_t head = series_ring_head(pos, 0, C);
+  pos[0] = C > 0 ? (head + Tc) % C : 0;
+  pos[1] += Tc;
 }
 
 // Wd[(h', nn), (k, c)] = W[k, H - 1 - h', c, nn]: the weight of the input gradient as a sliding-window GEMM over g.

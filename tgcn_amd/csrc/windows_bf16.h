@@ -44,6 +44,7 @@ struct SeriesGemmBf16Params {
   const hbf16* ring;                // CARRY only (windows.h): (nterms, S, n, ring_ld), slot j at j * f
   int64_t ring_ks, ring_ss, ring_is;
   int32_t C, head;
+  const int64_t* pos;               // CARRY only (windows.h): non-null -> head is read from pos[0], series_ring_head's rule
 };
 
 __host__ __device__ inline int series_bf16_row_elems(int f, int lst) {
@@ -62,7 +63,7 @@ __host__ __device__ inline int64_t series_bf16_span_elems(int hc, int f, bool ve
 // DILATED: series_gemm_kernel's phase-major tiles (windows.h) -- 32 windows of one phase q = w % dil, staged from the sub-series
 // t = (q - padl) + u * dil; span, bank rule and A reads are the step-1 form's.
 // CARRY: series_gemm_kernel's ring staging (windows.h) -- a time row t < 0 comes from slot head + t + C (mod C) of the ring; a pure load,
-// the bf16 values of the ring reach the span as they are.
+// the bf16 values of the ring reach the span as they are.  head from the struct or, p.pos non-null, from device memory (series_ring_head).
 template <int NT, bool VEC8, bool STRIDED, typename OutT, bool DILATED = false, bool CARRY = false>
 __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGemmBf16Params p) {
   constexpr int NW = NT * 16;
@@ -88,6 +89,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
     live = live && ph + w0 * p.dil < p.nwin;
   }
   const int tstep = DILATED ? p.dil : stride;             // time rows between two windows' first span rows
+  const int head = CARRY ? series_ring_head(p.pos, p.head, p.C) : 0;
   const int64_t s = si / p.n, iv = si % p.n;
   const int n0 = blockIdx.y * NW;
   const int J = p.H * p.f;
@@ -118,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
         int slot = 0;
         if constexpr (CARRY) {
           carried = live && hh < hcn && t < 0 && t >= -p.C;
-          slot = p.head + t + p.C;
+          slot = head + t + p.C;
           if (slot >= p.C) slot -= p.C;
         }
         if constexpr (VEC8) {

@@ -1702,21 +1702,38 @@ class SeriesStreamState:
     C = (H-1)*dilation time rows of its own hop stack in a ring (K, S, n, ring_ld), in the operand's vertex labels and the layer's dtype --
     slot j (elements j*f ..) holds the row whose absolute index is j (mod C), head = seen mod C is the slot of the oldest row kept, seen
     the number of time rows passed through.  A zero ring is the causal zero padding, so a fresh state starts a recording.  Made for one
-    operand, dtype, (S, n, f, K, H) and dilation; updated in place by every call.  H == 1 keeps no ring (C == 0, ring None)."""
+    operand, dtype, (S, n, f, K, H) and dilation; updated in place by every call.  H == 1 keeps no ring (C == 0, ring None).
+    capturable=True keeps the position on the device -- pos, an int64 tensor {head, seen} next to the ring, read by the kernels and moved
+    by a launch of its own -- so that one step captured into a hipGraph can be replayed for the whole recording (GraphedStream).  head and
+    seen then READ pos: each read synchronises with the device, so leave them alone between the steps of a hot loop."""
 
-    def __init__(self, op, dtype, S, n, f, K, H, dilation, device):
+    def __init__(self, op, dtype, S, n, f, K, H, dilation, device, capturable=False):
         self.op, self.dtype, self.dilation = op, dtype, int(dilation)
         self.S, self.n, self.f, self.K, self.H = int(S), int(n), int(f), int(K), int(H)
         self.C = (self.H - 1) * self.dilation
         self.ring_ld = self.C * self.f      # f % 4 == 0 (bf16: 8) makes it a multiple of the 16-byte staging unit; any other f stages narrow
         self.ring = torch.zeros((self.K, self.S, self.n, self.ring_ld), dtype=dtype, device=device) if self.C else None
-        self.head = self.seen = 0
+        self.capturable = bool(capturable)
+        self.pos = torch.zeros(2, dtype=torch.int64, device=device) if self.capturable else None
+        self._head = self._seen = 0
+
+    @property
+    def head(self):
+        """slot of the oldest row kept; a capturable state reads it from the device (synchronises)"""
+        return int(self.pos[0]) if self.capturable else self._head
+
+    @property
+    def seen(self):
+        """time rows passed through; a capturable state reads it from the device (synchronises)"""
+        return int(self.pos[1]) if self.capturable else self._seen
 
     def reset(self):
-        """start a new recording: zero ring, head = seen = 0"""
+        """start a new recording: zero ring, head = seen = 0 (a capturable state: stream-ordered zero_() of ring and pos, no synchronisation)"""
         if self.ring is not None:
             self.ring.zero_()
-        self.head = self.seen = 0
+        if self.capturable:
+            self.pos.zero_()
+        self._head = self._seen = 0
         return self
 
     def mismatch(self, dtype, S, n, f, K, H, dilation):
@@ -1730,15 +1747,24 @@ class SeriesStreamState:
         return None
 
     def advance(self, Tc):
-        self.seen += Tc
+        """the host's position moves by one chunk; a capturable state's moves on the device (tgcn_series_stream_advance's kernel)"""
+        if self.capturable:
+            return
+        self._seen += Tc
         if self.C:
-            self.head = (self.head + Tc) % self.C
+            self._head = (self._head + Tc) % self.C
+
+
+def stream_is_capturing():
+    """True while the current stream records a hipGraph (torch.cuda.graph); False without touching the device when none is initialised"""
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
 
 
 @_on_device
 def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state):
     """one chunk (S, n, Tc, f) in the operand's labels through the ring of `state`: plan query, K-1 hops on rows of Tc*f, the stream entry (the
-    projection and the ring update), head and seen moved; H == 1: the _conv entry on the chunk"""
+    projection and the ring update), head and seen moved; H == 1: the _conv entry on the chunk.  A capturable state runs the _pos entries,
+    which read the head from state.pos and move it on the device (H == 1: the _conv entry, then tgcn_series_stream_advance)"""
     L = _lib.lib()
     S, n, Tc, f = chunk.shape
     K, H, _, N = weight_khfg.shape
@@ -1765,23 +1791,28 @@ def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state):
     out = torch.empty((S, n, Tc, N), dtype=state.dtype, device=x3.device)
     b = bias.to(state.dtype).contiguous() if bias is not None else None
     head = (_lib.stream_ptr(), S, n, Tc, f, H, N, K, _lib.ptr(stack))
+    where = _lib.ptr(state.pos) if state.capturable else state.head      # the ring's position: device memory, or the host's scalar
     if bf16:
         mid = (ld, _lib.ptr(Wt), _lib.ptr(b), _lib.DTYPE_BF16, bias_kind)
         if state.C:
-            _lib.check(L.tgcn_cheb_project_series_stream_bf16(*head, *mid, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld, state.head, state.dilation))
+            entry = L.tgcn_cheb_project_series_stream_pos_bf16 if state.capturable else L.tgcn_cheb_project_series_stream_bf16
+            _lib.check(entry(*head, *mid, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld, where, state.dilation))
         else:
             _lib.check(L.tgcn_cheb_project_series_conv_bf16(*head, *mid, 1, _lib.ptr(out), 1, 0, 0))
     else:
         mid = (_lib.ptr(Wt), _lib.ptr(b), bias_kind)
         if state.C:
-            _lib.check(L.tgcn_cheb_project_series_stream_f32(*head, *mid, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld, state.head, state.dilation))
+            entry = L.tgcn_cheb_project_series_stream_pos_f32 if state.capturable else L.tgcn_cheb_project_series_stream_f32
+            _lib.check(entry(*head, *mid, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld, where, state.dilation))
         else:
             _lib.check(L.tgcn_cheb_project_series_conv_f32(*head, *mid, 1, _lib.ptr(out), 1, 0, 0))
+    if state.capturable and not state.C:
+        _lib.check(L.tgcn_series_stream_advance(_lib.stream_ptr(), where, Tc, 0))       # no ring, but seen still counts
     state.advance(Tc)
     return out
 
 
-def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream"):
+def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream", capturable=False):
     """Everything cheb_time_stream refuses that does not need the operand -- the modules run it before they build one.
     -> (dtype, (S, n, f, K, H), the dilation the call runs at)"""
     dt = param_dtype(weight, bias, who)
@@ -1808,10 +1839,17 @@ def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream"
         bad = state.mismatch(dt, S, n, f, K, H, dilation)
         if bad:
             raise _lib.TgcnError("%s: the state was made for %s -- one state per layer and recording batch" % (who, bad))
+        if capturable and not state.capturable:
+            raise _lib.TgcnError("%s: capturable=True with a state that keeps its head on the host -- the state's kind rules; start the "
+                                 "recording with state=None, capturable=True" % who)
+    # a head kept on the host is a launch argument: a captured step would replay the head of the capture on every chunk
+    if (H - 1) * dilation > 0 and not (state.capturable if state is not None else capturable) and stream_is_capturing():
+        raise _lib.TgcnError("%s: the stream is capturing a hipGraph and the state keeps its ring position on the host, which a replay "
+                             "cannot move -- make the state with capturable=True (tgcn_amd.GraphedStream captures a chain)" % who)
     return dt, (S, n, f, K, H), dilation
 
 
-def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=None, dilation=1):
+def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=None, dilation=1, capturable=False):
     """The causal streaming layer on the NEXT Tc time rows of S recordings (inference only): chunk (S, n, Tc) with weight (K, H, N), or
     (S, n, Tc, f) with weight (K, H, f, N) -> (out (S, n, Tc, N) contiguous, state).  out equals rows [state.seen, state.seen + Tc) of
     cheb_time_windows(op, whole, ..., as_series=True, padding="causal", dilation=dilation) on the whole series: the layer keeps the last
@@ -1820,13 +1858,16 @@ def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=
     in place and returned.  The series layout is the only one: a chain is l2(relu(o1), s2) with one state per layer.
     TgcnError before an operand is relabelled or anything launches: a state made for another operand, dtype, shape or dilation; grad mode with
     a chunk or a parameter that requires grad (there is no backward: torch.no_grad(); training stays with cheb_time_windows); bfloat16
-    parameters with a chunk of another dtype; dilation < 1.  H == 1 keeps no ring and runs the _conv entry on the chunk."""
-    dt, (S, n, f, K, H), dilation = stream_precheck(chunk, weight, bias, state, dilation)
+    parameters with a chunk of another dtype; dilation < 1.  H == 1 keeps no ring and runs the _conv entry on the chunk.
+    capturable=True with state=None makes a state whose ring position lives on the device (SeriesStreamState), the kind a step captured
+    into a hipGraph needs; with a state given the state's kind rules, and capturable=True next to a host-head state is a TgcnError.  A
+    host-head state with a ring is refused while the current stream is capturing: its replay would read a stale head."""
+    dt, (S, n, f, K, H), dilation = stream_precheck(chunk, weight, bias, state, dilation, capturable=capturable)
     if state is not None and state.op is not op:
         raise _lib.TgcnError("cheb_time_stream: the state was made for another operand -- one state per layer and graph")
     _lib.require_device(chunk, weight, bias)
     if state is None:
-        state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device)
+        state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device, capturable=capturable)
     with torch.no_grad():
         if chunk.dim() == 3:
             chunk, weight = chunk.unsqueeze(3), weight.unsqueeze(2)

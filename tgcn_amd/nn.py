@@ -211,20 +211,24 @@ class TGCNCheb_H(_DenseLBase):
                                    F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series,
                                    stride=geom[0], padding=geom[1:3], dilation=geom[3])
 
-    def forward_stream(self, chunk, state=None, dilation=1):
+    def forward_stream(self, chunk, state=None, dilation=1, capturable=False):
         """Additive API, inference only: the causal layer on the next Tc time rows of S recordings.  chunk (S, n, Tc) or (S, n, Tc, f) ->
         (out (S, n, Tc, g) contiguous, state); out equals rows [seen, seen + Tc) of forward_series(whole, as_series=True, padding="causal",
         dilation=dilation), seen = the time rows already passed through state (F.SeriesStreamState: the last (H-1)*dilation rows of the hop
         stack in a ring, updated in place; None starts a recording, state.reset() another one).  Every time row is hopped once and memory
         follows the chunk, not the recording.  A chain keeps one state per layer: l2.forward_stream(relu(o1), s2, dilation=2).
         No autograd (TgcnError in grad mode when the chunk or a parameter requires grad: use torch.no_grad()); training stays with
-        forward_series.  A state of another shape, dtype, dilation or layer raises TgcnError before anything launches."""
+        forward_series.  A state of another shape, dtype, dilation or layer raises TgcnError before anything launches.
+        capturable=True (with state=None; afterwards the state's kind rules) keeps the ring's position on the device, so that the step can
+        be captured into a hipGraph and replayed -- GraphedStream does the capture; state.head / state.seen then synchronise when read.
+        A state that keeps its head on the host is refused (TgcnError) while the current stream is capturing."""
         _compute_dtype(self)
         chunk, W = _stream_args(self, chunk)
-        F.stream_precheck(chunk, W, self.bias, state, dilation, "TGCNCheb_H.forward_stream")      # refusals come before the operand is built
+        F.stream_precheck(chunk, W, self.bias, state, dilation, "TGCNCheb_H.forward_stream", capturable)      # refusals come before the operand is built
         _state_operand_check(self, state, self._operand_key(chunk.device))
         return F.cheb_time_stream(self._operand(chunk.device), chunk, W, None if self.bias is None else self.bias.reshape(-1),
-                                  F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, state=state, dilation=dilation)
+                                  F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, state=state, dilation=dilation,
+                                  capturable=capturable)
 
 
 def _state_operand_check(module, state, key):
@@ -511,21 +515,85 @@ class ChebTimeConv(_EdgeBase):
                                    as_series=as_series,
                                    stride=geom[0], padding=geom[1:3], dilation=geom[3])
 
-    def forward_stream(self, chunk, edge_index, edge_weight=None, state=None, dilation=1):
+    def forward_stream(self, chunk, edge_index, edge_weight=None, state=None, dilation=1, capturable=False):
         """Additive API, inference only: TGCNCheb_H.forward_stream's contract for this class -- chunk (S, n, Tc[, f]) -> (out (S, n, Tc, g),
         state), the rows [seen, seen + Tc) of forward_series(whole, edge_index, edge_weight, as_series=True, padding="causal",
         dilation=dilation); true recurrence, per-channel bias.  The state belongs to the operand of (edge_index, edge_weight): another graph
-        needs its own.  A learnable edge_weight raises TgcnError, as in forward_series."""
+        needs its own.  A learnable edge_weight raises TgcnError, as in forward_series.  capturable: as in TGCNCheb_H.forward_stream."""
         if edge_weight is not None and edge_weight.requires_grad:
             raise _lib.TgcnError("ChebTimeConv.forward_stream: learnable edge weights (edge_weight.requires_grad) are not supported -- "
                                  "streaming is inference only; detach() the weight")
         _compute_dtype(self, edge_weight)
         chunk, W = _stream_args(self, chunk)
-        F.stream_precheck(chunk, W, self.bias, state, dilation, "ChebTimeConv.forward_stream")      # refusals come before the operand is built
+        F.stream_precheck(chunk, W, self.bias, state, dilation, "ChebTimeConv.forward_stream", capturable)      # refusals come before the operand is built
         _state_operand_check(self, state, self._operand_key(chunk, edge_index, edge_weight))
         op = self._operand(chunk, edge_index, edge_weight)
         return F.cheb_time_stream(op, chunk, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
-                                  state=state, dilation=dilation)
+                                  state=state, dilation=dilation, capturable=capturable)
+
+
+# ------------------------------------------------------------------------------------ a streaming chain as one hipGraph
+def _stream_states(states):
+    """the SeriesStreamState objects of what a step returned: one state, or a list / tuple of them"""
+    flat = [states] if isinstance(states, F.SeriesStreamState) else (list(states) if isinstance(states, (list, tuple)) else None)
+    if not flat or not all(isinstance(st, F.SeriesStreamState) for st in flat):
+        raise _lib.TgcnError("GraphedStream: step(chunk, states) returns (out, states) with states a SeriesStreamState or a list / tuple of them")
+    return flat
+
+
+class GraphedStream:
+    """One step of a streaming chain captured into a hipGraph and replayed chunk after chunk (DESIGN.md 3.10 "Streaming state"): a step of a
+    few time rows on a small graph is dozens of short launches, and the host time between them is a large part of it.
+    step(chunk, states) -> (out, states) is the caller's chain; states is None on the first call and the chain passes capturable=True in it:
+        def step(chunk, states):
+            s1, s2 = states or (None, None)
+            o1, s1 = l1.forward_stream(chunk, state=s1, capturable=True)
+            o2, s2 = l2.forward_stream(torch.relu(o1), state=s2, dilation=2, capturable=True)
+            return o2, (s1, s2)
+    The constructor runs `warmup` >= 1 eager steps on a side stream (they build operands, states and lazily loaded code), resets every
+    state and captures one step on a static copy of example_chunk, all under torch.no_grad().  gs(chunk) copies the chunk into the static
+    input, replays the graph and returns the STATIC output: the next call overwrites it, so clone() what must be kept.  gs.reset() starts
+    another recording; gs.states is what step returned.  One graph per chunk shape: a chunk of another shape, dtype or device than the
+    example raises TgcnError, and so does a step whose states keep a ring position on the host (refused before the capture)."""
+
+    def __init__(self, step, example_chunk, warmup=3):
+        _lib.require_device(example_chunk)
+        if not isinstance(warmup, int) or warmup < 1:
+            raise _lib.TgcnError("GraphedStream: warmup is an integer >= 1 (the first eager step makes the states), got %r" % (warmup,))
+        self._in = example_chunk.detach().clone()
+        with torch.cuda.device(self._in.device), torch.no_grad():
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                states = None
+                for _ in range(warmup):
+                    _, states = step(self._in, states)
+            torch.cuda.current_stream().wait_stream(side)
+            flat = _stream_states(states)
+            for st in flat:
+                if st.C and not st.capturable:
+                    raise _lib.TgcnError("GraphedStream: the step returned a state that keeps its ring position on the host, which a "
+                                         "replay cannot move -- pass capturable=True to forward_stream / cheb_time_stream")
+            for st in flat:
+                st.reset()
+            self.states, self._flat = states, flat
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self._out, _ = step(self._in, states)
+
+    def __call__(self, chunk):
+        if chunk.shape != self._in.shape or chunk.dtype != self._in.dtype or chunk.device != self._in.device:
+            raise _lib.TgcnError("GraphedStream: captured for chunks %s %s on %s, got %s %s on %s -- one graph per chunk shape"
+                                 % (tuple(self._in.shape), self._in.dtype, self._in.device, tuple(chunk.shape), chunk.dtype, chunk.device))
+        self._in.copy_(chunk)
+        self.graph.replay()
+        return self._out
+
+    def reset(self):
+        """start another recording: every state's ring and position zeroed, stream-ordered"""
+        for st in self._flat:
+            st.reset()
+        return self
 
 
 # ------------------------------------------------------------------------------------ fused caller pattern

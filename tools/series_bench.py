@@ -7,6 +7,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py --dtype bf16 [--out profiles/r10_series_bf16.json]
     python tools/series_bench.py --dilation [--out profiles/r11_series_dilation.json]
     python tools/series_bench.py --stream [--out profiles/r12_series_stream.json]
+    python tools/series_bench.py --stream --graph [--include parent=FILE] [--out profiles/r13_series_stream_graph.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -23,7 +24,11 @@ layers with dilations 1, 2, 4 (1 -> 32 -> 32 -> 64 channels, 284 steps in, 284 o
 the materialised dilated windows on the same commit; default --out profiles/r11_series_dilation.json.
 --stream times the streaming state (DESIGN.md 3.10 "Streaming state"): ms per chunk of that three-layer causal chain through forward_stream at
 chunk sizes 1, 8 and 64 (states warmed by 64 time rows), next to what a caller has to do without it on the same commit -- keep the trailing
-He - 1 + Tc input rows of every layer and run forward_series on them; default --out profiles/r12_series_stream.json."""
+He - 1 + Tc input rows of every layer and run forward_series on them; default --out profiles/r12_series_stream.json.
+--stream --graph times that chain's step captured into one hipGraph (tgcn_amd.GraphedStream, states with capturable=True) next to the eager
+forward_stream step on the same commit, at chunk sizes 1, 8 and 64, and records whether the two gave torch.equal outputs over the warm-up
+recording; --include LABEL=FILE embeds a --stream run of another commit (the parent's eager column); default --out
+profiles/r13_series_stream_graph.json."""
 import argparse
 import json
 import os
@@ -265,6 +270,78 @@ def main_stream(args):
         json.dump(res, f, indent=1)
 
 
+def events_ms(fn, steps, warmup):
+    """ms per call between two events, no launch record: the record's own events would be host work inside a step that is host-bound"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return round(a.elapsed_time(b) / steps, 4)
+
+
+def main_stream_graph(args):
+    dev = torch.device("cuda:0")
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, cases={})
+    torch.manual_seed(0)
+    op = dti148(dev)
+    S, K, Hc, dils, chans = 8, 10, 5, (1, 2, 4), (1, 32, 32, 64)
+    layers = [tgcn_amd.TGCNCheb_H(op, chans[i], chans[i + 1], K, Hc).to(dev) for i in range(3)]
+
+    def chain(capturable):
+        def step(x, states):
+            states = list(states or [None] * 3)
+            h = x
+            for i, (layer, d) in enumerate(zip(layers, dils)):
+                h, states[i] = layer.forward_stream(h, state=states[i], dilation=d, capturable=capturable)
+                if i < 2:
+                    h = torch.relu(h)
+            return h, states
+        return step
+
+    for Tc in (1, 8, 64):
+        chunk = torch.randn(S, op.n, Tc, 1, device=dev)
+        eager, host = chain(False), [None]
+        gs = tgcn_amd.GraphedStream(chain(True), chunk)
+
+        def eager_step(x=chunk):
+            out, host[0] = eager(x, host[0])
+            return out
+
+        def graph_step(x=chunk):
+            return gs(x)
+
+        equal = True
+        with torch.no_grad():
+            for _ in range(-(-64 // Tc)):           # one recording of 64 time rows through both, chunk by chunk
+                x = torch.randn(S, op.n, Tc, 1, device=dev)
+                equal = equal and bool(torch.equal(eager_step(x), graph_step(x)))
+            recorded = timed(eager_step, False, args.steps, args.warmup)        # with the launch record, as --stream times it
+            e_ms = events_ms(eager_step, args.steps, args.warmup)
+        g_ms = events_ms(graph_step, args.steps, args.warmup)
+        entry = dict(desc="dti148 S=8: three causal TGCNCheb_H(., ., 10, 5) layers 1 -> 32 -> 32 -> 64 with dilations 1, 2, 4, chunks of %d time rows" % Tc,
+                     forward_stream=recorded, eager_ms_per_chunk=e_ms, graphed_ms_per_chunk=g_ms, outputs_torch_equal=equal,
+                     eager_over_graphed=round(e_ms / g_ms, 3))
+        res["cases"]["chain_chunk%d" % Tc] = entry
+        print(json.dumps({"chain_chunk%d" % Tc: entry}), flush=True)
+        del gs
+    for item in args.include:
+        label, path = item.split("=", 1)
+        with open(path) as f:
+            other = json.load(f)
+        rel = {name: round(entry["forward_stream"]["ms_per_call"] / res["cases"][name]["forward_stream"]["ms_per_call"], 3)
+               for name, entry in other["cases"].items() if name in res["cases"]}
+        res.setdefault("runs", {})[label] = dict(run=other, forward_stream_ms_over_this_run=rel)
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r13_series_stream_graph.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32", help="bf16: the bfloat16 streaming cases (profiles/r10_series_bf16.json)")
@@ -275,6 +352,7 @@ def main():
     ap.add_argument("--conv", action="store_true", help="add the stride-4 and causal-chain cases")
     ap.add_argument("--dilation", action="store_true", help="the dilated cases (profiles/r11_series_dilation.json)")
     ap.add_argument("--stream", action="store_true", help="the streaming-state cases (profiles/r12_series_stream.json)")
+    ap.add_argument("--graph", action="store_true", help="with --stream: the captured step next to the eager one (profiles/r13_series_stream_graph.json)")
     ap.add_argument("--include", action="append", default=[], metavar="LABEL=FILE",
                     help="put another run's --out file (the parent commit's, a repeat of this one) into this one under runs[LABEL], with "
                          "each shared case's ms per call relative to this run")
@@ -284,6 +362,10 @@ def main():
         return main_bf16(args)
     if args.dilation:
         return main_dilation(args)
+    if args.graph and not args.stream:
+        ap.error("--graph goes with --stream")
+    if args.stream and args.graph:
+        return main_stream_graph(args)
     if args.stream:
         return main_stream(args)
     dev = torch.device("cuda:0")
