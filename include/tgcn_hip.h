@@ -448,6 +448,30 @@ int tgcn_cheb_project_series_stream_pos_bf16(void* stream, int64_t S, int64_t n_
                                              int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int64_t* pos, int32_t dilation);
 int tgcn_series_stream_advance(void* stream, int64_t* pos, int32_t Tc, int32_t C);
 
+/* One streaming step in ONE launch, for operands that fit in LDS ("One launch per step"; fp32): the K - 1 hops on the
+ * chunk's rows, the stream entry's projection and its ring update, out of LDS.  chunk (S, n, Tc*f) is the INPUT of the layer in the operand's
+ * labels (not a hop stack: the terms are made here, mode 0 the monomials P_k = A P_{k-1}, mode 1 Chebyshev T_k = 2 A T_{k-1} - T_{k-2}); W
+ * (K, H*f, N) in the basis of that mode, bias / bias_kind, out (S, n, Tc, N), ring (K, S, n, ring_ld), head and dilation as in
+ * tgcn_cheb_project_series_stream_f32, and the ring after the call is the ring that entry leaves.  One workgroup per recording owns every
+ * ring row of it, so no workgroup waits for another; the chunk is walked in sub-chunks of tb time rows, each an ordinary stream step, and
+ * the sums (fp32 products and sums, terms ascending, (h, c) ascending within a term, bias last) are grouped as the stream entry's: equal to
+ * it up to the order in which a hop adds its neighbours.  Any f, N, K >= 1 (K = 1: no hop), H >= 2, no alignment asked of any pointer.
+ * pos non-null: the head is read from pos[0] on the device by the _pos entries' defensive rule (the head argument is unused), and the caller
+ * follows the call with tgcn_series_stream_advance -- every workgroup has read the old head before it moves; pos is never written here.
+ * tgcn_cheb_stream_small_plan answers 0 with *tb (time rows per sub-chunk), *dense (1: the dense n x (n|1) copy of the operand in LDS, 0: its
+ * CSR -- the smaller of the two) and *lds_bytes, or TGCN_ERR_UNSUPPORTED where the shape does not fit: n > 1024, more than 2^20 entries,
+ * operand + the mode's 2 / 3 term buffers at tb = 1 above 160 KB of LDS, or more (vertex tile, column tile) pairs than the accumulators of
+ * 1024 threads hold (ceil(n/16) * ceil(N/16) > 256); TGCN_ERR_INVALID for a non-positive f, H, N, K, Tc or dilation, a mode other than 0 / 1
+ * or a null result pointer.  A is square (the caller's check: tgcn_csr has no column count).
+ * _f32: TGCN_ERR_INVALID for what the stream entry refuses (head outside [0, C) with pos == NULL, Tc < 1, dilation < 1, ring_ld < C*f,
+ * H < 2, a null pointer, bias_kind); TGCN_ERR_UNSUPPORTED where the plan refuses; nothing is launched in either case.  One launch; the
+ * entry does not synchronise and does not allocate. */
+int tgcn_cheb_stream_small_plan(int64_t n, int64_t nnz, int32_t mode, int32_t f, int32_t H, int32_t N, int32_t K, int32_t Tc, int32_t dilation,
+                                int32_t* tb, int32_t* dense, int32_t* lds_bytes);
+int tgcn_cheb_stream_small_f32(void* stream, const tgcn_csr* A, int32_t mode, int64_t S, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                               const float* chunk, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                               int64_t ring_ld, int32_t head, const int64_t* pos, int32_t dilation);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

@@ -44,6 +44,7 @@ namespace {
 #include "pool_relayout.h"
 #include "windows.h"
 #include "windows_bf16.h"
+#include "stream_small.h"
 #include "device_build.h"
 #include "graph_build.h"
 
@@ -1447,6 +1448,60 @@ int tgcn_cheb_project_series_stream_pos_f32(void* stream, int64_t S, int64_t n_v
   if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, 0, pos,
                                           dilation, "project_series_stream_pos")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pos_f32");
+  return TGCN_OK;
+}
+
+// ---- one launch per step (stream_small.h): the hops, the stream entry's projection and its ring update out of LDS
+int tgcn_cheb_stream_small_plan(int64_t n, int64_t nnz, int32_t mode, int32_t f, int32_t H, int32_t N, int32_t K, int32_t Tc, int32_t dilation,
+                                int32_t* tb, int32_t* dense, int32_t* lds_bytes) {
+  if (f < 1 || H < 1 || N < 1 || K < 1 || Tc < 1 || dilation < 1 || (mode != 0 && mode != 1) || !tb || !dense || !lds_bytes)
+    TGCN_FAIL(TGCN_ERR_INVALID, "stream_small_plan: bad argument");
+  StreamSmallPlan pl;
+  if (!stream_small_plan(n, nnz, mode, f, N, Tc, &pl))
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "stream_small_plan: n=%lld nnz=%lld f=%d N=%d does not fit one workgroup", (long long)n, (long long)nnz, f, N);
+  *tb = pl.tb; *dense = pl.dense; *lds_bytes = pl.lds;
+  return TGCN_OK;
+}
+
+int tgcn_cheb_stream_small_f32(void* stream, const tgcn_csr* A, int32_t mode, int64_t S, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                               const float* chunk, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                               int64_t ring_ld, int32_t head, const int64_t* pos, int32_t dilation) {
+  int32_t C = 0;
+  if (!A || !chunk || !W || !out || !ring || (mode != 0 && mode != 1) ||
+      series_stream_check(S, A->n, Tc, f, H, N, K, dilation, ring_ld, pos ? 0 : head, &C))
+    TGCN_FAIL(TGCN_ERR_INVALID, "stream_small: bad argument");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "stream_small: bias_kind %d", bias_kind);
+  StreamSmallPlan pl;
+  if (!stream_small_plan(A->n, A->nnz, mode, f, N, Tc, &pl))
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "stream_small: n=%lld nnz=%lld f=%d N=%d does not fit one workgroup", (long long)A->n, (long long)A->nnz, f, N);
+  // the kernel's 32-bit offsets: one recording's rows of the chunk, of the output and of one term of the ring; the whole weight
+  const int64_t lim = (int64_t)INT32_MAX;
+  if (S > lim || A->n * Tc * f > lim || A->n * Tc * N > lim || A->n * ring_ld > lim || (int64_t)K * H * f * N > lim)
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "stream_small: a recording's rows or the weight exceed 32-bit offsets");
+  if (!A->rowptr || !A->edges) TGCN_FAIL(TGCN_ERR_INVALID, "stream_small: bad argument");
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "stream_small")) return drc;
+  StreamSmallParams p;
+  memset(&p, 0, sizeof(p));
+  p.rowptr = A->rowptr; p.ev = A->edges; p.chunk = chunk; p.W = W; p.bias = bias; p.out = out; p.ring = ring; p.pos = pos;
+  p.S = (int32_t)S; p.ring_ld = (int32_t)ring_ld;
+  p.n = (int32_t)A->n; p.nnz = (int32_t)A->nnz; p.Tc = Tc; p.f = f; p.fp = (f + 3) / 4 * 4; p.H = H; p.N = N; p.K = K;
+  p.bias_kind = bias_kind; p.TB = pl.tb; p.ld = pl.ld; p.C = C; p.head = head; p.dil = dilation;
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 grid((unsigned)S), block((unsigned)pl.nthr);
+  ProfScope ps(TGCN_PROF_PROJECT, st);
+#define TGCN_STREAM_SMALL(DENSE_, NTW_, MODE_)                                                                        \
+  do {                                                                                                                \
+    if (pl.lds > 64 * 1024) allow_large_lds((const void*)small_stream_kernel<DENSE_, NTW_, MODE_>, pl.lds);           \
+    hipLaunchKernelGGL((small_stream_kernel<DENSE_, NTW_, MODE_>), grid, block, pl.lds, st, p);                       \
+  } while (0)
+#define TGCN_STREAM_SMALL_NTW(DENSE_, MODE_)                                                                          \
+  do { if (pl.ntw == 4) TGCN_STREAM_SMALL(DENSE_, 4, MODE_); else if (pl.ntw == 2) TGCN_STREAM_SMALL(DENSE_, 2, MODE_); \
+       else TGCN_STREAM_SMALL(DENSE_, 1, MODE_); } while (0)
+  if (pl.dense) { if (mode == 0) TGCN_STREAM_SMALL_NTW(true, 0); else TGCN_STREAM_SMALL_NTW(true, 1); }
+  else { if (mode == 0) TGCN_STREAM_SMALL_NTW(false, 0); else TGCN_STREAM_SMALL_NTW(false, 1); }
+#undef TGCN_STREAM_SMALL_NTW
+#undef TGCN_STREAM_SMALL
+  TGCN_CHECK_LAUNCH("tgcn_cheb_stream_small_f32");
   return TGCN_OK;
 }
 

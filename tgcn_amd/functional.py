@@ -1812,10 +1812,62 @@ def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state):
     return out
 
 
-def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream", capturable=False):
+# "auto" fuses a step of at most this many time rows: the largest measured Tc at which the fused step beat the parent commit's eager step by
+# more than the spread of three repeats of each.  profiles/r14_series_stream_fused.json (DESIGN.md 3.10 "One launch per step"): the fused
+# step is slower at Tc = 1, 8 and 64 (1.15 against 0.69 ms per chunk at Tc = 1, spreads under 0.03 ms), so 0 -- "auto" never fuses, and
+# fused=True is the opt-in.
+STREAM_FUSED_AUTO_MAX_TC = 0
+
+
+def _stream_small_plan(op, f, H, N, K, Tc, dilation, mode):
+    """tgcn_cheb_stream_small_plan on a square operand -> (rc, tb, dense, lds_bytes)"""
+    tb, dense, lds = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    rc = _lib.lib().tgcn_cheb_stream_small_plan(op.n, op.nnz, int(mode), int(f), int(H), int(N), int(K), int(Tc), int(dilation),
+                                                C.byref(tb), C.byref(dense), C.byref(lds))
+    return rc, tb.value, dense.value, lds.value
+
+
+def stream_fused_supported(op, f, H, N, K, Tc, dilation, mode):
+    """True where cheb_time_stream(..., fused=True) runs a float32 step of Tc time rows on this operand: a square operand, a ring (H >= 2)
+    and a plan that accepts (tgcn_cheb_stream_small_plan: operand and term buffers in one workgroup's LDS).  A host query: nothing launches."""
+    if op.n_cols != op.n or H < 2 or min(f, N, K, Tc, dilation) < 1:
+        return False
+    return _stream_small_plan(op, f, H, N, K, Tc, dilation, mode)[0] == 0
+
+
+@_on_device
+def _stream_chunk_fused(chunk, weight_khfg, bias, op, mode, bias_kind, state):
+    """_stream_chunk's step in one launch (tgcn_cheb_stream_small_f32; float32, H >= 2, a plan that accepted): the fold in power mode with
+    K > 2, the fused entry on the chunk itself -- hops, projection and ring update out of LDS -- and, for a capturable state, the advance"""
+    L = _lib.lib()
+    S, n, Tc, f = chunk.shape
+    K, H, _, N = weight_khfg.shape
+    W = weight_khfg.float().contiguous().view(K, H * f, N)
+    Wt = _working_weight(_power_fold(mode, W), W)       # folded on every call: each chunk is projected with the weight of its own call
+    x3 = chunk.float().contiguous().view(S, n, Tc * f)
+    out = torch.empty((S, n, Tc, N), dtype=torch.float32, device=x3.device)
+    b = bias.float().contiguous() if bias is not None else None
+    pos = _lib.ptr(state.pos) if state.capturable else None
+    _lib.check(L.tgcn_cheb_stream_small_f32(_lib.stream_ptr(), C.byref(op.struct), int(mode), S, Tc, f, H, N, K, _lib.ptr(x3), _lib.ptr(Wt),
+                                            _lib.ptr(b), bias_kind, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld,
+                                            0 if state.capturable else state.head, pos, state.dilation))
+    if state.capturable:        # behind the step on the same stream: every workgroup has read the old head
+        _lib.check(L.tgcn_series_stream_advance(_lib.stream_ptr(), pos, Tc, state.C))
+    state.advance(Tc)
+    return out
+
+
+def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream", capturable=False, fused=False):
     """Everything cheb_time_stream refuses that does not need the operand -- the modules run it before they build one.
     -> (dtype, (S, n, f, K, H), the dilation the call runs at)"""
     dt = param_dtype(weight, bias, who)
+    if fused is not False and fused is not True and fused != "auto":
+        raise _lib.TgcnError("%s: fused is False, True or \"auto\", got %r" % (who, fused))
+    if fused is True:       # the one-launch step is fp32 and needs a ring ("auto" takes the general route for both)
+        if dt == BF16:
+            raise _lib.TgcnError("%s: fused=True runs in float32 only -- the parameters are bfloat16 (fused=False or \"auto\")" % who)
+        if weight.dim() in (3, 4) and weight.shape[1] == 1:
+            raise _lib.TgcnError("%s: fused=True needs a ring, and a one-tap layer (H = 1) keeps none (fused=False or \"auto\")" % who)
     if chunk.dim() not in (3, 4) or weight.dim() != chunk.dim():
         raise _lib.TgcnError("%s: a (S, n, Tc) chunk takes a (K, H, N) weight and a (S, n, Tc, f) chunk a (K, H, f, N) weight (got %s and %s)"
                              % (who, tuple(chunk.shape), tuple(weight.shape)))
@@ -1849,7 +1901,7 @@ def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream"
     return dt, (S, n, f, K, H), dilation
 
 
-def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=None, dilation=1, capturable=False):
+def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=None, dilation=1, capturable=False, fused=False):
     """The causal streaming layer on the NEXT Tc time rows of S recordings (inference only): chunk (S, n, Tc) with weight (K, H, N), or
     (S, n, Tc, f) with weight (K, H, f, N) -> (out (S, n, Tc, N) contiguous, state).  out equals rows [state.seen, state.seen + Tc) of
     cheb_time_windows(op, whole, ..., as_series=True, padding="causal", dilation=dilation) on the whole series: the layer keeps the last
@@ -1861,10 +1913,26 @@ def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=
     parameters with a chunk of another dtype; dilation < 1.  H == 1 keeps no ring and runs the _conv entry on the chunk.
     capturable=True with state=None makes a state whose ring position lives on the device (SeriesStreamState), the kind a step captured
     into a hipGraph needs; with a state given the state's kind rules, and capturable=True next to a host-head state is a TgcnError.  A
-    host-head state with a ring is refused while the current stream is capturing: its replay would read a stale head."""
-    dt, (S, n, f, K, H), dilation = stream_precheck(chunk, weight, bias, state, dilation, capturable=capturable)
+    host-head state with a ring is refused while the current stream is capturing: its replay would read a stale head.
+    fused=True runs the step in ONE launch (tgcn_cheb_stream_small_f32: hops, projection and ring update out of LDS, one workgroup per
+    recording) on the same state -- fused and unfused calls may alternate within a recording.  It asks the plan first and raises TgcnError
+    before anything launches for bfloat16 parameters, H = 1, a non-square operand and a plan that refuses (stream_fused_supported tells).
+    fused="auto" fuses where the plan accepts and Tc <= STREAM_FUSED_AUTO_MAX_TC, and is fused=False everywhere else.  The results agree to
+    rounding (the hops add their neighbours in another order), not bit for bit."""
+    dt, (S, n, f, K, H), dilation = stream_precheck(chunk, weight, bias, state, dilation, capturable=capturable, fused=fused)
     if state is not None and state.op is not op:
         raise _lib.TgcnError("cheb_time_stream: the state was made for another operand -- one state per layer and graph")
+    if fused is not False:
+        Tc, N = chunk.shape[2], weight.shape[-1]
+        if fused is True:
+            if op.n_cols != op.n:
+                raise _lib.TgcnError("cheb_time_stream: fused=True needs a square operand, got %d x %d" % (op.n, op.n_cols))
+            if _stream_small_plan(op, f, H, N, K, Tc, dilation, mode)[0] != 0:
+                raise _lib.TgcnError("cheb_time_stream: fused=True, but n = %d, nnz = %d, f = %d, N = %d do not fit the one-launch step "
+                                     "(stream_fused_supported; fused=False or \"auto\")" % (op.n, op.nnz, f, N))
+        else:
+            fused = (dt != BF16 and H >= 2 and Tc <= STREAM_FUSED_AUTO_MAX_TC and op.n_cols == op.n
+                     and _stream_small_plan(op, f, H, N, K, Tc, dilation, mode)[0] == 0)
     _lib.require_device(chunk, weight, bias)
     if state is None:
         state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device, capturable=capturable)
@@ -1872,7 +1940,7 @@ def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=
         if chunk.dim() == 3:
             chunk, weight = chunk.unsqueeze(3), weight.unsqueeze(2)
         chunk, bias = _to_operand_labels(op, chunk, bias, bias_kind)      # the ring lives in the operand's labels
-        out = _stream_chunk(chunk, weight, bias, op, mode, bias_kind, state)
+        out = (_stream_chunk_fused if fused else _stream_chunk)(chunk, weight, bias, op, mode, bias_kind, state)
         if op.perm is not None:
             out = relabel_rows(out, op.inv_perm, op.perm).to(dt)
     return out, state

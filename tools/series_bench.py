@@ -8,6 +8,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py --dilation [--out profiles/r11_series_dilation.json]
     python tools/series_bench.py --stream [--out profiles/r12_series_stream.json]
     python tools/series_bench.py --stream --graph [--include parent=FILE] [--out profiles/r13_series_stream_graph.json]
+    python tools/series_bench.py --stream --fused [--include parent=FILE] [--out profiles/r14_series_stream_fused.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -28,7 +29,13 @@ He - 1 + Tc input rows of every layer and run forward_series on them; default --
 --stream --graph times that chain's step captured into one hipGraph (tgcn_amd.GraphedStream, states with capturable=True) next to the eager
 forward_stream step on the same commit, at chunk sizes 1, 8 and 64, and records whether the two gave torch.equal outputs over the warm-up
 recording; --include LABEL=FILE embeds a --stream run of another commit (the parent's eager column); default --out
-profiles/r13_series_stream_graph.json."""
+profiles/r13_series_stream_graph.json.
+--stream --fused times that chain's step in one launch per layer (forward_stream(..., fused=True), DESIGN.md 3.10 "One launch per step")
+next to the eager host-head step (fused=False, the code the parent commit runs) and the GraphedStream replay of the fused step, at chunk
+sizes 1, 8 and 64: three repeats of each, events only (no launch record inside a timed region), the library launches of one step of each
+counted in a separate untimed step, and the largest relative difference of fused and eager outputs over the warm-up recording.  --include
+LABEL=FILE embeds a --stream --graph run of the parent commit (its eager_ms_per_chunk is the comparison column); default --out
+profiles/r14_series_stream_fused.json."""
 import argparse
 import json
 import os
@@ -342,6 +349,94 @@ def main_stream_graph(args):
         json.dump(res, f, indent=1)
 
 
+def launches_of(fn):
+    """library launches of one call, by kind (the launch record, outside every timed region)"""
+    torch.cuda.synchronize()
+    _lib.profile_start(1 << 12)
+    with torch.no_grad():
+        fn()
+    torch.cuda.synchronize()
+    kinds = [k for k, _ in _lib.profile_stop(1 << 12)]
+    return len(kinds)
+
+
+def main_stream_fused(args):
+    dev = torch.device("cuda:0")
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, repeats=3,
+               auto_max_tc=F.STREAM_FUSED_AUTO_MAX_TC, cases={})
+    torch.manual_seed(0)
+    op = dti148(dev)
+    S, K, Hc, dils, chans = 8, 10, 5, (1, 2, 4), (1, 32, 32, 64)
+    layers = [tgcn_amd.TGCNCheb_H(op, chans[i], chans[i + 1], K, Hc).to(dev) for i in range(3)]
+
+    def chain(capturable, fused):
+        def step(x, states):
+            states = list(states or [None] * 3)
+            h = x
+            for i, (layer, d) in enumerate(zip(layers, dils)):
+                h, states[i] = layer.forward_stream(h, state=states[i], dilation=d, capturable=capturable, fused=fused)
+                if i < 2:
+                    h = torch.relu(h)
+            return h, states
+        return step
+
+    for Tc in (1, 8, 64):
+        chunk = torch.randn(S, op.n, Tc, 1, device=dev)
+        plans = [F._stream_small_plan(op, chans[i], Hc, chans[i + 1], K, Tc, dils[i], F.MODE_POWER) for i in range(3)]
+        eager, fused, cap = chain(False, False), chain(False, True), chain(True, True)
+        st_e, st_f, st_c = [None], [None], [None]
+        gs = tgcn_amd.GraphedStream(cap, chunk)
+
+        def eager_step(x=chunk):
+            out, st_e[0] = eager(x, st_e[0])
+            return out
+
+        def fused_step(x=chunk):
+            out, st_f[0] = fused(x, st_f[0])
+            return out
+
+        def cap_step(x=chunk):
+            out, st_c[0] = cap(x, st_c[0])
+            return out
+
+        def graph_step(x=chunk):
+            return gs(x)
+
+        err, equal = 0.0, True
+        with torch.no_grad():
+            for _ in range(-(-64 // Tc)):           # one recording of 64 time rows through all three, chunk by chunk
+                x = torch.randn(S, op.n, Tc, 1, device=dev)
+                a, b, c = eager_step(x), fused_step(x), graph_step(x)
+                err = max(err, float((a - b).abs().max() / a.abs().max()))
+                equal = equal and bool(torch.equal(b, c))
+            counts = dict(eager=launches_of(eager_step), fused=launches_of(fused_step), graphed_fused=launches_of(cap_step))
+            e_ms = [events_ms(eager_step, args.steps, args.warmup) for _ in range(3)]
+            f_ms = [events_ms(fused_step, args.steps, args.warmup) for _ in range(3)]
+        g_ms = [events_ms(graph_step, args.steps, args.warmup) for _ in range(3)]
+        med = lambda v: sorted(v)[1]      # noqa: E731
+        entry = dict(desc="dti148 S=8: three causal TGCNCheb_H(., ., 10, 5) layers 1 -> 32 -> 32 -> 64 with dilations 1, 2, 4, chunks of %d time rows" % Tc,
+                     plans=[dict(rc=rc, tb=tb, dense=dn, lds_bytes=lds) for rc, tb, dn, lds in plans],
+                     eager_ms_per_chunk=e_ms, fused_ms_per_chunk=f_ms, graphed_fused_ms_per_chunk=g_ms,
+                     spread_ms=dict(eager=round(max(e_ms) - min(e_ms), 4), fused=round(max(f_ms) - min(f_ms), 4),
+                                    graphed_fused=round(max(g_ms) - min(g_ms), 4)),
+                     library_launches_per_chunk=counts, max_rel_difference_fused_vs_eager=err, graphed_fused_torch_equal_fused=equal,
+                     eager_over_fused=round(med(e_ms) / med(f_ms), 3), eager_over_graphed_fused=round(med(e_ms) / med(g_ms), 3))
+        res["cases"]["chain_chunk%d" % Tc] = entry
+        print(json.dumps({"chain_chunk%d" % Tc: entry}), flush=True)
+        del gs
+    for item in args.include:
+        label, path = item.split("=", 1)
+        with open(path) as f:
+            other = json.load(f)
+        rel = {name: round(entry["eager_ms_per_chunk"] / sorted(res["cases"][name]["eager_ms_per_chunk"])[1], 3)
+               for name, entry in other["cases"].items() if name in res["cases"]}
+        res.setdefault("runs", {})[label] = dict(run=other, eager_ms_over_this_run=rel)
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r14_series_stream_fused.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32", help="bf16: the bfloat16 streaming cases (profiles/r10_series_bf16.json)")
@@ -353,6 +448,7 @@ def main():
     ap.add_argument("--dilation", action="store_true", help="the dilated cases (profiles/r11_series_dilation.json)")
     ap.add_argument("--stream", action="store_true", help="the streaming-state cases (profiles/r12_series_stream.json)")
     ap.add_argument("--graph", action="store_true", help="with --stream: the captured step next to the eager one (profiles/r13_series_stream_graph.json)")
+    ap.add_argument("--fused", action="store_true", help="with --stream: the one-launch step next to the eager one (profiles/r14_series_stream_fused.json)")
     ap.add_argument("--include", action="append", default=[], metavar="LABEL=FILE",
                     help="put another run's --out file (the parent commit's, a repeat of this one) into this one under runs[LABEL], with "
                          "each shared case's ms per call relative to this run")
@@ -364,6 +460,10 @@ def main():
         return main_dilation(args)
     if args.graph and not args.stream:
         ap.error("--graph goes with --stream")
+    if args.fused and not args.stream:
+        ap.error("--fused goes with --stream")
+    if args.stream and args.fused:
+        return main_stream_fused(args)
     if args.stream and args.graph:
         return main_stream_graph(args)
     if args.stream:
