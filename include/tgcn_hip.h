@@ -488,6 +488,20 @@ int tgcn_cheb_project_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32
                            const void* W, const void* bias, int32_t bias_kind, int32_t bias_dtype, int32_t bias_cols, int64_t n_vertices,
                            int64_t interleave, int32_t accumulate, void* out, int64_t ldo, int32_t out_dtype);
 
+/* tgcn_cheb_project_bf16's contraction through tgcn_cheb_project_mapped_f32's ROW MAP at interleave = 1 (the building block of the compacted
+ * bf16 layers): tile row m is the caller's vertex rowmap[m] (int32 device array of M entries, each < n_vertices) -- its output
+ * row, its bias row, and its row in every term t whose bit t is set in `mapped_terms`; the other terms are read at row m.  nbatch samples share
+ * the tile rows (grid.z): sample b reads term t at a[t] + b * a_bs[t] ELEMENTS and writes out + b * out_bs elements.  a_bs: HOST array of
+ * nterms strides (nullable for nbatch = 1).  The bias (fp32 or bf16, all N columns) is added in fp32; out is fp32, or rounded once to bf16;
+ * rows that the map does not name are not touched.  Row offsets are 64-bit after the map.  16-byte A loads when every a[t] is 16-byte
+ * aligned and Kc, lda[t] and a_bs[t] are multiples of 8, element loads otherwise.  A mapped row holds the bits tgcn_cheb_project_bf16 gives
+ * the same row of explicitly gathered terms.  TGCN_ERR_INVALID for a null rowmap, nbatch < 1, nbatch > 1 without a_bs, M <= 0 (an empty map
+ * is the caller's case) or what tgcn_cheb_project_bf16 refuses; nothing is launched then. */
+int tgcn_cheb_project_mapped_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const void* const* a, const int64_t* lda,
+                                  const void* W, const void* bias, int32_t bias_kind, int32_t bias_dtype, int64_t n_vertices, const int32_t* rowmap,
+                                  uint32_t mapped_terms, int32_t nbatch, const int64_t* a_bs, int64_t out_bs, void* out, int64_t ldo,
+                                  int32_t out_dtype);
+
 /* tgcn_cheb_wgrad_f32 on bf16 A_t and G (fp32 dW and partials): bf16 matrix pipe (exact products), the same two-stage reduction in fixed
  * order (deterministic); workspace: tgcn_cheb_wgrad_workspace_bytes. */
 int tgcn_cheb_wgrad_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const void* const* a, const int64_t* lda,
@@ -637,6 +651,9 @@ int tgcn_csr_sddmm_f32(void* stream, const tgcn_csr* A, int64_t n_cols, int32_t 
  * out[i, 0:C] = src[idx[i], 0:C] -- the rows of a hop tensor that a neighbouring shard needs, packed into one message.
  * idx: int64 device array; src rows ld_src floats apart; out contiguous. */
 int tgcn_pack_rows_f32(void* stream, const float* src, int64_t ld_src, const int64_t* idx, int64_t nrows, int32_t C, float* out);
+/* The same on 2-byte elements (bf16 rows: the kept rows of the output gradient of a compacted bf16 layer): ld_src and C in elements; 16-byte
+ * pieces when C and ld_src are multiples of 8 and src and out are 16-byte aligned, element by element otherwise.  Values move unchanged. */
+int tgcn_pack_rows_bf16(void* stream, const void* src, int64_t ld_src, const int64_t* idx, int64_t nrows, int32_t C, void* out);
 
 /* gcn_pool / gcn_pool_4 (gcn.py:246-255): max over p consecutive vertices; idx (nullable) receives the
  * arg-max offset 0..p-1 for the backward. */

@@ -111,6 +111,20 @@ __global__ __launch_bounds__(kBlock) void pack_rows_kernel(const float* __restri
   }
 }
 
+// pack_rows_kernel on 2-byte elements (tgcn_pack_rows_bf16: the kept rows of the output gradient of a compacted bf16 layer): UNIT = uint4 moves
+// 16-byte pieces (C and ld_src multiples of 8 elements, both bases 16-byte aligned: the host's test), UNIT = uint16_t single elements; C and
+// ld_src arrive in UNITs.  The bits move unchanged.
+template <typename UNIT>
+__global__ __launch_bounds__(kBlock) void pack_rows_2b_kernel(const UNIT* __restrict__ src, const int64_t* __restrict__ idx, UNIT* __restrict__ out,
+                                                              int64_t nrows, int32_t C, int64_t ld_src) {
+  const int64_t total = nrows * C;
+  for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
+    const int64_t r = i / C;
+    const int c = (int)(i - r * C);
+    out[i] = src[idx[r] * ld_src + c];
+  }
+}
+
 // out[r, :] = src[idx[r], :] with int32 row ids and 16-byte pieces when the rows allow it: T_0 of the compacted Chebyshev layer (the kept rows of
 // x packed to compact ids, tgcn_cheb_compact_layer_f32 mode 1) and the wide-row form of tgcn_pack_rows_f32
 template <int VEC>

@@ -1312,8 +1312,25 @@ __device__ __forceinline__ float pb_load_scalar(const ProjBf16Params& p, int64_t
   return bf16_lo(*reinterpret_cast<const uint16_t*>(p.a[t] + m * p.lda[t] + c));
 }
 
-template <int NT, bool VEC8>
-__global__ __launch_bounds__(256) void project_bf16_kernel(const ProjBf16Params p) {
+// MAPPED (tgcn_cheb_project_mapped_bf16, the compacted bf16 layers): tile row m is the caller's vertex rowmap[m] -- its output row, its bias
+// row, and its row in every term whose bit is set in `mapped`; the other terms (compact hop tensors) are read at row m.  Sample blockIdx.z
+// reads term t at a[t] + z * a_bs[t] and writes out + z * out_bs (elements).  Row offsets are 64-bit after the map.  A row's sums do not
+// depend on the tile row it sits in (one MFMA row per tile row, the k steps in order), so a mapped row holds the bits the unmapped kernel
+// gives the same row.  The unmapped instantiations take ProjBf16Params as before: nothing below touches them.
+struct ProjBf16MappedParams : ProjBf16Params {
+  const int32_t* rowmap;
+  uint32_t mapped;
+  int64_t a_bs[kMaxTerms];
+  int64_t out_bs;
+};
+
+// element offset of (tile row m, term t) of sample z: the mapped vertex `vm` where the term's bit is set
+__device__ __forceinline__ int64_t pb_mapped_off(const ProjBf16MappedParams& p, int t, int64_t m, int64_t vm, int64_t z) {
+  return (((p.mapped >> t) & 1u) ? vm : m) * p.lda[t] + z * p.a_bs[t];
+}
+
+template <int NT, bool VEC8, bool MAPPED = false>
+__global__ __launch_bounds__(256) void project_bf16_kernel(const typename std::conditional<MAPPED, ProjBf16MappedParams, ProjBf16Params>::type p) {
   constexpr int NW = NT * 16;
   __shared__ __align__(16) hbf16 Ws[NW * kPbLd];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1327,6 +1344,14 @@ __global__ __launch_bounds__(256) void project_bf16_kernel(const ProjBf16Params 
 #pragma unroll
     for (int i = 0; i < NT; ++i) acc[r][i] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int lr = lane & 15, lk = (lane >> 4) * 8;
+  int64_t vm[2] = {0, 0};       // MAPPED: the vertex of this lane's two A rows, read once
+  if constexpr (MAPPED) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+      const int64_t m = m0 + r * 16 + lr;
+      if (m < p.M) vm[r] = (int64_t)p.rowmap[m];
+    }
+  }
   for (int k0 = 0; k0 < kpad; k0 += kPbKch) {
     __syncthreads();
     for (int idx = tid; idx < kPbKch * NW; idx += 256) {
@@ -1350,9 +1375,20 @@ __global__ __launch_bounds__(256) void project_bf16_kernel(const ProjBf16Params 
           uint4 raw = make_uint4(0u, 0u, 0u, 0u);
           if (m < p.M && kg < ktot) {
             const int t = kg / p.Kc, c = kg - t * p.Kc;
-            raw = *reinterpret_cast<const uint4*>(p.a[t] + m * p.lda[t] + c);
+            if constexpr (MAPPED) raw = *reinterpret_cast<const uint4*>(p.a[t] + pb_mapped_off(p, t, m, vm[r], blockIdx.z) + c);
+            else raw = *reinterpret_cast<const uint4*>(p.a[t] + m * p.lda[t] + c);
           }
           a[r] = __builtin_bit_cast(bf16x8, raw);
+        } else if constexpr (MAPPED) {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            float v = 0.f;
+            if (m < p.M && kg + j < ktot) {
+              const int t = (kg + j) / p.Kc, c = kg + j - t * p.Kc;
+              v = bf16_lo(*reinterpret_cast<const uint16_t*>(p.a[t] + pb_mapped_off(p, t, m, vm[r], blockIdx.z) + c));
+            }
+            a[r][j] = (hbf16)v;
+          }
         } else {
 #pragma unroll
           for (int j = 0; j < 8; ++j) a[r][j] = (hbf16)pb_load_scalar(p, m, kg + j, ktot);
@@ -1373,8 +1409,14 @@ __global__ __launch_bounds__(256) void project_bf16_kernel(const ProjBf16Params 
     for (int i = 0; i < 4; ++i) {
       const int64_t m = m0 + r * 16 + (lane >> 4) * 4 + i;
       if (m >= p.M) continue;
-      const int64_t orow = (p.interleave == 1) ? m : (m % p.interleave) * p.n_vertices + m / p.interleave;
-      const int64_t vert = orow < p.n_vertices ? orow : orow % p.n_vertices;
+      int64_t orow, vert, obase = 0;
+      if constexpr (MAPPED) {
+        orow = vert = (int64_t)p.rowmap[m];
+        obase = (int64_t)blockIdx.z * p.out_bs;
+      } else {
+        orow = (p.interleave == 1) ? m : (m % p.interleave) * p.n_vertices + m / p.interleave;
+        vert = orow < p.n_vertices ? orow : orow % p.n_vertices;
+      }
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
         const int col = n0 + nt * 16 + lr;
@@ -1384,7 +1426,7 @@ __global__ __launch_bounds__(256) void project_bf16_kernel(const ProjBf16Params 
           const int64_t bi = (p.bias_kind == 2 ? vert * p.bias_cols : 0) + col;
           v += p.bias_bf16 ? bf16_lo(reinterpret_cast<const uint16_t*>(p.bias)[bi]) : reinterpret_cast<const float*>(p.bias)[bi];
         }
-        const int64_t o = orow * p.ldo + col;
+        const int64_t o = obase + orow * p.ldo + col;
         if (p.out_bf16) {
           hbf16* out = reinterpret_cast<hbf16*>(p.out);
           if (p.accumulate) v += bf16_lo(reinterpret_cast<const uint16_t*>(out)[o]);

@@ -572,6 +572,55 @@ int tgcn_cheb_project_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32
   return TGCN_OK;
 }
 
+int tgcn_cheb_project_mapped_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const void* const* a, const int64_t* lda,
+                                  const void* W, const void* bias, int32_t bias_kind, int32_t bias_dtype, int64_t n_vertices, const int32_t* rowmap,
+                                  uint32_t mapped_terms, int32_t nbatch, const int64_t* a_bs, int64_t out_bs, void* out, int64_t ldo,
+                                  int32_t out_dtype) {
+  if (!rowmap || nbatch < 1 || (nbatch > 1 && !a_bs)) TGCN_FAIL(TGCN_ERR_INVALID, "project_mapped_bf16: bad argument");
+  if (M <= 0 || Kc <= 0 || N <= 0 || nterms <= 0 || !a || !lda || !W || !out || ldo < N) TGCN_FAIL(TGCN_ERR_INVALID, "project_mapped_bf16: bad argument");
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_mapped_bf16")) return drc;
+  if (nterms > kMaxTerms) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project_mapped_bf16: nterms %d > %d", nterms, kMaxTerms);
+  if ((int64_t)nterms * Kc >= (int64_t)INT32_MAX / 2) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project_mapped_bf16: nterms * Kc too large");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_mapped_bf16: bias_kind %d", bias_kind);
+  if ((bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) || (out_dtype != TGCN_DTYPE_F32 && out_dtype != TGCN_DTYPE_BF16))
+    TGCN_FAIL(TGCN_ERR_INVALID, "project_mapped_bf16: dtype codes %d / %d", bias_dtype, out_dtype);
+  if (n_vertices < 1) TGCN_FAIL(TGCN_ERR_INVALID, "project_mapped_bf16: n_vertices");
+  ProjBf16MappedParams p;
+  memset(&p, 0, sizeof(p));
+  bool vec8 = Kc % 8 == 0;
+  for (int t = 0; t < nterms; ++t) {
+    if (!a[t]) TGCN_FAIL(TGCN_ERR_INVALID, "project_mapped_bf16: null term %d", t);
+    p.lda[t] = lda[t];
+    p.a_bs[t] = nbatch > 1 ? a_bs[t] : 0;
+    vec8 = vec8 && (((uintptr_t)a[t] & 15) == 0) && (lda[t] % 8 == 0) && (p.a_bs[t] % 8 == 0);
+  }
+  p.W = (const hbf16*)W; p.bias = bias;
+  p.M = M; p.ldo = ldo; p.n_vertices = n_vertices; p.interleave = 1;
+  p.Kc = Kc; p.N = N; p.nterms = nterms; p.bias_kind = bias_kind; p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
+  p.bias_cols = N; p.out_bf16 = out_dtype == TGCN_DTYPE_BF16;
+  p.rowmap = rowmap; p.mapped = mapped_terms; p.out_bs = out_bs;
+  const int tiles = (N + 15) / 16;
+  const int nt = tiles <= 1 ? 1 : (tiles <= 2 ? 2 : 4);
+  const int64_t gx = (M + 127) / 128;
+  if (gx > (int64_t)INT32_MAX) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project_mapped_bf16: M too large");
+  hipStream_t st = (hipStream_t)stream;
+  const size_t out_elem = p.out_bf16 ? 2 : 4;
+  for (int32_t b0 = 0; b0 < nbatch; b0 += 65535) {       // the samples ride on grid.z
+    const int32_t nb = std::min<int32_t>(65535, nbatch - b0);
+    for (int t = 0; t < nterms; ++t) p.a[t] = (const hbf16*)a[t] + (int64_t)b0 * p.a_bs[t];
+    p.out = (char*)out + (size_t)((int64_t)b0 * out_bs) * out_elem;
+    const dim3 grid((unsigned)gx, (unsigned)((tiles + nt - 1) / nt), (unsigned)nb);
+    ProfScope ps(TGCN_PROF_PROJECT, st);
+#define TGCN_PROJ_BM(NTV)                                                                                          \
+  if (vec8) hipLaunchKernelGGL((project_bf16_kernel<NTV, true, true>), grid, dim3(256), 0, st, p);                 \
+  else hipLaunchKernelGGL((project_bf16_kernel<NTV, false, true>), grid, dim3(256), 0, st, p);
+    if (nt == 1) { TGCN_PROJ_BM(1) } else if (nt == 2) { TGCN_PROJ_BM(2) } else { TGCN_PROJ_BM(4) }
+#undef TGCN_PROJ_BM
+  }
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_mapped_bf16");
+  return TGCN_OK;
+}
+
 int tgcn_cheb_wgrad_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const void* const* a, const int64_t* lda,
                          const void* G, int64_t ldg, float* dW, void* workspace, size_t workspace_bytes) {
   if (M <= 0 || Kc <= 0 || N <= 0 || nterms <= 0 || !a || !lda || !G || !dW) TGCN_FAIL(TGCN_ERR_INVALID, "wgrad_bf16: bad argument");
@@ -2001,6 +2050,20 @@ int tgcn_pack_rows_f32(void* stream, const float* src, int64_t ld_src, const int
   if (nrows == 0) return TGCN_OK;
   hipLaunchKernelGGL(pack_rows_kernel, dim3(grid_1d(nrows * C)), dim3(kBlock), 0, (hipStream_t)stream, src, idx, out, nrows, C, ld_src);
   TGCN_CHECK_LAUNCH("tgcn_pack_rows_f32");
+  return TGCN_OK;
+}
+
+int tgcn_pack_rows_bf16(void* stream, const void* src, int64_t ld_src, const int64_t* idx, int64_t nrows, int32_t C, void* out) {
+  if (!src || !idx || !out || nrows < 0 || C <= 0 || ld_src < C) TGCN_FAIL(TGCN_ERR_INVALID, "pack_rows_bf16: bad argument");
+  if (nrows == 0) return TGCN_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (C % 8 == 0 && ld_src % 8 == 0 && (((uintptr_t)src | (uintptr_t)out) & 15) == 0)
+    hipLaunchKernelGGL((pack_rows_2b_kernel<uint4>), dim3(grid_1d(nrows * (C / 8))), dim3(kBlock), 0, st, (const uint4*)src, idx, (uint4*)out, nrows, C / 8,
+                       ld_src / 8);
+  else
+    hipLaunchKernelGGL((pack_rows_2b_kernel<uint16_t>), dim3(grid_1d(nrows * C)), dim3(kBlock), 0, st, (const uint16_t*)src, idx, (uint16_t*)out, nrows, C,
+                       ld_src);
+  TGCN_CHECK_LAUNCH("tgcn_pack_rows_bf16");
   return TGCN_OK;
 }
 

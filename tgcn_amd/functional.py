@@ -1004,6 +1004,7 @@ def cheb_forward_pf(op, x3, Wt_kcn, bias, bias_kind, mode):
 
 PROJECT_FIRST = True   # developer switch
 COMPACT = True         # developer switch: compact hop tensors for operands with many empty rows (graph.CompactPlan)
+COMPACT_BF16 = True    # developer switch: the bf16 reference-power layers take the compact plan too (compact_forward_bf16); COMPACT gates both
 COMPACT_Q_CHUNK = None # developer switch: time steps per pass of the compacted forward (None: chosen by cheb_forward_compact)
 
 
@@ -1491,6 +1492,119 @@ def cheb_wgrad_bf16(terms, g2d):
     return dW
 
 
+@_on_device
+def pack_rows_bf16(src, idx, out):
+    """pack_rows on bf16 rows (tgcn_pack_rows_bf16): out[i] = src[idx[i]], the values unchanged"""
+    _lib.require_device(src, idx, out)
+    assert src.dim() == 2 and src.dtype == BF16 and out.dtype == BF16 and src.stride(1) == 1 and out.is_contiguous()
+    assert idx.dtype == torch.int64 and idx.is_contiguous()
+    _lib.check(_lib.lib().tgcn_pack_rows_bf16(_lib.stream_ptr(), _lib.ptr(src), src.stride(0), _lib.ptr(idx), idx.numel(), src.shape[1], _lib.ptr(out)))
+    return out
+
+
+@_on_device
+def project_mapped_bf16(terms, term_bs, W2d, bias, bias_kind, n_vertices, rowmap, mapped_terms, q, out):
+    """out[b, rowmap[m]] = sum_t terms[t][b, row_t(m)] @ W[t] + bias through tgcn_cheb_project_mapped_bf16 (project_mapped on bf16 terms and
+    weight, interleave 1); term_bs in elements; out: (q, n_vertices, N) contiguous, bf16 (rounded once) or fp32."""
+    T = len(terms)
+    Kc = W2d.shape[0] // T
+    N = W2d.shape[1]
+    M = int(rowmap.numel())
+    if M == 0:
+        return out
+    a = (C.c_void_p * T)(*[t.data_ptr() for t in terms])
+    lda = (C.c_int64 * T)(*[Kc] * T)
+    a_bs = (C.c_int64 * T)(*term_bs)
+    bdt = _lib.DTYPE_BF16 if (bias is not None and bias.dtype == BF16) else _lib.DTYPE_F32
+    _lib.check(_lib.lib().tgcn_cheb_project_mapped_bf16(_lib.stream_ptr(), M, Kc, N, T, a, lda, _lib.ptr(W2d), _lib.ptr(bias), bias_kind, bdt, n_vertices,
+                                                        _lib.ptr(rowmap), mapped_terms, q, a_bs, n_vertices * N, _lib.ptr(out), N,
+                                                        _lib.DTYPE_BF16 if out.dtype == BF16 else _lib.DTYPE_F32))
+    return out
+
+
+def _compact_hops_bf16(plan, x3, buf):
+    """buf[k - 1][:, :n_c] = P_k = L^k x for k = 1 .. K-1 on the kept rows of `plan` (bf16 hops: plan.first gathers from x3, plan.rest from
+    the previous compact term); buf: (K-1, q, n_c + 1, C) with zero rows n_c.  _compact_hop's rule at 2 bytes per element: one launch per
+    sample when a sample's (n_c, C) slab is beyond COMPACT_SLAB_BYTES"""
+    q, n_c = x3.shape[0], plan.n_c
+    per_sample = q > 1 and n_c * x3.shape[2] * 2 > COMPACT_SLAB_BYTES
+    src = x3
+    for k in range(buf.shape[0]):
+        op = plan.first if k == 0 else plan.rest
+        for sl in ([slice(b, b + 1) for b in range(q)] if per_sample else [slice(0, q)]):
+            csr_hop_bf16(op, src[sl], out=buf[k][sl, :n_c])
+        src = buf[k]
+
+
+def _compact_q_chunk_bf16(plan, q, K, C_row, device):
+    """samples per pass of the compacted bf16 forward: equal passes whose K-1 compact terms stay within COMPACT_WS_FRACTION of the memory that
+    is free when the shape is first seen; asked once per shape (no host query on later calls, nor under hipGraph capture)"""
+    key = ("bf16", K, C_row, q)
+    qc = plan.q_chunk_cache.get(key)
+    if qc is None:
+        free = torch.cuda.mem_get_info(device)[0]
+        per_q = (K - 1) * (plan.n_c + 1) * C_row * 2
+        most = int(max(1, min(q, int(free * COMPACT_WS_FRACTION) // max(per_q, 1))))
+        passes = -(-q // most)
+        qc = plan.q_chunk_cache[key] = -(-q // passes)
+    return qc
+
+
+@_on_device
+def compact_forward_bf16(plan, x3, Wt, bias, bias_kind, keep=False):
+    """Reference-power layer forward on bf16 tensors with hop tensors for the plan's n_c kept vertices only: K-1 bf16 hops on (q, n_c + 1, C)
+    buffers, then two row-mapped bf16 projections written in place into the (q, n, N) bf16 output -- the kept rows (x through plan.rows, the
+    compact terms at their own rows) and the left-out rows (x[i] . W'_0 + bias through plan.empty).  Wt: (K, C, N) bf16 in the working basis.
+    The samples run in equal passes (_compact_q_chunk_bf16); keep=True is one pass whose compact terms are returned as the basis
+    [x3, P_1, ..., P_{K-1}].  Every row holds the bits the uncompacted bf16 layer gives it.  -> (out, terms or None)"""
+    _lib.require_device(x3, Wt, bias)
+    q, n, Crow = x3.shape
+    K, _, N = Wt.shape
+    assert x3.is_contiguous() and Wt.is_contiguous() and n == plan.n and 2 <= K <= 32 and x3.dtype == BF16 and Wt.dtype == BF16
+    auto = not keep
+    qc = _compact_q_chunk_bf16(plan, q, K, Crow, x3.device) if auto else q
+    while True:
+        try:
+            buf = torch.empty((K - 1, qc, plan.n_c + 1, Crow), dtype=BF16, device=x3.device)
+            break
+        except torch.OutOfMemoryError:
+            if not auto or qc <= 1:
+                raise
+            torch.cuda.empty_cache()
+            qc = plan.q_chunk_cache[("bf16", K, Crow, q)] = max(1, qc // 2)      # the cached choice no longer fits: fewer samples per pass from now on
+    buf[:, :, plan.n_c].zero_()
+    out = torch.empty((q, n, N), dtype=BF16, device=x3.device)
+    W2 = Wt.view(K * Crow, N)
+    cs = (plan.n_c + 1) * Crow
+    for b0 in range(0, q, qc):
+        nb = min(qc, q - b0)
+        xs, bs = x3[b0:b0 + nb], buf[:, :nb]
+        _compact_hops_bf16(plan, xs, bs)
+        project_mapped_bf16([xs] + [bs[k] for k in range(K - 1)], [n * Crow] + [cs] * (K - 1), W2, bias, bias_kind, n, plan.rows, 1, nb, out[b0:b0 + nb])
+        if plan.n_empty:
+            project_mapped_bf16([xs], [n * Crow], W2[:Crow], bias, bias_kind, n, plan.empty, 1, nb, out[b0:b0 + nb])
+    return out, ([x3] + [buf[k] for k in range(K - 1)] if keep else None)
+
+
+@_on_device
+def compact_wgrad_bf16(plan, x3, terms, g):
+    """dW (K, C, N) fp32 in the working basis from the compact bf16 terms [x3, P_1, ..]: dW_0 = x^T g over every vertex, dW_k = P_k^T g_c for
+    k >= 1 with g_c the kept rows of g gathered once (tgcn_pack_rows_bf16) into a zero-tailed (q, n_c + 1, N) buffer; both contractions are
+    tgcn_cheb_wgrad_bf16"""
+    q, n, Crow = x3.shape
+    N = g.shape[2]
+    dW0 = cheb_wgrad_bf16([x3.view(q * n, Crow)], g.view(q * n, N))
+    if len(terms) == 1:
+        return dW0
+    g_c = torch.empty((q, plan.n_c + 1, N), dtype=BF16, device=g.device)
+    g_c[:, plan.n_c].zero_()
+    rows64 = plan.rows64()
+    for b in range(q):
+        pack_rows_bf16(g[b], rows64, g_c[b, : plan.n_c])
+    rest = cheb_wgrad_bf16([t.view(q * (plan.n_c + 1), Crow) for t in terms[1:]], g_c.view(q * (plan.n_c + 1), N))
+    return torch.cat([dW0, rest])
+
+
 def _working_weight_bf16(fold, W):
     """the bf16 weight in the kernels' basis: the fold of the dense-L classes (coefficients +-1 / +-2) runs in fp32 on the upcast weight and
     is rounded to bf16 once"""
@@ -1527,7 +1641,9 @@ def _forward_pf_bf16(op, x3, Wt, b, bias_kind, mode):
 class ChebLayerBf16Fn(torch.autograd.Function):
     """The layer with bf16 parameters: bf16 tensors, fp32 sums, each rounding point once (DESIGN.md "bf16 layers").  Paths (_layer_path):
     "small" -- the fp32 one-launch kernels on the upcast operands, output rounded; "project_first" -- _forward_pf_bf16; otherwise the bf16
-    hops (full size, layout 0: a compacted bf16 layer is out of scope) and tgcn_cheb_project_bf16.  Backward: dW = basis^T g on the bf16
+    hops and tgcn_cheb_project_bf16 at full size, or, for MODE_POWER on an operand with a compact plan (compact_plan_for, COMPACT_BF16),
+    compact_forward_bf16 / compact_wgrad_bf16: hop tensors for the kept vertices only, the same bits in the output (MODE_CHEBYSHEV is not
+    compacted: its left-out weight W_0 - W_2 + ... would be one more rounding point).  Backward: dW = basis^T g on the bf16
     matrix pipe (the kept basis, or recomputed with the bf16 hop), fold transposed in fp32, rounded; dx = the layer on (L^T, g, W^T) with
     fp32 adjoint hops on the fp32 output of the bf16 projection, rounded; the bias gradient is reduced in fp32.  The small path's backward
     is the fp32 layer_backward on the upcast operands, each gradient rounded."""
@@ -1543,19 +1659,25 @@ class ChebLayerBf16Fn(torch.autograd.Function):
         fold = _power_fold(mode, W)
         path = _layer_path(op, q, n, Crow, N, K, mode, compact=False)
         ctx.basis = None
+        plan = None
+        if path.kind == "hops" and mode == MODE_POWER and COMPACT_BF16:
+            plan = compact_plan_for(op, mode, K, q, n, Crow, N)
         if path.kind == "small":
             out = cheb_forward_small(op, x3.float(), W.float(), fold, None if b is None else b.float(), bias_kind, mode).to(BF16)
         else:
             Wt = _working_weight_bf16(fold, W)
             if path.kind == "project_first":
                 out = _forward_pf_bf16(op, x3, Wt, b, bias_kind, mode)
+            elif plan is not None:
+                keep = bool(grad_mode and ctx.needs_input_grad[1] and K * q * (plan.n_c + 1) * Crow * 2 <= KEEP_BASIS_BYTES)
+                out, ctx.basis = compact_forward_bf16(plan, x3, Wt.contiguous(), b, bias_kind, keep=keep)
             else:
                 terms = _basis_bf16(op, x3, K, mode)
                 out = cheb_project_bf16([t.view(q * n, Crow) for t in terms], Wt, b, bias_kind, n).view(q, n, N)
                 if grad_mode and ctx.needs_input_grad[1] and K * x3.numel() * 2 <= KEEP_BASIS_BYTES:
                     ctx.basis = terms
         ctx.save_for_backward(x3, W)
-        ctx.op, ctx.mode, ctx.bias_kind, ctx.fold, ctx.path = op, mode, bias_kind, fold, path
+        ctx.op, ctx.mode, ctx.bias_kind, ctx.fold, ctx.path, ctx.plan = op, mode, bias_kind, fold, path, plan
         ctx.bias_shape = None if bias is None else bias.shape
         return out
 
@@ -1573,7 +1695,16 @@ class ChebLayerBf16Fn(torch.autograd.Function):
             return rnd(gx), rnd(gW), rnd(gb), None, None, None, None
         g = g.to(BF16).contiguous()
         gx = gW = None
-        if needs[1]:
+        if needs[1] and ctx.plan is not None:
+            terms = ctx.basis
+            if terms is None:                                           # over KEEP_BASIS_BYTES: the same compact hops again
+                buf = torch.empty((K - 1, q, ctx.plan.n_c + 1, Crow), dtype=BF16, device=x3.device)
+                buf[:, :, ctx.plan.n_c].zero_()
+                _compact_hops_bf16(ctx.plan, x3, buf)
+                terms = [x3] + [buf[k] for k in range(K - 1)]
+            dW = compact_wgrad_bf16(ctx.plan, x3, terms, g)
+            gW = (fold_weight(fold, dW, transpose=True) if fold is not None else dW).to(BF16)
+        elif needs[1]:
             terms = ctx.basis if ctx.basis is not None else _basis_bf16(op, x3, K, mode)
             dW = cheb_wgrad_bf16([t.view(q * n, Crow) for t in terms], g.view(q * n, N))
             gW = (fold_weight(fold, dW, transpose=True) if fold is not None else dW).to(BF16)

@@ -7,7 +7,11 @@ of every row element per hop: 4 + 4 B in fp32, 2 + 2 B in bf16).  Developer tool
 
 Cases: cfg4 (sheet mesh n = 90 k, TGCNCheb_H(L, 1, 32, 5, 1200), q = 1: the project-first path) forward and forward + backward; an
 R-MAT at reduced scale (n = 2 M, nnz = 32 M, C = 64 -> 64, K = 5, 16 time steps: the hops path) forward, fp32 on the uncompacted
-operand too, so that both dtypes' hops run over the same rows."""
+operand too, so that both dtypes' hops run over the same rows.
+
+On the R-MAT case the bf16 layer is also timed on compact hop tensors against full-size ones (F.COMPACT_BF16 on / off) in the same process,
+alternating, three repeats each: median and max - min of the ms per call, the per-kind kernel times of each setting's median repeat, and
+torch.equal of the two outputs -> --compact-out (profiles/r15_bf16_compact.json).  --only-compact runs nothing else."""
 import argparse
 import collections
 import json
@@ -78,10 +82,21 @@ def main():
     ap.add_argument("--rmat-n", type=int, default=2_000_000)
     ap.add_argument("--rmat-nnz", type=int, default=32_000_000)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--compact-out", default=None)
+    ap.add_argument("--only-compact", action="store_true")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, cases={})
+    if not args.only_compact:
+        cfg4_case(args, dev, res)
+    rmat_case(args, dev, res)
+    if args.out and not args.only_compact:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
 
+
+def cfg4_case(args, dev, res):
     # cfg4: the project-first path (2 N <= C): the hops run on the fp32 projection in both dtypes
     n, row, col, val = synth.sheet_mesh(300, device=dev)
     op = GraphOperand.from_coo(n, row, col, val, dev)
@@ -102,6 +117,41 @@ def main():
     del x, W, b, op
     torch.cuda.empty_cache()
 
+
+def compact_bf16_case(args, op, x, W, b, desc):
+    """the bf16 layer with F.COMPACT_BF16 on and off, alternating, three repeats each (the yardstick is the uncompacted path of this run)"""
+    plan = op.compact_plan("rows")
+    runs = {True: [], False: []}
+    outs = {}
+    saved = F.COMPACT_BF16
+    try:
+        for rep in range(3):
+            for on in (True, False):
+                F.COMPACT_BF16 = on
+                r, _ = measure(run_layer(op, x, W, b, F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, False), args.steps, args.warmup)
+                runs[on].append(r)
+        for on in (True, False):
+            F.COMPACT_BF16 = on
+            with torch.no_grad():
+                outs[on] = F.cheb_layer(op, x, W, b, F.BIAS_VERTEX_CHANNEL, F.MODE_POWER)
+    finally:
+        F.COMPACT_BF16 = saved
+
+    def summary(rs):
+        ms = sorted(r["ms_per_call"] for r in rs)
+        mid = sorted(rs, key=lambda r: r["ms_per_call"])[1]
+        return dict(ms_per_call=[r["ms_per_call"] for r in rs], median_ms=ms[1], spread_ms=round(ms[-1] - ms[0], 4),
+                    kernel_ms_per_call=mid["kernel_ms_per_call"], launches_per_call=mid["launches_per_call"], mean_launch_ms=mid["mean_launch_ms"])
+    on, off = summary(runs[True]), summary(runs[False])
+    gain = off["median_ms"] - on["median_ms"]
+    return dict(desc=desc, plan=None if plan is None else dict(n=plan.n, n_c=plan.n_c, n_empty=plan.n_empty,
+                                                               hop_tensor_share_left_out=round(plan.n_empty / plan.n, 4)),
+                compact_bf16_on=on, compact_bf16_off=off, median_gain_ms=round(gain, 4),
+                faster_beyond_spread=bool(gain > max(on["spread_ms"], off["spread_ms"])),
+                outputs_equal=bool(torch.equal(outs[True], outs[False])))
+
+
+def rmat_case(args, dev, res):
     # R-MAT at reduced scale: the hops path, fp32 uncompacted and bf16 over the same rows
     n, row, col, val = synth.rmat(args.rmat_n, args.rmat_nnz, seed=12345, labeling="random", device=dev)
     op = GraphOperand.from_coo(n, row, col, val, dev)
@@ -111,6 +161,16 @@ def main():
     W = torch.empty(K, C, N, device=dev).uniform_(-0.056, 0.056)
     b = torch.empty(n, N, device=dev).uniform_(-0.056, 0.056)
     entry = dict(desc="R-MAT n=%d nnz=%d random labels, TGCNCheb(L,64,64,5), q=16" % (n, op.nnz))
+    if args.compact_out:
+        BF = torch.bfloat16
+        cres = dict(device=res["device"], lib_hash=res["lib_hash"], steps=args.steps, warmup=args.warmup,
+                    case=compact_bf16_case(args, op, x.to(BF), W.to(BF), b.to(BF), entry["desc"] + ", bf16 forward"))
+        print(json.dumps({"rmat_bf16_compact": cres["case"]}), flush=True)
+        os.makedirs(os.path.dirname(os.path.abspath(args.compact_out)), exist_ok=True)
+        with open(args.compact_out, "w") as f:
+            json.dump(cres, f, indent=1)
+    if args.only_compact:
+        return
     for label, dt, compact in (("float32_compact", torch.float32, True), ("float32", torch.float32, False), ("bfloat16", torch.bfloat16, False)):
         F.COMPACT = compact
         try:
@@ -126,10 +186,6 @@ def main():
         entry["bf16_over_fp32_hop_time"] = round(h16["hop_ms_per_forward"] / h32["hop_ms_per_forward"], 3)
     res["cases"]["rmat_reduced_forward"] = entry
     print(json.dumps({"rmat_reduced_forward": entry}), flush=True)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            json.dump(res, f, indent=1)
 
 
 if __name__ == "__main__":
