@@ -448,6 +448,28 @@ int tgcn_cheb_project_series_stream_pos_bf16(void* stream, int64_t S, int64_t n_
                                              int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int64_t* pos, int32_t dilation);
 int tgcn_series_stream_advance(void* stream, int64_t* pos, int32_t Tc, int32_t C);
 
+/* A window step on the streaming state ("Window step"): the stream entries' chunk, ring and position at dilation 1, with
+ * only every stride-th window projected.  pos == NULL: head is the host's (0 <= head < C); pos non-null: the _pos entries' device position
+ * {head, seen} and defensive read (the head argument is unused).  win_off (0 <= win_off < stride) is the chunk row at which the chunk's
+ * first window ends -- (-seen) mod stride for a chunk that starts at absolute row seen -- m = win_off < Tc ? (Tc - win_off - 1)/stride + 1 : 0
+ * windows end inside the chunk, out is (S, n, m, N), and window r ends at chunk row win_off + r*stride:
+ *   out[(s, i, r), :] = sum_k sum_{h, c} row[k, s, i, win_off + r*stride - (H-1) + h][c] . W[k, h*f + c, :] + bias
+ * with rows t < 0 from the ring's slot (head + t + C) mod C: the rows [(seen + win_off)/stride, ... + m) of the _conv entry on the whole
+ * stack at pads (H-1, 0), as_series = 1 and the same stride, bit-identical to them.  Launches, sequential on the stream: the GEMM if
+ * m > 0; the stream entries' ring update if H > 1 (the ring keeps EVERY row, not every stride-th); tgcn_series_stream_advance's kernel
+ * if pos is non-null.  m == 0 admits out == NULL.  H == 1 is admitted: C = 0, ring may be NULL, no update.  stride == 1 (win_off == 0)
+ * makes the launches of the entries above at dilation 1.
+ * Planned with the step: tgcn_series_conv_plan(H, f, N, vec, stride) / _bf16 (TGCN_ERR_UNSUPPORTED where it refuses).
+ * TGCN_ERR_INVALID: stride < 1, win_off outside [0, stride), and everything the stream entries refuse (the head rule only when pos is
+ * NULL and H > 1).  Nothing is launched on either error; the entries do not synchronise and do not allocate. */
+int tgcn_cheb_project_series_stream_strided_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                                                int64_t ring_ld, int32_t head, int64_t* pos, int32_t stride, int32_t win_off);
+int tgcn_cheb_project_series_stream_strided_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                 const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                                 int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int64_t* pos,
+                                                 int32_t stride, int32_t win_off);
+
 /* One streaming step in ONE launch, for operands that fit in LDS ("One launch per step"; fp32): the K - 1 hops on the
  * chunk's rows, the stream entry's projection and its ring update, out of LDS.  chunk (S, n, Tc*f) is the INPUT of the layer in the operand's
  * labels (not a hop stack: the terms are made here, mode 0 the monomials P_k = A P_{k-1}, mode 1 Chebyshev T_k = 2 A T_{k-1} - T_{k-2}); W

@@ -172,6 +172,11 @@ SIGNATURES = {
     "tgcn_cheb_project_series_stream_pos_bf16": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64,
                                                            _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),
     "tgcn_series_stream_advance": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
+    "tgcn_cheb_project_series_stream_strided_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                                              _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32]),
+    "tgcn_cheb_project_series_stream_strided_bf16": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                                               C.c_int64, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32,
+                                                               C.c_int32]),
     "tgcn_cheb_stream_small_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                               C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "tgcn_cheb_stream_small_f32": (C.c_int, [_P, C.POINTER(CsrStruct), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

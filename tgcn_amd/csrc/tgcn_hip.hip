@@ -1277,7 +1277,8 @@ static void series_dilated_tiles(int32_t nwin, int32_t dil, int32_t* tpp, int32_
 
 // stride >= 2 takes the STRIDED instantiations; stride 1 (the input gradient's phases included) the ones without a step; dil >= 2 (at step 1)
 // the DILATED ones, planned as step 1
-// carry (step 1, the stream entries): the CARRY instantiations, which stage the time rows before the chunk from p.ring
+// carry (the stream entries): the CARRY instantiations, which stage the time rows before the chunk from p.ring -- at step 1 (dilated or
+// not), or STRIDED && CARRY for a window step on a chunk (the _stream_strided entry, p.win_off)
 static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1, int dil = 1,
                               bool carry = false) {
   p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
@@ -1304,7 +1305,8 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
   do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_, DIL_, ##__VA_ARGS__); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_, DIL_, ##__VA_ARGS__);   \
        else TGCN_SERIES_GEMM(4, VEC_, STR_, DIL_, ##__VA_ARGS__); } while (0)
   if (carry) {
-    if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, true); else TGCN_SERIES_GEMM_NT(false, false, true, true); }
+    if (stride > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, true, false, true); else TGCN_SERIES_GEMM_NT(false, true, false, true); }
+    else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, true); else TGCN_SERIES_GEMM_NT(false, false, true, true); }
     else { if (vec) TGCN_SERIES_GEMM_NT(true, false, false, true); else TGCN_SERIES_GEMM_NT(false, false, false, true); }
   } else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true); else TGCN_SERIES_GEMM_NT(false, false, true); }
   else if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, false); else TGCN_SERIES_GEMM_NT(false, false, false); }
@@ -1497,6 +1499,67 @@ int tgcn_cheb_project_series_stream_pos_f32(void* stream, int64_t S, int64_t n_v
   if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, 0, pos,
                                           dilation, "project_series_stream_pos")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pos_f32");
+  return TGCN_OK;
+}
+
+// ---- a window step on the streaming state: the chunk's windows end at chunk rows win_off + r * stride (DESIGN.md 3.10 "Window step")
+// What the two _stream_strided entries check before anything is launched: the step and its phase, then the stream entries' rules at
+// dilation 1 (head only where the host's head is used and a ring exists); H == 1 is admitted and keeps no ring (C = 0).
+// *m_out: windows that end inside the chunk; *sc_out: the step the kernel runs at, clamped like the _conv entries' (a step above the
+// padded chunk leaves one window, and 32 * step stays a 32-bit number).
+static int series_stream_strided_check(int64_t S, int64_t n, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K, int64_t ring_ld, int32_t head,
+                                       bool device_pos, int32_t stride, int32_t win_off, int32_t* C_out, int32_t* m_out, int32_t* sc_out) {
+  if (stride < 1 || win_off < 0 || win_off >= stride || Tc < 1 || H < 1) return TGCN_ERR_INVALID;
+  int32_t C = 0;
+  if (H == 1) { if (!series_conv_shape_ok(S, n, Tc, f, 1, N, K, 1, 0, 0)) return TGCN_ERR_INVALID; }
+  else if (series_stream_check(S, n, Tc, f, H, N, K, 1, ring_ld, device_pos ? 0 : head, &C)) return TGCN_ERR_INVALID;
+  *C_out = C;
+  *m_out = win_off < Tc ? (Tc - win_off - 1) / stride + 1 : 0;
+  *sc_out = series_conv_stride(Tc, stride, C, 0);
+  return TGCN_OK;
+}
+
+int tgcn_cheb_project_series_stream_strided_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
+                                                int64_t ring_ld, int32_t head, int64_t* pos, int32_t stride, int32_t win_off) {
+  const char* who = "project_series_stream_strided";
+  int32_t C = 0, m = 0, sc = 1;
+  if (series_stream_strided_check(S, n_vertices, Tc, f, H, N, K, ring_ld, head, pos != nullptr, stride, win_off, &C, &m, &sc) || !stack || !W ||
+      (m > 0 && !out) || (C > 0 && !ring))
+    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (stride == 1 && C > 0) {        // step 1 on a ring: the stream entries' own launches
+    if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, pos ? 0 : head,
+                                            pos, 1, who)) return rc;
+    TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_strided_f32");
+    return TGCN_OK;
+  }
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = n_vertices, Tf = (int64_t)Tc * f;
+  // 16-byte staging and copies: the stack's rule, and a ring that keeps it
+  const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0) && (C == 0 || ((ring_ld % 4 == 0) && (((uintptr_t)ring & 15) == 0)));
+  int hc = 0;
+  if (!series_gemm_lds(H, f, series_gemm_nt(N), vec, sc, &hc))       // the plan's refusal comes before the first launch, windows or none
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, f);
+  if (m > 0) {
+    if (int drc = check_pointer_device(out, st, who)) return drc;
+    SeriesGemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.src = stack; p.W = W; p.bias = bias; p.out = out;
+    p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
+    p.o_ss = n * (int64_t)m * N; p.o_is = (int64_t)m * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, m, N)
+    p.n = n; p.Tin = Tc; p.padl = C; p.nwin = m; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
+    if (C > 0) {
+      p.ring = ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
+      p.win_off = win_off;
+    } else {       // one tap reads no row before the chunk: the chunk from row win_off on through the instantiations without a ring
+      p.src = stack + (int64_t)win_off * f; p.Tin = Tc - win_off;
+    }
+    if (int rc = series_gemm_launch(st, p, S, vec, who, sc, 1, C > 0)) return rc;
+  }
+  if (C > 0) series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, vec, Tc, C, head, pos);
+  if (pos) series_stream_advance_launch(st, pos, Tc, C);
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_strided_f32");
   return TGCN_OK;
 }
 
@@ -1761,8 +1824,9 @@ static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int6
   do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                                 \
        else if (NT == 2) TGCN_SERIES_GEMM_B(2, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                            \
        else TGCN_SERIES_GEMM_B(4, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__); } while (0)
-  if (carry) {          // the stream entries: bf16 out, step 1, the time rows before the chunk from p.ring
-    if (dil > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true, true); }
+  if (carry) {          // the stream entries: bf16 out, the time rows before the chunk from p.ring (a window step: STRIDED && CARRY)
+    if (stride > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16, false, true); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16, false, true); }
+    else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true, true); }
     else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, false, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, false, true); }
   } else if (dil > 1) {        // dilated taps at step 1: the forward, and the input gradient in one launch
     if (out_f32) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, true); else TGCN_SERIES_GEMM_B_NT(false, false, float, true); }
@@ -1876,6 +1940,54 @@ int tgcn_cheb_project_series_stream_pos_bf16(void* stream, int64_t S, int64_t n_
   if (int rc = project_series_stream_bf16_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, out, ring,
                                                ring_ld, 0, pos, dilation, "project_series_stream_pos_bf16")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pos_bf16");
+  return TGCN_OK;
+}
+
+// The bf16 _stream_strided entry: tgcn_cheb_project_series_stream_strided_f32's contract on bf16 tensors with a row leading dimension
+int tgcn_cheb_project_series_stream_strided_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                 const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                                 int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int64_t* pos,
+                                                 int32_t stride, int32_t win_off) {
+  const char* who = "project_series_stream_strided_bf16";
+  int32_t C = 0, m = 0, sc = 1;
+  if (series_stream_strided_check(S, n_vertices, Tc, f, H, N, K, ring_ld, head, pos != nullptr, stride, win_off, &C, &m, &sc) || !stack || !W ||
+      (m > 0 && !out) || (C > 0 && !ring) || !series_stack_ld_ok(Tc, f, stack_ld))
+    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (stride == 1 && C > 0) {        // step 1 on a ring: the stream entries' own launches
+    if (int rc = project_series_stream_bf16_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, out, ring,
+                                                 ring_ld, pos ? 0 : head, pos, 1, who)) return rc;
+    TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_strided_bf16");
+    return TGCN_OK;
+  }
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
+  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "%s: dtype code %d", who, bias_dtype);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = n_vertices;
+  const bool vec = (f % 8 == 0) && (stack_ld % 8 == 0) && (((uintptr_t)stack & 15) == 0) &&
+                   (C == 0 || ((ring_ld % 8 == 0) && (((uintptr_t)ring & 15) == 0)));
+  int hc = 0;
+  if (!series_gemm_bf16_lds(H, f, series_gemm_nt(N), vec, sc, &hc))       // the plan's refusal comes before the first launch
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, f);
+  if (m > 0) {
+    if (int drc = check_pointer_device(out, st, who)) return drc;
+    SeriesGemmBf16Params p;
+    memset(&p, 0, sizeof(p));
+    p.src = (const hbf16*)stack; p.W = (const hbf16*)W; p.bias = bias; p.out = out;
+    p.src_ks = S * n * stack_ld; p.src_ss = n * stack_ld; p.src_is = stack_ld; p.src_ts = f;
+    p.o_ss = n * (int64_t)m * N; p.o_is = (int64_t)m * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, m, N)
+    p.n = n; p.Tin = Tc; p.padl = C; p.nwin = m; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
+    p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
+    if (C > 0) {
+      p.ring = (const hbf16*)ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
+      p.win_off = win_off;
+    } else {       // one tap: the chunk from row win_off on through the instantiations without a ring
+      p.src = (const hbf16*)stack + (int64_t)win_off * f; p.Tin = Tc - win_off;
+    }
+    if (int rc = series_gemm_bf16_launch(st, p, S, vec, false, who, sc, 1, C > 0)) return rc;
+  }
+  if (C > 0) series_ring_update_launch(st, stack, ring, K * S * n, stack_ld, ring_ld, f, 2, vec, Tc, C, head, pos);
+  if (pos) series_stream_advance_launch(st, pos, Tc, C);
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_strided_bf16");
   return TGCN_OK;
 }
 

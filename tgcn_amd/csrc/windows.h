@@ -32,6 +32,7 @@ struct SeriesGemmParams {
   int64_t ring_ks, ring_ss, ring_is;
   int32_t C, head;                  // CARRY only: slots of the ring, slot of its oldest row
   const int64_t* pos;               // CARRY only: non-null -> the slot of the oldest row is read from pos[0] in device memory (head is ignored)
+  int32_t win_off;                  // STRIDED && CARRY only: the chunk row at which window 0 ends (window r ends at win_off + r * stride)
 };
 
 constexpr int kSgWin = 32;    // windows per wave
@@ -74,6 +75,10 @@ __host__ __device__ constexpr int series_ws_stride(int NT) { return (NT * 16) % 
 // wave-uniform load per workgroup, before any store.  The host cannot check a device value without a synchronisation, so the loaded value is
 // used only if 0 <= value < C and 0 is taken otherwise (one compare): whatever that memory holds, head + t + C stays in [0, 2C) and no ring
 // access leaves the ring.  Only the source of head differs between the two forms.
+// STRIDED && CARRY (a window step on a chunk): window r of the chunk ENDS at chunk row win_off + r * stride, 0 <= win_off < stride -- the
+// phase of the chunk's first row in the recording -- so t0 gains win_off and, win_off being >= 0, t >= -C still holds.  The STRIDED staging
+// already forms the time row t of every staged element; a row -C <= t < 0 takes the ring's slot head + t + C (mod C) as above.  lst, the
+// row padding and its bank rule, the A offsets r * lst, the regimes and the epilogue are the STRIDED form's.
 __device__ __forceinline__ int series_ring_head(const int64_t* pos, int head, int C) {
   if (!pos) return head;
   const int64_t v = pos[0];
@@ -90,7 +95,6 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
   const int lst = STRIDED ? p.lst : 1;          // span rows between consecutive windows
   float* span = sg_lds + kSgKT * NS + wave * (int)(STRIDED ? series_span_floats(p.HC, p.f, VEC, p.stride) : series_span_floats(p.HC, p.f, VEC));
   static_assert(!(STRIDED && DILATED), "a window step with dilated taps is not built");
-  static_assert(!(STRIDED && CARRY), "a carried ring with a window step is not built");
   const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
   bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
@@ -120,7 +124,8 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
     for (int hc0 = 0; hc0 < p.H; hc0 += p.HC) {
       const int hcn = min(p.HC, p.H - hc0);
       const int rows = (kSgWin - 1) * lst + hcn,
-                t0 = DILATED ? ph - p.padl + (w0 + hc0) * p.dil : (STRIDED ? w0 * p.stride : w0) + hc0 - p.padl;
+                t0 = DILATED ? ph - p.padl + (w0 + hc0) * p.dil
+                             : (STRIDED ? w0 * p.stride + (CARRY ? p.win_off : 0) : w0) + hc0 - p.padl;
       // ---- this wave's span: time rows t0 .. t0 + rows - 1 (zeros outside the series, and for a wave without a tile)
       if constexpr (STRIDED) {
         // span row tr = wr * lst + hh holds time row t0 + wr * stride + hh; rows hh >= hcn lie between two windows (lst == HC > hcn): zeros
@@ -131,9 +136,17 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
           const int wr = tr / lst, hh = tr - wr * lst;
           const int t = t0 + wr * p.stride + hh;
           const bool ok = live && tr < rows && hh < hcn && t >= 0 && t < p.Tin;
+          bool carried = false;
+          int slot = 0;
+          if constexpr (CARRY) {
+            carried = live && tr < rows && hh < hcn && t < 0 && t >= -p.C;
+            slot = head + t + p.C;
+            if (slot >= p.C) slot -= p.C;
+          }
           if constexpr (VEC) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (ok) v = *reinterpret_cast<const float4*>(base + (int64_t)t * p.src_ts + cu * 4);
+            if constexpr (CARRY) { if (carried) v = *reinterpret_cast<const float4*>(rbase + (int64_t)slot * p.f + cu * 4); }
             float* d = span + tr * fp + cu * 4;
             if (fp & 1) { d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w; }      // odd rows: 4-byte aligned only
             else {
@@ -141,7 +154,9 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
               reinterpret_cast<float2*>(d)[1] = make_float2(v.z, v.w);
             }
           } else {
-            span[e] = ok ? base[(int64_t)t * p.src_ts + cu] : 0.f;
+            float v = ok ? base[(int64_t)t * p.src_ts + cu] : 0.f;
+            if constexpr (CARRY) { if (carried) v = rbase[(int64_t)slot * p.f + cu]; }
+            span[e] = v;
           }
         }
       } else if constexpr (VEC) {

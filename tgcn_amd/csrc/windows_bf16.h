@@ -45,6 +45,7 @@ struct SeriesGemmBf16Params {
   int64_t ring_ks, ring_ss, ring_is;
   int32_t C, head;
   const int64_t* pos;               // CARRY only (windows.h): non-null -> head is read from pos[0], series_ring_head's rule
+  int32_t win_off;                  // STRIDED && CARRY only (windows.h): the chunk row at which window 0 ends
 };
 
 __host__ __device__ inline int series_bf16_row_elems(int f, int lst) {
@@ -64,6 +65,7 @@ __host__ __device__ inline int64_t series_bf16_span_elems(int hc, int f, bool ve
 // t = (q - padl) + u * dil; span, bank rule and A reads are the step-1 form's.
 // CARRY: series_gemm_kernel's ring staging (windows.h) -- a time row t < 0 comes from slot head + t + C (mod C) of the ring; a pure load,
 // the bf16 values of the ring reach the span as they are.  head from the struct or, p.pos non-null, from device memory (series_ring_head).
+// STRIDED && CARRY: a window step on a chunk (windows.h) -- t0 gains p.win_off, the staging below is shared by every form.
 template <int NT, bool VEC8, bool STRIDED, typename OutT, bool DILATED = false, bool CARRY = false>
 __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGemmBf16Params p) {
   constexpr int NW = NT * 16;
@@ -76,7 +78,6 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
   hbf16* span = Ws + NW * kPbLd + wave * (int)series_bf16_span_elems(p.HC, p.f, VEC8, stride);
   const uint16_t* span16 = reinterpret_cast<const uint16_t*>(span);
   static_assert(!(STRIDED && DILATED), "a window step with dilated taps is not built");
-  static_assert(!(STRIDED && CARRY), "a carried ring with a window step is not built");
   const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
   bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
     const hbf16* __restrict__ rbase = CARRY ? p.ring + term * p.ring_ks + s * p.ring_ss + iv * p.ring_is : nullptr;
     for (int hc0 = 0; hc0 < p.H; hc0 += p.HC) {
       const int hcn = min(p.HC, p.H - hc0);
-      const int rows = (kSgWin - 1) * lst + hcn, t0 = DILATED ? ph - p.padl + (w0 + hc0) * p.dil : w0 * stride + hc0 - p.padl;
+      const int rows = (kSgWin - 1) * lst + hcn, t0 = DILATED ? ph - p.padl + (w0 + hc0) * p.dil : w0 * stride + (STRIDED && CARRY ? p.win_off : 0) + hc0 - p.padl;
       // ---- this wave's span: span row tr = wr * lst + hh holds time row t0 + wr * stride + hh; rows hh >= hcn lie between two windows
       // (lst == HC > hcn), rows outside the series and the span of a wave without a tile are zeros
       const int fq = VEC8 ? p.f >> 3 : p.f;                  // staged units (8 elements / 1 element) per time row

@@ -1836,10 +1836,12 @@ class SeriesStreamState:
     operand, dtype, (S, n, f, K, H) and dilation; updated in place by every call.  H == 1 keeps no ring (C == 0, ring None).
     capturable=True keeps the position on the device -- pos, an int64 tensor {head, seen} next to the ring, read by the kernels and moved
     by a launch of its own -- so that one step captured into a hipGraph can be replayed for the whole recording (GraphedStream).  head and
-    seen then READ pos: each read synchronises with the device, so leave them alone between the steps of a hot loop."""
+    seen then READ pos: each read synchronises with the device, so leave them alone between the steps of a hot loop.
+    stride is the window step the state was made for (cheb_time_stream(..., stride=s)): the ring is the same -- every row, not every s-th --
+    and seen counts INPUT rows; the step only says which windows a chunk returns, so a state serves one step."""
 
-    def __init__(self, op, dtype, S, n, f, K, H, dilation, device, capturable=False):
-        self.op, self.dtype, self.dilation = op, dtype, int(dilation)
+    def __init__(self, op, dtype, S, n, f, K, H, dilation, device, capturable=False, stride=1):
+        self.op, self.dtype, self.dilation, self.stride = op, dtype, int(dilation), int(stride)
         self.S, self.n, self.f, self.K, self.H = int(S), int(n), int(f), int(K), int(H)
         self.C = (self.H - 1) * self.dilation
         self.ring_ld = self.C * self.f      # f % 4 == 0 (bf16: 8) makes it a multiple of the 16-byte staging unit; any other f stages narrow
@@ -1867,12 +1869,15 @@ class SeriesStreamState:
         self._head = self._seen = 0
         return self
 
-    def mismatch(self, dtype, S, n, f, K, H, dilation):
-        """None when the state was made for this call's dtype, shape and dilation, else what differs (the operand is cheb_time_stream's check)"""
+    def mismatch(self, dtype, S, n, f, K, H, dilation, stride=1):
+        """None when the state was made for this call's dtype, shape, dilation and stride, else what differs (the operand is
+        cheb_time_stream's check)"""
         if self.dtype != dtype:
             return "dtype %s, the call is %s" % (self.dtype, dtype)
         if self.dilation != dilation:
             return "dilation %d, the call has %d" % (self.dilation, dilation)
+        if self.stride != stride:
+            return "stride %d, the call has %d" % (self.stride, stride)
         if (self.S, self.n, self.f, self.K, self.H) != (S, n, f, K, H):
             return "(S, n, f, K, H) = %s, the call has %s" % ((self.S, self.n, self.f, self.K, self.H), (S, n, f, K, H))
         return None
@@ -1891,20 +1896,30 @@ def stream_is_capturing():
     return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
 
 
+def stream_windows(seen, Tc, stride):
+    """(m, off) of a chunk of Tc time rows behind `seen` rows at window step `stride`: window j of the causal series ends at absolute row
+    j * stride, so the chunk returns the m = ceil((seen + Tc) / stride) - ceil(seen / stride) windows j with seen <= j * stride < seen + Tc,
+    the first of them at chunk row off = (-seen) mod stride.  Over the chunks of a recording of T rows the m add up to (T - 1) // stride + 1."""
+    return -(-(seen + Tc) // stride) - -(-seen // stride), (-seen) % stride
+
+
 @_on_device
 def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state):
     """one chunk (S, n, Tc, f) in the operand's labels through the ring of `state`: plan query, K-1 hops on rows of Tc*f, the stream entry (the
     projection and the ring update), head and seen moved; H == 1: the _conv entry on the chunk.  A capturable state runs the _pos entries,
-    which read the head from state.pos and move it on the device (H == 1: the _conv entry, then tgcn_series_stream_advance)"""
+    which read the head from state.pos and move it on the device (H == 1: the _conv entry, then tgcn_series_stream_advance).
+    state.stride > 1: the plan at that step and ONE call of the _stream_strided entry (H == 1 included) with the host's head or the device
+    position, the step and win_off; out is (S, n, m, N) (stream_windows), empty when no window ends inside the chunk."""
     L = _lib.lib()
     S, n, Tc, f = chunk.shape
     K, H, _, N = weight_khfg.shape
     bf16 = state.dtype == BF16
+    step = state.stride
     hc, lds = C.c_int32(0), C.c_int32(0)
     if bf16:
-        _lib.check(L.tgcn_series_conv_plan_bf16(H, f, N, int(f % 8 == 0), 1, C.byref(hc), C.byref(lds)))
+        _lib.check(L.tgcn_series_conv_plan_bf16(H, f, N, int(f % 8 == 0), step, C.byref(hc), C.byref(lds)))
     else:
-        _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), 1, C.byref(hc), C.byref(lds)))
+        _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), step, C.byref(hc), C.byref(lds)))
     W = weight_khfg.to(state.dtype).contiguous().view(K, H * f, N)
     fold = _power_fold(mode, W)
     Wt = _working_weight_bf16(fold, W) if bf16 else _working_weight(fold, W)      # folded on every call, as forward_series does
@@ -1919,10 +1934,21 @@ def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state):
     else:
         x3 = _aligned_input(chunk.float().contiguous().view(S, n, Tf))
         stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)
-    out = torch.empty((S, n, Tc, N), dtype=state.dtype, device=x3.device)
+    # a capturable state takes only chunks of Tc % step == 0 (stream_precheck): off = 0 and m = Tc / step whatever the device position holds
+    m, off = (Tc, 0) if step == 1 else ((Tc // step, 0) if state.capturable else stream_windows(state.seen, Tc, step))
+    out = torch.empty((S, n, m, N), dtype=state.dtype, device=x3.device)
     b = bias.to(state.dtype).contiguous() if bias is not None else None
     head = (_lib.stream_ptr(), S, n, Tc, f, H, N, K, _lib.ptr(stack))
     where = _lib.ptr(state.pos) if state.capturable else state.head      # the ring's position: device memory, or the host's scalar
+    if step > 1:
+        tail = (_lib.ptr(out) if m else None, _lib.ptr(state.ring), state.ring_ld, 0 if state.capturable else state.head,
+                _lib.ptr(state.pos) if state.capturable else None, step, off)
+        if bf16:
+            _lib.check(L.tgcn_cheb_project_series_stream_strided_bf16(*head, ld, _lib.ptr(Wt), _lib.ptr(b), _lib.DTYPE_BF16, bias_kind, *tail))
+        else:
+            _lib.check(L.tgcn_cheb_project_series_stream_strided_f32(*head, _lib.ptr(Wt), _lib.ptr(b), bias_kind, *tail))
+        state.advance(Tc)
+        return out
     if bf16:
         mid = (ld, _lib.ptr(Wt), _lib.ptr(b), _lib.DTYPE_BF16, bias_kind)
         if state.C:
@@ -1988,9 +2014,13 @@ def _stream_chunk_fused(chunk, weight_khfg, bias, op, mode, bias_kind, state):
     return out
 
 
-def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream", capturable=False, fused=False):
+def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream", capturable=False, fused=False, stride=1):
     """Everything cheb_time_stream refuses that does not need the operand -- the modules run it before they build one.
-    -> (dtype, (S, n, f, K, H), the dilation the call runs at)"""
+    -> (dtype, (S, n, f, K, H), the dilation the call runs at)
+    stride: an integer >= 1; stride > 1 is refused together with dilation > 1 (series_geometry's rule), with fused=True (the one-launch
+    step has no window step; "auto" takes the unfused path), with a state made for another stride, and on a capturable state for a chunk
+    with Tc % stride != 0 -- a captured step needs a static output shape, and chunks of whole steps keep off = 0 and m = Tc / stride
+    whatever the device position holds (a shape rule: nothing is read from the device)."""
     dt = param_dtype(weight, bias, who)
     if fused is not False and fused is not True and fused != "auto":
         raise _lib.TgcnError("%s: fused is False, True or \"auto\", got %r" % (who, fused))
@@ -2009,7 +2039,11 @@ def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream"
     K, H, N = weight.shape[0], weight.shape[1], weight.shape[-1]
     if Tc < 1:
         raise _lib.TgcnError("%s: a chunk holds at least one time row, got %s" % (who, tuple(chunk.shape)))
-    series_geometry(Tc, H, 1, "causal", who, dilation)       # the dilation's rule; stride 1 and causal padding are the only geometry
+    series_geometry(Tc, H, stride, "causal", who, dilation)  # the dilation's and the step's rules (not both above 1); causal padding is the only one
+    stride = int(stride)
+    if stride > 1 and fused is True:
+        raise _lib.TgcnError("%s: fused=True has no window step (stride=%d) -- the one-launch step runs at stride 1 (fused=False or \"auto\")"
+                             % (who, stride))
     dilation = series_dilation(H, dilation)
     if dt == BF16 and chunk.dtype != BF16:
         raise _lib.TgcnError("%s: the parameters are bfloat16 but the chunk is %s -- cast it once (chunk.to(torch.bfloat16))" % (who, chunk.dtype))
@@ -2019,12 +2053,15 @@ def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream"
     if state is not None:
         if not isinstance(state, SeriesStreamState):
             raise _lib.TgcnError("%s: state is a SeriesStreamState or None, got %s" % (who, type(state).__name__))
-        bad = state.mismatch(dt, S, n, f, K, H, dilation)
+        bad = state.mismatch(dt, S, n, f, K, H, dilation, stride)
         if bad:
             raise _lib.TgcnError("%s: the state was made for %s -- one state per layer and recording batch" % (who, bad))
         if capturable and not state.capturable:
             raise _lib.TgcnError("%s: capturable=True with a state that keeps its head on the host -- the state's kind rules; start the "
                                  "recording with state=None, capturable=True" % who)
+    if stride > 1 and (state.capturable if state is not None else capturable) and Tc % stride:
+        raise _lib.TgcnError("%s: a capturable state with stride=%d takes chunks of whole steps (Tc %% stride == 0), got Tc = %d -- a captured "
+                             "step needs a static output shape" % (who, stride, Tc))
     # a head kept on the host is a launch argument: a captured step would replay the head of the capture on every chunk
     if (H - 1) * dilation > 0 and not (state.capturable if state is not None else capturable) and stream_is_capturing():
         raise _lib.TgcnError("%s: the stream is capturing a hipGraph and the state keeps its ring position on the host, which a replay "
@@ -2032,7 +2069,7 @@ def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream"
     return dt, (S, n, f, K, H), dilation
 
 
-def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=None, dilation=1, capturable=False, fused=False):
+def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=None, dilation=1, capturable=False, fused=False, stride=1):
     """The causal streaming layer on the NEXT Tc time rows of S recordings (inference only): chunk (S, n, Tc) with weight (K, H, N), or
     (S, n, Tc, f) with weight (K, H, f, N) -> (out (S, n, Tc, N) contiguous, state).  out equals rows [state.seen, state.seen + Tc) of
     cheb_time_windows(op, whole, ..., as_series=True, padding="causal", dilation=dilation) on the whole series: the layer keeps the last
@@ -2049,8 +2086,20 @@ def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=
     recording) on the same state -- fused and unfused calls may alternate within a recording.  It asks the plan first and raises TgcnError
     before anything launches for bfloat16 parameters, H = 1, a non-square operand and a plan that refuses (stream_fused_supported tells).
     fused="auto" fuses where the plan accepts and Tc <= STREAM_FUSED_AUTO_MAX_TC, and is fused=False everywhere else.  The results agree to
-    rounding (the hops add their neighbours in another order), not bit for bit."""
-    dt, (S, n, f, K, H), dilation = stream_precheck(chunk, weight, bias, state, dilation, capturable=capturable, fused=fused)
+    rounding (the hops add their neighbours in another order), not bit for bit.
+    stride=s (an integer >= 1, a property of the state like the dilation) returns only the windows of cheb_time_windows(op, whole, ...,
+    as_series=True, padding="causal", stride=s) that END inside the chunk.  Window j ends at absolute row j*s, so with seen = state.seen
+    the call returns the m = ceil((seen + Tc)/s) - ceil(seen/s) windows j in [ceil(seen/s), ceil((seen + Tc)/s)), the first at chunk row
+    off = (-seen) mod s: out is (S, n, m, N), and over a recording of T rows the m add up to (T-1)//s + 1.  The hops, the ring (every
+    row, not every s-th) and the position run as at stride 1, and seen counts INPUT rows.  m may be 0 (host-head states only, e.g.
+    Tc = 1 at an odd seen with s = 2): out is then an empty (S, n, 0, N) tensor and no projection launches; a chain skips its later
+    layers for such a chunk, because an empty chunk is still refused.  A capturable state takes only chunks with Tc % s == 0 (off = 0,
+    m = Tc/s on every step: a captured step has a static shape).  TgcnError before anything launches: stride > 1 with dilation > 1, with
+    fused=True (fused="auto" runs unfused), with a state of another stride."""
+    dt, (S, n, f, K, H), dilation = stream_precheck(chunk, weight, bias, state, dilation, capturable=capturable, fused=fused, stride=stride)
+    stride = int(stride)
+    if stride > 1:
+        fused = False       # "auto": the one-launch step has no window step (True was refused above)
     if state is not None and state.op is not op:
         raise _lib.TgcnError("cheb_time_stream: the state was made for another operand -- one state per layer and graph")
     if fused is not False:
@@ -2066,12 +2115,12 @@ def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=
                      and _stream_small_plan(op, f, H, N, K, Tc, dilation, mode)[0] == 0)
     _lib.require_device(chunk, weight, bias)
     if state is None:
-        state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device, capturable=capturable)
+        state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device, capturable=capturable, stride=stride)
     with torch.no_grad():
         if chunk.dim() == 3:
             chunk, weight = chunk.unsqueeze(3), weight.unsqueeze(2)
         chunk, bias = _to_operand_labels(op, chunk, bias, bias_kind)      # the ring lives in the operand's labels
         out = (_stream_chunk_fused if fused else _stream_chunk)(chunk, weight, bias, op, mode, bias_kind, state)
-        if op.perm is not None:
+        if op.perm is not None and out.shape[2]:
             out = relabel_rows(out, op.inv_perm, op.perm).to(dt)
     return out, state

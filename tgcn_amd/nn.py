@@ -211,7 +211,7 @@ class TGCNCheb_H(_DenseLBase):
                                    F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series,
                                    stride=geom[0], padding=geom[1:3], dilation=geom[3])
 
-    def forward_stream(self, chunk, state=None, dilation=1, capturable=False, fused=False):
+    def forward_stream(self, chunk, state=None, dilation=1, capturable=False, fused=False, stride=1):
         """Additive API, inference only: the causal layer on the next Tc time rows of S recordings.  chunk (S, n, Tc) or (S, n, Tc, f) ->
         (out (S, n, Tc, g) contiguous, state); out equals rows [seen, seen + Tc) of forward_series(whole, as_series=True, padding="causal",
         dilation=dilation), seen = the time rows already passed through state (F.SeriesStreamState: the last (H-1)*dilation rows of the hop
@@ -224,14 +224,22 @@ class TGCNCheb_H(_DenseLBase):
         A state that keeps its head on the host is refused (TgcnError) while the current stream is capturing.
         fused=True runs the step in one launch on a graph that fits in LDS (float32, H >= 2; TgcnError where it cannot:
         F.stream_fused_supported), fused="auto" where that is measured to pay (F.STREAM_FUSED_AUTO_MAX_TC); the state is the same, so
-        fused and unfused calls may alternate (F.cheb_time_stream)."""
+        fused and unfused calls may alternate (F.cheb_time_stream).
+        stride=s (an integer >= 1; the state is made for one step) returns the rows of forward_series(whole, as_series=True,
+        padding="causal", stride=s) whose window ENDS inside the chunk: window j ends at absolute row j*s, so the call returns
+        m = ceil((seen + Tc)/s) - ceil(seen/s) rows, the first at chunk row off = (-seen) mod s, as (S, n, m, g); over a recording of T
+        rows the m add up to (T-1)//s + 1.  The ring still keeps every row and seen counts input rows.  m may be 0 (host-head states):
+        the call returns an empty (S, n, 0, g) tensor, and a chain skips its later layers for that chunk -- forward_stream refuses an
+        empty chunk.  A capturable state takes chunks with Tc % s == 0 only (m = Tc/s on every step, so GraphedStream's next layer sees
+        chunks of Tc/s rows).  TgcnError: stride > 1 with dilation > 1, with fused=True ("auto" runs unfused), with a state of another
+        stride."""
         _compute_dtype(self)
         chunk, W = _stream_args(self, chunk)
-        F.stream_precheck(chunk, W, self.bias, state, dilation, "TGCNCheb_H.forward_stream", capturable, fused=fused)      # refusals come before the operand is built
+        F.stream_precheck(chunk, W, self.bias, state, dilation, "TGCNCheb_H.forward_stream", capturable, fused=fused, stride=stride)      # refusals come before the operand is built
         _state_operand_check(self, state, self._operand_key(chunk.device))
         return F.cheb_time_stream(self._operand(chunk.device), chunk, W, None if self.bias is None else self.bias.reshape(-1),
                                   F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, state=state, dilation=dilation,
-                                  capturable=capturable, fused=fused)
+                                  capturable=capturable, fused=fused, stride=stride)
 
 
 def _state_operand_check(module, state, key):
@@ -518,22 +526,25 @@ class ChebTimeConv(_EdgeBase):
                                    as_series=as_series,
                                    stride=geom[0], padding=geom[1:3], dilation=geom[3])
 
-    def forward_stream(self, chunk, edge_index, edge_weight=None, state=None, dilation=1, capturable=False, fused=False):
+    def forward_stream(self, chunk, edge_index, edge_weight=None, state=None, dilation=1, capturable=False, fused=False, stride=1):
         """Additive API, inference only: TGCNCheb_H.forward_stream's contract for this class -- chunk (S, n, Tc[, f]) -> (out (S, n, Tc, g),
         state), the rows [seen, seen + Tc) of forward_series(whole, edge_index, edge_weight, as_series=True, padding="causal",
         dilation=dilation); true recurrence, per-channel bias.  The state belongs to the operand of (edge_index, edge_weight): another graph
         needs its own.  A learnable edge_weight raises TgcnError, as in forward_series.  capturable and fused: as in
-        TGCNCheb_H.forward_stream."""
+        TGCNCheb_H.forward_stream.  stride=s: as there -- the m = ceil((seen + Tc)/s) - ceil(seen/s) rows of forward_series(...,
+        padding="causal", stride=s) whose window ends inside the chunk, the first at chunk row off = (-seen) mod s, as (S, n, m, g); m may
+        be 0 (an empty tensor; a chain skips its later layers for that chunk, an empty chunk being refused); a capturable state takes
+        Tc % s == 0 only."""
         if edge_weight is not None and edge_weight.requires_grad:
             raise _lib.TgcnError("ChebTimeConv.forward_stream: learnable edge weights (edge_weight.requires_grad) are not supported -- "
                                  "streaming is inference only; detach() the weight")
         _compute_dtype(self, edge_weight)
         chunk, W = _stream_args(self, chunk)
-        F.stream_precheck(chunk, W, self.bias, state, dilation, "ChebTimeConv.forward_stream", capturable, fused=fused)      # refusals come before the operand is built
+        F.stream_precheck(chunk, W, self.bias, state, dilation, "ChebTimeConv.forward_stream", capturable, fused=fused, stride=stride)      # refusals come before the operand is built
         _state_operand_check(self, state, self._operand_key(chunk, edge_index, edge_weight))
         op = self._operand(chunk, edge_index, edge_weight)
         return F.cheb_time_stream(op, chunk, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
-                                  state=state, dilation=dilation, capturable=capturable, fused=fused)
+                                  state=state, dilation=dilation, capturable=capturable, fused=fused, stride=stride)
 
 
 # ------------------------------------------------------------------------------------ a streaming chain as one hipGraph

@@ -9,6 +9,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py --stream [--out profiles/r12_series_stream.json]
     python tools/series_bench.py --stream --graph [--include parent=FILE] [--out profiles/r13_series_stream_graph.json]
     python tools/series_bench.py --stream --fused [--include parent=FILE] [--out profiles/r14_series_stream_fused.json]
+    python tools/series_bench.py --stream --stride 2,2,2 [--repeats 3] [--include parent=FILE] [--out profiles/r16_series_stream_stride.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -35,7 +36,13 @@ next to the eager host-head step (fused=False, the code the parent commit runs) 
 sizes 1, 8 and 64: three repeats of each, events only (no launch record inside a timed region), the library launches of one step of each
 counted in a separate untimed step, and the largest relative difference of fused and eager outputs over the warm-up recording.  --include
 LABEL=FILE embeds a --stream --graph run of the parent commit (its eager_ms_per_chunk is the comparison column); default --out
-profiles/r14_series_stream_fused.json."""
+profiles/r14_series_stream_fused.json.
+--stream --stride S1,S2,S3 times that three-layer chain undilated with the window steps S1, S2, S3 (forward_stream(..., stride=s), DESIGN.md
+3.10 "Window step") at chunks of S1*S2*S3, 64 and 512 time rows, next to what a caller does without the keyword: the same chain through the
+step-1 forward_stream with every layer's output sliced out[:, :, ::s] before the next layer.  Per column: --repeats event timings of --steps
+chunks each (ms per chunk, their median and spread) and one pass with the launch record.  On a tree whose forward_stream has no `stride`
+keyword only the sliced column is timed, which is how the parent commit's file for --include LABEL=FILE is made; default --out
+profiles/r16_series_stream_stride.json."""
 import argparse
 import json
 import os
@@ -437,12 +444,85 @@ def main_stream_fused(args):
         json.dump(res, f, indent=1)
 
 
+def main_stream_stride(args):
+    import inspect
+    dev = torch.device("cuda:0")
+    steps3 = args.stride
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, repeats=args.repeats,
+               strides=list(steps3), cases={})
+    torch.manual_seed(0)
+    op = dti148(dev)
+    S, K, Hc, chans = 8, 10, 5, (1, 32, 32, 64)
+    layers = [tgcn_amd.TGCNCheb_H(op, chans[i], chans[i + 1], K, Hc).to(dev) for i in range(3)]
+    has_step = "stride" in inspect.signature(tgcn_amd.TGCNCheb_H.forward_stream).parameters
+    whole = steps3[0] * steps3[1] * steps3[2]
+
+    def repeated(fn):
+        ms = [events_ms(fn, args.steps, args.warmup) for _ in range(args.repeats)]
+        return dict(ms_per_chunk=ms, median=sorted(ms)[len(ms) // 2], spread=round(max(ms) - min(ms), 4))
+
+    for Tc in sorted({whole, -(-64 // whole) * whole, -(-512 // whole) * whole}):        # chunks of whole steps: the sliced chain's phase is 0 on every chunk
+        chunk = torch.randn(S, op.n, Tc, 1, device=dev)
+        st_states, sl_states = [None] * 3, [None] * 3
+
+        def strided_step(x=chunk):
+            h = x
+            for i, (layer, s) in enumerate(zip(layers, steps3)):
+                h, st_states[i] = layer.forward_stream(h, st_states[i], stride=s)
+                if i < 2:
+                    h = torch.relu(h)
+            return h
+
+        # without the keyword: every layer at step 1, every window projected, s - 1 of s of them dropped by the caller
+        def sliced_step(x=chunk):
+            h = x
+            for i, (layer, s) in enumerate(zip(layers, steps3)):
+                h, sl_states[i] = layer.forward_stream(h, sl_states[i])
+                h = h[:, :, ::s].contiguous()
+                if i < 2:
+                    h = torch.relu(h)
+            return h
+
+        entry = dict(desc="dti148 S=8: three causal TGCNCheb_H(., ., 10, 5) layers 1 -> 32 -> 32 -> 64 with window steps %d, %d, %d, chunks of %d "
+                          "time rows" % (steps3 + (Tc,)))
+        with torch.no_grad():
+            for _ in range(-(-64 // Tc)):
+                b = sliced_step()
+                if has_step:
+                    a = strided_step()
+                    assert a.shape == b.shape == (S, op.n, Tc // whole, chans[-1])
+                    entry["max_rel_difference"] = float((a - b).abs().max() / b.abs().max())
+            entry["step1_sliced"] = dict(repeated(sliced_step), record=timed(sliced_step, False, args.steps, args.warmup))
+            if has_step:
+                entry["strided"] = dict(repeated(strided_step), record=timed(strided_step, False, args.steps, args.warmup))
+                entry["sliced_over_strided"] = round(entry["step1_sliced"]["median"] / entry["strided"]["median"], 3)
+        res["cases"]["chain_chunk%d" % Tc] = entry
+        print(json.dumps({"chain_chunk%d" % Tc: entry}), flush=True)
+    for item in args.include:
+        label, path = item.split("=", 1)
+        with open(path) as f:
+            other = json.load(f)
+        rel = {name: round(entry["step1_sliced"]["median"] / res["cases"][name]["step1_sliced"]["median"], 3)
+               for name, entry in other["cases"].items() if name in res["cases"]}
+        res.setdefault("runs", {})[label] = dict(run=other, step1_sliced_ms_over_this_run=rel)
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r16_series_stream_stride.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
+def stride_arg(text):
+    parts = tuple(int(v) for v in text.split(","))
+    return parts[0] if len(parts) == 1 else parts
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32", help="bf16: the bfloat16 streaming cases (profiles/r10_series_bf16.json)")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--stride", type=int, default=1)
+    ap.add_argument("--stride", type=stride_arg, default=1, help="the window step; with --stream: S1,S2,S3, the three layers' steps")
+    ap.add_argument("--repeats", type=int, default=3, help="with --stream --stride: event timings per column")
     ap.add_argument("--padding", type=padding_arg, default=0)
     ap.add_argument("--conv", action="store_true", help="add the stride-4 and causal-chain cases")
     ap.add_argument("--dilation", action="store_true", help="the dilated cases (profiles/r11_series_dilation.json)")
@@ -462,6 +542,10 @@ def main():
         ap.error("--graph goes with --stream")
     if args.fused and not args.stream:
         ap.error("--fused goes with --stream")
+    if isinstance(args.stride, tuple):
+        if not args.stream or args.graph or args.fused or len(args.stride) != 3 or min(args.stride) < 1:
+            ap.error("--stride S1,S2,S3 (three steps >= 1) goes with --stream alone")
+        return main_stream_stride(args)
     if args.stream and args.fused:
         return main_stream_fused(args)
     if args.stream and args.graph:
