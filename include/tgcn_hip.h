@@ -448,6 +448,38 @@ int tgcn_cheb_project_series_stream_pos_bf16(void* stream, int64_t S, int64_t n_
                                              int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int64_t* pos, int32_t dilation);
 int tgcn_series_stream_advance(void* stream, int64_t* pos, int32_t Tc, int32_t C);
 
+/* Time chunks of the causal layer with a backward ("Time chunks"; fp32, step 1, the host's head): forward_series walks a
+ * recording chunk by chunk through the ring in both directions, so nothing of the hop stack's whole size is ever held.
+ * tgcn_cheb_project_series_stream_at_f32 is tgcn_cheb_project_series_stream_f32 writing its Tc rows into rows [out_t0, out_t0 + Tc) of
+ * an output of out_T time rows, (S, n, out_T, N) for out_as_series != 0 and (S*out_T, n, N) otherwise; only the output's strides and
+ * base differ, so on one stack and ring its rows and the ring afterwards are bit-identical to that entry's.  H == 1 is admitted: no ring
+ * (NULL, ring_ld and head unused), one launch, nothing to update.  TGCN_ERR_INVALID: out_T < 1, out_t0 < 0, out_t0 + Tc > out_T, and
+ * everything the stream entry refuses (for H == 1: the _conv entry's rules for the chunk).
+ * tgcn_cheb_series_chunk_backward_f32: both gradients of the chunk's windows.  g is the WHOLE output gradient, (S, n, g_T, N) for
+ * g_as_series != 0 and (S*g_T, n, N) otherwise, read in place from row g_t0 on with its own strides; 0 <= g_t0, g_t0 + Tc <= g_T.
+ *   G  (K, S, n, Tc*f), non-null: rows [g_t0, g_t0 + Tc) of tgcn_cheb_series_dilated_backward_f32's G on the whole g at stride 1 and pads
+ *      (C, 0), bit-identical to them -- the weight flip into the workspace and ONE launch of the sliding-window GEMM over the rows
+ *      [g_t0, min(g_T, g_t0 + Tc + C)) of g; needs W (K, H*f, N).
+ *   dW (K, H*f, N), non-null: the contribution of the windows that END in the chunk,
+ *        dW[k][h*f + c][:] = sum_{s, i, w < Tc} row[k, s, i, w - C + h*dilation][c] . g[(s, i, g_t0 + w), :]
+ *      with rows t >= 0 from stack (K, S, n, Tc*f) and rows t < 0 from the ring's slot (head + t + C) mod C, as the forward stages them;
+ *      partials per row block in the workspace, folded in block order: deterministic.  Needs stack and, for H > 1, ring.
+ *   ring non-null (H > 1): after both, the stream entries' ring update from stack; the caller then sets head = (head + Tc) mod C.
+ * G == NULL or dW == NULL (then stack and ring may be NULL: no ring is read or moved) are the one-sided forms; both NULL is refused.
+ * workspace: 16-byte aligned, tgcn_cheb_series_chunk_backward_workspace_bytes(...) bytes (0 for a shape the entry refuses).
+ * TGCN_ERR_INVALID: the stream entry's rules for the chunk (head and ring_ld where a ring is given), the place of the chunk in g, a
+ * missing pointer; TGCN_ERR_WORKSPACE; TGCN_ERR_UNSUPPORTED where the plan of the GEMM over g -- tgcn_series_conv_plan(H, N, K*f, vec, 1)
+ * -- or a grid limit refuses.  Nothing is launched on any error; the entries do not synchronise and do not allocate. */
+int tgcn_cheb_project_series_stream_at_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                           const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, int32_t out_T,
+                                           int32_t out_t0, int32_t out_as_series, float* ring, int64_t ring_ld, int32_t head, int32_t dilation);
+size_t tgcn_cheb_series_chunk_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                       int32_t dilation);
+int tgcn_cheb_series_chunk_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                        const float* stack, float* ring, int64_t ring_ld, int32_t head, const float* g, int32_t g_T,
+                                        int32_t g_t0, int32_t g_as_series, const float* W, float* G, float* dW, void* workspace,
+                                        size_t workspace_bytes, int32_t dilation);
+
 /* A window step on the streaming state ("Window step"): the stream entries' chunk, ring and position at dilation 1, with
  * only every stride-th window projected.  pos == NULL: head is the host's (0 <= head < C); pos non-null: the _pos entries' device position
  * {head, seen} and defensive read (the head argument is unused).  win_off (0 <= win_off < stride) is the chunk row at which the chunk's

@@ -172,6 +172,13 @@ SIGNATURES = {
     "tgcn_cheb_project_series_stream_pos_bf16": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64,
                                                            _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int64, _P, C.c_int32]),
     "tgcn_series_stream_advance": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
+    "tgcn_cheb_project_series_stream_at_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                                         C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64, C.c_int32, C.c_int32]),
+    "tgcn_cheb_series_chunk_backward_workspace_bytes": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                                     C.c_int32]),
+    "tgcn_cheb_series_chunk_backward_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                                      C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_size_t,
+                                                      C.c_int32]),
     "tgcn_cheb_project_series_stream_strided_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                                               _P, C.c_int32, _P, _P, C.c_int64, C.c_int32, _P, C.c_int32, C.c_int32]),
     "tgcn_cheb_project_series_stream_strided_bf16": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,

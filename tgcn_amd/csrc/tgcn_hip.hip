@@ -1456,14 +1456,28 @@ int tgcn_series_stream_advance(void* stream, int64_t* pos, int32_t Tc, int32_t C
   return TGCN_OK;
 }
 
+// A chunk's rows inside an output of out_T time rows (the _at entry): rows [out_t0, out_t0 + Tc) of (S, n, out_T, N) or (S*out_T, n, N)
+static bool series_out_slice_ok(int32_t Tc, int32_t out_T, int32_t out_t0) {
+  return out_T >= 1 && out_t0 >= 0 && (int64_t)out_t0 + Tc <= (int64_t)out_T;
+}
+static void series_out_slice(SeriesGemmParams& p, int64_t n, int32_t N, int32_t out_T, int32_t out_t0, int32_t as_series) {
+  if (as_series) { p.o_ss = n * out_T * N; p.o_is = (int64_t)out_T * N; p.o_ws = N; }      // (S, n, out_T, N)
+  else { p.o_ss = (int64_t)out_T * n * N; p.o_is = N; p.o_ws = n * N; }                     // (S, out_T, n, N)
+  p.out += (int64_t)out_t0 * p.o_ws;
+}
+
 // Both fp32 stream entries: pos null -> the host's head and two launches; pos non-null -> head read on the device (the head argument is
 // unused and passes the check as 0) and the advance as a third launch
+// out_T > 0 (the _at entry): the chunk's rows go to rows [out_t0, out_t0 + Tc) of an output of out_T time rows, in either layout -- the
+// kernel addresses its output by (o_ss, o_is, o_ws), so only the strides and the base differ; out_T == 0: the chunk-shaped (S, n, Tc, N)
 static int project_series_stream_impl(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
                                       const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
-                                      int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation, const char* who) {
+                                      int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation, const char* who, int32_t out_T = 0,
+                                      int32_t out_t0 = 0, int32_t out_as_series = 1) {
   int32_t C = 0;
   if (series_stream_check(S, n_vertices, Tc, f, H, N, K, dilation, ring_ld, head, &C) || !stack || !W || !out || !ring)
     TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (out_T && !series_out_slice_ok(Tc, out_T, out_t0)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
   if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
   if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
   hipStream_t st = (hipStream_t)stream;
@@ -1473,6 +1487,7 @@ static int project_series_stream_impl(void* stream, int64_t S, int64_t n_vertice
   p.src = stack; p.W = W; p.bias = bias; p.out = out;
   p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
   p.o_ss = n * Tc * N; p.o_is = (int64_t)Tc * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, Tc, N)
+  if (out_T) series_out_slice(p, n, N, out_T, out_t0, out_as_series);
   p.n = n; p.Tin = Tc; p.padl = C; p.nwin = Tc; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
   p.ring = ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
   // 16-byte staging and copies: the stack's rule, and a ring that keeps it
@@ -1499,6 +1514,38 @@ int tgcn_cheb_project_series_stream_pos_f32(void* stream, int64_t S, int64_t n_v
   if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, 0, pos,
                                           dilation, "project_series_stream_pos")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pos_f32");
+  return TGCN_OK;
+}
+
+// ---- time chunks of forward_series (DESIGN.md 3.10 "Time chunks"): the stream entry's chunk projected into rows [out_t0, out_t0 + Tc) of the
+// whole output, in either layout; H == 1 keeps no ring (null admitted, nothing to update) and runs the launch without one
+int tgcn_cheb_project_series_stream_at_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                           const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, int32_t out_T,
+                                           int32_t out_t0, int32_t out_as_series, float* ring, int64_t ring_ld, int32_t head, int32_t dilation) {
+  const char* who = "project_series_stream_at";
+  if (H != 1) {
+    if (out_T < 1) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+    if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, head, nullptr,
+                                            dilation, who, out_T, out_t0, out_as_series)) return rc;
+    TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_at_f32");
+    return TGCN_OK;
+  }
+  if (Tc < 1 || dilation < 1 || !series_conv_shape_ok(S, n_vertices, Tc, f, 1, N, K, 1, 0, 0) || !series_out_slice_ok(Tc, out_T, out_t0) ||
+      !stack || !W || !out)
+    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
+  const int64_t n = n_vertices, Tf = (int64_t)Tc * f;
+  SeriesGemmParams p;
+  memset(&p, 0, sizeof(p));
+  p.src = stack; p.W = W; p.bias = bias; p.out = out;
+  p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
+  p.o_gs = 0; p.ocg = N;
+  series_out_slice(p, n, N, out_T, out_t0, out_as_series);
+  p.n = n; p.Tin = Tc; p.padl = 0; p.nwin = Tc; p.H = 1; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
+  const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0);
+  if (int rc = series_gemm_launch((hipStream_t)stream, p, S, vec, who)) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_at_f32");
   return TGCN_OK;
 }
 
@@ -1773,6 +1820,109 @@ int tgcn_cheb_series_dilated_backward_f32(void* stream, int64_t S, int64_t n_ver
   if (int rc = series_backward_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, 1, pad_left,
                                     pad_right, "series_dilated_backward", dilation)) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_series_dilated_backward_f32");
+  return TGCN_OK;
+}
+
+// ---- time chunks of forward_series, backward (DESIGN.md 3.10 "Time chunks"): one chunk of Tc time rows of the causal layer's two gradients.
+// What the entry and its workspace query check: the stream entries' rules for the chunk (H == 1: no ring, C = 0), the chunk's place in the
+// whole gradient, and the input gradient's launch over g as a series of N channels (Tc + C rows of N floats inside 32 bits).
+static int series_chunk_check(int64_t S, int64_t n, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K, int32_t dil, int64_t ring_ld,
+                              int32_t head, int32_t g_T, int32_t g_t0, int32_t* C_out) {
+  if (dil < 1 || Tc < 1 || H < 1) return TGCN_ERR_INVALID;
+  int32_t C = 0;
+  if (H == 1) { if (!series_conv_shape_ok(S, n, Tc, f, 1, N, K, 1, 0, 0)) return TGCN_ERR_INVALID; }
+  else if (series_stream_check(S, n, Tc, f, H, N, K, dil, ring_ld, head, &C)) return TGCN_ERR_INVALID;
+  if (!series_out_slice_ok(Tc, g_T, g_t0)) return TGCN_ERR_INVALID;
+  if (((int64_t)Tc + C) * N >= (int64_t)INT32_MAX || ((int64_t)Tc + C) * 64 >= (int64_t)INT32_MAX) return TGCN_ERR_INVALID;
+  *C_out = C;
+  return TGCN_OK;
+}
+
+size_t tgcn_cheb_series_chunk_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                       int32_t dilation) {
+  int32_t C = 0;
+  if (dilation < 1 || H < 1) return 0;
+  if (series_chunk_check(S, n_vertices, Tc, f, H, N, K, H == 1 ? 1 : dilation, (int64_t)(H - 1) * dilation * f, 0, Tc, 0, &C)) return 0;
+  return series_backward_workspace(S * n_vertices * Tc, (int64_t)K * H * f * N);
+}
+
+int tgcn_cheb_series_chunk_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                        const float* stack, float* ring, int64_t ring_ld, int32_t head, const float* g, int32_t g_T,
+                                        int32_t g_t0, int32_t g_as_series, const float* W, float* G, float* dW, void* workspace,
+                                        size_t workspace_bytes, int32_t dilation) {
+  const char* who = "series_chunk_backward";
+  if (H == 1 && dilation >= 1) dilation = 1;      // one tap has nothing to dilate
+  int32_t C = 0;
+  // the one-sided form without a weight gradient reads and moves no ring: ring null, and ring_ld and head are then unused
+  const bool carried = ring != nullptr && H > 1;
+  if (H < 1 || dilation < 1 ||
+      series_chunk_check(S, n_vertices, Tc, f, H, N, K, dilation, carried ? ring_ld : (int64_t)(H - 1) * dilation * f, carried ? head : 0, g_T, g_t0,
+                         &C) || !g || (!G && !dW))
+    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if ((G && !W) || ((dW || carried) && !stack) || (dW && H > 1 && !ring)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (int drc = check_pointer_device(g, (hipStream_t)stream, who)) return drc;
+  const size_t need = tgcn_cheb_series_chunk_backward_workspace_bytes(S, n_vertices, Tc, f, H, N, K, dilation);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) TGCN_FAIL(TGCN_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t n = n_vertices, Tf = (int64_t)Tc * f, wf = (int64_t)K * H * f * N;
+  int64_t g_ss, g_is, g_ws;      // the WHOLE gradient's strides; the chunk's rows start g_t0 rows in
+  if (g_as_series) { g_ss = n * (int64_t)g_T * N; g_is = (int64_t)g_T * N; g_ws = N; }
+  else { g_ss = (int64_t)g_T * n * N; g_is = N; g_ws = n * N; }
+  const float* gc = g + (int64_t)g_t0 * g_ws;
+  // ---- everything that can refuse, before the first launch
+  const bool vecg = (N % 4 == 0) && (((uintptr_t)gc & 15) == 0);
+  if (G) {
+    int hc = 0;
+    const int NT = series_gemm_nt(K * f);
+    if (!series_gemm_lds(H, N, NT, vecg, 1, &hc)) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, N);
+    int32_t tpp = 0, tpv = (Tc + kSgWin - 1) / kSgWin;
+    if (dilation > 1) series_dilated_tiles(Tc, dilation, &tpp, &tpv);
+    if ((S * n * tpv + 3) / 4 > (int64_t)INT32_MAX || ((int64_t)K * f + NT * 16 - 1) / (NT * 16) > 65535)
+      TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
+  }
+  const int64_t M = S * n * Tc, rpb = series_wgrad_rows_per_block(M, wf), nblocks = (M + rpb - 1) / rpb;
+  const int64_t jtiles = ((int64_t)H * f + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
+  if (dW && (rpb + Tc >= (int64_t)INT32_MAX || rpb / Tc + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX || (N + 63) / 64 > 65535 ||
+             jtiles * tgroups > 65535))
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: weight gradient shape too large", who);
+  if (G) {      // rows [g_t0, g_t0 + Tc) of the whole input gradient: time row t sums g[t + h' * dil] Wd[h'] over the rows of g that exist
+    float* Wd = (float*)workspace;
+    { ProfScope ps(TGCN_PROF_RELAYOUT, st);
+      hipLaunchKernelGGL(series_flip_weight_kernel, dim3(grid_1d(wf)), dim3(kBlock), 0, st, W, Wd, (int)K, (int)H, (int)f, (int)N, 1); }
+    SeriesGemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.src = gc; p.W = Wd; p.bias = nullptr; p.bias_kind = 0; p.out = G;
+    p.src_ks = 0; p.src_ss = g_ss; p.src_is = g_is; p.src_ts = g_ws;
+    p.o_ss = n * Tf; p.o_is = Tf; p.o_ws = f; p.o_gs = S * n * Tf; p.ocg = f;      // columns (k, c) into the chunk-shaped (K, S, n, Tc*f)
+    const int64_t left = (int64_t)g_T - g_t0;
+    p.n = n; p.Tin = (int32_t)(left < (int64_t)Tc + C ? left : (int64_t)Tc + C); p.padl = 0; p.nwin = Tc; p.H = H; p.f = N; p.N = K * f; p.nterms = 1;
+    if (int rc = series_gemm_launch(st, p, S, vecg, who, 1, dilation)) return rc;
+  }
+  if (dW) {
+    SeriesWgradParams q;
+    memset(&q, 0, sizeof(q));
+    q.stack = stack; q.g = gc; q.partial = (float*)((char*)workspace + align_up((size_t)wf * sizeof(float), 256));
+    q.st_ks = S * n * Tf; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
+    q.M = M; q.rows_per_block = rpb; q.n = n;
+    q.Tf = (int32_t)Tf; q.f = f; q.nwin = Tc; q.J = H * f; q.N = N; q.K = K;
+    q.stride = 1; q.padl = C; q.T = Tc; q.dil = dilation;
+    q.ring = ring; q.ring_ks = S * n * ring_ld; q.ring_is = ring_ld; q.C = C; q.head = head;
+    { ProfScope ps(TGCN_PROF_WGRAD, st);
+      const dim3 grid((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups));
+      if (C == 0) hipLaunchKernelGGL(series_wgrad_partial_kernel<false>, grid, dim3(64), 0, st, q);      // one tap: the window is its own row
+      else if (dilation > 1) hipLaunchKernelGGL((series_wgrad_partial_kernel<true, true, true>), grid, dim3(64), 0, st, q);
+      else hipLaunchKernelGGL((series_wgrad_partial_kernel<true, false, true>), grid, dim3(64), 0, st, q); }
+    WgradParams r;
+    memset(&r, 0, sizeof(r));
+    r.partial = q.partial; r.dW = dW; r.Kc = q.J; r.N = N; r.nterms = K; r.nblocks = (int32_t)nblocks;
+    { ProfScope ps(TGCN_PROF_WGRAD, st);
+      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
+  }
+  if (carried) {      // behind both on the same stream: the weight gradient has read the old ring
+    const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0) && (ring_ld % 4 == 0) && (((uintptr_t)ring & 15) == 0);
+    series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, vec, Tc, C, head, nullptr);
+  }
+  TGCN_CHECK_LAUNCH("tgcn_cheb_series_chunk_backward_f32");
   return TGCN_OK;
 }
 

@@ -315,11 +315,20 @@ struct SeriesWgradParams {
   int32_t Tf, f, nwin, J, N, K;
   int32_t stride, padl, T;        // CONV only
   int32_t dil;                    // DIL only
+  const float* ring;              // CARRY only: the C = padl time rows before the chunk, (K, S, n, ring_ld), slot j at j * f
+  int64_t ring_ks, ring_is;       // CARRY only: term and (recording, vertex) row strides of the ring
+  int32_t C, head;                // CARRY only: slots of the ring, slot of its oldest row (the host's: this form is not captured)
 };
 
 // DIL (with CONV, step 1): weight row j = h*f + c of window w reads element (tw + h * dil) * f + c, tw = w - padl, where that time row exists.
-template <bool CONV, bool DIL = false>
+// CARRY (with CONV, step 1, padl == C): the stack is one CHUNK of a longer series, T = nwin = Tc, and row (s, i, w) is the window that ENDS at
+// chunk row w.  A lane's element lies at local time row t = w - C + h * dil, -C <= t <= w: t >= 0 reads the chunk's stack as above, t < 0 the
+// ring's slot head + t + C (one conditional subtraction of C: the sum lies in [0, 2C)) with the ring's own term and row strides at channel
+// c = j - h*f -- the staging rule of the CARRY GEMM; a zeroed ring is the causal padding, so every element exists.  g is addressed by the
+// strides of the WHOLE gradient from the chunk's first row on (the host offsets p.g), in either layout.
+template <bool CONV, bool DIL = false, bool CARRY = false>
 __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWgradParams p) {
+  static_assert(!CARRY || CONV, "a carried chunk is a causal geometry");
   const int lane = threadIdx.x;
   const int r = lane & 15, kq = lane >> 4;
   const int64_t m_lo = (int64_t)blockIdx.x * p.rows_per_block;
@@ -357,15 +366,28 @@ __global__ __launch_bounds__(64) void series_wgrad_partial_kernel(const SeriesWg
       const float* grow = p.g + s * p.g_ss + (int64_t)i * p.g_is + (int64_t)w * p.g_ws;
       const int tw = CONV ? (int)w * p.stride - p.padl : (int)w;      // first time row of the window
       const float* arow = p.stack + (s * p.n + i) * (int64_t)p.Tf;
-      const bool tok = !CONV || (tw + hd >= 0 && tw + hd < p.T);
+      const bool tok = !CONV || (tw + hd >= 0 && tw + hd < p.T) || (CARRY && tw + hd < 0);     // CARRY: -C <= tw + hd, a slot of the ring
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int nn = n0 + q * 16 + r;
         gv[u][q] = (mok && nn < p.N) ? grow[nn] : 0.f;
       }
+      if constexpr (CARRY) {
+        const float* ap = arow + (int64_t)tw * p.f + jd;      // the element in term 0, and the distance between two terms
+        int64_t aks = p.st_ks;
+        if (tw + hd < 0) {
+          int slot = p.head + tw + hd + p.C;
+          if (slot >= p.C) slot -= p.C;
+          ap = p.ring + (s * p.n + i) * p.ring_is + (int64_t)slot * p.f + (j - hj * p.f);
+          aks = p.ring_ks;
+        }
 #pragma unroll
-      for (int t = 0; t < kWgTerms; ++t)
-        av[u][t] = (mok && tok && j < p.J && t0 + t < p.K) ? arow[(int64_t)(t0 + t) * p.st_ks + (int64_t)tw * p.f + jd] : 0.f;
+        for (int t = 0; t < kWgTerms; ++t) av[u][t] = (mok && tok && j < p.J && t0 + t < p.K) ? ap[(int64_t)(t0 + t) * aks] : 0.f;
+      } else {
+#pragma unroll
+        for (int t = 0; t < kWgTerms; ++t)
+          av[u][t] = (mok && tok && j < p.J && t0 + t < p.K) ? arow[(int64_t)(t0 + t) * p.st_ks + (int64_t)tw * p.f + jd] : 0.f;
+      }
     }
 #pragma unroll
     for (int u = 0; u < kWgUnroll; ++u)

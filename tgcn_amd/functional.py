@@ -530,7 +530,118 @@ class ChebSeriesFn(torch.autograd.Function):
         return gx, dW, gb, None, None, None, None, None
 
 
-def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_series=False, stride=1, padding=0, dilation=1):
+def check_time_chunk(time_chunk, stride, padding, bf16, who="cheb_time_windows"):
+    """what time_chunk= asks of a streaming call, checked before an operand is built: None (no chunks: today's call) or an integer >= 1,
+    padding="causal" (the zero ring is that padding), stride=1 and float32 parameters.  -> the chunk length or None"""
+    if time_chunk is None:
+        return None
+    if not isinstance(time_chunk, numbers.Integral) or isinstance(time_chunk, bool) or time_chunk < 1:
+        raise _lib.TgcnError("%s: time_chunk is None or an integer >= 1, got %r" % (who, time_chunk))
+    if not (isinstance(padding, str) and padding == "causal"):
+        raise _lib.TgcnError('%s: time_chunk runs with padding="causal" only (the chunks pass through the streaming ring), got padding=%r'
+                             % (who, padding))
+    if not isinstance(stride, numbers.Integral) or isinstance(stride, bool) or stride != 1:
+        raise _lib.TgcnError("%s: time_chunk runs at stride=1 only, got stride=%r" % (who, stride))
+    if bf16:
+        raise _lib.TgcnError("%s: time_chunk runs in float32 only -- the parameters are bfloat16" % who)
+    return int(time_chunk)
+
+
+@_on_device
+def _chunk_stack(op, x, t0, tc, K, mode):
+    """the hop stack (K, S, n, tc*f) of time rows [t0, t0 + tc) of a contiguous series (S, n, T, f) in the operand's labels: K - 1 hops on rows
+    of tc*f floats, as _stream_chunk's"""
+    S, n, _, f = x.shape
+    x3 = x[:, :, t0:t0 + tc].reshape(S, n, tc * f)       # a view (time and channel merge); the stack's term 0 is the contiguous copy
+    return _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)
+
+
+class ChebSeriesChunkFn(torch.autograd.Function):
+    """ChebSeriesFn on a causal series at stride 1, time_chunk rows at a time (DESIGN.md 3.10 "Time chunks"): checkpointing in time on the
+    streaming ring.  Same output and the exact gradients, but nothing of the hop stack's size (K, S, n, T*f) is held in either direction:
+    the forward keeps the relabelled series and the working weight, not the stack.
+    forward: the step-1 plan once, a zero ring (SeriesStreamState, host head: the causal padding), then per chunk the K - 1 hops on rows of
+    Tc*f floats and tgcn_cheb_project_series_stream_at_f32, which projects the chunk through the ring into rows [t0, t0 + Tc) of the whole
+    output (either layout) and updates the ring.
+    backward: a second pass in forward time order from a zero ring.  Per chunk the hops again (the same values, so the same ring) if the
+    weight needs a gradient, one tgcn_cheb_series_chunk_backward_f32 call -- the chunk's G (K, S, n, Tc*f) from g rows [t0, t0 + Tc + C)
+    read in place, and / or the dW of the windows that end in the chunk from the ring and the chunk's stack, then the ring update -- and
+    _adjoint_hops on G into d series[:, :, t0:t0 + Tc].  dW is summed over the chunks in fp32 in chunk order (a re-run is bit-identical)
+    and un-folded once.  A frozen weight: no second hop pass and no ring; a series without grad: no G and no adjoint hops."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, dil, time_chunk):
+        L = _lib.lib()
+        S, n, T, f = series.shape
+        K, H, _, N = weight_khfg.shape
+        hc, lds = C.c_int32(0), C.c_int32(0)
+        _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), 1, C.byref(hc), C.byref(lds)))
+        x = series.float().contiguous()
+        W = weight_khfg.float().contiguous().view(K, H * f, N)
+        fold = _power_fold(mode, W)
+        Wt = _working_weight(fold, W)
+        state = SeriesStreamState(op, torch.float32, S, n, f, K, H, dil, x.device)
+        out = torch.empty((S, n, T, N) if as_series else (S * T, n, N), dtype=torch.float32, device=x.device)
+        b = bias.contiguous() if bias is not None else None
+        for t0 in range(0, T, time_chunk):
+            tc = min(time_chunk, T - t0)
+            stack = _chunk_stack(op, x, t0, tc, K, mode)
+            _lib.check(L.tgcn_cheb_project_series_stream_at_f32(_lib.stream_ptr(), S, n, tc, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b),
+                                                                bias_kind, _lib.ptr(out), T, t0, 1 if as_series else 0, _lib.ptr(state.ring),
+                                                                state.ring_ld, state.head, dil))
+            state.advance(tc)
+            stack = None        # released before the next chunk's is allocated: one chunk tensor at a time
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, Wt)
+        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
+        ctx.dims = (S, n, T, f, H, N, K, dil, time_chunk)
+        ctx.bias_shape = None if bias is None else bias.shape
+        return out
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, g):
+        x, Wt = ctx.saved_tensors
+        S, n, T, f, H, N, K, dil, time_chunk = ctx.dims
+        L = _lib.lib()
+        g = _aligned_input(g.float().contiguous())
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gx = dW = None
+        if need_x or need_w:
+            opT = ctx.op.transpose() if need_x else None
+            state = SeriesStreamState(ctx.op, torch.float32, S, n, f, K, H, dil, g.device) if need_w else None
+            gx = torch.empty((S, n, T, f), dtype=torch.float32, device=g.device) if need_x else None
+            for t0 in range(0, T, time_chunk):
+                tc = min(time_chunk, T - t0)
+                stack = _chunk_stack(ctx.op, x, t0, tc, K, ctx.mode) if need_w else None
+                G = torch.empty((K, S, n, tc * f), dtype=torch.float32, device=g.device) if need_x else None
+                dWc = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
+                ws = _workspace(L.tgcn_cheb_series_chunk_backward_workspace_bytes(S, n, tc, f, H, N, K, dil), g.device, floor=16)
+                _lib.check(L.tgcn_cheb_series_chunk_backward_f32(_lib.stream_ptr(), S, n, tc, f, H, N, K, _lib.ptr(stack),
+                                                                 _lib.ptr(state.ring) if need_w else None, state.ring_ld if need_w else 0,
+                                                                 state.head if need_w else 0, _lib.ptr(g), T, t0, 1 if ctx.as_series else 0,
+                                                                 _lib.ptr(Wt) if need_x else None, _lib.ptr(G), _lib.ptr(dWc), _lib.ptr(ws),
+                                                                 ws.numel(), dil))
+                if need_w:
+                    state.advance(tc)
+                    dW = dWc if dW is None else dW.add_(dWc)        # fp32, in chunk order
+                if need_x:
+                    gx[:, :, t0:t0 + tc] = _adjoint_hops(opT, G, ctx.mode).view(S, n, tc, f)
+                stack = G = None        # released before the next chunk's are allocated: two chunk tensors at a time
+            if need_w:
+                if ctx.fold is not None:
+                    dW = fold_weight(ctx.fold, dW, transpose=True)      # the sum un-folded once
+                dW = dW.view(K, H, f, N)
+        gb = None
+        if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
+            if ctx.as_series:
+                gb = (g.sum(dim=(0, 1, 2)) if ctx.bias_kind == BIAS_CHANNEL else g.sum(dim=(0, 2))).reshape(ctx.bias_shape)
+            else:
+                gb = _bias_grad(g, ctx.bias_kind, ctx.bias_shape, True)
+        return gx, dW, gb, None, None, None, None, None, None
+
+
+def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_series=False, stride=1, padding=0, dilation=1, time_chunk=None):
     """Streaming form of TGCNCheb_H / ChebTimeConv on sliding windows: series (S, n, T) raw recordings with weight (K, H, N), or
     (S, n, T, f) with weight (K, H, f, N), in the reference basis.  Returns (S * (T-H+1), n, N), identical to running the layer on the
     windowed batch x[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c] (load/data_hcp.py:146-152), but the K-1 hops run once on the T time
@@ -547,8 +658,15 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     runs at stride 1 only (TgcnError otherwise) through the _dilated entries, f == 1 included; a chain with dilations 1, 2, 4, ... sees
     exponentially many time steps with a few taps per layer.  A one-tap layer (H == 1) has nothing to dilate and makes the calls of dilation 1.
     bfloat16 parameters take ChebSeriesBf16Fn (bf16 series, stack and output, fp32 sums) for every call but the scalar-load form; that one, and
-    a series that is not bfloat16 itself, raise TgcnError before anything is built (check_series_bf16)."""
+    a series that is not bfloat16 itself, raise TgcnError before anything is built (check_series_bf16).
+    time_chunk=Tc (an integer >= 1; None: everything above, call for call) returns the same tensor with the same autograd behaviour, but walks
+    the recording Tc time rows at a time through the streaming ring in both directions (ChebSeriesChunkFn; the last chunk is shorter, Tc >= T
+    is one chunk): nothing of size K*T is allocated in the forward or the backward, at the price of a third hop pass when the weight trains.
+    It runs the causal layer at step 1 -- padding="causal", stride=1, any dilation, float32 parameters, either layout, a single channel on
+    the general kernels -- and anything else raises TgcnError before an operand is built (check_time_chunk).  The causal result holds a row
+    for every time step; the windows that lie wholly inside the recording (padding=0) are out[:, :, He-1:] of it."""
     bf16 = param_dtype(weight, bias, "cheb_time_windows") == BF16
+    time_chunk = check_time_chunk(time_chunk, stride, padding, bf16)
     if series.dim() not in (3, 4) or weight.dim() != series.dim():
         raise _lib.TgcnError("cheb_time_windows: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
                              "(got %s and %s)" % (tuple(series.shape), tuple(weight.shape)))
@@ -565,6 +683,12 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
         series, bias = _to_operand_labels(op, series, bias, bias_kind)      # (the relabelling kernel is fp32: bf16 values pass through it exactly)
         out = ChebSeriesBf16Fn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom)
         return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm).to(BF16)
+    if time_chunk is not None:
+        if series.dim() == 3:
+            series, weight = series.unsqueeze(3), weight.unsqueeze(2)
+        series, bias = _to_operand_labels(op, series, bias, bias_kind)
+        out = ChebSeriesChunkFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom[3], time_chunk)
+        return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)
     if f == 1 and not as_series and geom == (1, 0, 0, 1):
         if series.dim() == 4:
             series, weight = series.reshape(series.shape[:3]), weight.reshape(weight.shape[0], weight.shape[1], weight.shape[3])

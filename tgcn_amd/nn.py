@@ -189,7 +189,7 @@ class TGCNCheb_H(_DenseLBase):
             X = X.unsqueeze(3)
         return self._stack(X)
 
-    def forward_series(self, series, as_series=False, stride=1, padding=0, dilation=1):
+    def forward_series(self, series, as_series=False, stride=1, padding=0, dilation=1, time_chunk=None):
         """Additive API (not in the reference): series (S, n, T) or (S, n, T, f) raw recordings, f == in_channels -> the layer's output
         for all T-H+1 sliding windows of every recording without materialising the windows (load/data_hcp.py:116-154 builds them on
         the host and the hops then run H times too often): layer(xw) for xw[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c].
@@ -201,15 +201,23 @@ class TGCNCheb_H(_DenseLBase):
         stride-th window.  nwin = (T + left + right - H) // stride + 1 replaces T-H+1 above.
         dilation: the taps of a window lie that many time rows apart, xw[., i, h, c] = padded_series[s, i, w*stride + h*dilation, c]; the
         window spans He = (H-1)*dilation + 1 rows and He replaces H in the padding rules and in nwin ("causal" = He-1 rows in front).
-        dilation > 1 needs stride=1.  A causal chain with dilations 1, 2, 4, ... sees hundreds of time steps with a few taps per layer."""
+        dilation > 1 needs stride=1.  A causal chain with dilations 1, 2, 4, ... sees hundreds of time steps with a few taps per layer.
+        time_chunk=Tc (an integer >= 1; None: the calls above) trains on recordings whose hop stack does not fit: the same tensor and the
+        same gradients, computed Tc time rows at a time through the streaming ring of forward_stream in both directions, so that memory
+        follows the chunk and nothing of size K*T is allocated (F.ChebSeriesChunkFn; one more hop pass in the backward).  The causal
+        layer at step 1 only: padding="causal", stride=1, any dilation, float32 parameters, either layout -- TgcnError before the operand
+        is built for anything else.  The causal output has T rows; the windows that lie inside the recording are out[:, :, He-1:]
+        (as_series=True) of it."""
         bf16 = _compute_dtype(self) == torch.bfloat16      # F.cheb_time_windows routes it: every call but the scalar-load form
         series, W, geom = _series_args(self, series, stride, padding, dilation)
+        F.check_time_chunk(time_chunk, stride, padding, bf16, "TGCNCheb_H.forward_series")
         if bf16:
             F.check_series_bf16(self.weight.shape[2], as_series, geom, series.dtype)
         return F.cheb_time_windows(self._operand(series.device), series, W,
                                    None if self.bias is None else self.bias.reshape(-1),
                                    F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series,
-                                   stride=geom[0], padding=geom[1:3], dilation=geom[3])
+                                   stride=geom[0], padding=geom[1:3] if time_chunk is None else "causal", dilation=geom[3],
+                                   time_chunk=time_chunk)
 
     def forward_stream(self, chunk, state=None, dilation=1, capturable=False, fused=False, stride=1):
         """Additive API, inference only: the causal layer on the next Tc time rows of S recordings.  chunk (S, n, Tc) or (S, n, Tc, f) ->
@@ -507,24 +515,27 @@ class ChebTimeConv(_EdgeBase):
         return F.cheb_layer(*args, values=self._values(x, edge_index, edge_weight, args[0]))
 
 
-    def forward_series(self, series, edge_index, edge_weight=None, as_series=False, stride=1, padding=0, dilation=1):
+    def forward_series(self, series, edge_index, edge_weight=None, as_series=False, stride=1, padding=0, dilation=1, time_chunk=None):
         """Additive API: TGCNCheb_H.forward_series' contract for this class -- series (S, n, T) or (S, n, T, f), f == in_channels, ->
         forward(xw, edge_index, edge_weight) on the windowed batch xw[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c], as
         (S*(T-H+1), n, g) or, as_series=True, (S, n, T-H+1, g); true recurrence, per-channel bias.  The operand is the one forward builds
         and caches.  A learnable edge_weight (requires_grad) raises TgcnError: its gradient needs the basis of every window, which
         this entry exists not to form -- call forward on materialised windows to train edge weights.
-        stride, padding, dilation as in TGCNCheb_H.forward_series."""
+        stride, padding, dilation and time_chunk as in TGCNCheb_H.forward_series (time_chunk: the causal layer at step 1 in float32, walked
+        Tc time rows at a time in both directions, out[:, :, He-1:] the windows inside the recording)."""
         if edge_weight is not None and edge_weight.requires_grad:
             raise _lib.TgcnError("ChebTimeConv.forward_series: learnable edge weights (edge_weight.requires_grad) are not supported -- "
                                  "use forward on the windowed batch")
         bf16 = _compute_dtype(self, edge_weight) == torch.bfloat16      # as in TGCNCheb_H.forward_series
         series, W, geom = _series_args(self, series, stride, padding, dilation)
+        F.check_time_chunk(time_chunk, stride, padding, bf16, "ChebTimeConv.forward_series")
         if bf16:
             F.check_series_bf16(self.weight.shape[2], as_series, geom, series.dtype)
         op = self._operand(series, edge_index, edge_weight)
         return F.cheb_time_windows(op, series, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
                                    as_series=as_series,
-                                   stride=geom[0], padding=geom[1:3], dilation=geom[3])
+                                   stride=geom[0], padding=geom[1:3] if time_chunk is None else "causal", dilation=geom[3],
+                                   time_chunk=time_chunk)
 
     def forward_stream(self, chunk, edge_index, edge_weight=None, state=None, dilation=1, capturable=False, fused=False, stride=1):
         """Additive API, inference only: TGCNCheb_H.forward_stream's contract for this class -- chunk (S, n, Tc[, f]) -> (out (S, n, Tc, g),

@@ -10,6 +10,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py --stream --graph [--include parent=FILE] [--out profiles/r13_series_stream_graph.json]
     python tools/series_bench.py --stream --fused [--include parent=FILE] [--out profiles/r14_series_stream_fused.json]
     python tools/series_bench.py --stream --stride 2,2,2 [--repeats 3] [--include parent=FILE] [--out profiles/r16_series_stream_stride.json]
+    python tools/series_bench.py --time-chunk 64,256 [--repeats 3] [--include parent=FILE] [--out profiles/r17_series_time_chunk.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -42,7 +43,12 @@ profiles/r14_series_stream_fused.json.
 step-1 forward_stream with every layer's output sliced out[:, :, ::s] before the next layer.  Per column: --repeats event timings of --steps
 chunks each (ms per chunk, their median and spread) and one pass with the launch record.  On a tree whose forward_stream has no `stride`
 keyword only the sliced column is timed, which is how the parent commit's file for --include LABEL=FILE is made; default --out
-profiles/r16_series_stream_stride.json."""
+profiles/r16_series_stream_stride.json.
+--time-chunk Tc[,Tc...] times a training step (forward + backward, all three gradients) of forward_series(..., padding="causal") on long
+recordings, T = 1200: (a) 32 -> 64 and (b), the unchunked call against time_chunk=Tc for each Tc (DESIGN.md 3.10 "Time chunks"), in the same
+run, alternating, --repeats event timings of --steps steps each, and torch.cuda.max_memory_allocated above the allocation before the step.
+On a tree whose forward_series has no `time_chunk` keyword only the unchunked column is taken, which is how the parent commit's file for
+--include LABEL=FILE is made; default --out profiles/r17_series_time_chunk.json."""
 import argparse
 import json
 import os
@@ -511,6 +517,78 @@ def main_stream_stride(args):
         json.dump(res, f, indent=1)
 
 
+def main_time_chunk(args):
+    import inspect
+    dev = torch.device("cuda:0")
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, repeats=args.repeats,
+               time_chunks=list(args.time_chunk), T=1200, cases={})
+    torch.manual_seed(0)
+    has_kw = "time_chunk" in inspect.signature(tgcn_amd.TGCNCheb_H.forward_series).parameters
+    columns = [None] + (list(args.time_chunk) if has_kw else [])
+    T = 1200
+
+    def case(name, desc, layer, series):
+        series = series.requires_grad_(True)
+
+        def step_of(tc):
+            kw = {} if tc is None else dict(time_chunk=tc)
+
+            def step():
+                layer.zero_grad(set_to_none=True)
+                series.grad = None
+                out = layer.forward_series(series, as_series=True, padding="causal", **kw)
+                out.backward(torch.ones_like(out))
+            return step
+
+        ms, peak = {c: [] for c in columns}, {}
+        for _ in range(args.repeats):               # alternating: every column once per repeat
+            for c in columns:
+                step = step_of(c)
+                ms[c].append(events_ms(step, args.steps, args.warmup))
+                layer.zero_grad(set_to_none=True)
+                series.grad = None
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                step()
+                torch.cuda.synchronize()
+                peak[c] = torch.cuda.max_memory_allocated() - base
+        label = lambda c: "unchunked" if c is None else "time_chunk_%d" % c      # noqa: E731
+        entry = dict(desc=desc, series_bytes=series.numel() * 4)
+        for c in columns:
+            entry[label(c)] = dict(ms_per_step=ms[c], median=sorted(ms[c])[len(ms[c]) // 2], spread=round(max(ms[c]) - min(ms[c]), 4),
+                                   peak_bytes_above_baseline=peak[c], peak_over_series_bytes=round(peak[c] / (series.numel() * 4), 2))
+            if c is not None:
+                entry[label(c)]["ms_over_unchunked"] = round(entry[label(c)]["median"] / entry["unchunked"]["median"], 3)
+                entry[label(c)]["peak_over_unchunked"] = round(peak[c] / peak[None], 3)
+        res["cases"][name] = entry
+        print(json.dumps({name: entry}), flush=True)
+        layer.zero_grad(set_to_none=True)
+        series.grad = None
+        torch.cuda.empty_cache()
+
+    op = dti148(dev)
+    l2 = tgcn_amd.TGCNCheb_H(op, 32, 64, 10, 15).to(dev)
+    case("a_dti148_32to64_T1200", "dti148 S=8 T=1200 H=15 K=10 f=32 -> g=64 causal, forward + backward", l2, torch.randn(8, op.n, T, 32, device=dev))
+    del l2
+    n, row, col, val = synth.sheet_mesh(300, device=dev)
+    opm = GraphOperand.from_coo(n, row, col, val, dev)
+    lm = tgcn_amd.TGCNCheb_H(opm, 4, 32, 5, 15).to(dev)
+    case("b_mesh90k_4to32_T1200", "sheet_mesh(300) n=%d S=1 T=1200 H=15 K=5 f=4 -> g=32 causal, forward + backward" % n, lm,
+         torch.randn(1, n, T, 4, device=dev))
+    for item in args.include:
+        label, path = item.split("=", 1)
+        with open(path) as f:
+            other = json.load(f)
+        rel = {name: round(entry["unchunked"]["median"] / res["cases"][name]["unchunked"]["median"], 3)
+               for name, entry in other["cases"].items() if name in res["cases"]}
+        res.setdefault("runs", {})[label] = dict(run=other, unchunked_ms_over_this_run=rel)
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r17_series_time_chunk.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def stride_arg(text):
     parts = tuple(int(v) for v in text.split(","))
     return parts[0] if len(parts) == 1 else parts
@@ -522,13 +600,15 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--stride", type=stride_arg, default=1, help="the window step; with --stream: S1,S2,S3, the three layers' steps")
-    ap.add_argument("--repeats", type=int, default=3, help="with --stream --stride: event timings per column")
+    ap.add_argument("--repeats", type=int, default=3, help="with --stream --stride and --time-chunk: event timings per column")
     ap.add_argument("--padding", type=padding_arg, default=0)
     ap.add_argument("--conv", action="store_true", help="add the stride-4 and causal-chain cases")
     ap.add_argument("--dilation", action="store_true", help="the dilated cases (profiles/r11_series_dilation.json)")
     ap.add_argument("--stream", action="store_true", help="the streaming-state cases (profiles/r12_series_stream.json)")
     ap.add_argument("--graph", action="store_true", help="with --stream: the captured step next to the eager one (profiles/r13_series_stream_graph.json)")
     ap.add_argument("--fused", action="store_true", help="with --stream: the one-launch step next to the eager one (profiles/r14_series_stream_fused.json)")
+    ap.add_argument("--time-chunk", type=lambda t: tuple(int(v) for v in t.split(",")), default=None, metavar="Tc[,Tc...]",
+                    help="a training step on T = 1200, unchunked against each time_chunk (profiles/r17_series_time_chunk.json)")
     ap.add_argument("--include", action="append", default=[], metavar="LABEL=FILE",
                     help="put another run's --out file (the parent commit's, a repeat of this one) into this one under runs[LABEL], with "
                          "each shared case's ms per call relative to this run")
@@ -536,6 +616,10 @@ def main():
     args = ap.parse_args()
     if args.dtype == "bf16":
         return main_bf16(args)
+    if args.time_chunk is not None:
+        if min(args.time_chunk) < 1 or args.stream or args.dilation or args.conv:
+            ap.error("--time-chunk Tc[,Tc...] (integers >= 1) runs alone")
+        return main_time_chunk(args)
     if args.dilation:
         return main_dilation(args)
     if args.graph and not args.stream:
