@@ -448,6 +448,27 @@ int tgcn_cheb_project_series_stream_pos_bf16(void* stream, int64_t S, int64_t n_
                                              int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int64_t* pos, int32_t dilation);
 int tgcn_series_stream_advance(void* stream, int64_t* pos, int32_t Tc, int32_t C);
 
+/* relu + vertex max-pool as the epilogue of the streaming projection ("relu + pool epilogue"; fp32, forward only):
+ *   z[.., j, ..] = max over i in [j*pool, (j+1)*pool) of relu(y[.., i, ..]),   y the output of the _conv / _dilated entry of the same arguments,
+ * bit-identical to tgcn_relu_pool_f32 applied to y (members ascending, first maximum wins, NaN propagates), with y never written: a
+ * workgroup owns 32 windows of four consecutive vertices and takes the max out of LDS.  pool is 2 or 4 and divides n_vertices.
+ * z and idx are (S*nwin, n/pool, N) for as_series == 0 and (S, n/pool, nwin, N) otherwise; idx (one arg-max byte per element of z, what
+ * tgcn_relu_pool_bwd_f32 reads) may be NULL.  Geometry (stride, pads, dilation) by the rules of the _conv / _dilated entries.
+ * tgcn_series_pool_plan: tgcn_series_conv_plan's *hc and refusal -- the epilogue never changes the regime -- and *lds_bytes =
+ * max(the GEMM's bytes, the scratch's 4 * 32 * (16 | 32 | 64) * 4 for N <= 16 | <= 32 | above).
+ * tgcn_cheb_project_series_stream_pool_f32: the step of tgcn_cheb_project_series_stream_f32 (pos == NULL: the host's head) or of
+ * tgcn_cheb_project_series_stream_pos_f32 (pos non-null: the device position, head unused, and the advance), ring update included, with
+ * z (S, n/pool, Tc, N) in out's place.  H == 1 keeps no ring: the first entry on the chunk (ring, head and pos unused and not moved).
+ * TGCN_ERR_INVALID before any launch: pool outside {2, 4}, n_vertices % pool != 0, a null stack, W, z (or ring for H > 1), and everything
+ * the entries they extend refuse; TGCN_ERR_UNSUPPORTED where the plan refuses or a dilation meets a window step. */
+int tgcn_series_pool_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t pool, int32_t* hc, int32_t* lds_bytes);
+int tgcn_cheb_project_series_pool_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* z,
+                                      uint8_t* idx, int32_t pool, int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation);
+int tgcn_cheb_project_series_stream_pool_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                             const float* stack, const float* W, const float* bias, int32_t bias_kind, float* z, int32_t pool,
+                                             float* ring, int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation);
+
 /* Time chunks of the causal layer with a backward ("Time chunks"; fp32, step 1, the host's head): forward_series walks a
  * recording chunk by chunk through the ring in both directions, so nothing of the hop stack's whole size is ever held.
  * tgcn_cheb_project_series_stream_at_f32 is tgcn_cheb_project_series_stream_f32 writing its Tc rows into rows [out_t0, out_t0 + Tc) of

@@ -1267,6 +1267,19 @@ int tgcn_series_gemm_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t*
   return TGCN_OK;
 }
 
+// The pooled form's scratch [wave][window][col] lives where the weight tile and the spans were: the launch takes the larger of the two
+static int series_pool_lds(int gemm_lds, int NT) { const int sc = 4 * kSgWin * NT * 16 * (int)sizeof(float); return gemm_lds > sc ? gemm_lds : sc; }
+static bool series_pool_ok(int64_t n, int32_t pool) { return (pool == 2 || pool == 4) && n >= 1 && n % pool == 0; }
+
+int tgcn_series_pool_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t pool, int32_t* hc, int32_t* lds_bytes) {
+  if (H < 1 || f < 1 || N < 1 || stride < 1 || (pool != 2 && pool != 4) || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_pool_plan: bad argument");
+  int h = 0;
+  const int lds = series_gemm_lds(H, f, series_gemm_nt(N), vec != 0, stride, &h);
+  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_pool_plan: %d channels per time row do not fit the LDS span", f);
+  *hc = h; *lds_bytes = series_pool_lds(lds, series_gemm_nt(N));
+  return TGCN_OK;
+}
+
 // Phase-major tiles of the DILATED kernels: min(dil, nwin) phases hold a window, the longest ceil(nwin / dil) of them.
 // 2 <= dil < the padded series (series_dilated_check), so nothing here leaves 32 bits.
 static void series_dilated_tiles(int32_t nwin, int32_t dil, int32_t* tpp, int32_t* tpv) {
@@ -1279,19 +1292,27 @@ static void series_dilated_tiles(int32_t nwin, int32_t dil, int32_t* tpp, int32_
 // the DILATED ones, planned as step 1
 // carry (the stream entries): the CARRY instantiations, which stage the time rows before the chunk from p.ring -- at step 1 (dilated or
 // not), or STRIDED && CARRY for a window step on a chunk (the _stream_strided entry, p.win_off)
+// pool (2 / 4; 0: none): the POOLED instantiations of the same form -- one workgroup per (recording, vertex quad, window block), the
+// scratch's bytes where they exceed the GEMM's; not built with a window step on a chunk
 static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1, int dil = 1,
-                              bool carry = false) {
+                              bool carry = false, int pool = 0) {
   p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
   p.dil = dil;
   if (dil > 1) series_dilated_tiles(p.nwin, dil, &p.tpp, &p.tpv);
   p.ntiles = S * p.n * p.tpv;
-  const int64_t gx = (p.ntiles + 3) / 4;
+  p.pool = pool;
+  if (pool) { p.nq = (p.n + 3) / 4; p.ntiles = S * p.nq * p.tpv; }
+  const int64_t gx = pool ? p.ntiles : (p.ntiles + 3) / 4;
   const int NT = series_gemm_nt(p.N);
   const int64_t gy = (p.N + NT * 16 - 1) / (NT * 16);
   if (gx > (int64_t)INT32_MAX || gy > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
   int hc = 0;
-  const int lds = series_gemm_lds(p.H, p.f, NT, vec, stride, &hc);
+  int lds = series_gemm_lds(p.H, p.f, NT, vec, stride, &hc);
   if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, p.f);
+  if (pool) {
+    if (carry && stride > 1) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a pooled window step on a chunk is not built", who);
+    lds = series_pool_lds(lds, NT);
+  }
   p.HC = hc;
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = series_row_floats(hc, p.f, vec, stride);
   const dim3 grid((unsigned)gx, (unsigned)gy);
@@ -1304,7 +1325,14 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
 #define TGCN_SERIES_GEMM_NT(VEC_, STR_, DIL_, ...)                                                                        \
   do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_, DIL_, ##__VA_ARGS__); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_, DIL_, ##__VA_ARGS__);   \
        else TGCN_SERIES_GEMM(4, VEC_, STR_, DIL_, ##__VA_ARGS__); } while (0)
-  if (carry) {
+  if (pool) {
+    if (carry) {
+      if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, true, true); else TGCN_SERIES_GEMM_NT(false, false, true, true, true); }
+      else { if (vec) TGCN_SERIES_GEMM_NT(true, false, false, true, true); else TGCN_SERIES_GEMM_NT(false, false, false, true, true); }
+    } else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, false, true); else TGCN_SERIES_GEMM_NT(false, false, true, false, true); }
+    else if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, false, false, true); else TGCN_SERIES_GEMM_NT(false, false, false, false, true); }
+    else { if (vec) TGCN_SERIES_GEMM_NT(true, true, false, false, true); else TGCN_SERIES_GEMM_NT(false, true, false, false, true); }
+  } else if (carry) {
     if (stride > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, true, false, true); else TGCN_SERIES_GEMM_NT(false, true, false, true); }
     else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, true); else TGCN_SERIES_GEMM_NT(false, false, true, true); }
     else { if (vec) TGCN_SERIES_GEMM_NT(true, false, false, true); else TGCN_SERIES_GEMM_NT(false, false, false, true); }
@@ -1355,18 +1383,19 @@ static int series_dilated_check(int64_t S, int64_t n, int32_t T, int32_t f, int3
 
 static int project_series_impl(hipStream_t st, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, const float* stack,
                                const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out, int32_t stride, int32_t pl,
-                               int32_t pr, const char* who, int32_t dil = 1) {
+                               int32_t pr, const char* who, int32_t dil = 1, int32_t pool = 0, uint8_t* idx = nullptr) {
   const int64_t Tf = (int64_t)T * f, nwin = series_conv_nwin(T, (H - 1) * dil + 1, stride, pl, pr);
+  const int64_t no = pool ? n / pool : n;       // vertices of the output: pooled, out and idx are (S*nwin, n/pool, N) or (S, n/pool, nwin, N)
   SeriesGemmParams p;
   memset(&p, 0, sizeof(p));
   p.src = stack; p.W = W; p.bias = bias; p.out = out;
   p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
-  if (as_series) { p.o_ss = n * nwin * N; p.o_is = nwin * N; p.o_ws = N; }      // (S, n, nwin, N)
-  else { p.o_ss = nwin * n * N; p.o_is = N; p.o_ws = n * N; }                     // (S, nwin, n, N)
-  p.o_gs = 0; p.ocg = N;
+  if (as_series) { p.o_ss = no * nwin * N; p.o_is = nwin * N; p.o_ws = N; }     // (S, n, nwin, N)
+  else { p.o_ss = nwin * no * N; p.o_is = N; p.o_ws = no * N; }                   // (S, nwin, n, N)
+  p.o_gs = 0; p.ocg = N; p.idx = idx;
   p.n = n; p.Tin = T; p.padl = pl; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
   const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0);
-  return series_gemm_launch(st, p, S, vec, who, stride, dil);
+  return series_gemm_launch(st, p, S, vec, who, stride, dil, false, pool);
 }
 
 int tgcn_cheb_project_series_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
@@ -1408,6 +1437,31 @@ int tgcn_cheb_project_series_dilated_f32(void* stream, int64_t S, int64_t n_vert
   if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, 1, pad_left,
                                    pad_right, "project_series_dilated", dilation)) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_dilated_f32");
+  return TGCN_OK;
+}
+
+// ---- relu + vertex max-pool as the projection's epilogue ("relu + pool epilogue"): the _conv / _dilated entries' geometry
+int tgcn_cheb_project_series_pool_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* z,
+                                      uint8_t* idx, int32_t pool, int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
+  const char* who = "project_series_pool";
+  if (!series_pool_ok(n_vertices, pool)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: pool %d of %lld vertices", who, pool, (long long)n_vertices);
+  if (series_dilation_is_one(H, stride, dilation)) {
+    if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+    dilation = 1;
+    stride = series_conv_stride(T, stride, pad_left, pad_right);
+  } else {
+    int32_t He = 0;
+    const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
+    if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "%s: dilation %d with stride %d is not built", who, dilation, stride);
+    if (grc) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  }
+  if (!stack || !W || !z) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
+  if (int drc = check_pointer_device(z, (hipStream_t)stream, who)) return drc;
+  if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, z, stride, pad_left,
+                                   pad_right, who, dilation, pool, idx)) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_pool_f32");
   return TGCN_OK;
 }
 
@@ -1473,8 +1527,9 @@ static void series_out_slice(SeriesGemmParams& p, int64_t n, int32_t N, int32_t 
 static int project_series_stream_impl(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
                                       const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
                                       int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation, const char* who, int32_t out_T = 0,
-                                      int32_t out_t0 = 0, int32_t out_as_series = 1) {
+                                      int32_t out_t0 = 0, int32_t out_as_series = 1, int32_t pool = 0) {
   int32_t C = 0;
+  if (pool && (!series_pool_ok(n_vertices, pool) || out_T)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: pool %d of %lld vertices", who, pool, (long long)n_vertices);
   if (series_stream_check(S, n_vertices, Tc, f, H, N, K, dilation, ring_ld, head, &C) || !stack || !W || !out || !ring)
     TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
   if (out_T && !series_out_slice_ok(Tc, out_T, out_t0)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
@@ -1486,13 +1541,13 @@ static int project_series_stream_impl(void* stream, int64_t S, int64_t n_vertice
   memset(&p, 0, sizeof(p));
   p.src = stack; p.W = W; p.bias = bias; p.out = out;
   p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
-  p.o_ss = n * Tc * N; p.o_is = (int64_t)Tc * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, Tc, N)
+  p.o_ss = (pool ? n / pool : n) * Tc * N; p.o_is = (int64_t)Tc * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, Tc, N); pooled: n / pool
   if (out_T) series_out_slice(p, n, N, out_T, out_t0, out_as_series);
   p.n = n; p.Tin = Tc; p.padl = C; p.nwin = Tc; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
   p.ring = ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
   // 16-byte staging and copies: the stack's rule, and a ring that keeps it
   const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0) && (ring_ld % 4 == 0) && (((uintptr_t)ring & 15) == 0);
-  if (int rc = series_gemm_launch(st, p, S, vec, who, 1, dilation, true)) return rc;
+  if (int rc = series_gemm_launch(st, p, S, vec, who, 1, dilation, true, pool)) return rc;
   series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, vec, Tc, C, head, pos);
   if (pos) series_stream_advance_launch(st, pos, Tc, C);
   return TGCN_OK;
@@ -1514,6 +1569,23 @@ int tgcn_cheb_project_series_stream_pos_f32(void* stream, int64_t S, int64_t n_v
   if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, 0, pos,
                                           dilation, "project_series_stream_pos")) return rc;
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pos_f32");
+  return TGCN_OK;
+}
+
+// The stream entries' step with the pooled epilogue: z (S, n/pool, Tc, N).  pos null: the host's head; non-null: the device position and the
+// advance.  H == 1 keeps no ring: the pooled entry on the chunk (ring, head and pos unused; the caller's advance counts seen).
+int tgcn_cheb_project_series_stream_pool_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                             const float* stack, const float* W, const float* bias, int32_t bias_kind, float* z, int32_t pool,
+                                             float* ring, int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation) {
+  const char* who = "project_series_stream_pool";
+  if (!series_pool_ok(n_vertices, pool)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: pool %d of %lld vertices", who, pool, (long long)n_vertices);
+  if (H == 1) {
+    if (dilation < 1) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+    return tgcn_cheb_project_series_pool_f32(stream, S, n_vertices, Tc, f, 1, N, K, stack, W, bias, bias_kind, 1, z, nullptr, pool, 1, 0, 0, 1);
+  }
+  if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, z, ring, ring_ld, pos ? 0 : head, pos,
+                                          dilation, who, 0, 0, 1, pool)) return rc;
+  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pool_f32");
   return TGCN_OK;
 }
 

@@ -33,6 +33,9 @@ struct SeriesGemmParams {
   int32_t C, head;                  // CARRY only: slots of the ring, slot of its oldest row
   const int64_t* pos;               // CARRY only: non-null -> the slot of the oldest row is read from pos[0] in device memory (head is ignored)
   int32_t win_off;                  // STRIDED && CARRY only: the chunk row at which window 0 ends (window r ends at win_off + r * stride)
+  uint8_t* idx;                     // POOLED only: arg-max byte per pooled output, in the layout of out; null: not stored
+  int64_t nq;                       // POOLED only: vertex quads per recording, ceil(n / 4)
+  int32_t pool;                     // POOLED only: 2 or 4 consecutive vertices per output vertex, n % pool == 0
 };
 
 constexpr int kSgWin = 32;    // windows per wave
@@ -84,7 +87,20 @@ __device__ __forceinline__ int series_ring_head(const int64_t* pos, int head, in
   const int64_t v = pos[0];
   return (v >= 0 && v < (int64_t)C) ? (int)v : 0;
 }
-template <int NT, bool VEC, bool STRIDED = false, bool DILATED = false, bool CARRY = false>
+// POOLED (the forward with relu + max over `pool` consecutive vertices as its epilogue; pool 2 or 4, n % pool == 0): a workgroup owns ONE
+// block of 32 windows (in the DILATED form: of one phase) of a vertex QUAD -- tile = blockIdx.x -> (recording, quad vq < nq = ceil(n / 4),
+// block), wave v the vertex 4 * vq + v -- so a pool group lies inside one workgroup.  Staging, span, banks, regimes, A offsets and the MFMA
+// loop are the form's own: every value acc + bias has the bits the unpooled kernel stores.  After the loop's last barrier the weight tile and
+// the spans are free; each wave with a vertex writes its 32 x NT*16 values, bias added (kind 2: its own vertex's), into the scratch
+// [wave][window][col] at the start of the LDS, ONE barrier, and the 256 threads walk (group, window, col), col fastest, taking the max by
+// relu_pool_kernel's rules -- members ascending, first maximum wins, NaN propagates, then best > 0 ? best : (NaN ? NaN : 0) -- and store one
+// float (and, idx non-null, one arg-max byte) at vertex iv / pool through the output strides.
+// Barrier rule: the epilogue's barrier is reached by all four waves.  A wave without a vertex (the last quad of n = 2 (mod 4) at pool 2)
+// stages zeros, writes no scratch, and stays; no group with a vertex reads its part (n % pool == 0: a group exists whole or not at all).
+// Lanes of windows w >= nwin hold sums over zero rows; nothing reads them out.  A DILATED block that starts past its phase is dead for the
+// four waves alike and leaves before the barrier, together.
+// LDS: max(the GEMM's bytes, 4 * 32 * NT*16 floats <= 32 KB); the scratch never changes the regime (HC).
+template <int NT, bool VEC, bool STRIDED = false, bool DILATED = false, bool CARRY = false, bool POOLED = false>
 __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmParams p) {
   constexpr int NW = NT * 16, NS = series_ws_stride(NT), WREG = (kSgKT * NW) / kBlock;
   extern __shared__ __attribute__((aligned(16))) float sg_lds[];
@@ -95,7 +111,8 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
   const int lst = STRIDED ? p.lst : 1;          // span rows between consecutive windows
   float* span = sg_lds + kSgKT * NS + wave * (int)(STRIDED ? series_span_floats(p.HC, p.f, VEC, p.stride) : series_span_floats(p.HC, p.f, VEC));
   static_assert(!(STRIDED && DILATED), "a window step with dilated taps is not built");
-  const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+  static_assert(!(POOLED && STRIDED && CARRY), "a pooled window step on a chunk is not built");
+  const int64_t tile = POOLED ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + wave;
   bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
   int w0 = live ? (int)(tile % p.tpv) * kSgWin : 0;      // DILATED: the first window's index v0 inside its phase
@@ -108,7 +125,17 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
   }
   const int tstep = DILATED ? p.dil : 1;                  // time rows between two span rows
   const int head = CARRY ? series_ring_head(p.pos, p.head, p.C) : 0;
-  const int64_t s = si / p.n, iv = si % p.n;
+  const bool wg_live = live;                              // POOLED: the same for the four waves (they share the tile)
+  int64_t s, iv;
+  if constexpr (POOLED) {
+    s = si / p.nq;
+    iv = (si % p.nq) * 4 + wave;
+    live = live && iv < p.n;
+    if (!live) iv = 0;
+  } else {
+    s = si / p.n;
+    iv = si % p.n;
+  }
   const int n0 = blockIdx.y * NW;
   const int J = p.H * p.f;
   f32x4 acc[2][NT];
@@ -225,6 +252,49 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
       }
       __syncthreads();                          // span and weight tile are free again
     }
+  }
+  if constexpr (POOLED) {
+    // ---- pooled epilogue: bias into the scratch [wave][window][col], one barrier, relu + max over the group's waves
+    if (!wg_live) return;                       // the whole workgroup: a DILATED block past its phase
+    if (live) {
+      float* sc = sg_lds + wave * (kSgWin * NW);
+#pragma unroll
+      for (int nt = 0; nt < NT; ++nt) {
+        const int col = n0 + nt * 16 + r;
+        float b = 0.f;
+        if (col < p.N) {
+          if (p.bias_kind == 1) b = p.bias[col];
+          else if (p.bias_kind == 2) b = p.bias[iv * p.N + col];
+        }
+#pragma unroll
+        for (int rt = 0; rt < 2; ++rt)
+#pragma unroll
+          for (int i = 0; i < 4; ++i) sc[(rt * 16 + kq * 4 + i) * NW + nt * 16 + r] = acc[rt][nt][i] + b;
+      }
+    }
+    __syncthreads();                            // all four waves: the scratch is written
+    const int pool = p.pool;
+    const int64_t v00 = (si % p.nq) * 4;        // first vertex of the quad
+    float* orow0 = p.out + s * p.o_ss;
+    uint8_t* irow0 = p.idx ? p.idx + s * p.o_ss : nullptr;
+    for (int e = tid; e < (4 / pool) * kSgWin * NW; e += kBlock) {
+      const int c = e % NW, wl = (e / NW) % kSgWin, grp = e / (NW * kSgWin);
+      const int col = n0 + c;
+      const int64_t v0 = v00 + grp * pool;
+      const int w = DILATED ? ph + (w0 + wl) * p.dil : w0 + wl;
+      if (col >= p.N || v0 >= p.n || w >= p.nwin) continue;
+      const float* src = sg_lds + (grp * pool) * (kSgWin * NW) + wl * NW + c;
+      float best = src[0];
+      int bi = 0;
+      for (int j = 1; j < pool; ++j) {
+        const float v = src[j * (kSgWin * NW)];
+        if (v > best || (v != v && best == best)) { best = v; bi = j; }
+      }
+      const int64_t off = (v0 / pool) * p.o_is + (int64_t)w * p.o_ws + (int64_t)(col / p.ocg) * p.o_gs + col % p.ocg;
+      orow0[off] = best > 0.f ? best : (best != best ? best : 0.f);
+      if (irow0) irow0[off] = (uint8_t)bi;
+    }
+    return;
   }
   if (!live) return;
   // ---- epilogue (D: col = lane & 15, row = (lane >> 4) * 4 + reg): bias, column-group addressing, store

@@ -491,43 +491,165 @@ class ChebSeriesFn(torch.autograd.Function):
     @staticmethod
     @_on_device
     def backward(ctx, g):
-        Wt, = ctx.saved_tensors
-        S, n, T, f, H, N, K = ctx.dims
+        return _series_backward(ctx, ctx.saved_tensors[0], g) + (None,) * 5
+
+
+def _series_backward(ctx, Wt, g):
+    """(d series, dW, d bias) of ChebSeriesFn from the gradient g of its output in the forward's layout -- the body ChebSeriesFn.backward and
+    ChebSeriesReluPoolFn.backward share; reads ctx.geom, stack, op, mode, fold, bias_kind, as_series, dims, bias_shape of the forward"""
+    S, n, T, f, H, N, K = ctx.dims
+    L = _lib.lib()
+    g = _aligned_input(g.float().contiguous())
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    gx = dW = None
+    if need_x or need_w:
+        G = torch.empty((K, S, n, T * f), dtype=torch.float32, device=g.device) if need_x else None
+        dW = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
+        if ctx.geom is None:
+            ws = _workspace(L.tgcn_cheb_series_backward_workspace_bytes(S, n, T, f, H, N, K), g.device, floor=16)
+            _lib.check(L.tgcn_cheb_series_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
+                                                       1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel()))
+        elif len(ctx.geom) == 4:
+            ws = _workspace(L.tgcn_cheb_series_dilated_backward_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
+            _lib.check(L.tgcn_cheb_series_dilated_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
+                                                               1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
+                                                               ws.numel(), *ctx.geom))
+        else:
+            ws = _workspace(L.tgcn_cheb_series_conv_backward_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
+            _lib.check(L.tgcn_cheb_series_conv_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
+                                                            1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
+                                                            ws.numel(), *ctx.geom))
+        ctx.stack = None
+        if need_x:
+            gx = _adjoint_hops(ctx.op.transpose(), G, ctx.mode).reshape(S, n, T, f)
+        if need_w:
+            if ctx.fold is not None:
+                dW = fold_weight(ctx.fold, dW, transpose=True)
+            dW = dW.view(K, H, f, N)
+    gb = None
+    if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
+        if ctx.as_series:
+            gb = (g.sum(dim=(0, 1, 2)) if ctx.bias_kind == BIAS_CHANNEL else g.sum(dim=(0, 2))).reshape(ctx.bias_shape)
+        else:
+            gb = _bias_grad(g, ctx.bias_kind, ctx.bias_shape, True)
+    return gx, dW, gb
+
+
+def check_pool(pool, n, who):
+    """what the relu + pool epilogue of the streaming layers asks: pool 2 or 4 consecutive vertices, dividing the graph"""
+    if not isinstance(pool, numbers.Integral) or isinstance(pool, bool) or pool not in (2, 4):
+        raise _lib.TgcnError("%s: pool is 2 or 4, got %r" % (who, pool))
+    if n % pool:
+        raise _lib.TgcnError("%s: %d vertices are not a multiple of pool = %d" % (who, n, pool))
+    return int(pool)
+
+
+def series_pool_is_fused(op, pool=4, stream=False):
+    """True where cheb_time_windows_relu_pool / cheb_time_stream_relu_pool (stream=True) run relu + pool inside the projection's epilogue
+    (ChebSeriesReluPoolFn, tgcn_cheb_project_series_stream_pool_f32), False where they run the unfused composition -- the layer, then
+    tgcn_relu_pool_f32 on a view of its output.  The two are bit-identical, so this is a question of speed and memory only.
+    A reordered operand is never fused: pool groups are consecutive vertices of the CALLER's labels, scattered rows of the operand's.
+    Nothing else is excluded: profiles/r18_series_relu_pool.json (DESIGN.md 3.10 "relu + pool epilogue") has the fused call at 0.99 of the
+    composition's forward at 32 -> 64 on the 148-parcel graph (4.525 against 4.591 ms, spreads 0.015 / 0.035; a tie in training), 0.80 / 0.92 on
+    the 90 k mesh at 4 -> 32 and 0.48 at 1 -> 32 -- no measured shape class where it is slower by more than the spread.  pool = 2 and the
+    stream call are not measured."""
+    return op.perm is None
+
+
+class ChebSeriesReluPoolFn(torch.autograd.Function):
+    """z = max over `pool` consecutive vertices of relu(ChebSeriesFn's output), the max taken in the projection's epilogue
+    (tgcn_cheb_project_series_pool_f32, csrc/windows.h POOLED): the (S, n, nwin, N) layer output is never allocated, in the forward or --
+    beyond the gradient w.r.t. it, which the layer's backward reads -- in the backward.  z is (S*nwin, n/pool, N) or, as_series,
+    (S, n/pool, nwin, N), bit-identical to tgcn_relu_pool_f32 on the unfused output.  Asks tgcn_series_pool_plan before the hops.
+    need_idx (the caller's: grad mode and a leaf that requires grad) stores the arg-max bytes; the backward routes gz through them
+    (tgcn_relu_pool_bwd_f32 on the forward's layout: q = S*nwin, f = N window-major, q = S, f = nwin*N as a series) and runs ChebSeriesFn's
+    backward body on the result.  Saves z, idx, the working weight, and the stack only if the weight trains."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx):
         L = _lib.lib()
-        g = _aligned_input(g.float().contiguous())
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gx = dW = None
-        if need_x or need_w:
-            G = torch.empty((K, S, n, T * f), dtype=torch.float32, device=g.device) if need_x else None
-            dW = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
-            if ctx.geom is None:
-                ws = _workspace(L.tgcn_cheb_series_backward_workspace_bytes(S, n, T, f, H, N, K), g.device, floor=16)
-                _lib.check(L.tgcn_cheb_series_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
-                                                           1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel()))
-            elif len(ctx.geom) == 4:
-                ws = _workspace(L.tgcn_cheb_series_dilated_backward_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
-                _lib.check(L.tgcn_cheb_series_dilated_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
-                                                                   1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
-                                                                   ws.numel(), *ctx.geom))
-            else:
-                ws = _workspace(L.tgcn_cheb_series_conv_backward_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
-                _lib.check(L.tgcn_cheb_series_conv_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
-                                                                1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
-                                                                ws.numel(), *ctx.geom))
-            ctx.stack = None
-            if need_x:
-                gx = _adjoint_hops(ctx.op.transpose(), G, ctx.mode).reshape(S, n, T, f)
-            if need_w:
-                if ctx.fold is not None:
-                    dW = fold_weight(ctx.fold, dW, transpose=True)
-                dW = dW.view(K, H, f, N)
-        gb = None
-        if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
-            if ctx.as_series:
-                gb = (g.sum(dim=(0, 1, 2)) if ctx.bias_kind == BIAS_CHANNEL else g.sum(dim=(0, 2))).reshape(ctx.bias_shape)
-            else:
-                gb = _bias_grad(g, ctx.bias_kind, ctx.bias_shape, True)
-        return gx, dW, gb, None, None, None, None, None
+        S, n, T, f = series.shape
+        K, H, _, N = weight_khfg.shape
+        stride, left, right, dil = _geom4(geom)
+        conv = (stride, left, right) != (1, 0, 0)
+        nwin = (T + left + right - (H - 1) * dil - 1) // stride + 1
+        hc, lds = C.c_int32(0), C.c_int32(0)
+        _lib.check(L.tgcn_series_pool_plan(H, f, N, int(f % 4 == 0), stride, pool, C.byref(hc), C.byref(lds)))
+        x3 = _aligned_input(series.float().contiguous().view(S, n, T * f))
+        W = weight_khfg.float().contiguous().view(K, H * f, N)
+        fold = _power_fold(mode, W)
+        Wt = _working_weight(fold, W)
+        stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)   # (K, S, n, T*f)
+        shape = (S, n // pool, nwin, N) if as_series else (S * nwin, n // pool, N)
+        z = torch.empty(shape, dtype=torch.float32, device=x3.device)
+        idx = torch.empty(shape, dtype=torch.uint8, device=x3.device) if need_idx else None
+        b = bias.contiguous() if bias is not None else None
+        _lib.check(L.tgcn_cheb_project_series_pool_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind,
+                                                       1 if as_series else 0, _lib.ptr(z), _lib.ptr(idx), pool, stride, left, right, dil))
+        ctx.geom = (stride, left, right, dil) if dil > 1 else ((stride, left, right) if conv else None)
+        ctx.save_for_backward(Wt, z, idx)
+        ctx.stack = stack if ctx.needs_input_grad[1] else None
+        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.pool = op, mode, fold, bias_kind, as_series, pool
+        ctx.dims = (S, n, T, f, H, N, K)
+        ctx.nwin = nwin
+        ctx.bias_shape = None if bias is None else bias.shape
+        return z
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, gz):
+        Wt, z, idx = ctx.saved_tensors
+        S, n, T, f, H, N, K = ctx.dims
+        if idx is None:
+            raise _lib.TgcnError("cheb_time_windows_relu_pool: the forward ran without grad mode and kept no arg-max")
+        gy = torch.empty((S, n, ctx.nwin, N) if ctx.as_series else (S * ctx.nwin, n, N), dtype=torch.float32, device=gz.device)
+        q, fN = (S, ctx.nwin * N) if ctx.as_series else (S * ctx.nwin, N)
+        _lib.check(_lib.lib().tgcn_relu_pool_bwd_f32(_lib.stream_ptr(), _lib.ptr(gz.float().contiguous()), _lib.ptr(z), _lib.ptr(idx), _lib.ptr(gy),
+                                                     q, n, fN, ctx.pool))
+        return _series_backward(ctx, Wt, gy) + (None,) * 7
+
+
+def _relu_pool_view(y, pool):
+    """relu + pool as its own pass (ReluPoolFn) over the vertex axis (dim 1) of a layer output in either layout: (q, n, N) as it is,
+    (S, n, nwin, N) through its (S, n, nwin*N) view"""
+    if y.dim() == 3:
+        return ReluPoolFn.apply(y, pool)
+    S, n, nwin, N = y.shape
+    return ReluPoolFn.apply(y.reshape(S, n, nwin * N), pool).view(S, n // pool, nwin, N)
+
+
+def cheb_time_windows_relu_pool(op, series, weight, bias, bias_kind, mode, pool, as_series=False, stride=1, padding=0, dilation=1):
+    """gcn_pool_4(relu(cheb_time_windows(...))) (pool=4; pool=2: gcn_pool) with relu and the max over `pool` consecutive vertices in the
+    projection's epilogue: series (S, n, T) with weight (K, H, N), or (S, n, T, f) with (K, H, f, N) -> z (S*nwin, n/pool, N) or,
+    as_series=True, (S, n/pool, nwin, N) -- a series on the coarsened graph.  The layer's full output is never allocated; values and every
+    gradient are bit-identical to the hand-written composition.  as_series, stride, padding, dilation: cheb_time_windows'.
+    A single-channel series runs the MFMA kernels (ChebSeriesFn's) in every geometry -- the scalar-load form has no pooled epilogue.
+    A reordered operand runs the unfused composition (series_pool_is_fused): the layer, relabelled back, then tgcn_relu_pool_f32 on a view.
+    Dropout between relu and pool, as the reference's training script has it, is not this function: call the layer, relu, dropout and
+    gcn_pool_4 one after the other.
+    TgcnError before anything is built or launched: bfloat16 parameters, pool outside {2, 4}, n % pool != 0, and every refusal
+    cheb_time_windows makes for the same arguments.  There is no time_chunk."""
+    who = "cheb_time_windows_relu_pool"
+    if param_dtype(weight, bias, who) == BF16:
+        raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
+    if series.dim() not in (3, 4) or weight.dim() != series.dim():
+        raise _lib.TgcnError("%s: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
+                             "(got %s and %s)" % (who, tuple(series.shape), tuple(weight.shape)))
+    f = series.shape[3] if series.dim() == 4 else 1
+    if series.dim() == 4 and weight.shape[2] != f:
+        raise _lib.TgcnError("%s: the series has %d channels, the weight %d" % (who, f, weight.shape[2]))
+    pool = check_pool(pool, series.shape[1], who)
+    geom = series_geometry(series.shape[2], weight.shape[1], stride, padding, who, dilation)[:3] + (series_dilation(weight.shape[1], dilation),)
+    _lib.require_device(series, weight, bias)
+    if series.dim() == 3:
+        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
+    if not series_pool_is_fused(op, pool):
+        s2, b2 = _to_operand_labels(op, series, bias, bias_kind)
+        y = ChebSeriesFn.apply(s2, weight, b2, op, mode, bias_kind, bool(as_series), geom)
+        return _relu_pool_view(y if op.perm is None else relabel_rows(y, op.inv_perm, op.perm), pool)
+    need_idx = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (series, weight, bias))
+    return ChebSeriesReluPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, pool, need_idx)
 
 
 def check_time_chunk(time_chunk, stride, padding, bf16, who="cheb_time_windows"):
@@ -2028,19 +2150,23 @@ def stream_windows(seen, Tc, stride):
 
 
 @_on_device
-def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state):
+def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state, pool=0):
     """one chunk (S, n, Tc, f) in the operand's labels through the ring of `state`: plan query, K-1 hops on rows of Tc*f, the stream entry (the
     projection and the ring update), head and seen moved; H == 1: the _conv entry on the chunk.  A capturable state runs the _pos entries,
     which read the head from state.pos and move it on the device (H == 1: the _conv entry, then tgcn_series_stream_advance).
     state.stride > 1: the plan at that step and ONE call of the _stream_strided entry (H == 1 included) with the host's head or the device
-    position, the step and win_off; out is (S, n, m, N) (stream_windows), empty when no window ends inside the chunk."""
+    position, the step and win_off; out is (S, n, m, N) (stream_windows), empty when no window ends inside the chunk.
+    pool = 2 / 4 (float32, step 1: cheb_time_stream_relu_pool): tgcn_series_pool_plan, then ONE call of the _stream_pool entry -- the same
+    projection and ring update with relu + pool as the epilogue, z (S, n/pool, Tc, N) -- or, H == 1, of the pooled entry on the chunk."""
     L = _lib.lib()
     S, n, Tc, f = chunk.shape
     K, H, _, N = weight_khfg.shape
     bf16 = state.dtype == BF16
     step = state.stride
     hc, lds = C.c_int32(0), C.c_int32(0)
-    if bf16:
+    if pool:
+        _lib.check(L.tgcn_series_pool_plan(H, f, N, int(f % 4 == 0), 1, pool, C.byref(hc), C.byref(lds)))
+    elif bf16:
         _lib.check(L.tgcn_series_conv_plan_bf16(H, f, N, int(f % 8 == 0), step, C.byref(hc), C.byref(lds)))
     else:
         _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), step, C.byref(hc), C.byref(lds)))
@@ -2060,10 +2186,22 @@ def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state):
         stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)
     # a capturable state takes only chunks of Tc % step == 0 (stream_precheck): off = 0 and m = Tc / step whatever the device position holds
     m, off = (Tc, 0) if step == 1 else ((Tc // step, 0) if state.capturable else stream_windows(state.seen, Tc, step))
-    out = torch.empty((S, n, m, N), dtype=state.dtype, device=x3.device)
+    out = torch.empty((S, n // pool if pool else n, m, N), dtype=state.dtype, device=x3.device)
     b = bias.to(state.dtype).contiguous() if bias is not None else None
     head = (_lib.stream_ptr(), S, n, Tc, f, H, N, K, _lib.ptr(stack))
     where = _lib.ptr(state.pos) if state.capturable else state.head      # the ring's position: device memory, or the host's scalar
+    if pool:
+        mid = (_lib.ptr(Wt), _lib.ptr(b), bias_kind)
+        if state.C:
+            _lib.check(L.tgcn_cheb_project_series_stream_pool_f32(*head, *mid, _lib.ptr(out), pool, _lib.ptr(state.ring), state.ring_ld,
+                                                                  0 if state.capturable else state.head,
+                                                                  _lib.ptr(state.pos) if state.capturable else None, state.dilation))
+        else:
+            _lib.check(L.tgcn_cheb_project_series_pool_f32(*head, *mid, 1, _lib.ptr(out), None, pool, 1, 0, 0, 1))
+            if state.capturable:
+                _lib.check(L.tgcn_series_stream_advance(_lib.stream_ptr(), where, Tc, 0))       # no ring, but seen still counts
+        state.advance(Tc)
+        return out
     if step > 1:
         tail = (_lib.ptr(out) if m else None, _lib.ptr(state.ring), state.ring_ld, 0 if state.capturable else state.head,
                 _lib.ptr(state.pos) if state.capturable else None, step, off)
@@ -2248,3 +2386,33 @@ def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=
         if op.perm is not None and out.shape[2]:
             out = relabel_rows(out, op.inv_perm, op.perm).to(dt)
     return out, state
+
+
+def cheb_time_stream_relu_pool(op, chunk, weight, bias, bias_kind, mode, pool, state=None, dilation=1, capturable=False):
+    """cheb_time_stream with relu and the max over `pool` consecutive vertices in the projection's epilogue (inference only): chunk
+    (S, n, Tc[, f]) -> (z (S, n/pool, Tc, N), state), z bit-identical to tgcn_relu_pool_f32 on cheb_time_stream's out.  The state is
+    cheb_time_stream's own and leaves the call as that function leaves it, so pooled and unpooled steps may alternate within a recording
+    and GraphedStream captures a chain with pooled layers unchanged; state, dilation and capturable as there.
+    A reordered operand runs the unfused composition (series_pool_is_fused).  TgcnError before anything launches: bfloat16 parameters,
+    pool outside {2, 4}, n % pool != 0, and every refusal cheb_time_stream makes; there is no fused= and no stride= (a state made for a
+    window step is refused as a state of another stride)."""
+    who = "cheb_time_stream_relu_pool"
+    if param_dtype(weight, bias, who) == BF16:
+        raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
+    dt, (S, n, f, K, H), dilation = stream_precheck(chunk, weight, bias, state, dilation, who, capturable=capturable)
+    pool = check_pool(pool, n, who)
+    if state is not None and state.op is not op:
+        raise _lib.TgcnError("%s: the state was made for another operand -- one state per layer and graph" % who)
+    _lib.require_device(chunk, weight, bias)
+    if state is None:
+        state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device, capturable=capturable)
+    with torch.no_grad():
+        if chunk.dim() == 3:
+            chunk, weight = chunk.unsqueeze(3), weight.unsqueeze(2)
+        chunk, bias = _to_operand_labels(op, chunk, bias, bias_kind)      # the ring lives in the operand's labels
+        if series_pool_is_fused(op, pool, stream=True):
+            return _stream_chunk(chunk, weight, bias, op, mode, bias_kind, state, pool=pool), state
+        out = _stream_chunk(chunk, weight, bias, op, mode, bias_kind, state)
+        if op.perm is not None:
+            out = relabel_rows(out, op.inv_perm, op.perm)
+        return _relu_pool_view(out, pool), state

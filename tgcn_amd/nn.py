@@ -633,3 +633,73 @@ def cheb_relu_pool(layer, x, *graph_args, pool=4):
         # learnable edge weights: the gradient w.r.t. them belongs to the layer function; relu + pool as their own pass behind it
         return F.ReluPoolFn.apply(layer(x, *graph_args), pool)
     return F.cheb_relu_pool(*layer._layer_args(x, *graph_args), pool)
+
+
+def _series_pool_layer(layer, graph_args, who):
+    """(edge_index, edge_weight) of a cheb_series_relu_pool / cheb_stream_relu_pool call after the checks that need no operand: the layer's
+    class, float32 parameters, fixed edge weights"""
+    if not isinstance(layer, (TGCNCheb_H, ChebTimeConv)):
+        raise _lib.TgcnError("%s: the layer is a TGCNCheb_H or a ChebTimeConv, got %s" % (who, type(layer).__name__))
+    edge = isinstance(layer, ChebTimeConv)
+    if len(graph_args) not in ((1, 2) if edge else (0,)):
+        raise _lib.TgcnError("%s: %s takes %s after the series" % (who, type(layer).__name__, "edge_index[, edge_weight]" if edge else "no graph arguments"))
+    edge_index, edge_weight = (tuple(graph_args) + (None, None))[:2]
+    if _compute_dtype(layer, edge_weight) != torch.float32:
+        raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
+    if edge_weight is not None and edge_weight.requires_grad:
+        raise _lib.TgcnError("%s: learnable edge weights (edge_weight.requires_grad) are not supported -- use forward on the windowed batch, "
+                             "then gcn_pool / gcn_pool_4" % who)
+    return edge_index, edge_weight
+
+
+def _series_pool_bias(layer):
+    """(bias, bias_kind, mode) of the two time layers as the F.cheb_time_* functions take them"""
+    if isinstance(layer, TGCNCheb_H):
+        return (None if layer.bias is None else layer.bias.reshape(-1), F.BIAS_NONE if layer.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER)
+    return layer.bias, F.BIAS_NONE if layer.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV
+
+
+def cheb_series_relu_pool(layer, series, *graph_args, pool=4, as_series=False, stride=1, padding=0, dilation=1):
+    """gcn_pool_4(F.relu(layer.forward_series(series, ...)))  (pool=4; pool=2: gcn_pool)  in one fused op -- the caller pattern of
+    cheb_relu_pool for the streaming time-window layers.  layer is a TGCNCheb_H or a ChebTimeConv, graph_args are ChebTimeConv's
+    (edge_index[, edge_weight]); as_series, stride, padding, dilation as in forward_series.  -> z (S*nwin, n/pool, g) or, as_series=True,
+    (S, n/pool, nwin, g): a series on the coarsened graph, which the next layer streams over.  relu and the max over `pool` consecutive
+    vertices run in the projection's epilogue, so the layer's full output -- the large tensor of this path, g/f times the series -- is never
+    allocated, in inference or in training; values and all gradients are bit-identical to the hand-written composition
+    (F.cheb_time_windows_relu_pool).  A single channel runs the MFMA kernels in every geometry; an operand the layer keeps reordered runs
+    the unfused calls.  Dropout between relu and pool, as in the reference's training script, means the unfused calls: forward_series,
+    relu, dropout, gcn_pool_4.
+    TgcnError before an operand is built: bfloat16 parameters, pool outside {2, 4}, n % pool != 0, a learnable edge_weight, and every
+    refusal forward_series makes for the same arguments.  No time_chunk."""
+    who = "cheb_series_relu_pool"
+    edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
+    if series.dim() in (3, 4):
+        F.check_pool(pool, series.shape[1], who)
+    series, W, geom = _series_args(layer, series, stride, padding, dilation)
+    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
+    bias, bias_kind, mode = _series_pool_bias(layer)
+    return F.cheb_time_windows_relu_pool(op, series, W, bias, bias_kind, mode, pool, as_series=as_series, stride=geom[0], padding=geom[1:3],
+                                         dilation=geom[3])
+
+
+def cheb_stream_relu_pool(layer, chunk, *graph_args, pool=4, state=None, dilation=1, capturable=False):
+    """gcn_pool_4(F.relu(out)) of (out, state) = layer.forward_stream(chunk, ...) in one fused op (inference only): -> (z (S, n/pool, Tc, g),
+    state).  The state is forward_stream's own F.SeriesStreamState and leaves the call as forward_stream leaves it: pooled and unpooled
+    steps may alternate on it, and a chain with pooled layers is captured by GraphedStream unchanged (capturable=True).  layer,
+    graph_args and pool as in cheb_series_relu_pool; state, dilation, capturable as in forward_stream.  TgcnError before an operand is
+    built: bfloat16 parameters, pool outside {2, 4}, n % pool != 0, a learnable edge_weight, and every refusal forward_stream makes.
+    No fused= and no stride=."""
+    who = "cheb_stream_relu_pool"
+    edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
+    chunk, W = _stream_args(layer, chunk)
+    F.check_pool(pool, chunk.shape[1], who)
+    F.stream_precheck(chunk, W, layer.bias, state, dilation, who, capturable)      # refusals come before the operand is built
+    if isinstance(layer, TGCNCheb_H):
+        _state_operand_check(layer, state, layer._operand_key(chunk.device))
+        op = layer._operand(chunk.device)
+    else:
+        _state_operand_check(layer, state, layer._operand_key(chunk, edge_index, edge_weight))
+        op = layer._operand(chunk, edge_index, edge_weight)
+    bias, bias_kind, mode = _series_pool_bias(layer)
+    return F.cheb_time_stream_relu_pool(op, chunk, W, bias, bias_kind, mode, pool, state=state, dilation=dilation, capturable=capturable)
+

@@ -11,6 +11,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py --stream --fused [--include parent=FILE] [--out profiles/r14_series_stream_fused.json]
     python tools/series_bench.py --stream --stride 2,2,2 [--repeats 3] [--include parent=FILE] [--out profiles/r16_series_stream_stride.json]
     python tools/series_bench.py --time-chunk 64,256 [--repeats 3] [--include parent=FILE] [--out profiles/r17_series_time_chunk.json]
+    python tools/series_bench.py --relu-pool 4 [--repeats 3] [--out profiles/r18_series_relu_pool.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -48,7 +49,12 @@ profiles/r16_series_stream_stride.json.
 recordings, T = 1200: (a) 32 -> 64 and (b), the unchunked call against time_chunk=Tc for each Tc (DESIGN.md 3.10 "Time chunks"), in the same
 run, alternating, --repeats event timings of --steps steps each, and torch.cuda.max_memory_allocated above the allocation before the step.
 On a tree whose forward_series has no `time_chunk` keyword only the unchunked column is taken, which is how the parent commit's file for
---include LABEL=FILE is made; default --out profiles/r17_series_time_chunk.json."""
+--include LABEL=FILE is made; default --out profiles/r17_series_time_chunk.json.
+--relu-pool P (2 or 4) times tgcn_amd.cheb_series_relu_pool(layer, series, pool=P) against the hand-written composition
+gcn_pool_4(relu(layer.forward_series(series))) (P = 2: gcn_pool; on the series layout through the (S, n, nwin*g) view) on the same commit:
+case (a) at 1 -> 32 window-major and at 32 -> 64 in the series layout, and case (b), forward and forward + backward.  The two sides
+alternate within the run, --repeats event timings each (median and spread); per side the peak of max_memory_allocated above the pre-call
+level, and torch.equal of the results and of every gradient; default --out profiles/r18_series_relu_pool.json."""
 import argparse
 import json
 import os
@@ -589,6 +595,94 @@ def main_time_chunk(args):
         json.dump(res, f, indent=1)
 
 
+def main_relu_pool(args):
+    dev = torch.device("cuda:0")
+    pool = args.relu_pool
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, repeats=args.repeats,
+               pool=pool, cases={})
+    torch.manual_seed(0)
+    pool_fn = tgcn_amd.gcn_pool_4 if pool == 4 else tgcn_amd.gcn_pool
+
+    def case(name, desc, layer, series, as_series):
+        series = series.requires_grad_(True)
+
+        def fused():
+            return tgcn_amd.cheb_series_relu_pool(layer, series, pool=pool, as_series=as_series)
+
+        def composition():
+            out = torch.relu(layer.forward_series(series, as_series=as_series))
+            if not as_series:
+                return pool_fn(out)
+            S, n, nwin, g = out.shape
+            return pool_fn(out.view(S, n, -1)).view(S, n // pool, nwin, g)
+
+        def clear():
+            layer.zero_grad(set_to_none=True)
+            series.grad = None
+
+        def step_of(fn, train):
+            def step():
+                if train:
+                    clear()
+                    z = fn()
+                    z.backward(torch.ones_like(z))
+                else:
+                    with torch.no_grad():
+                        fn()
+            return step
+
+        sides = (("fused", fused), ("composition", composition))
+        entry = dict(desc=desc, fused_by_predicate=bool(F.series_pool_is_fused(layer._operand(dev), pool)), series_bytes=series.numel() * 4)
+        grads = {}
+        for train in (False, True):
+            ms, peak = {k: [] for k, _ in sides}, {}
+            for _ in range(args.repeats):               # alternating: both sides once per repeat
+                for k, fn in sides:
+                    step = step_of(fn, train)
+                    ms[k].append(events_ms(step, args.steps, args.warmup))
+                    clear()
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    base = torch.cuda.memory_allocated()
+                    step()
+                    torch.cuda.synchronize()
+                    peak[k] = torch.cuda.max_memory_allocated() - base
+                    if train:
+                        grads[k] = [series.grad.clone()] + [p.grad.clone() for p in layer.parameters()]
+            col = {}
+            for k, _ in sides:
+                col[k] = dict(ms_per_call=ms[k], median=sorted(ms[k])[len(ms[k]) // 2], spread=round(max(ms[k]) - min(ms[k]), 4),
+                              peak_bytes_above_baseline=peak[k])
+            col["fused_over_composition_ms"] = round(col["fused"]["median"] / col["composition"]["median"], 3)
+            col["fused_over_composition_peak"] = round(peak["fused"] / peak["composition"], 3)
+            entry["forward_backward" if train else "forward"] = col
+        with torch.no_grad():
+            entry["results_equal"] = bool(torch.equal(fused(), composition()))
+        entry["gradients_equal"] = all(bool(torch.equal(a, b)) for a, b in zip(grads["fused"], grads["composition"]))
+        res["cases"][name] = entry
+        print(json.dumps({name: entry}), flush=True)
+        grads.clear()
+        clear()
+        torch.cuda.empty_cache()
+
+    op = dti148(dev)
+    S, T, H, K = 8, 284, 15, 10
+    l1 = tgcn_amd.TGCNCheb_H(op, 1, 32, K, H).to(dev)
+    case("a_dti148_1to32", "dti148 S=8 T=284 H=15 K=10 f=1 -> g=32, window-major", l1, torch.randn(S, op.n, T, device=dev), False)
+    del l1
+    l2 = tgcn_amd.TGCNCheb_H(op, 32, 64, K, H).to(dev)
+    case("a_dti148_32to64_series", "dti148 S=8 T=284 H=15 K=10 f=32 -> g=64, series layout", l2, torch.randn(S, op.n, T, 32, device=dev), True)
+    del l2
+    n, row, col, val = synth.sheet_mesh(300, device=dev)
+    opm = GraphOperand.from_coo(n, row, col, val, dev)
+    lm = tgcn_amd.TGCNCheb_H(opm, 4, 32, 5, 15).to(dev)
+    case("b_mesh90k_4to32", "sheet_mesh(300) n=%d S=1 T=75 H=15 K=5 f=4 -> g=32, window-major" % n, lm, torch.randn(1, n, 75, 4, device=dev), False)
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r18_series_relu_pool.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def stride_arg(text):
     parts = tuple(int(v) for v in text.split(","))
     return parts[0] if len(parts) == 1 else parts
@@ -609,6 +703,8 @@ def main():
     ap.add_argument("--fused", action="store_true", help="with --stream: the one-launch step next to the eager one (profiles/r14_series_stream_fused.json)")
     ap.add_argument("--time-chunk", type=lambda t: tuple(int(v) for v in t.split(",")), default=None, metavar="Tc[,Tc...]",
                     help="a training step on T = 1200, unchunked against each time_chunk (profiles/r17_series_time_chunk.json)")
+    ap.add_argument("--relu-pool", type=int, choices=(2, 4), default=None, metavar="P",
+                    help="cheb_series_relu_pool against gcn_pool_4(relu(forward_series)) on the same commit (profiles/r18_series_relu_pool.json)")
     ap.add_argument("--include", action="append", default=[], metavar="LABEL=FILE",
                     help="put another run's --out file (the parent commit's, a repeat of this one) into this one under runs[LABEL], with "
                          "each shared case's ms per call relative to this run")
@@ -616,6 +712,10 @@ def main():
     args = ap.parse_args()
     if args.dtype == "bf16":
         return main_bf16(args)
+    if args.relu_pool is not None:
+        if args.time_chunk is not None or args.stream or args.dilation or args.conv:
+            ap.error("--relu-pool P runs alone")
+        return main_relu_pool(args)
     if args.time_chunk is not None:
         if min(args.time_chunk) < 1 or args.stream or args.dilation or args.conv:
             ap.error("--time-chunk Tc[,Tc...] (integers >= 1) runs alone")
