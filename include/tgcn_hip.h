@@ -203,7 +203,12 @@ int tgcn_profile_stop(int32_t* kinds, float* ms, int32_t capacity, int32_t* coun
  *   "x3_tail"         1 (default): the rows of a thinly filled last round of the wide bf16x3 kernel go out as 128-row tiles; 0: never
  *   "small_dense"     dense small operands: 2 (default) bf16x3 on the matrix pipe when the batch fills the chip, 1 exact
  *                     fp32 MFMA only, 0 vector-ALU one-launch kernels
- *   "small_narrow"    0: C <= 4 inputs use the output-side one-launch kernel (default 1: input-side recursion) */
+ *   "small_narrow"    0: C <= 4 inputs use the output-side one-launch kernel (default 1: input-side recursion)
+ *   "x3_stream_cap"   workgroups of the co-schedulable streaming projection (0, default: one per two CUs)
+ *   "compact_overlap" 1 (default): the compacted fp32 layer runs projections on the library's side stream beside its hop launches
+ *                     where that pays; 0: everything on the caller's stream, one kernel after the other
+ *   "compact_overlap_group"   time steps per group (default 3): a group's projection runs beside the next group's hops
+ *   "compact_overlap_min_mb"  ... only when one time step's compact hop tensor is larger than this (default 256, the Infinity Cache) */
 int tgcn_set_tuning(const char* key, int32_t value);
 /* Every switch above back to its default, for the calling thread (ABI v5; thread-local since v7).  A harness that sets one restores
  * them with this call in its teardown, whatever happened in between (tests/conftest.py does after every test). */
@@ -284,6 +289,20 @@ int tgcn_cheb_project_f32(void* stream, int64_t M, int32_t Kc, int32_t N, int32_
 int tgcn_cheb_project_mapped_f32(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const float* const* a, const int64_t* lda,
                                  const float* W, const float* bias, int32_t bias_kind, int64_t n_vertices, int64_t interleave, const int32_t* rowmap,
                                  uint32_t mapped_terms, int32_t nbatch, const int64_t* a_bs, int64_t out_bs, float* out, int64_t ldo);
+
+/* tgcn_cheb_project_mapped_f32 at interleave = 1 through the STREAMING bf16x3 kernel, whatever the number of rows (rows of 32 / 64 floats,
+ * N <= 64, 16-byte aligned operands and strides, no more weight than the LDS holds: TGCN_ERR_UNSUPPORTED otherwise); rowmap nullable.
+ * tile_counter == NULL: the form the dispatch takes on its own (1024-thread workgroups, one per CU, tiles dealt round robin).
+ * tile_counter != NULL (4 bytes of device memory, zeroed by this call on `stream`): the co-schedulable form the compacted layer runs beside
+ * its hop launches -- 256-thread workgroups, by default one per two CUs ("x3_stream_cap"), whose waves claim their tiles from the counter.  Both forms
+ * give the same bits. */
+int tgcn_cheb_project_stream_f32(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const float* const* a, const int64_t* lda,
+                                 const float* W, const float* bias, int32_t bias_kind, int64_t n_vertices, const int32_t* rowmap, uint32_t mapped_terms,
+                                 int32_t nbatch, const int64_t* a_bs, int64_t out_bs, float* out, int64_t ldo, int32_t* tile_counter);
+
+/* Kernels the calling thread has launched on the library's side stream so far (the compacted layer's projections beside the hops; none
+ * while the caller's stream is being captured, on small operands, or with "compact_overlap" = 0). */
+int64_t tgcn_side_stream_launches(void);
 
 /* Streaming time windows (replaces materialising the T-H+1 overlapping windows of
  * load/data_hcp.py:116-154 and running TGCNCheb_H on each): series[t] are the hop tensors of ONE recording,

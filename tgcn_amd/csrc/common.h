@@ -106,6 +106,38 @@ thread_local TuneInt g_x3_form{2};          // bf16x3 projection, aligned operan
 thread_local TuneInt g_x3_tail{1};          // project_x3v2_kernel: rows of a thinly filled last round as 128-row tiles (0: 256-row tiles throughout)
 thread_local TuneInt g_small_narrow{1};     // C <= 4 inputs of the one-launch path: input-side recursion (0: output-side kernel)
 thread_local TuneInt g_small_dense{2};      // small dense operands: 2 bf16x3 matrix pipe, 1 fp32 matrix pipe, 0 vector-ALU kernels only
+thread_local TuneInt g_x3_stream_cap{0};    // project_x3_claim_kernel: workgroups per launch (0: one per two CUs, docs/EXPERIMENTS.md A.7)
+thread_local TuneInt g_overlap{1};          // compacted layer: projections on the side stream beside the hops (0: everything on the caller's stream)
+thread_local TuneInt g_overlap_group{3};    // ... time steps per group: a group's kept-row projection runs beside the next group's hops
+thread_local TuneInt g_overlap_min_mb{256}; // ... only when one time step's hop tensor is larger than this many MB (the Infinity Cache)
+
+// ---- the library's own side stream (compacted layer: projections beside the hops).  One lowest-priority, non-blocking
+// stream and a small pool of events per CALLING THREAD and device, created on first use and kept for the life of the process (a thread's
+// exit may come after the runtime's: nothing is destroyed).  Events are handed out round robin: hipStreamWaitEvent takes the record that
+// is current when it is called, so an event may be recorded again as soon as its wait has been issued.
+struct SideStream {
+  hipStream_t st = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  int next = 0;
+  hipEvent_t event() { hipEvent_t e = ev[next]; next = (next + 1) & 3; return e; }
+};
+thread_local std::map<int, SideStream>* g_side = nullptr;
+thread_local int64_t g_side_launches = 0;      // kernels the calling thread has put on its side streams (tgcn_side_stream_launches)
+
+inline SideStream* side_stream() {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  if (!g_side) g_side = new std::map<int, SideStream>();
+  SideStream& s = (*g_side)[dev];
+  if (s.st) return &s;
+  int least = 0, greatest = 0;
+  if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) { (void)hipGetLastError(); least = 0; }
+  // events first, the stream last: whatever a failed attempt did create is kept in `s` and reused by the next one
+  for (auto& e : s.ev)
+    if (!e && hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); e = nullptr; return nullptr; }
+  if (hipStreamCreateWithPriority(&s.st, hipStreamNonBlocking, least) != hipSuccess) { (void)hipGetLastError(); s.st = nullptr; return nullptr; }
+  return &s;
+}
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

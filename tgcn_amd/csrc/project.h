@@ -854,8 +854,16 @@ __global__ __launch_bounds__(512) void project_x3v2_kernel(const ProjParams p, c
 //     all samples of the pass (registers).
 // Same arithmetic as project_x3_kernel (three-way split, six products, smallest first, fp32 accumulate over terms and k tiles in order);
 // the order of the 32 products inside one MFMA differs (slot permutation), so results agree to fp32 rounding, not bit for bit.
-template <int NT, int KTILES>
-__global__ __launch_bounds__(1024) void project_x3_stream_kernel(const ProjParams p, const int64_t ntiles) {
+// NWAVES = 16 (project_x3_stream_kernel: one 1024-thread workgroup per CU, tiles dealt round robin) is the form of a launch that has the chip to itself.  NWAVES = 4
+// (project_x3_claim_kernel) is the CO-SCHEDULABLE form the compacted layer puts on its side stream while hop launches fill the chip: a 256-thread workgroup takes 4 of
+// a CU's 32 wave slots (and the LDS the hop does not use), so it finds room in the tail of a hop launch and stays through the launches that follow, and its waves CLAIM their
+// 16-row tiles from a counter in device memory (`claim`, zeroed before the launch; one atomicAdd per wave and tile, issued a tile ahead) --
+// a workgroup that has not been placed yet holds no work, whatever the number of workgroups that do run.  A tile's arithmetic does not depend on
+// the wave that computes it: both forms give the same bits.  No workgroup waits for another one.
+template <int NT, int KTILES, int NWAVES>
+__device__ __forceinline__ void x3_stream_body(const ProjParams& p, const int64_t ntiles, int32_t* __restrict__ claim) {
+  static_assert(NWAVES == 16 || NWAVES == 4, "1024-thread static form or 256-thread claiming form");
+  constexpr bool CLAIM = NWAVES == 4;
   extern __shared__ __align__(16) unsigned char stream_smem[];
   using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
   bf16x8* Wf = reinterpret_cast<bf16x8*>(stream_smem);        // [term][kt][nt][plane][lane]: 16 bytes per lane
@@ -864,7 +872,7 @@ __global__ __launch_bounds__(1024) void project_x3_stream_kernel(const ProjParam
   const int r16 = lane & 15, g = lane >> 4;
   {
     const int nfrag = p.nterms * KTILES * NT * 64;
-    for (int f = tid; f < nfrag; f += 1024) {
+    for (int f = tid; f < nfrag; f += NWAVES * 64) {
       const int fl = f & 63, blk = f >> 6;                      // blk = (term * KTILES + kt) * NT + nt
       const int fnt = blk % NT, fkt = (blk / NT) % KTILES, ft = blk / (NT * KTILES);
       const int n = fnt * 16 + (fl & 15), fg = fl >> 4;
@@ -882,7 +890,9 @@ __global__ __launch_bounds__(1024) void project_x3_stream_kernel(const ProjParam
     }
   }
   __syncthreads();
-  const int64_t nwaves = (int64_t)gridDim.x * 16;
+  const int64_t nwaves = (int64_t)gridDim.x * NWAVES;
+  // claiming form: the next unclaimed tile (lane 0 asks, the wave shares the answer; numbers at or beyond ntiles mean "none left")
+  auto claim_issue = [&]() -> int32_t { return lane == 0 ? atomicAdd(claim, 1) : 0; };
   const bool map_out = p.rowmap != nullptr;
   const int units = p.nbatch * p.nterms;                        // (sample, term) units of one tile, sample-major
 
@@ -893,7 +903,14 @@ __global__ __launch_bounds__(1024) void project_x3_stream_kernel(const ProjParam
   // (round 6: the tile number is wave-uniform and lives in scalar registers, and a lane's clamped row of a tile is RECOMPUTED from it where
   //  it is needed -- two vector instructions -- instead of being carried across the tile loop for this and the next tile: the <4, 2>
   //  instantiation kept four loop-invariant registers in scratch before its loop)
-  int64_t tile = (int64_t)blockIdx.x * 16 + wave;
+  int64_t tile, tile_n;                                          // this tile and the one after it
+  if constexpr (CLAIM) {
+    tile = __builtin_amdgcn_readfirstlane(claim_issue());
+    tile_n = tile < ntiles ? (int64_t)__builtin_amdgcn_readfirstlane(claim_issue()) : ntiles;
+  } else {
+    tile = (int64_t)blockIdx.x * 16 + wave;
+    tile_n = tile + nwaves;
+  }
   int32_t rrow = 0, rrow_next = 0;
   auto row_of = [&](int64_t t) -> int32_t { const int64_t m = t * 16 + r16; return (int32_t)(m < p.M ? m : p.M - 1); };
   auto ok_of = [&](int64_t t) -> bool { return t * 16 + r16 < p.M; };
@@ -988,14 +1005,16 @@ __global__ __launch_bounds__(1024) void project_x3_stream_kernel(const ProjParam
 
   if (tile < ntiles) {
     rrow = fetch_map(tile);
-    rrow_next = fetch_map(tile + nwaves);
+    rrow_next = fetch_map(tile_n);
     load_unit(0, row_of(tile), rrow, xa);
   }
   while (tile < ntiles) {
     const int64_t orow = map_out ? rrow : row_of(tile);
     const bool row_ok = ok_of(tile);
+    // the tile after the next one is claimed now and looked at when this tile is done: the counter's round trip hides behind the tile's units
+    int32_t claimed = 0;
+    if constexpr (CLAIM) { if (tile_n < ntiles) claimed = claim_issue(); }
     load_bias(orow);
-    const int64_t tile_n = tile + nwaves;
     // units of this tile two at a time (statically named register buffers); the unit after the tile's last one is unit 0 of the next tile
     for (int u = 0; u < units; u += 2) {
       if (u + 1 < units) load_unit(u + 1, row_of(tile), rrow, xb);
@@ -1011,8 +1030,21 @@ __global__ __launch_bounds__(1024) void project_x3_stream_kernel(const ProjParam
       compute_unit(u + 1, xb, orow, row_ok);
     }
     tile = tile_n; rrow = rrow_next;
-    rrow_next = fetch_map(tile + nwaves);
+    if constexpr (CLAIM) tile_n = tile < ntiles ? (int64_t)__builtin_amdgcn_readfirstlane(claimed) : ntiles;
+    else tile_n = tile + nwaves;
+    rrow_next = fetch_map(tile_n);
   }
+}
+
+template <int NT, int KTILES>
+__global__ __launch_bounds__(1024) void project_x3_stream_kernel(const ProjParams p, const int64_t ntiles) {
+  x3_stream_body<NT, KTILES, 16>(p, ntiles, nullptr);
+}
+
+// (4 waves per SIMD as the register bound, like the 1024-thread form: a wave of this kernel displaces two of the headline's hop waves, not more)
+template <int NT, int KTILES>
+__global__ __launch_bounds__(256, 4) void project_x3_claim_kernel(const ProjParams p, const int64_t ntiles, int32_t* __restrict__ claim) {
+  x3_stream_body<NT, KTILES, 4>(p, ntiles, claim);
 }
 
 // W-resident variant for the common case where the whole folded weight fits in LDS (nterms*Kc*N*4 <= 80 KB).

@@ -61,6 +61,7 @@ int tgcn_abi_version(void) { return TGCN_ABI_VERSION; }
 void tgcn_reset_tuning(void) {
   g_hop_variant.store(0); g_hop_remap.store(1); g_hop_seg_remap.store(0); g_hop_mix.store(0); g_hop_stream.store(1); g_hop_lds_pad.store(0);
   g_proj_variant.store(0); g_small_dense.store(2); g_small_narrow.store(1); g_x3_form.store(2); g_x3_tail.store(1);
+  g_x3_stream_cap.store(0); g_overlap.store(1); g_overlap_group.store(3); g_overlap_min_mb.store(256);
 }
 
 int tgcn_set_tuning(const char* key, int32_t value) {
@@ -75,8 +76,14 @@ int tgcn_set_tuning(const char* key, int32_t value) {
   if (key && strcmp(key, "small_narrow") == 0) { g_small_narrow.store(value); return TGCN_OK; }
   if (key && strcmp(key, "x3_form") == 0) { g_x3_form.store(value); return TGCN_OK; }
   if (key && strcmp(key, "x3_tail") == 0) { g_x3_tail.store(value != 0); return TGCN_OK; }
+  if (key && strcmp(key, "x3_stream_cap") == 0) { if (value < 0) TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: x3_stream_cap %d", value); g_x3_stream_cap.store(value); return TGCN_OK; }
+  if (key && strcmp(key, "compact_overlap") == 0) { g_overlap.store(value != 0); return TGCN_OK; }
+  if (key && strcmp(key, "compact_overlap_group") == 0) { if (value < 1) TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: compact_overlap_group %d", value); g_overlap_group.store(value); return TGCN_OK; }
+  if (key && strcmp(key, "compact_overlap_min_mb") == 0) { if (value < 0) TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: compact_overlap_min_mb %d", value); g_overlap_min_mb.store(value); return TGCN_OK; }
   TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: unknown key");
 }
+
+int64_t tgcn_side_stream_launches(void) { return g_side_launches; }
 
 int tgcn_profile_start(int32_t capacity) {
   if (capacity <= 0) TGCN_FAIL(TGCN_ERR_INVALID, "profile: capacity %d", capacity);
@@ -204,11 +211,19 @@ int tgcn_csr_hop2_bf16(void* stream, const tgcn_csr* A, const tgcn_csr_sched* S,
   return hop_impl(stream, A, S, nb, C, X, Z, alpha, beta, Z2, gamma, Y, P, workspace, workspace_bytes, 1);
 }
 
+// What the compacted layer (and tgcn_cheb_project_stream_f32) ask of project_impl beyond a plain call:
+struct StreamAsk {
+  bool query;          // launch nothing: `streams` = whether this call would take the streaming bf16x3 kernel
+  bool streams;
+  bool force;          // the streaming kernel also below its row threshold (a part of a pass that takes it as a whole); TGCN_ERR_UNSUPPORTED where the shape has none
+  int32_t* claim;      // non-null: the 256-thread claiming form on a capped number of workgroups, tiles from this device counter (zeroed here, stream-ordered)
+};
 static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const float* const* a,
                         const int64_t* lda, const float* W, const float* bias, int32_t bias_kind,
                         int64_t n_vertices, int64_t interleave, int32_t accumulate, float* out, int64_t ldo,
                         int32_t win_n, int32_t win_t, int32_t bias_cols = -1, const int32_t* rowmap = nullptr, uint32_t mapped = 0,
-                        int32_t nbatch = 1, const int64_t* a_bs = nullptr, int64_t out_bs = 0, int32_t pool = 0, uint8_t* pool_idx = nullptr);
+                        int32_t nbatch = 1, const int64_t* a_bs = nullptr, int64_t out_bs = 0, int32_t pool = 0, uint8_t* pool_idx = nullptr,
+                        StreamAsk* ask = nullptr);
 
 // THE dispatch of the projection: which kernel a shape takes.  project_impl launches what this returns and project_pool_fusable asks the
 // same function, so the fused relu + pool epilogue can never be requested from a kernel that does not have it.
@@ -231,7 +246,7 @@ struct ProjChoice {
 // stream_ok: the call has nothing the streaming kernel lacks (pool epilogue, accumulate, interleave, windows) -- project_impl knows,
 // the shape-only query (pool fusability) passes false: that form lives in project_x3_kernel.
 static ProjChoice project_choose(int64_t M, int32_t Kc, int32_t N, int32_t nterms, bool vec4, bool vec_epilogue, bool has_rowmap, bool windows,
-                                 bool stream_ok = false, int32_t nbatch = 1) {
+                                 bool stream_ok = false, int32_t nbatch = 1, bool force_stream = false) {
   ProjChoice c;
   const int pv = g_proj_variant.load();
   c.nt = N <= 16 ? 1 : (N <= 32 ? 2 : 4);
@@ -257,7 +272,7 @@ static ProjChoice project_choose(int64_t M, int32_t Kc, int32_t N, int32_t nterm
   if (stream_ok && !windows && vec4 && vec_epilogue && (Kc == 32 || Kc == 64) && N <= 64 && x3_stream_lds(Kc, N, nterms) <= kX3StreamMaxLds &&
       x3_stream_lds(Kc, N, nterms) <= (size_t)lds_optin_limit() && M < (int64_t)INT32_MAX &&
       /* n_vertices is checked by the caller of this function where it matters: project_impl passes it through stream_ok */
-      (pv == 6 || (pv == 0 && use_x3 && M * (int64_t)nbatch >= kX3StreamMinRows))) {
+      (pv == 6 || force_stream || (pv == 0 && use_x3 && M * (int64_t)nbatch >= kX3StreamMinRows))) {
     c.kernel = kProjX3Stream;
     return c;
   }
@@ -299,6 +314,16 @@ int tgcn_cheb_project_mapped_f32(void* stream, int64_t M, int32_t Kc, int32_t N,
                       a_bs ? a_bs : zero_bs, out_bs);
 }
 
+int tgcn_cheb_project_stream_f32(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t nterms, const float* const* a, const int64_t* lda,
+                                 const float* W, const float* bias, int32_t bias_kind, int64_t n_vertices, const int32_t* rowmap, uint32_t mapped_terms,
+                                 int32_t nbatch, const int64_t* a_bs, int64_t out_bs, float* out, int64_t ldo, int32_t* tile_counter) {
+  if (nbatch < 1 || (nbatch > 1 && !a_bs)) TGCN_FAIL(TGCN_ERR_INVALID, "project_stream: bad argument");
+  int64_t zero_bs[kMaxTerms] = {0};
+  StreamAsk ask = {false, false, true, tile_counter};
+  return project_impl(stream, M, Kc, N, nterms, a, lda, W, bias, bias_kind, n_vertices, 1, 0, out, ldo, 0, 0, -1, rowmap, mapped_terms, nbatch,
+                      a_bs ? a_bs : zero_bs, out_bs, 0, nullptr, &ask);
+}
+
 int tgcn_cheb_project_windows_f32(void* stream, int64_t n_vertices, int32_t T, int32_t H, int32_t N, int32_t nterms,
                                   const float* const* series, const float* W, const float* bias, int32_t bias_kind,
                                   float* out) {
@@ -313,7 +338,7 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
                         const int64_t* lda, const float* W, const float* bias, int32_t bias_kind,
                         int64_t n_vertices, int64_t interleave, int32_t accumulate, float* out, int64_t ldo,
                         int32_t win_n, int32_t win_t, int32_t bias_cols, const int32_t* rowmap, uint32_t mapped,
-                        int32_t nbatch, const int64_t* a_bs, int64_t out_bs, int32_t pool, uint8_t* pool_idx) {
+                        int32_t nbatch, const int64_t* a_bs, int64_t out_bs, int32_t pool, uint8_t* pool_idx, StreamAsk* ask) {
   if (nbatch < 1 || (nbatch > 1 && !a_bs)) TGCN_FAIL(TGCN_ERR_INVALID, "project: nbatch %d", nbatch);
   if (M <= 0 || Kc <= 0 || N <= 0 || nterms <= 0 || !a || !lda || !W || !out) TGCN_FAIL(TGCN_ERR_INVALID, "project: bad argument");
   if (int drc = check_pointer_device(out, (hipStream_t)stream, "project")) return drc;
@@ -344,7 +369,10 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
   bool strides4 = (out_bs % 4 == 0);
   if (nbatch > 1) for (int t = 0; t < nterms; ++t) strides4 = strides4 && (a_bs[t] % 4 == 0);
   const bool stream_ok = pool <= 1 && !accumulate && interleave == 1 && win_n == 0 && strides4 && bias_cols < 0 && n_vertices < (int64_t)INT32_MAX;
-  const ProjChoice choice = project_choose(M, Kc, N, nterms, vec4, p.vec_epilogue != 0, rowmap != nullptr, win_n != 0, stream_ok, nbatch);
+  const ProjChoice choice = project_choose(M, Kc, N, nterms, vec4, p.vec_epilogue != 0, rowmap != nullptr, win_n != 0, stream_ok, nbatch, ask && ask->force);
+  if (ask && ask->query) { ask->streams = choice.kernel == kProjX3Stream; return TGCN_OK; }
+  if (ask && (ask->force || ask->claim) && choice.kernel != kProjX3Stream)
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project: no streaming bf16x3 kernel for this shape (rows of 32 / 64 floats, <= 64 columns, 16-byte aligned operands; Kc=%d N=%d terms=%d)", Kc, N, nterms);
   if (rowmap && interleave != 1 && choice.kernel != kProjNarrow)
     TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project: a row map together with interleave is the vector-ALU kernel's form (nterms*Kc <= %d, N %% 4 == 0, M >= 4096)", kNarrowMaxK);
   if (pool > 1) {     // fused relu + max-pool epilogue: only where the dispatch takes a kernel that has it
@@ -399,11 +427,23 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
     const int snt = x3_stream_nt(N);
     const size_t lds = x3_stream_lds(Kc, N, nterms);
     const int64_t ntiles = (M + 15) / 16;
+    int32_t* claim = ask ? ask->claim : nullptr;
     int64_t gx = (ntiles + 15) / 16;
     if (gx > cu_count()) gx = cu_count();           // persistent: one 1024-thread workgroup per CU, waves take tiles round robin
+    if (claim) {
+      // the form that runs beside other kernels: 256-thread workgroups, at most `cap` of them, tiles claimed from *claim.  One per two CUs:
+      // what the hops lose is the same per byte streamed beside them at 64 ... 256 workgroups, the forward is 1 ms shorter at 128 than at 256 (A.7)
+      const int64_t cap = g_x3_stream_cap.load() > 0 ? g_x3_stream_cap.load() : (cu_count() + 1) / 2;
+      gx = (ntiles + 3) / 4;
+      if (gx > cap) gx = cap;
+      if (hipMemsetAsync(claim, 0, sizeof(int32_t), st) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "project: memset of the tile counter failed");
+    }
     ProfScope ps(TGCN_PROF_PROJECT, st);
 #define TGCN_PROJ_S(NTV, KTV)                                                                                              \
-  {                                                                                                                        \
+  if (claim) {                                                                                                             \
+    allow_large_lds((const void*)project_x3_claim_kernel<NTV, KTV>, (int)kX3StreamMaxLds);                                 \
+    hipLaunchKernelGGL((project_x3_claim_kernel<NTV, KTV>), dim3((unsigned)gx), dim3(256), lds, st, p, ntiles, claim);     \
+  } else {                                                                                                                 \
     allow_large_lds((const void*)project_x3_stream_kernel<NTV, KTV>, (int)kX3StreamMaxLds);                                \
     hipLaunchKernelGGL((project_x3_stream_kernel<NTV, KTV>), dim3((unsigned)gx), dim3(1024), lds, st, p, ntiles);          \
   }
@@ -997,6 +1037,7 @@ static void cfwd_ws_layout(const tgcn_csr_sched* S, int32_t mode, int32_t K, int
   *hop_bytes = align_up((size_t)qc * (size_t)(n_c + 1) * C * sizeof(float), 256) + 65 * 256;   // staggered like fwd_ws_layout
   *off_part = keep ? 0 : (size_t)compact_nterm_bufs(mode, K) * *hop_bytes;
   *total = *off_part + align_up(tgcn_csr_hop_workspace_bytes(S, 1, C, 1), 256);      // hops run one time step per launch
+  *total += 256;            // last: the tile counter of the side stream's projections (one at a time: the side stream is one queue)
 }
 
 size_t tgcn_cheb_compact_layer_workspace_bytes(const tgcn_csr_sched* S, int32_t mode, int32_t K, int64_t q, int64_t n_c, int32_t C, int64_t q_chunk,
@@ -1041,7 +1082,8 @@ int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgc
   if (!workspace || workspace_bytes < total) TGCN_FAIL(TGCN_ERR_WORKSPACE, "compact_layer: workspace %zu < %zu", workspace_bytes, total);
   char* ws = (char*)workspace;
   float* part = (float*)(ws + off_part);
-  const size_t part_bytes = total - off_part;
+  const size_t part_bytes = total - 256 - off_part;
+  int32_t* claim = (int32_t*)(ws + total - 256);
   const int64_t bs_c = (n_c + 1) * (int64_t)C;            // sample stride of a compact hop tensor
   const int k_first = mode == 1 ? 0 : 1;                  // first term that lives in a compact buffer
   // term k of the pass: in the caller's buffer the terms are contiguous ([term][q][n_c + 1][C]), in the workspace staggered
@@ -1062,9 +1104,82 @@ int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgc
   a_bs[0] = mode == 1 ? bs_c : n * (int64_t)C;
   for (int k = 1; k < K; ++k) a_bs[k] = bs_c;
   const bool vec_rows = (C % 4 == 0) && (((uintptr_t)x & 15) == 0);
+  // Projections beside the hops: a hop launch leaves the matrix pipes, the LDS and most of the HBM bandwidth unused, and the
+  // projections are streams that need little else.  Where a pass's projections take the streaming kernel, the left-out rows' projection
+  // of the whole pass and the kept rows' projection of every group of `grp` time steps but the last go to the side stream in the
+  // co-schedulable form (256-thread workgroups that claim their tiles), the former from the start of the pass, the latter behind its
+  // group's last hop; the last group's projection follows on the caller's stream with the chip to itself.  The side stream is joined at the
+  // end of every pass (the next pass's hops overwrite the hop tensors).  Only where one time step's hop tensor exceeds the Infinity Cache
+  // (smaller operands are launch-bound) and never under stream capture (a captured graph gets no parallel branch).  Same kernels' arithmetic
+  // row by row: the result does not depend on the path.
+  const int64_t grp = g_overlap_group.load();
+  bool overlap = g_overlap.load() != 0 && n_c * (int64_t)C * (int64_t)sizeof(float) > ((int64_t)g_overlap_min_mb.load() << 20) && qc > grp;
+  if (overlap) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); overlap = false; }
+    else if (cs != hipStreamCaptureStatusNone) overlap = false;
+  }
+  SideStream* side = overlap ? side_stream() : nullptr;
+  if (overlap && !side) TGCN_FAIL(TGCN_ERR_LAUNCH, "compact_layer: no side stream");
+  // joins the side stream into the caller's on every way out of a pass, errors included
+  struct SideJoin {
+    SideStream* s; hipStream_t st; bool forked = false;
+    int fork() {
+      hipEvent_t e = s->event();
+      if (hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(s->st, e, 0) != hipSuccess) return -1;
+      forked = true;
+      return 0;
+    }
+    int join() {
+      if (!forked) return 0;
+      forked = false;
+      hipEvent_t e = s->event();
+      return (hipEventRecord(e, s->st) != hipSuccess || hipStreamWaitEvent(st, e, 0) != hipSuccess) ? -1 : 0;
+    }
+    ~SideJoin() { (void)join(); }
+  } sj{side, st};
   for (int64_t q0 = 0; q0 < q; q0 += qc) {
     const int64_t qn = (q - q0 < qc) ? (q - q0) : qc;
     const float* x0 = x + q0 * n * C;
+    float* const o = out + q0 * n * N;
+    const float* const W_empty = (mode == 1 || W_left) ? W_left : W;
+    const float* xt[1] = {x0};
+    const int64_t xbs[1] = {n * (int64_t)C};
+    terms[0] = mode == 1 ? hop_ptr(0) : x0;
+    for (int k = 1; k < K; ++k) terms[k] = hop_ptr(k);
+    // what of this pass goes to the side stream: asked of the projection's own dispatch, for the pass as a whole
+    bool side_kept = false, side_empty = false;
+    if (overlap && qn > grp) {            // at least two groups: something to run beside
+      StreamAsk ask = {true, false, false, nullptr};
+      rc = project_impl(stream, n_c, C, N, K, terms, ldas, W, bias, bias_kind, n, 1, 0, o, N, 0, 0, -1, rows, mode == 1 ? 0u : 1u, (int32_t)qn, a_bs,
+                        n * (int64_t)N, 0, nullptr, &ask);
+      if (rc != TGCN_OK) return rc;
+      side_kept = ask.streams;
+      if (n_empty > 0) {
+        rc = project_impl(stream, n_empty, C, N, 1, xt, ldas, W_empty, bias, bias_kind, n, 1, 0, o, N, 0, 0, -1, empty_rows, 1u, (int32_t)qn, xbs,
+                          n * (int64_t)N, 0, nullptr, &ask);
+        if (rc != TGCN_OK) return rc;
+        side_empty = ask.streams;
+      }
+    }
+    if (side_kept || side_empty) {
+      if (sj.fork() != 0) TGCN_FAIL(TGCN_ERR_LAUNCH, "compact_layer: fork to the side stream failed");
+    }
+    if (side_empty) {
+      StreamAsk ask = {false, false, true, claim};
+      rc = project_impl(side->st, n_empty, C, N, 1, xt, ldas, W_empty, bias, bias_kind, n, 1, 0, o, N, 0, 0, -1, empty_rows, 1u, (int32_t)qn, xbs,
+                        n * (int64_t)N, 0, nullptr, &ask);
+      if (rc != TGCN_OK) return rc;
+      ++g_side_launches;
+    }
+    // the kept rows' projection of time steps [b0, b1) of the pass, every term and the output moved to the group's first time step
+    auto project_group = [&](int64_t b0, int64_t b1, bool on_side) -> int {
+      const float* gt[kMaxTerms];
+      for (int k = 0; k < K; ++k) gt[k] = terms[k] + b0 * a_bs[k];
+      StreamAsk ask = {false, false, true, on_side ? claim : nullptr};
+      return project_impl(on_side ? (void*)side->st : stream, n_c, C, N, K, gt, ldas, W, bias, bias_kind, n, 1, 0, o + b0 * n * N, N, 0, 0, -1, rows,
+                          mode == 1 ? 0u : 1u, (int32_t)(b1 - b0), a_bs, n * (int64_t)N, 0, nullptr, &ask);
+    };
     // hops: one launch per hop and time step (a launch's gather working set stays one (n_c, C) slab).
     // mode 0 (monomials of the folded weight): P_1 = A_first x (columns in the caller's labels), P_k = A_rest P_{k-1}.
     // mode 1 (Chebyshev): T_0 = the kept rows of x, T_1 = A_rest T_0, T_k = 2 A_rest T_{k-1} - T_{k-2}.
@@ -1086,24 +1201,30 @@ int tgcn_cheb_compact_layer_f32(void* stream, const tgcn_csr* A_first, const tgc
         }
         if (rc != TGCN_OK) return rc;
       }
+      // a group of time steps is through its hops: its projection goes behind them on the side stream, beside the next group's hops
+      if (side_kept && (b + 1) % grp == 0 && b + 1 < qn) {
+        hipEvent_t e = side->event();
+        if (hipEventRecord(e, st) != hipSuccess || hipStreamWaitEvent(side->st, e, 0) != hipSuccess)
+          TGCN_FAIL(TGCN_ERR_LAUNCH, "compact_layer: event for the side stream failed");
+        if ((rc = project_group(b + 1 - grp, b + 1, true)) != TGCN_OK) return rc;
+        ++g_side_launches;
+      }
     }
-    // projection of the pass's qn time steps in one launch per row class: the per-vertex bias is read once per pass
-    terms[0] = mode == 1 ? hop_ptr(0) : x0;
-    for (int k = 1; k < K; ++k) terms[k] = hop_ptr(k);
-    float* o = out + q0 * n * N;
+    // projection of the pass's qn time steps in one launch per row class: the per-vertex bias is read once per pass (once per group where
+    // the groups' projections run beside the hops)
     // kept vertices: all K terms (mode 0: x through the row map, hop tensors in compact rows; mode 1: every term in compact rows)
-    rc = project_impl(stream, n_c, C, N, K, terms, ldas, W, bias, bias_kind, n, 1, 0, o, N, 0, 0, -1, rows, mode == 1 ? 0u : 1u, (int32_t)qn, a_bs,
-                      n * (int64_t)N);
+    if (side_kept) rc = project_group((qn - 1) / grp * grp, qn, false);
+    else rc = project_impl(stream, n_c, C, N, K, terms, ldas, W, bias, bias_kind, n, 1, 0, o, N, 0, 0, -1, rows, mode == 1 ? 0u : 1u, (int32_t)qn, a_bs,
+                           n * (int64_t)N);
     if (rc != TGCN_OK) return rc;
     // the others.  mode 0: P_k = 0 for k >= 1, so out = x W'_0 + bias.  mode 1: the left-out vertices are ISOLATED (no entries, never pointed at):
     // T_k = x, 0, -x, 0, ... so out = x (W_0 - W_2 + W_4 - ...) + bias = x W_left + bias.
-    if (n_empty > 0) {
-      const float* xt[1] = {x0};
-      const int64_t xbs[1] = {n * (int64_t)C};
-      rc = project_impl(stream, n_empty, C, N, 1, xt, ldas, (mode == 1 || W_left) ? W_left : W, bias, bias_kind, n, 1, 0, o, N, 0, 0, -1, empty_rows, 1u, (int32_t)qn,
+    if (n_empty > 0 && !side_empty) {
+      rc = project_impl(stream, n_empty, C, N, 1, xt, ldas, W_empty, bias, bias_kind, n, 1, 0, o, N, 0, 0, -1, empty_rows, 1u, (int32_t)qn,
                         xbs, n * (int64_t)N);
       if (rc != TGCN_OK) return rc;
     }
+    if (sj.join() != 0) TGCN_FAIL(TGCN_ERR_LAUNCH, "compact_layer: join of the side stream failed");
   }
   return TGCN_OK;
 }
