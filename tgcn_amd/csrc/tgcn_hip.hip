@@ -1354,7 +1354,14 @@ int tgcn_cheb_windows_backward_f32(void* stream, int64_t S, int64_t n_vertices, 
   return TGCN_OK;
 }
 
-// ---- streaming time windows of multi-channel series (windows.h)
+// ---- streaming time windows of multi-channel series (windows.h, windows_bf16.h)
+// The host side of every entry below is built from four pieces: one geometry (series_geom, series_stream_check), one set
+// of fillers for the kernels' parameter structs, one trait per element type (SeriesF32, SeriesBf16) and three drivers templated on it --
+// series_forward (a whole series), series_chunk_forward (a chunk behind a ring) and series_backward.  The exported entries name their
+// rule and forward.
+// The drivers are templates, so the section leaves the extern "C" block; its exported entries keep C linkage from tgcn_hip.h's declarations.
+}  // extern "C"
+
 // Chooses HC (weight time rows per staged span) and the dynamic LDS of series_gemm_kernel: the whole horizon when four spans and the weight
 // tile fit 64 KB, else the largest chunk that does, else the largest that fits the device's opt-in limit; 0 when even one row does not.
 // stride: the window step (the span of hc rows then holds 31 * min(stride, hc) + hc time rows, series_span_floats).
@@ -1368,37 +1375,45 @@ static int series_gemm_lds(int H, int f, int NT, bool vec, int stride, int* hc_o
   return 0;
 }
 
+// series_gemm_lds's three regimes on bf16 span bytes: the weight tile is NT*16 columns of kPbLd bf16
+static int series_gemm_bf16_lds(int H, int f, int NT, bool vec, int stride, int* hc_out) {
+  auto bytes = [&](int hc) { return ((size_t)NT * 16 * kPbLd + 4 * (size_t)series_bf16_span_elems(hc, f, vec, stride)) * sizeof(hbf16); };   // 64-bit
+  const size_t limits[2] = {64 * 1024, (size_t)lds_optin_limit()};
+  for (size_t lim : limits)
+    for (int hc = H; hc >= 1; --hc)
+      if (bytes(hc) <= lim) { *hc_out = hc; return (int)bytes(hc); }
+  return 0;
+}
+typedef int (*SeriesLdsFn)(int H, int f, int NT, bool vec, int stride, int* hc_out);
+
 static int series_gemm_nt(int N) { return N <= 16 ? 1 : (N <= 32 ? 2 : 4); }
-
-int tgcn_series_conv_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes) {
-  if (H < 1 || f < 1 || N < 1 || stride < 1 || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_conv_plan: bad argument");
-  int h = 0;
-  const int lds = series_gemm_lds(H, f, series_gemm_nt(N), vec != 0, stride, &h);
-  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_conv_plan: %d channels per time row do not fit the LDS span", f);
-  *hc = h; *lds_bytes = lds;
-  return TGCN_OK;
-}
-
-int tgcn_series_gemm_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t* hc, int32_t* lds_bytes) {
-  if (H < 1 || f < 1 || N < 1 || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_gemm_plan: bad argument");
-  int h = 0;
-  const int lds = series_gemm_lds(H, f, series_gemm_nt(N), vec != 0, 1, &h);
-  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_gemm_plan: %d channels per time row do not fit the LDS span", f);
-  *hc = h; *lds_bytes = lds;
-  return TGCN_OK;
-}
 
 // The pooled form's scratch [wave][window][col] lives where the weight tile and the spans were: the launch takes the larger of the two
 static int series_pool_lds(int gemm_lds, int NT) { const int sc = 4 * kSgWin * NT * 16 * (int)sizeof(float); return gemm_lds > sc ? gemm_lds : sc; }
 static bool series_pool_ok(int64_t n, int32_t pool) { return (pool == 2 || pool == 4) && n >= 1 && n % pool == 0; }
 
-int tgcn_series_pool_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t pool, int32_t* hc, int32_t* lds_bytes) {
-  if (H < 1 || f < 1 || N < 1 || stride < 1 || (pool != 2 && pool != 4) || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_pool_plan: bad argument");
+// The four plan queries: pooled asks for pool 2 / 4 and answers the pooled launch's bytes
+static int series_plan(const char* who, SeriesLdsFn lds_of, int32_t H, int32_t f, int32_t N, bool vec, int32_t stride, bool pooled, int32_t pool,
+                       int32_t* hc, int32_t* lds_bytes) {
+  if (H < 1 || f < 1 || N < 1 || stride < 1 || (pooled && pool != 2 && pool != 4) || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
   int h = 0;
-  const int lds = series_gemm_lds(H, f, series_gemm_nt(N), vec != 0, stride, &h);
-  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_pool_plan: %d channels per time row do not fit the LDS span", f);
-  *hc = h; *lds_bytes = series_pool_lds(lds, series_gemm_nt(N));
+  const int lds = lds_of(H, f, series_gemm_nt(N), vec, stride, &h);
+  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, f);
+  *hc = h; *lds_bytes = pooled ? series_pool_lds(lds, series_gemm_nt(N)) : lds;
   return TGCN_OK;
+}
+
+int tgcn_series_gemm_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t* hc, int32_t* lds_bytes) {
+  return series_plan("series_gemm_plan", series_gemm_lds, H, f, N, vec != 0, 1, false, 0, hc, lds_bytes);
+}
+int tgcn_series_conv_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes) {
+  return series_plan("series_conv_plan", series_gemm_lds, H, f, N, vec != 0, stride, false, 0, hc, lds_bytes);
+}
+int tgcn_series_pool_plan(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t pool, int32_t* hc, int32_t* lds_bytes) {
+  return series_plan("series_pool_plan", series_gemm_lds, H, f, N, vec != 0, stride, true, pool, hc, lds_bytes);
+}
+int tgcn_series_conv_plan_bf16(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes) {
+  return series_plan("series_conv_plan_bf16", series_gemm_bf16_lds, H, f, N, vec != 0 && f % 8 == 0, stride, false, 0, hc, lds_bytes);
 }
 
 // Phase-major tiles of the DILATED kernels: min(dil, nwin) phases hold a window, the longest ceil(nwin / dil) of them.
@@ -1409,6 +1424,24 @@ static void series_dilated_tiles(int32_t nwin, int32_t dil, int32_t* tpp, int32_
   *tpv = nph * *tpp;
 }
 
+// Everything about one GEMM launch that can refuse: the tiles and the grid's limits, then the plan.  Both launchers start here, and so does
+// the chunk backward, which has to know before its first launch.
+struct SeriesLaunchPlan { int32_t tpp, tpv, hc, lds, NT; int64_t nq, ntiles, gx, gy; };
+static int series_launch_plan(SeriesLdsFn lds_of, int64_t S, int64_t n, int32_t nwin, int32_t H, int32_t f, int32_t N, bool vec, int stride, int dil,
+                              int pool, const char* who, SeriesLaunchPlan* o) {
+  o->tpp = 0; o->tpv = (nwin + kSgWin - 1) / kSgWin;
+  if (dil > 1) series_dilated_tiles(nwin, dil, &o->tpp, &o->tpv);
+  o->nq = pool ? (n + 3) / 4 : 0;                      // pooled: one workgroup per (recording, vertex quad, window block)
+  o->ntiles = S * (pool ? o->nq : n) * o->tpv;
+  o->gx = pool ? o->ntiles : (o->ntiles + 3) / 4;
+  o->NT = series_gemm_nt(N);
+  o->gy = ((int64_t)N + o->NT * 16 - 1) / (o->NT * 16);
+  if (o->gx > (int64_t)INT32_MAX || o->gy > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
+  o->lds = lds_of(H, f, o->NT, vec, stride, &o->hc);
+  if (!o->lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, f);
+  return TGCN_OK;
+}
+
 // stride >= 2 takes the STRIDED instantiations; stride 1 (the input gradient's phases included) the ones without a step; dil >= 2 (at step 1)
 // the DILATED ones, planned as step 1
 // carry (the stream entries): the CARRY instantiations, which stage the time rows before the chunk from p.ring -- at step 1 (dilated or
@@ -1417,26 +1450,16 @@ static void series_dilated_tiles(int32_t nwin, int32_t dil, int32_t* tpp, int32_
 // scratch's bytes where they exceed the GEMM's; not built with a window step on a chunk
 static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1, int dil = 1,
                               bool carry = false, int pool = 0) {
-  p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
-  p.dil = dil;
-  if (dil > 1) series_dilated_tiles(p.nwin, dil, &p.tpp, &p.tpv);
-  p.ntiles = S * p.n * p.tpv;
-  p.pool = pool;
-  if (pool) { p.nq = (p.n + 3) / 4; p.ntiles = S * p.nq * p.tpv; }
-  const int64_t gx = pool ? p.ntiles : (p.ntiles + 3) / 4;
-  const int NT = series_gemm_nt(p.N);
-  const int64_t gy = (p.N + NT * 16 - 1) / (NT * 16);
-  if (gx > (int64_t)INT32_MAX || gy > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
-  int hc = 0;
-  int lds = series_gemm_lds(p.H, p.f, NT, vec, stride, &hc);
-  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, p.f);
-  if (pool) {
-    if (carry && stride > 1) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a pooled window step on a chunk is not built", who);
-    lds = series_pool_lds(lds, NT);
-  }
+  SeriesLaunchPlan lp;
+  if (int rc = series_launch_plan(series_gemm_lds, S, p.n, p.nwin, p.H, p.f, p.N, vec, stride, dil, pool, who, &lp)) return rc;
+  if (pool && carry && stride > 1) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a pooled window step on a chunk is not built", who);
+  p.tpv = lp.tpv; p.dil = dil; p.ntiles = lp.ntiles; p.pool = pool;
+  if (dil > 1) p.tpp = lp.tpp;
+  if (pool) p.nq = lp.nq;
+  const int NT = lp.NT, hc = lp.hc, lds = pool ? series_pool_lds(lp.lds, NT) : lp.lds;
   p.HC = hc;
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = series_row_floats(hc, p.f, vec, stride);
-  const dim3 grid((unsigned)gx, (unsigned)gy);
+  const dim3 grid((unsigned)lp.gx, (unsigned)lp.gy);
   ProfScope ps(TGCN_PROF_PROJECT, st);
 #define TGCN_SERIES_GEMM(NT_, VEC_, STR_, DIL_, ...)                                                                      \
   do {                                                                                                                    \
@@ -1465,6 +1488,101 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
   return TGCN_OK;
 }
 
+// out_f32: the input gradient's fp32 columns; otherwise bf16 output.  stride >= 2 takes the STRIDED instantiations, dil >= 2 (at step 1) the
+// DILATED ones, planned as step 1.
+static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride = 1,
+                                   int dil = 1, bool carry = false) {
+  SeriesLaunchPlan lp;
+  if (int rc = series_launch_plan(series_gemm_bf16_lds, S, p.n, p.nwin, p.H, p.f, p.N, vec, stride, dil, 0, who, &lp)) return rc;
+  p.tpv = lp.tpv; p.dil = dil; p.ntiles = lp.ntiles;
+  if (dil > 1) p.tpp = lp.tpp;
+  const int NT = lp.NT, hc = lp.hc, lds = lp.lds;
+  p.HC = hc;
+  p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = vec ? series_bf16_row_elems(p.f, p.lst) : p.f;
+  const dim3 grid((unsigned)lp.gx, (unsigned)lp.gy);
+  ProfScope ps(TGCN_PROF_PROJECT, st);
+#define TGCN_SERIES_GEMM_B(NT_, VEC_, STR_, OUT_, DIL_, ...)                                                                      \
+  do {                                                                                                                            \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>, lds);  \
+    hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>), grid, dim3(kBlock), lds, st, p);    \
+  } while (0)
+#define TGCN_SERIES_GEMM_B_NT(VEC_, STR_, OUT_, DIL_, ...)                                                                        \
+  do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                                 \
+       else if (NT == 2) TGCN_SERIES_GEMM_B(2, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                            \
+       else TGCN_SERIES_GEMM_B(4, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__); } while (0)
+  if (carry) {          // the stream entries: bf16 out, the time rows before the chunk from p.ring (a window step: STRIDED && CARRY)
+    if (stride > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16, false, true); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16, false, true); }
+    else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true, true); }
+    else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, false, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, false, true); }
+  } else if (dil > 1) {        // dilated taps at step 1: the forward, and the input gradient in one launch
+    if (out_f32) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, true); else TGCN_SERIES_GEMM_B_NT(false, false, float, true); }
+    else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true); }
+  } else if (out_f32) {        // the input gradient: one launch per phase, each at step 1
+    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, false); else TGCN_SERIES_GEMM_B_NT(false, false, float, false);
+  } else if (stride == 1) {
+    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, false); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, false);
+  } else {
+    if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16, false); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16, false);
+  }
+#undef TGCN_SERIES_GEMM_B_NT
+#undef TGCN_SERIES_GEMM_B
+  return TGCN_OK;
+}
+
+// ---- one trait per element type: what the drivers below need to know about fp32 and bf16 tensors
+struct SeriesF32 {
+  typedef float Elem;
+  typedef SeriesGemmParams Params;
+  typedef SeriesWgradParams WgradParams;
+  static constexpr int kUnit = 4;                    // elements per 16-byte access
+  static constexpr const char* kSuffix = "_f32";     // "tgcn_cheb_" + who + kSuffix is the entry's name
+  static constexpr SeriesLdsFn lds = series_gemm_lds;
+  static int launch(hipStream_t st, Params& p, int64_t S, bool vec, bool, const char* who, int stride, int dil, bool carry, int pool) {
+    return series_gemm_launch(st, p, S, vec, who, stride, dil, carry, pool);
+  }
+  static void set_bias(Params& p, const void* bias, int32_t kind, int32_t) { p.bias = (const float*)bias; p.bias_kind = kind; }
+  static void flip(hipStream_t st, const float* W, float* Wd, int K, int H, int f, int N, int stride) {
+    hipLaunchKernelGGL(series_flip_weight_kernel, dim3(grid_1d((int64_t)K * H * f * N)), dim3(kBlock), 0, st, W, Wd, K, H, f, N, stride);
+  }
+  static void wgrad_rows(WgradParams& q, int64_t ld) { q.Tf = (int32_t)ld; }
+  static void wgrad_ring(WgradParams& q, const void* ring, int64_t S, int64_t n, int64_t ring_ld, int32_t C, int32_t head) {
+    q.ring = (const float*)ring; q.ring_ks = S * n * ring_ld; q.ring_is = ring_ld; q.C = C; q.head = head;
+  }
+  // conv: a step or padding; carried: the chunk behind a ring
+  static void wgrad(hipStream_t st, dim3 grid, const WgradParams& q, bool conv, bool dilated, bool carried) {
+    if (carried) {
+      if (dilated) hipLaunchKernelGGL((series_wgrad_partial_kernel<true, true, true>), grid, dim3(64), 0, st, q);
+      else hipLaunchKernelGGL((series_wgrad_partial_kernel<true, false, true>), grid, dim3(64), 0, st, q);
+    } else if (dilated) hipLaunchKernelGGL((series_wgrad_partial_kernel<true, true>), grid, dim3(64), 0, st, q);
+    else if (conv) hipLaunchKernelGGL(series_wgrad_partial_kernel<true>, grid, dim3(64), 0, st, q);
+    else hipLaunchKernelGGL(series_wgrad_partial_kernel<false>, grid, dim3(64), 0, st, q);
+  }
+};
+
+struct SeriesBf16 {
+  typedef hbf16 Elem;
+  typedef SeriesGemmBf16Params Params;
+  typedef SeriesWgradBf16Params WgradParams;
+  static constexpr int kUnit = 8;
+  static constexpr const char* kSuffix = "";         // who ends in _bf16
+  static constexpr SeriesLdsFn lds = series_gemm_bf16_lds;
+  static int launch(hipStream_t st, Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride, int dil, bool carry, int) {
+    return series_gemm_bf16_launch(st, p, S, vec, out_f32, who, stride, dil, carry);
+  }
+  static void set_bias(Params& p, const void* bias, int32_t kind, int32_t dtype) { p.bias = bias; p.bias_kind = kind; p.bias_bf16 = dtype == TGCN_DTYPE_BF16; }
+  static void flip(hipStream_t st, const hbf16* W, hbf16* Wd, int K, int H, int f, int N, int stride) {
+    hipLaunchKernelGGL(series_flip_weight_bf16_kernel, dim3(grid_1d((int64_t)K * H * f * N)), dim3(kBlock), 0, st, W, Wd, K, H, f, N, stride);
+  }
+  static void wgrad_rows(WgradParams& q, int64_t ld) { q.st_is = ld; }
+  static void wgrad_ring(WgradParams&, const void*, int64_t, int64_t, int64_t, int32_t, int32_t) {}      // no bf16 chunk backward
+  static void wgrad(hipStream_t st, dim3 grid, const WgradParams& q, bool conv, bool dilated, bool) {
+    if (dilated) hipLaunchKernelGGL((series_wgrad_bf16_partial_kernel<true, true>), grid, dim3(64), 0, st, q);
+    else if (conv) hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<true>, grid, dim3(64), 0, st, q);
+    else hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<false>, grid, dim3(64), 0, st, q);
+  }
+};
+
+// ---- one geometry
 static bool series_shape_ok(int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K) {
   return S >= 1 && n >= 1 && n < (int64_t)INT32_MAX && f >= 1 && H >= 1 && T >= H && N >= 1 && K >= 1 && (int64_t)T * f < (int64_t)INT32_MAX &&
          (int64_t)H * f < (int64_t)INT32_MAX / 2 && (int64_t)H * N < (int64_t)INT32_MAX / 2 && (int64_t)K * f < (int64_t)INT32_MAX;
@@ -1481,10 +1599,6 @@ static bool series_conv_shape_ok(int64_t S, int64_t n, int32_t T, int32_t f, int
 static int32_t series_conv_stride(int32_t T, int32_t stride, int32_t pl, int32_t pr) { return stride < T + pl + pr ? stride : T + pl + pr; }
 static int64_t series_conv_nwin(int32_t T, int32_t H, int32_t stride, int32_t pl, int32_t pr) { return ((int64_t)T + pl + pr - H) / stride + 1; }
 
-// One tap has nothing to dilate: H == 1 at any dilation >= 1 is the undilated window, and the _dilated entries hand it to the _conv entries
-// (at stride 1; with a step the combination stays refused like every dilation > 1), so no dilation without a bound reaches a kernel.
-static bool series_dilation_is_one(int32_t H, int32_t stride, int32_t dil) { return dil == 1 || (H == 1 && dil > 1 && stride == 1); }
-
 // Dilated taps: the window spans He = (H - 1) * dilation + 1 time rows, and He takes H's place in the geometry rules of the _conv entries.
 // TGCN_OK, TGCN_ERR_INVALID for a bad value, TGCN_ERR_UNSUPPORTED for dilation > 1 with stride > 1 (not built).  *He_out: the span.
 // For H >= 2 the span bounds the dilation, dil < He <= Tp < 2^25: the 32 windows of a wave, dil time rows apart, stay inside 32 bits.
@@ -1497,101 +1611,41 @@ static int series_dilated_check(int64_t S, int64_t n, int32_t T, int32_t f, int3
   if (!series_conv_shape_ok(S, n, T, f, (int32_t)He, N, K, stride, pl, pr) || !series_shape_ok(S, n, (int32_t)((int64_t)T + pl + pr), f, H, N, K))
     return TGCN_ERR_INVALID;
   if (dil > 1 && stride > 1) return TGCN_ERR_UNSUPPORTED;
-  if (dil > 1 && dil >= He) return TGCN_ERR_INVALID;   // H == 1: no span bounds the dilation (the entries take series_dilation_is_one's way)
+  if (dil > 1 && dil >= He) return TGCN_ERR_INVALID;   // H == 1: no span bounds the dilation (series_geom takes it as the undilated window)
   *He_out = (int32_t)He;
   return TGCN_OK;
 }
 
-static int project_series_impl(hipStream_t st, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, const float* stack,
-                               const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out, int32_t stride, int32_t pl,
-                               int32_t pr, const char* who, int32_t dil = 1, int32_t pool = 0, uint8_t* idx = nullptr) {
-  const int64_t Tf = (int64_t)T * f, nwin = series_conv_nwin(T, (H - 1) * dil + 1, stride, pl, pr);
-  const int64_t no = pool ? n / pool : n;       // vertices of the output: pooled, out and idx are (S*nwin, n/pool, N) or (S, n/pool, nwin, N)
-  SeriesGemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.src = stack; p.W = W; p.bias = bias; p.out = out;
-  p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
-  if (as_series) { p.o_ss = no * nwin * N; p.o_is = nwin * N; p.o_ws = N; }     // (S, n, nwin, N)
-  else { p.o_ss = nwin * no * N; p.o_is = N; p.o_ws = no * N; }                   // (S, nwin, n, N)
-  p.o_gs = 0; p.ocg = N; p.idx = idx;
-  p.n = n; p.Tin = T; p.padl = pl; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
-  const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0);
-  return series_gemm_launch(st, p, S, vec, who, stride, dil, false, pool);
-}
-
-int tgcn_cheb_project_series_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                 const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out) {
-  if (!series_shape_ok(S, n_vertices, T, f, H, N, K) || !stack || !W || !out) TGCN_FAIL(TGCN_ERR_INVALID, "project_series: bad argument");
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series: bias_kind %d", bias_kind);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series")) return drc;
-  if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, 1, 0, 0,
-                                   "project_series")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_f32");
-  return TGCN_OK;
-}
-
-int tgcn_cheb_project_series_conv_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
-                                      int32_t stride, int32_t pad_left, int32_t pad_right) {
-  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right) || !stack || !W || !out)
-    TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv: bad argument");
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv: bias_kind %d", bias_kind);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_conv")) return drc;
-  stride = series_conv_stride(T, stride, pad_left, pad_right);
-  if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, stride, pad_left,
-                                   pad_right, "project_series_conv")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_conv_f32");
-  return TGCN_OK;
-}
-
-int tgcn_cheb_project_series_dilated_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                         const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
-                                         int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
-  if (series_dilation_is_one(H, stride, dilation))
-    return tgcn_cheb_project_series_conv_f32(stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, stride, pad_left, pad_right);
-  int32_t He = 0;
-  const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
-  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "project_series_dilated: dilation %d with stride %d is not built", dilation, stride);
-  if (grc || !stack || !W || !out) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_dilated: bad argument");
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_dilated: bias_kind %d", bias_kind);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, "project_series_dilated")) return drc;
-  if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, out, 1, pad_left,
-                                   pad_right, "project_series_dilated", dilation)) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_dilated_f32");
-  return TGCN_OK;
-}
-
-// ---- relu + vertex max-pool as the projection's epilogue ("relu + pool epilogue"): the _conv / _dilated entries' geometry
-int tgcn_cheb_project_series_pool_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* z,
-                                      uint8_t* idx, int32_t pool, int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
-  const char* who = "project_series_pool";
-  if (!series_pool_ok(n_vertices, pool)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: pool %d of %lld vertices", who, pool, (long long)n_vertices);
-  if (series_dilation_is_one(H, stride, dilation)) {
-    if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-    dilation = 1;
-    stride = series_conv_stride(T, stride, pad_left, pad_right);
-  } else {
-    int32_t He = 0;
-    const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
-    if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "%s: dilation %d with stride %d is not built", who, dilation, stride);
-    if (grc) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+// What a whole-series entry runs at, from what its caller passed, under the entry's rule: plain (no step, no pads: T * 64 is not bounded),
+// conv (step and pads; the step clamped) or dilated (conv's rules on the He-row window; at dilation 1 conv itself).  One tap has nothing to
+// dilate: H == 1 at any dilation >= 1 is the undilated window (at stride 1; with a step the combination stays refused like every
+// dilation > 1), so no dilation without a bound reaches a kernel.  Every forward entry, backward entry and workspace query starts here.
+enum SeriesRule { kSeriesPlain, kSeriesConv, kSeriesDilated };
+struct SeriesGeom { int32_t stride, pl, pr, dil, He; int64_t nwin; };
+static int series_geom(SeriesRule rule, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, int32_t stride, int32_t pl,
+                       int32_t pr, int32_t dil, SeriesGeom* g) {
+  if (rule == kSeriesDilated && (dil == 1 || (H == 1 && dil > 1 && stride == 1))) { rule = kSeriesConv; dil = 1; }
+  int32_t He = H;
+  if (rule == kSeriesPlain) {
+    if (!series_shape_ok(S, n, T, f, H, N, K)) return TGCN_ERR_INVALID;
+  } else if (rule == kSeriesConv) {
+    if (!series_conv_shape_ok(S, n, T, f, H, N, K, stride, pl, pr)) return TGCN_ERR_INVALID;
+    stride = series_conv_stride(T, stride, pl, pr);
+  } else if (int rc = series_dilated_check(S, n, T, f, H, N, K, stride, pl, pr, dil, &He)) {
+    return rc;                                           // accepted: dil > 1 at step 1
   }
-  if (!stack || !W || !z) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
-  if (int drc = check_pointer_device(z, (hipStream_t)stream, who)) return drc;
-  if (int rc = project_series_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, W, bias, bias_kind, as_series, z, stride, pad_left,
-                                   pad_right, who, dilation, pool, idx)) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_pool_f32");
+  *g = SeriesGeom{stride, pl, pr, dil, He, series_conv_nwin(T, He, stride, pl, pr)};
   return TGCN_OK;
 }
 
-// ---- streaming state ("Streaming state"): one chunk of Tc time rows, the C = (H - 1) * dilation rows before it in a ring
-// What both stream entries check before anything is launched: TGCN_OK and *C_out, or TGCN_ERR_INVALID.  The chunk behind C zero rows is a
-// geometry of the _dilated entries (Tp = Tc + C >= He, pad_left = C = He - 1), so their rules bound every number the kernels form.
+// The chunk entries' geometry (DESIGN.md 3.10 "Streaming state"): one chunk of Tc time rows, the C = (H - 1) * dilation rows before it in a
+// ring.  TGCN_OK and *C_out, or TGCN_ERR_INVALID.  The chunk behind C zero rows is a geometry of the _dilated entries (Tp = Tc + C >= He,
+// pad_left = C = He - 1), so their rules bound every number the kernels form.  One tap keeps no ring (C = 0; ring_ld and head unused) and is
+// admitted only where the entry says so (one_tap).
 static int series_stream_check(int64_t S, int64_t n, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K, int32_t dil, int64_t ring_ld,
-                               int32_t head, int32_t* C_out) {
-  if (dil < 1 || Tc < 1 || H < 2) return TGCN_ERR_INVALID;       // one tap keeps no ring: the _conv entry runs it
+                               int32_t head, int32_t* C_out, bool one_tap = false) {
+  if (dil < 1 || Tc < 1 || H < (one_tap ? 1 : 2)) return TGCN_ERR_INVALID;
+  if (H == 1) { *C_out = 0; return series_conv_shape_ok(S, n, Tc, f, 1, N, K, 1, 0, 0) ? TGCN_OK : TGCN_ERR_INVALID; }
   const int64_t C = ((int64_t)H - 1) * dil;
   if (C >= (int64_t)INT32_MAX / 64) return TGCN_ERR_INVALID;
   int32_t He = 0;
@@ -1602,6 +1656,139 @@ static int series_stream_check(int64_t S, int64_t n, int32_t Tc, int32_t f, int3
   return TGCN_OK;
 }
 
+// A chunk's rows inside an output of out_T time rows (the _at entry): rows [out_t0, out_t0 + Tc) of (S, n, out_T, N) or (S*out_T, n, N)
+static bool series_out_slice_ok(int32_t Tc, int32_t out_T, int32_t out_t0) {
+  return out_T >= 1 && out_t0 >= 0 && (int64_t)out_t0 + Tc <= (int64_t)out_T;
+}
+static bool series_stack_ld_ok(int32_t T, int32_t f, int64_t stack_ld) { return stack_ld >= (int64_t)T * f && stack_ld < (int64_t)INT32_MAX; }
+
+static int series_bias_check(const void* bias, int32_t bias_kind, int32_t bias_dtype, const char* who) {
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
+  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "%s: dtype code %d", who, bias_dtype);
+  return TGCN_OK;
+}
+
+// What every driver ends with: the entry's name is "tgcn_cheb_" + who + the trait's suffix
+static int series_launched(const char* who, const char* suffix) {
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "tgcn_cheb_%s%s: %s", who, suffix, hipGetErrorString(e));
+  return TGCN_OK;
+}
+
+// ---- one parameter builder: the fillers of SeriesGemmParams / SeriesGemmBf16Params (the same field names on purpose).  A field no filler
+// names stays zero, which is what its "X only" comment in windows.h asks of a launch without X.
+// The strides of rows of N values per (recording, vertex, time row): as a series (S, n, rows, N), else (S, rows, n, N)
+static void series_layout(int64_t n, int64_t rows, int32_t N, int32_t as_series, int64_t* ss, int64_t* is, int64_t* ws) {
+  if (as_series) { *ss = n * rows * N; *is = rows * N; *ws = N; }
+  else { *ss = rows * n * N; *is = N; *ws = n * N; }
+}
+template <class P>
+static P series_params(int64_t n, int32_t Tin, int32_t padl, int64_t nwin, int32_t H, int32_t f, int32_t N, int32_t nterms) {
+  P p;
+  memset(&p, 0, sizeof(p));
+  p.n = n; p.Tin = Tin; p.padl = padl; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = nterms;
+  return p;
+}
+// the hop stack (K, S, n, ld) with f channels per time row
+template <class P, class E>
+static void series_src_stack(P& p, const E* stack, int64_t S, int64_t n, int64_t ld, int32_t f) {
+  p.src = stack; p.src_ks = S * n * ld; p.src_ss = n * ld; p.src_is = ld; p.src_ts = f;
+}
+// out: rows [t0, t0 + nwin) of n_out vertices x rows time rows x N columns, in either layout
+template <class P, class E>
+static void series_out(P& p, E* out, int64_t n_out, int64_t rows, int32_t N, int32_t as_series, int32_t t0 = 0) {
+  series_layout(n_out, rows, N, as_series, &p.o_ss, &p.o_is, &p.o_ws);
+  p.o_gs = 0; p.ocg = N;
+  p.out = out + (int64_t)t0 * p.o_ws;
+}
+// the ring (nterms, S, n, ring_ld) of the C rows before the chunk
+template <class P, class E>
+static void series_ring(P& p, const E* ring, int64_t S, int64_t n, int64_t ring_ld, int32_t C, int32_t head, const int64_t* pos, int32_t win_off) {
+  p.ring = ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos; p.win_off = win_off;
+}
+// the input gradient: g as a series of N channels (strides g_ss, g_is, g_ws), one term, no bias, columns (k, c) into (K, S, n, Tf); the
+// caller adds W, out and its window step o_ws, and the windows (padl, nwin, H)
+template <class P, class E>
+static P series_over_g(const E* g, int64_t g_ss, int64_t g_is, int64_t g_ws, int32_t g_rows, int64_t S, int64_t n, int64_t Tf, int32_t f, int32_t N, int32_t K) {
+  P p = series_params<P>(n, g_rows, 0, 0, 0, N, K * f, 1);
+  p.src = g; p.src_ks = 0; p.src_ss = g_ss; p.src_is = g_is; p.src_ts = g_ws;
+  p.o_ss = n * Tf; p.o_is = Tf; p.o_gs = S * n * Tf; p.ocg = f;
+  return p;
+}
+// 16-byte staging and copies: whole units per time row and per row, an aligned base -- the stack's rule, and a ring that keeps it
+template <class X>
+static bool series_vec(int32_t f, const void* stack, int64_t ld, const void* ring = nullptr, int64_t ring_ld = 0) {
+  return f % X::kUnit == 0 && ld % X::kUnit == 0 && ((uintptr_t)stack & 15) == 0 && ring_ld % X::kUnit == 0 && ((uintptr_t)ring & 15) == 0;
+}
+
+// ---- driver 1, a whole series: the _series, _conv, _dilated and _pool entries of both element types.  stack_ld: elements between vertex
+// rows (fp32: T * f).  pool 0: none (the _pool entry has checked its own).
+template <class X>
+static int series_forward(const char* who, void* stream, SeriesRule rule, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                          const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype, int32_t bias_kind,
+                          int32_t as_series, void* out, uint8_t* idx, int32_t pool, int32_t stride, int32_t pl, int32_t pr, int32_t dil) {
+  typedef typename X::Elem E;
+  SeriesGeom ge;
+  const int grc = series_geom(rule, S, n, T, f, H, N, K, stride, pl, pr, dil, &ge);
+  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "%s: dilation %d with stride %d is not built", who, dil, stride);
+  if (grc || !stack || !W || !out || !series_stack_ld_ok(T, f, stack_ld)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (int rc = series_bias_check(bias, bias_kind, bias_dtype, who)) return rc;
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
+  typename X::Params p = series_params<typename X::Params>(n, T, ge.pl, ge.nwin, H, f, N, K);
+  series_src_stack(p, (const E*)stack, S, n, stack_ld, f);
+  p.W = (const E*)W;
+  X::set_bias(p, bias, bias_kind, bias_dtype);
+  series_out(p, (E*)out, pool ? n / pool : n, ge.nwin, N, as_series);      // pooled: out and idx hold n / pool vertices
+  if constexpr (std::is_same<E, float>::value) p.idx = idx;
+  if (int rc = X::launch((hipStream_t)stream, p, S, series_vec<X>(f, stack, stack_ld), false, who, ge.stride, ge.dil, false, pool)) return rc;
+  return series_launched(who, X::kSuffix);
+}
+
+int tgcn_cheb_project_series_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                 const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out) {
+  return series_forward<SeriesF32>("project_series", stream, kSeriesPlain, S, n_vertices, T, f, H, N, K, stack, (int64_t)T * f, W, bias, TGCN_DTYPE_F32,
+                                   bias_kind, as_series, out, nullptr, 0, 1, 0, 0, 1);
+}
+
+int tgcn_cheb_project_series_conv_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
+                                      int32_t stride, int32_t pad_left, int32_t pad_right) {
+  return series_forward<SeriesF32>("project_series_conv", stream, kSeriesConv, S, n_vertices, T, f, H, N, K, stack, (int64_t)T * f, W, bias,
+                                   TGCN_DTYPE_F32, bias_kind, as_series, out, nullptr, 0, stride, pad_left, pad_right, 1);
+}
+
+int tgcn_cheb_project_series_dilated_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                         const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
+                                         int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
+  return series_forward<SeriesF32>("project_series_dilated", stream, kSeriesDilated, S, n_vertices, T, f, H, N, K, stack, (int64_t)T * f, W, bias,
+                                   TGCN_DTYPE_F32, bias_kind, as_series, out, nullptr, 0, stride, pad_left, pad_right, dilation);
+}
+
+// relu + vertex max-pool as the projection's epilogue ("relu + pool epilogue"): the _dilated entry's geometry
+int tgcn_cheb_project_series_pool_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* z,
+                                      uint8_t* idx, int32_t pool, int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
+  if (!series_pool_ok(n_vertices, pool)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_pool: pool %d of %lld vertices", pool, (long long)n_vertices);
+  return series_forward<SeriesF32>("project_series_pool", stream, kSeriesDilated, S, n_vertices, T, f, H, N, K, stack, (int64_t)T * f, W, bias,
+                                   TGCN_DTYPE_F32, bias_kind, as_series, z, idx, pool, stride, pad_left, pad_right, dilation);
+}
+
+int tgcn_cheb_project_series_conv_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                       const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                       int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right) {
+  return series_forward<SeriesBf16>("project_series_conv_bf16", stream, kSeriesConv, S, n_vertices, T, f, H, N, K, stack, stack_ld, W, bias, bias_dtype,
+                                    bias_kind, as_series, out, nullptr, 0, stride, pad_left, pad_right, 1);
+}
+
+int tgcn_cheb_project_series_dilated_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                          const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                          int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right,
+                                          int32_t dilation) {
+  return series_forward<SeriesBf16>("project_series_dilated_bf16", stream, kSeriesDilated, S, n_vertices, T, f, H, N, K, stack, stack_ld, W, bias,
+                                    bias_dtype, bias_kind, as_series, out, nullptr, 0, stride, pad_left, pad_right, dilation);
+}
+
+// ---- streaming state ("Streaming state")
 // The ring update launch: rows = K * S * n rows of the stack (ld elements apart) and of the ring; esize: bytes per element (4 / 2);
 // vec: 16-byte accesses (4 floats / 8 bf16 per unit), else one element; pos non-null: head is read on the device (the _pos entries)
 static void series_ring_update_launch(hipStream_t st, const void* stack, void* ring, int64_t rows, int64_t stack_ld, int64_t ring_ld, int32_t f,
@@ -1631,70 +1818,84 @@ int tgcn_series_stream_advance(void* stream, int64_t* pos, int32_t Tc, int32_t C
   return TGCN_OK;
 }
 
-// A chunk's rows inside an output of out_T time rows (the _at entry): rows [out_t0, out_t0 + Tc) of (S, n, out_T, N) or (S*out_T, n, N)
-static bool series_out_slice_ok(int32_t Tc, int32_t out_T, int32_t out_t0) {
-  return out_T >= 1 && out_t0 >= 0 && (int64_t)out_t0 + Tc <= (int64_t)out_T;
-}
-static void series_out_slice(SeriesGemmParams& p, int64_t n, int32_t N, int32_t out_T, int32_t out_t0, int32_t as_series) {
-  if (as_series) { p.o_ss = n * out_T * N; p.o_is = (int64_t)out_T * N; p.o_ws = N; }      // (S, n, out_T, N)
-  else { p.o_ss = (int64_t)out_T * n * N; p.o_is = N; p.o_ws = n * N; }                     // (S, out_T, n, N)
-  p.out += (int64_t)out_t0 * p.o_ws;
-}
+// What tells the chunk entries apart.  The defaults are the _stream entry: every row of the chunk ends a window, written chunk-shaped.
+struct SeriesChunkAsk {
+  int32_t dil = 1, pool = 0;
+  bool sliced = false;           // the _at entry (DESIGN.md 3.10 "Time chunks"): rows [out_t0, out_t0 + Tc) of an output of out_T time rows
+  int32_t out_T = 0, out_t0 = 0, out_as_series = 1;
+  bool one_tap = false;          // H == 1 admitted: no ring (null allowed), nothing to update
+  bool stepped = false;          // the _stream_strided entries (DESIGN.md 3.10 "Window step"): windows end at chunk rows win_off + r * stride;
+  int32_t stride = 1, win_off = 0;     // a chunk may end no window (out null allowed), and the position advances all the same
+};
 
-// Both fp32 stream entries: pos null -> the host's head and two launches; pos non-null -> head read on the device (the head argument is
-// unused and passes the check as 0) and the advance as a third launch
-// out_T > 0 (the _at entry): the chunk's rows go to rows [out_t0, out_t0 + Tc) of an output of out_T time rows, in either layout -- the
-// kernel addresses its output by (o_ss, o_is, o_ws), so only the strides and the base differ; out_T == 0: the chunk-shaped (S, n, Tc, N)
-static int project_series_stream_impl(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
-                                      const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
-                                      int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation, const char* who, int32_t out_T = 0,
-                                      int32_t out_t0 = 0, int32_t out_as_series = 1, int32_t pool = 0) {
-  int32_t C = 0;
-  if (pool && (!series_pool_ok(n_vertices, pool) || out_T)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: pool %d of %lld vertices", who, pool, (long long)n_vertices);
-  if (series_stream_check(S, n_vertices, Tc, f, H, N, K, dilation, ring_ld, head, &C) || !stack || !W || !out || !ring)
-    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-  if (out_T && !series_out_slice_ok(Tc, out_T, out_t0)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
+// ---- driver 2, a chunk of Tc time rows behind the ring of the C rows before it: the _stream, _pos, _stream_pool, _at and _stream_strided
+// entries.  pos null: the host's head; non-null: head is read on the device (the head argument is unused) and the advance is the last
+// launch.  Launches: the CARRY GEMM over the m windows that end inside the chunk (STRIDED && CARRY at a step >= 2; without a ring, H == 1,
+// the plain forms on the chunk from row win_off on), the ring update, the advance.  At step 1 that is the _stream entry's sequence.
+template <class X>
+static int series_chunk_forward(const char* who, void* stream, int64_t S, int64_t n, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype, int32_t bias_kind,
+                                void* out, void* ring, int64_t ring_ld, int32_t head, int64_t* pos, const SeriesChunkAsk& ask) {
+  typedef typename X::Elem E;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t n = n_vertices, Tf = (int64_t)Tc * f;
-  SeriesGemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.src = stack; p.W = W; p.bias = bias; p.out = out;
-  p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
-  p.o_ss = (pool ? n / pool : n) * Tc * N; p.o_is = (int64_t)Tc * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, Tc, N); pooled: n / pool
-  if (out_T) series_out_slice(p, n, N, out_T, out_t0, out_as_series);
-  p.n = n; p.Tin = Tc; p.padl = C; p.nwin = Tc; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
-  p.ring = ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
-  // 16-byte staging and copies: the stack's rule, and a ring that keeps it
-  const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0) && (ring_ld % 4 == 0) && (((uintptr_t)ring & 15) == 0);
-  if (int rc = series_gemm_launch(st, p, S, vec, who, 1, dilation, true, pool)) return rc;
-  series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, vec, Tc, C, head, pos);
+  const int32_t stride = ask.stride, win_off = ask.win_off;
+  int32_t C = 0;
+  if (stride < 1 || win_off < 0 || win_off >= stride || series_stream_check(S, n, Tc, f, H, N, K, ask.dil, ring_ld, pos ? 0 : head, &C, ask.one_tap))
+    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  const bool carry = C > 0;
+  const int32_t dil = carry ? ask.dil : 1;            // one tap has nothing to dilate: no dilation without a bound reaches a kernel
+  const bool own_step = ask.stepped && !(stride == 1 && carry);      // the _stream_strided entries past the _stream entry's own sequence
+  if (pos && !own_step) head = 0;                     // unused with a device position; the _stream_strided entries pass the caller's on
+  const int32_t m = win_off < Tc ? (Tc - win_off - 1) / stride + 1 : 0;       // windows that end inside the chunk
+  // the step the kernel runs at, clamped like the _conv entries' (a step above the padded chunk leaves one window)
+  const int32_t sc = series_conv_stride(Tc, stride, C, 0);
+  if (!stack || !W || (m > 0 && !out) || (carry && !ring) || !series_stack_ld_ok(Tc, f, stack_ld) ||
+      (ask.sliced && !series_out_slice_ok(Tc, ask.out_T, ask.out_t0)))
+    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (int rc = series_bias_check(bias, bias_kind, bias_dtype, who)) return rc;
+  const bool vec = carry ? series_vec<X>(f, stack, stack_ld, ring, ring_ld) : series_vec<X>(f, stack, stack_ld);
+  if (own_step) {       // a chunk that ends no window still moves the ring: the plan's refusal comes first
+    int hc = 0;
+    if (!X::lds(H, f, series_gemm_nt(N), vec, sc, &hc)) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, f);
+  }
+  if (m > 0) {
+    if (int drc = check_pointer_device(out, st, who)) return drc;
+    typename X::Params p = series_params<typename X::Params>(n, Tc, C, m, H, f, N, K);
+    series_src_stack(p, (const E*)stack, S, n, stack_ld, f);
+    p.W = (const E*)W;
+    X::set_bias(p, bias, bias_kind, bias_dtype);
+    if (ask.sliced) series_out(p, (E*)out, n, ask.out_T, N, ask.out_as_series, ask.out_t0);
+    else series_out(p, (E*)out, ask.pool ? n / ask.pool : n, m, N, 1);      // (S, n, m, N); pooled: n / pool
+    if (carry) series_ring(p, (const E*)ring, S, n, ring_ld, C, head, pos, win_off);
+    else { p.src += (int64_t)win_off * f; p.Tin = Tc - win_off; }           // one tap reads no row before the chunk
+    if (int rc = X::launch(st, p, S, vec, false, who, sc, dil, carry, ask.pool)) return rc;
+  }
+  if (carry) series_ring_update_launch(st, stack, ring, K * S * n, stack_ld, ring_ld, f, (int)sizeof(E), vec, Tc, C, head, pos);
   if (pos) series_stream_advance_launch(st, pos, Tc, C);
-  return TGCN_OK;
+  return series_launched(who, X::kSuffix);
 }
 
 int tgcn_cheb_project_series_stream_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
                                         const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
                                         int64_t ring_ld, int32_t head, int32_t dilation) {
-  if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, head, nullptr,
-                                          dilation, "project_series_stream")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_f32");
-  return TGCN_OK;
+  SeriesChunkAsk ask;
+  ask.dil = dilation;
+  return series_chunk_forward<SeriesF32>("project_series_stream", stream, S, n_vertices, Tc, f, H, N, K, stack, (int64_t)Tc * f, W, bias, TGCN_DTYPE_F32,
+                                         bias_kind, out, ring, ring_ld, head, nullptr, ask);
 }
 
 int tgcn_cheb_project_series_stream_pos_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
                                             const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
                                             int64_t ring_ld, int64_t* pos, int32_t dilation) {
   if (!pos) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_pos: bad argument");
-  if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, 0, pos,
-                                          dilation, "project_series_stream_pos")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pos_f32");
-  return TGCN_OK;
+  SeriesChunkAsk ask;
+  ask.dil = dilation;
+  return series_chunk_forward<SeriesF32>("project_series_stream_pos", stream, S, n_vertices, Tc, f, H, N, K, stack, (int64_t)Tc * f, W, bias,
+                                         TGCN_DTYPE_F32, bias_kind, out, ring, ring_ld, 0, pos, ask);
 }
 
-// The stream entries' step with the pooled epilogue: z (S, n/pool, Tc, N).  pos null: the host's head; non-null: the device position and the
-// advance.  H == 1 keeps no ring: the pooled entry on the chunk (ring, head and pos unused; the caller's advance counts seen).
+// The stream entries' step with the pooled epilogue: z (S, n/pool, Tc, N).  H == 1 keeps no ring: the pooled entry on the chunk (ring, head
+// and pos unused; the caller's advance counts seen).
 int tgcn_cheb_project_series_stream_pool_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
                                              const float* stack, const float* W, const float* bias, int32_t bias_kind, float* z, int32_t pool,
                                              float* ring, int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation) {
@@ -1702,105 +1903,60 @@ int tgcn_cheb_project_series_stream_pool_f32(void* stream, int64_t S, int64_t n_
   if (!series_pool_ok(n_vertices, pool)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: pool %d of %lld vertices", who, pool, (long long)n_vertices);
   if (H == 1) {
     if (dilation < 1) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-    return tgcn_cheb_project_series_pool_f32(stream, S, n_vertices, Tc, f, 1, N, K, stack, W, bias, bias_kind, 1, z, nullptr, pool, 1, 0, 0, 1);
+    return series_forward<SeriesF32>(who, stream, kSeriesConv, S, n_vertices, Tc, f, 1, N, K, stack, (int64_t)Tc * f, W, bias, TGCN_DTYPE_F32, bias_kind,
+                                     1, z, nullptr, pool, 1, 0, 0, 1);
   }
-  if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, z, ring, ring_ld, pos ? 0 : head, pos,
-                                          dilation, who, 0, 0, 1, pool)) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pool_f32");
-  return TGCN_OK;
+  SeriesChunkAsk ask;
+  ask.dil = dilation; ask.pool = pool;
+  return series_chunk_forward<SeriesF32>(who, stream, S, n_vertices, Tc, f, H, N, K, stack, (int64_t)Tc * f, W, bias, TGCN_DTYPE_F32, bias_kind, z, ring,
+                                         ring_ld, head, pos, ask);
 }
 
-// ---- time chunks of forward_series (DESIGN.md 3.10 "Time chunks"): the stream entry's chunk projected into rows [out_t0, out_t0 + Tc) of the
-// whole output, in either layout; H == 1 keeps no ring (null admitted, nothing to update) and runs the launch without one
 int tgcn_cheb_project_series_stream_at_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
                                            const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, int32_t out_T,
                                            int32_t out_t0, int32_t out_as_series, float* ring, int64_t ring_ld, int32_t head, int32_t dilation) {
-  const char* who = "project_series_stream_at";
-  if (H != 1) {
-    if (out_T < 1) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-    if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, head, nullptr,
-                                            dilation, who, out_T, out_t0, out_as_series)) return rc;
-    TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_at_f32");
-    return TGCN_OK;
-  }
-  if (Tc < 1 || dilation < 1 || !series_conv_shape_ok(S, n_vertices, Tc, f, 1, N, K, 1, 0, 0) || !series_out_slice_ok(Tc, out_T, out_t0) ||
-      !stack || !W || !out)
-    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
-  const int64_t n = n_vertices, Tf = (int64_t)Tc * f;
-  SeriesGemmParams p;
-  memset(&p, 0, sizeof(p));
-  p.src = stack; p.W = W; p.bias = bias; p.out = out;
-  p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
-  p.o_gs = 0; p.ocg = N;
-  series_out_slice(p, n, N, out_T, out_t0, out_as_series);
-  p.n = n; p.Tin = Tc; p.padl = 0; p.nwin = Tc; p.H = 1; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
-  const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0);
-  if (int rc = series_gemm_launch((hipStream_t)stream, p, S, vec, who)) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_at_f32");
-  return TGCN_OK;
-}
-
-// ---- a window step on the streaming state: the chunk's windows end at chunk rows win_off + r * stride (DESIGN.md 3.10 "Window step")
-// What the two _stream_strided entries check before anything is launched: the step and its phase, then the stream entries' rules at
-// dilation 1 (head only where the host's head is used and a ring exists); H == 1 is admitted and keeps no ring (C = 0).
-// *m_out: windows that end inside the chunk; *sc_out: the step the kernel runs at, clamped like the _conv entries' (a step above the
-// padded chunk leaves one window, and 32 * step stays a 32-bit number).
-static int series_stream_strided_check(int64_t S, int64_t n, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K, int64_t ring_ld, int32_t head,
-                                       bool device_pos, int32_t stride, int32_t win_off, int32_t* C_out, int32_t* m_out, int32_t* sc_out) {
-  if (stride < 1 || win_off < 0 || win_off >= stride || Tc < 1 || H < 1) return TGCN_ERR_INVALID;
-  int32_t C = 0;
-  if (H == 1) { if (!series_conv_shape_ok(S, n, Tc, f, 1, N, K, 1, 0, 0)) return TGCN_ERR_INVALID; }
-  else if (series_stream_check(S, n, Tc, f, H, N, K, 1, ring_ld, device_pos ? 0 : head, &C)) return TGCN_ERR_INVALID;
-  *C_out = C;
-  *m_out = win_off < Tc ? (Tc - win_off - 1) / stride + 1 : 0;
-  *sc_out = series_conv_stride(Tc, stride, C, 0);
-  return TGCN_OK;
+  SeriesChunkAsk ask;
+  ask.dil = dilation; ask.one_tap = true; ask.sliced = true; ask.out_T = out_T; ask.out_t0 = out_t0; ask.out_as_series = out_as_series;
+  return series_chunk_forward<SeriesF32>("project_series_stream_at", stream, S, n_vertices, Tc, f, H, N, K, stack, (int64_t)Tc * f, W, bias,
+                                         TGCN_DTYPE_F32, bias_kind, out, ring, ring_ld, head, nullptr, ask);
 }
 
 int tgcn_cheb_project_series_stream_strided_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
                                                 const float* stack, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
                                                 int64_t ring_ld, int32_t head, int64_t* pos, int32_t stride, int32_t win_off) {
-  const char* who = "project_series_stream_strided";
-  int32_t C = 0, m = 0, sc = 1;
-  if (series_stream_strided_check(S, n_vertices, Tc, f, H, N, K, ring_ld, head, pos != nullptr, stride, win_off, &C, &m, &sc) || !stack || !W ||
-      (m > 0 && !out) || (C > 0 && !ring))
-    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-  if (stride == 1 && C > 0) {        // step 1 on a ring: the stream entries' own launches
-    if (int rc = project_series_stream_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, W, bias, bias_kind, out, ring, ring_ld, pos ? 0 : head,
-                                            pos, 1, who)) return rc;
-    TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_strided_f32");
-    return TGCN_OK;
-  }
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t n = n_vertices, Tf = (int64_t)Tc * f;
-  // 16-byte staging and copies: the stack's rule, and a ring that keeps it
-  const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0) && (C == 0 || ((ring_ld % 4 == 0) && (((uintptr_t)ring & 15) == 0)));
-  int hc = 0;
-  if (!series_gemm_lds(H, f, series_gemm_nt(N), vec, sc, &hc))       // the plan's refusal comes before the first launch, windows or none
-    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, f);
-  if (m > 0) {
-    if (int drc = check_pointer_device(out, st, who)) return drc;
-    SeriesGemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.src = stack; p.W = W; p.bias = bias; p.out = out;
-    p.src_ks = S * n * Tf; p.src_ss = n * Tf; p.src_is = Tf; p.src_ts = f;
-    p.o_ss = n * (int64_t)m * N; p.o_is = (int64_t)m * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, m, N)
-    p.n = n; p.Tin = Tc; p.padl = C; p.nwin = m; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
-    if (C > 0) {
-      p.ring = ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
-      p.win_off = win_off;
-    } else {       // one tap reads no row before the chunk: the chunk from row win_off on through the instantiations without a ring
-      p.src = stack + (int64_t)win_off * f; p.Tin = Tc - win_off;
-    }
-    if (int rc = series_gemm_launch(st, p, S, vec, who, sc, 1, C > 0)) return rc;
-  }
-  if (C > 0) series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, vec, Tc, C, head, pos);
-  if (pos) series_stream_advance_launch(st, pos, Tc, C);
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_strided_f32");
-  return TGCN_OK;
+  SeriesChunkAsk ask;
+  ask.one_tap = true; ask.stepped = true; ask.stride = stride; ask.win_off = win_off;
+  return series_chunk_forward<SeriesF32>("project_series_stream_strided", stream, S, n_vertices, Tc, f, H, N, K, stack, (int64_t)Tc * f, W, bias,
+                                         TGCN_DTYPE_F32, bias_kind, out, ring, ring_ld, head, pos, ask);
+}
+
+int tgcn_cheb_project_series_stream_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                         const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                         int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int32_t dilation) {
+  SeriesChunkAsk ask;
+  ask.dil = dilation;
+  return series_chunk_forward<SeriesBf16>("project_series_stream_bf16", stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias, bias_dtype,
+                                          bias_kind, out, ring, ring_ld, head, nullptr, ask);
+}
+
+int tgcn_cheb_project_series_stream_pos_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                             const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                             int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int64_t* pos, int32_t dilation) {
+  if (!pos) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_pos_bf16: bad argument");
+  SeriesChunkAsk ask;
+  ask.dil = dilation;
+  return series_chunk_forward<SeriesBf16>("project_series_stream_pos_bf16", stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias, bias_dtype,
+                                          bias_kind, out, ring, ring_ld, 0, pos, ask);
+}
+
+int tgcn_cheb_project_series_stream_strided_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                 const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
+                                                 int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int64_t* pos,
+                                                 int32_t stride, int32_t win_off) {
+  SeriesChunkAsk ask;
+  ask.one_tap = true; ask.stepped = true; ask.stride = stride; ask.win_off = win_off;
+  return series_chunk_forward<SeriesBf16>("project_series_stream_strided_bf16", stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias,
+                                          bias_dtype, bias_kind, out, ring, ring_ld, head, pos, ask);
 }
 
 // ---- one launch per step (stream_small.h): the hops, the stream entry's projection and its ring update out of LDS
@@ -1857,6 +2013,7 @@ int tgcn_cheb_stream_small_f32(void* stream, const tgcn_csr* A, int32_t mode, in
   return TGCN_OK;
 }
 
+// ---- backward
 // Row blocks of the series weight gradient: wgrad_rows_per_block's rule, with the partials held to 256 MB (each is a whole (K, H*f, N) weight)
 static int64_t series_wgrad_rows_per_block(int64_t M, int64_t weight_floats) {
   int64_t rpb = wgrad_rows_per_block(M);
@@ -1866,53 +2023,99 @@ static int64_t series_wgrad_rows_per_block(int64_t M, int64_t weight_floats) {
   return rpb;
 }
 
+// The workspace of every backward entry: the flipped weight (fp32 or bf16, in a slot of fp32 size) and the fp32 partials
 static size_t series_backward_workspace(int64_t M, int64_t wf) {
   const int64_t rpb = series_wgrad_rows_per_block(M, wf);
   return align_up((size_t)wf * sizeof(float), 256) + (size_t)((M + rpb - 1) / rpb) * wf * sizeof(float);
 }
-
-size_t tgcn_cheb_series_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K) {
-  if (!series_shape_ok(S, n_vertices, T, f, H, N, K)) return 0;
-  return series_backward_workspace(S * n_vertices * (T - H + 1), (int64_t)K * H * f * N);
+static size_t series_backward_workspace_bytes(SeriesRule rule, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                              int32_t stride, int32_t pl, int32_t pr, int32_t dil) {
+  SeriesGeom ge;
+  if (series_geom(rule, S, n, T, f, H, N, K, stride, pl, pr, dil, &ge)) return 0;
+  return series_backward_workspace(S * n * ge.nwin, (int64_t)K * H * f * N);
 }
 
-size_t tgcn_cheb_series_conv_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                                      int32_t stride, int32_t pad_left, int32_t pad_right) {
-  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right)) return 0;
-  stride = series_conv_stride(T, stride, pad_left, pad_right);
-  return series_backward_workspace(S * n_vertices * series_conv_nwin(T, H, stride, pad_left, pad_right), (int64_t)K * H * f * N);
+// The weight gradient's row blocks and grid: everything about its two launches that can refuse
+struct SeriesWgradPlan { int64_t M, rpb, nblocks, jtiles, tgroups; };
+static int series_wgrad_plan(int64_t S, int64_t n, int64_t nwin, int32_t f, int32_t H, int32_t N, int32_t K, const char* who, SeriesWgradPlan* o) {
+  o->M = S * n * nwin;
+  o->rpb = series_wgrad_rows_per_block(o->M, (int64_t)K * H * f * N);
+  o->nblocks = (o->M + o->rpb - 1) / o->rpb;
+  o->jtiles = ((int64_t)H * f + 15) / 16; o->tgroups = (K + kWgTerms - 1) / kWgTerms;
+  if (o->rpb + nwin >= (int64_t)INT32_MAX || o->rpb / nwin + n >= (int64_t)INT32_MAX || o->nblocks > (int64_t)INT32_MAX || (N + 63) / 64 > 65535 ||
+      o->jtiles * o->tgroups > 65535)
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: weight gradient shape too large", who);
+  return TGCN_OK;
 }
 
-// Both gradients for a window step and zero padding; (1, 0, 0) is tgcn_cheb_series_backward_f32's launch sequence, launch for launch.
-static int series_backward_impl(hipStream_t st, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K, const float* stack,
-                                const float* g, int32_t g_as_series, const float* W, float* G, float* dW, void* workspace, int32_t stride,
-                                int32_t pl, int32_t pr, const char* who, int32_t dil = 1) {
-  const int64_t Tf = (int64_t)T * f, nwin = series_conv_nwin(T, (H - 1) * dil + 1, stride, pl, pr), wf = (int64_t)K * H * f * N;
-  const bool conv = stride != 1 || pl != 0 || pr != 0;
+// dW from the stack (K, S, n, ld) and g (rows of N at strides g_ss, g_is, g_ws; nwin windows per vertex): partials per row block into the
+// workspace behind the flipped weight's slot, then the fold.  conv: a step or padding; ring non-null: the chunk's rows before it (carried).
+template <class X>
+static int series_wgrad_launch(hipStream_t st, const char* who, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                               const void* stack, int64_t ld, const void* g, int64_t g_ss, int64_t g_is, int64_t g_ws, int64_t nwin, float* dW,
+                               void* workspace, int32_t stride, int32_t padl, int32_t dil, bool conv, bool carried = false, const void* ring = nullptr,
+                               int64_t ring_ld = 0, int32_t C = 0, int32_t head = 0) {
+  typedef typename X::Elem E;
+  SeriesWgradPlan w;
+  if (int rc = series_wgrad_plan(S, n, nwin, f, H, N, K, who, &w)) return rc;
+  const int64_t wf = (int64_t)K * H * f * N;
+  typename X::WgradParams q;
+  memset(&q, 0, sizeof(q));
+  q.stack = (const E*)stack; q.g = (const E*)g; q.partial = (float*)((char*)workspace + align_up((size_t)wf * sizeof(float), 256));
+  q.st_ks = S * n * ld; X::wgrad_rows(q, ld); q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
+  q.M = w.M; q.rows_per_block = w.rpb; q.n = n;
+  q.f = f; q.nwin = (int32_t)nwin; q.J = H * f; q.N = N; q.K = K;
+  q.stride = stride; q.padl = padl; q.T = T; q.dil = dil;
+  if (carried) X::wgrad_ring(q, ring, S, n, ring_ld, C, head);
+  { ProfScope ps(TGCN_PROF_WGRAD, st);
+    X::wgrad(st, dim3((unsigned)w.nblocks, (unsigned)((N + 63) / 64), (unsigned)(w.jtiles * w.tgroups)), q, conv, dil > 1, carried && C > 0); }
+  WgradParams r;
+  memset(&r, 0, sizeof(r));
+  r.partial = q.partial; r.dW = dW; r.Kc = q.J; r.N = N; r.nterms = K; r.nblocks = (int32_t)w.nblocks;
+  { ProfScope ps(TGCN_PROF_WGRAD, st);
+    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
+  return TGCN_OK;
+}
+
+// ---- driver 3, both gradients of a whole series, for a window step, zero padding and dilated taps: every _backward entry of both element
+// types.  G and dW are fp32; stack_ld: elements between vertex rows (fp32: T * f).
+template <class X>
+static int series_backward(const char* who, void* stream, SeriesRule rule, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                           const void* stack, int64_t stack_ld, const void* g_, int32_t g_as_series, const void* W, float* G, float* dW,
+                           void* workspace, size_t workspace_bytes, int32_t stride, int32_t pl, int32_t pr, int32_t dil) {
+  typedef typename X::Elem E;
+  typedef typename X::Params P;
+  hipStream_t st = (hipStream_t)stream;
+  const E* g = (const E*)g_;
+  SeriesGeom ge;
+  const int grc = series_geom(rule, S, n, T, f, H, N, K, stride, pl, pr, dil, &ge);
+  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "%s: dilation %d with stride %d is not built", who, dil, stride);
+  if (grc || !g) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (int drc = check_pointer_device(g, st, who)) return drc;
+  const int64_t Tf = (int64_t)T * f, nwin = ge.nwin, wf = (int64_t)K * H * f * N;
+  const size_t need = series_backward_workspace(S * n * nwin, wf);
+  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) TGCN_FAIL(TGCN_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+  stride = ge.stride; dil = ge.dil;
   int64_t g_ss, g_is, g_ws;
-  if (g_as_series) { g_ss = n * nwin * N; g_is = nwin * N; g_ws = N; }
-  else { g_ss = nwin * n * N; g_is = N; g_ws = n * N; }
-  if (G) {      // the forward's kernel over g as a series of N channels, columns (k, c); per phase of the window step, each at step 1
+  series_layout(n, nwin, N, g_as_series, &g_ss, &g_is, &g_ws);
+  if (G) {      // the forward's kernel over g as a series of N channels, columns (k, c), fp32 out; per phase of the window step, each at step 1
     if (!W) TGCN_FAIL(TGCN_ERR_INVALID, "%s: the input gradient needs W", who);
-    float* Wd = (float*)workspace;
+    E* Wd = (E*)workspace;
     { ProfScope ps(TGCN_PROF_RELAYOUT, st);
-      hipLaunchKernelGGL(series_flip_weight_kernel, dim3(grid_1d(wf)), dim3(kBlock), 0, st, W, Wd, (int)K, (int)H, (int)f, (int)N, (int)stride); }
+      X::flip(st, (const E*)W, Wd, (int)K, (int)H, (int)f, (int)N, (int)stride); }
     // the time rows of the phases ph >= H (a step longer than the window) lie between the windows: exact zeros
     if (stride > H && hipMemsetAsync(G, 0, (size_t)K * S * n * Tf * sizeof(float), st) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "%s: memset failed", who);
-    const bool vec = (N % 4 == 0) && (((uintptr_t)g & 15) == 0);
-    SeriesGemmParams over_g;      // what every launch over g shares: g as a series of N channels, columns (k, c) into (K, S, n, T*f)
-    memset(&over_g, 0, sizeof(over_g));
-    over_g.src = g; over_g.bias = nullptr; over_g.bias_kind = 0;
-    over_g.src_ks = 0; over_g.src_ss = g_ss; over_g.src_is = g_is; over_g.src_ts = g_ws;
-    over_g.o_ss = n * Tf; over_g.o_is = Tf; over_g.o_gs = S * n * Tf; over_g.ocg = f;
-    over_g.n = n; over_g.Tin = (int32_t)nwin; over_g.f = N; over_g.N = K * f; over_g.nterms = 1;
+    // 16-byte loads of g's time rows: whole units of N make every stride of either layout a multiple of the unit.  The phases' weights start
+    // at rows of N*K*f elements: any alignment, the weight tile is loaded element by element.
+    const bool vec = (N % X::kUnit == 0) && (((uintptr_t)g & 15) == 0);
+    const P over_g = series_over_g<P>(g, g_ss, g_is, g_ws, (int32_t)nwin, S, n, Tf, f, N, K);      // what every launch over g shares
     if (dil > 1) {
       // dilated taps (step 1): time row t sums g[t + pl - h * dil] W[h]^T -- "window" t of the DILATED kernel over g with the flipped weight,
       // reaching (H - 1) * dil - pl rows back; all T rows in one launch
-      SeriesGemmParams p = over_g;
+      P p = over_g;
       p.W = Wd; p.out = G; p.o_ws = f;
       p.padl = (H - 1) * dil - pl; p.nwin = T; p.H = H;
-      if (int rc = series_gemm_launch(st, p, S, vec, who, 1, dil)) return rc;
+      if (int rc = X::launch(st, p, S, vec, true, who, 1, dil, false, 0)) return rc;
     } else {
       for (int ph = 0; ph < stride && ph < H; ++ph) {
         // time rows t = u * stride + ph - pl, u0 <= u <= u1; row u sums g[u - m] W[ph + m * stride]^T over m < Hp: "window" u - u0 of the
@@ -1922,110 +2125,88 @@ static int series_backward_impl(hipStream_t st, int64_t S, int64_t n, int32_t T,
         if ((int64_t)T - 1 + pl - ph < 0) continue;
         const int64_t u0 = ph >= pl ? 0 : (pl - ph + stride - 1) / stride, u1 = ((int64_t)T - 1 + pl - ph) / stride;
         if (u1 < u0) continue;
-        SeriesGemmParams p = over_g;
+        P p = over_g;
         p.W = Wd + (int64_t)series_phase_row0(H, stride, ph) * N * K * f;
         p.out = G + (u0 * stride + ph - pl) * f; p.o_ws = (int64_t)stride * f;
         p.padl = (int32_t)(Hp - 1 - u0); p.nwin = (int32_t)(u1 - u0 + 1); p.H = Hp;
-        if (int rc = series_gemm_launch(st, p, S, vec, who)) return rc;
+        if (int rc = X::launch(st, p, S, vec, true, who, 1, 1, false, 0)) return rc;
       }
     }
   }
   if (dW) {
-    if (!stack) TGCN_FAIL(TGCN_ERR_INVALID, "%s: the weight gradient needs the hop tensors", who);
-    const int64_t M = S * n * nwin;
-    SeriesWgradParams q;
-    memset(&q, 0, sizeof(q));
-    q.stack = stack; q.g = g; q.partial = (float*)((char*)workspace + align_up((size_t)wf * sizeof(float), 256));
-    q.st_ks = S * n * Tf; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
-    q.M = M; q.rows_per_block = series_wgrad_rows_per_block(M, wf); q.n = n;
-    q.Tf = (int32_t)Tf; q.f = f; q.nwin = (int32_t)nwin; q.J = H * f; q.N = N; q.K = K;
-    q.stride = stride; q.padl = pl; q.T = T; q.dil = dil;
-    const int64_t nblocks = (M + q.rows_per_block - 1) / q.rows_per_block;
-    const int64_t jtiles = (q.J + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
-    if (q.rows_per_block + nwin >= (int64_t)INT32_MAX || q.rows_per_block / nwin + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX ||
-        (N + 63) / 64 > 65535 || jtiles * tgroups > 65535)
-      TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: weight gradient shape too large", who);
-    { ProfScope ps(TGCN_PROF_WGRAD, st);
-      const dim3 grid((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups));
-      if (dil > 1) hipLaunchKernelGGL((series_wgrad_partial_kernel<true, true>), grid, dim3(64), 0, st, q);
-      else if (conv) hipLaunchKernelGGL(series_wgrad_partial_kernel<true>, grid, dim3(64), 0, st, q);
-      else hipLaunchKernelGGL(series_wgrad_partial_kernel<false>, grid, dim3(64), 0, st, q); }
-    WgradParams r;
-    memset(&r, 0, sizeof(r));
-    r.partial = q.partial; r.dW = dW; r.Kc = q.J; r.N = N; r.nterms = K; r.nblocks = (int32_t)nblocks;
-    { ProfScope ps(TGCN_PROF_WGRAD, st);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
+    if (!stack || !series_stack_ld_ok(T, f, stack_ld)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: the weight gradient needs the hop tensors", who);
+    if (int rc = series_wgrad_launch<X>(st, who, S, n, T, f, H, N, K, stack, stack_ld, g, g_ss, g_is, g_ws, nwin, dW, workspace, stride, pl, dil,
+                                        stride != 1 || pl != 0 || pr != 0)) return rc;
   }
-  return TGCN_OK;
+  return series_launched(who, X::kSuffix);
 }
 
+size_t tgcn_cheb_series_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K) {
+  return series_backward_workspace_bytes(kSeriesPlain, S, n_vertices, T, f, H, N, K, 1, 0, 0, 1);
+}
+size_t tgcn_cheb_series_conv_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                      int32_t stride, int32_t pad_left, int32_t pad_right) {
+  return series_backward_workspace_bytes(kSeriesConv, S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, 1);
+}
+size_t tgcn_cheb_series_dilated_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                         int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
+  return series_backward_workspace_bytes(kSeriesDilated, S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation);
+}
+// bf16: the flipped weight in the fp32 entries' slot and the fp32 partials -- the fp32 entries' size and 256 MB cap
+size_t tgcn_cheb_series_conv_backward_bf16_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                           int32_t stride, int32_t pad_left, int32_t pad_right) {
+  return series_backward_workspace_bytes(kSeriesConv, S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, 1);
+}
+size_t tgcn_cheb_series_dilated_backward_bf16_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                              int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
+  return series_backward_workspace_bytes(kSeriesDilated, S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation);
+}
+
+// (1, 0, 0) at dilation 1: no step, no pads
 int tgcn_cheb_series_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
                                   const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
                                   void* workspace, size_t workspace_bytes) {
-  if (!series_shape_ok(S, n_vertices, T, f, H, N, K) || !g) TGCN_FAIL(TGCN_ERR_INVALID, "series_backward: bad argument");
-  if (int drc = check_pointer_device(g, (hipStream_t)stream, "series_backward")) return drc;
-  const size_t need = tgcn_cheb_series_backward_workspace_bytes(S, n_vertices, T, f, H, N, K);
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) TGCN_FAIL(TGCN_ERR_WORKSPACE, "series_backward: workspace %zu < %zu", workspace_bytes, need);
-  if (int rc = series_backward_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, 1, 0, 0,
-                                    "series_backward")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_series_backward_f32");
-  return TGCN_OK;
+  return series_backward<SeriesF32>("series_backward", stream, kSeriesPlain, S, n_vertices, T, f, H, N, K, stack, (int64_t)T * f, g, g_as_series, W, G, dW,
+                                    workspace, workspace_bytes, 1, 0, 0, 1);
 }
 
 int tgcn_cheb_series_conv_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
                                        const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
                                        void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right) {
-  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right) || !g) TGCN_FAIL(TGCN_ERR_INVALID, "series_conv_backward: bad argument");
-  if (int drc = check_pointer_device(g, (hipStream_t)stream, "series_conv_backward")) return drc;
-  const size_t need = tgcn_cheb_series_conv_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))
-    TGCN_FAIL(TGCN_ERR_WORKSPACE, "series_conv_backward: workspace %zu < %zu", workspace_bytes, need);
-  stride = series_conv_stride(T, stride, pad_left, pad_right);
-  if (int rc = series_backward_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, stride, pad_left,
-                                    pad_right, "series_conv_backward")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_series_conv_backward_f32");
-  return TGCN_OK;
-}
-
-size_t tgcn_cheb_series_dilated_backward_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                                         int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
-  if (series_dilation_is_one(H, stride, dilation)) return tgcn_cheb_series_conv_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
-  int32_t He = 0;
-  if (series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He)) return 0;
-  return series_backward_workspace(S * n_vertices * series_conv_nwin(T, He, 1, pad_left, pad_right), (int64_t)K * H * f * N);
+  return series_backward<SeriesF32>("series_conv_backward", stream, kSeriesConv, S, n_vertices, T, f, H, N, K, stack, (int64_t)T * f, g, g_as_series, W, G,
+                                    dW, workspace, workspace_bytes, stride, pad_left, pad_right, 1);
 }
 
 int tgcn_cheb_series_dilated_backward_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
                                           const float* stack, const float* g, int32_t g_as_series, const float* W, float* G, float* dW,
                                           void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right,
                                           int32_t dilation) {
-  if (series_dilation_is_one(H, stride, dilation))
-    return tgcn_cheb_series_conv_backward_f32(stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, workspace_bytes,
-                                              stride, pad_left, pad_right);
-  int32_t He = 0;
-  const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
-  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "series_dilated_backward: dilation %d with stride %d is not built", dilation, stride);
-  if (grc || !g) TGCN_FAIL(TGCN_ERR_INVALID, "series_dilated_backward: bad argument");
-  if (int drc = check_pointer_device(g, (hipStream_t)stream, "series_dilated_backward")) return drc;
-  const size_t need = tgcn_cheb_series_dilated_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation);
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15))
-    TGCN_FAIL(TGCN_ERR_WORKSPACE, "series_dilated_backward: workspace %zu < %zu", workspace_bytes, need);
-  if (int rc = series_backward_impl((hipStream_t)stream, S, n_vertices, T, f, H, N, K, stack, g, g_as_series, W, G, dW, workspace, 1, pad_left,
-                                    pad_right, "series_dilated_backward", dilation)) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_series_dilated_backward_f32");
-  return TGCN_OK;
+  return series_backward<SeriesF32>("series_dilated_backward", stream, kSeriesDilated, S, n_vertices, T, f, H, N, K, stack, (int64_t)T * f, g, g_as_series,
+                                    W, G, dW, workspace, workspace_bytes, stride, pad_left, pad_right, dilation);
+}
+
+int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                        const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
+                                        float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right) {
+  return series_backward<SeriesBf16>("series_conv_backward_bf16", stream, kSeriesConv, S, n_vertices, T, f, H, N, K, stack, stack_ld, g, g_as_series, W, G,
+                                     dW, workspace, workspace_bytes, stride, pad_left, pad_right, 1);
+}
+
+int tgcn_cheb_series_dilated_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                           const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
+                                           float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right,
+                                           int32_t dilation) {
+  return series_backward<SeriesBf16>("series_dilated_backward_bf16", stream, kSeriesDilated, S, n_vertices, T, f, H, N, K, stack, stack_ld, g, g_as_series,
+                                     W, G, dW, workspace, workspace_bytes, stride, pad_left, pad_right, dilation);
 }
 
 // ---- time chunks of forward_series, backward (DESIGN.md 3.10 "Time chunks"): one chunk of Tc time rows of the causal layer's two gradients.
-// What the entry and its workspace query check: the stream entries' rules for the chunk (H == 1: no ring, C = 0), the chunk's place in the
-// whole gradient, and the input gradient's launch over g as a series of N channels (Tc + C rows of N floats inside 32 bits).
+// What the entry and its workspace query check: the chunk entries' rules (H == 1: no ring, C = 0), the chunk's place in the whole gradient,
+// and the input gradient's launch over g as a series of N channels (Tc + C rows of N floats inside 32 bits).
 static int series_chunk_check(int64_t S, int64_t n, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K, int32_t dil, int64_t ring_ld,
                               int32_t head, int32_t g_T, int32_t g_t0, int32_t* C_out) {
-  if (dil < 1 || Tc < 1 || H < 1) return TGCN_ERR_INVALID;
   int32_t C = 0;
-  if (H == 1) { if (!series_conv_shape_ok(S, n, Tc, f, 1, N, K, 1, 0, 0)) return TGCN_ERR_INVALID; }
-  else if (series_stream_check(S, n, Tc, f, H, N, K, dil, ring_ld, head, &C)) return TGCN_ERR_INVALID;
-  if (!series_out_slice_ok(Tc, g_T, g_t0)) return TGCN_ERR_INVALID;
+  if (series_stream_check(S, n, Tc, f, H, N, K, dil, ring_ld, head, &C, true) || !series_out_slice_ok(Tc, g_T, g_t0)) return TGCN_ERR_INVALID;
   if (((int64_t)Tc + C) * N >= (int64_t)INT32_MAX || ((int64_t)Tc + C) * 64 >= (int64_t)INT32_MAX) return TGCN_ERR_INVALID;
   *C_out = C;
   return TGCN_OK;
@@ -2043,6 +2224,7 @@ int tgcn_cheb_series_chunk_backward_f32(void* stream, int64_t S, int64_t n_verti
                                         const float* stack, float* ring, int64_t ring_ld, int32_t head, const float* g, int32_t g_T,
                                         int32_t g_t0, int32_t g_as_series, const float* W, float* G, float* dW, void* workspace,
                                         size_t workspace_bytes, int32_t dilation) {
+  typedef SeriesF32 X;
   const char* who = "series_chunk_backward";
   if (H == 1 && dilation >= 1) dilation = 1;      // one tap has nothing to dilate
   int32_t C = 0;
@@ -2057,404 +2239,37 @@ int tgcn_cheb_series_chunk_backward_f32(void* stream, int64_t S, int64_t n_verti
   const size_t need = tgcn_cheb_series_chunk_backward_workspace_bytes(S, n_vertices, Tc, f, H, N, K, dilation);
   if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) TGCN_FAIL(TGCN_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
   hipStream_t st = (hipStream_t)stream;
-  const int64_t n = n_vertices, Tf = (int64_t)Tc * f, wf = (int64_t)K * H * f * N;
+  const int64_t n = n_vertices, Tf = (int64_t)Tc * f;
   int64_t g_ss, g_is, g_ws;      // the WHOLE gradient's strides; the chunk's rows start g_t0 rows in
-  if (g_as_series) { g_ss = n * (int64_t)g_T * N; g_is = (int64_t)g_T * N; g_ws = N; }
-  else { g_ss = (int64_t)g_T * n * N; g_is = N; g_ws = n * N; }
+  series_layout(n, g_T, N, g_as_series, &g_ss, &g_is, &g_ws);
   const float* gc = g + (int64_t)g_t0 * g_ws;
-  // ---- everything that can refuse, before the first launch
+  // ---- everything that can refuse, before the first launch: the plans the two launchers will form again
   const bool vecg = (N % 4 == 0) && (((uintptr_t)gc & 15) == 0);
-  if (G) {
-    int hc = 0;
-    const int NT = series_gemm_nt(K * f);
-    if (!series_gemm_lds(H, N, NT, vecg, 1, &hc)) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, N);
-    int32_t tpp = 0, tpv = (Tc + kSgWin - 1) / kSgWin;
-    if (dilation > 1) series_dilated_tiles(Tc, dilation, &tpp, &tpv);
-    if ((S * n * tpv + 3) / 4 > (int64_t)INT32_MAX || ((int64_t)K * f + NT * 16 - 1) / (NT * 16) > 65535)
-      TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
-  }
-  const int64_t M = S * n * Tc, rpb = series_wgrad_rows_per_block(M, wf), nblocks = (M + rpb - 1) / rpb;
-  const int64_t jtiles = ((int64_t)H * f + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
-  if (dW && (rpb + Tc >= (int64_t)INT32_MAX || rpb / Tc + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX || (N + 63) / 64 > 65535 ||
-             jtiles * tgroups > 65535))
-    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: weight gradient shape too large", who);
+  SeriesLaunchPlan lp;
+  SeriesWgradPlan wp;
+  if (G) if (int rc = series_launch_plan(X::lds, S, n, Tc, H, N, K * f, vecg, 1, dilation, 0, who, &lp)) return rc;
+  if (dW) if (int rc = series_wgrad_plan(S, n, Tc, f, H, N, K, who, &wp)) return rc;
   if (G) {      // rows [g_t0, g_t0 + Tc) of the whole input gradient: time row t sums g[t + h' * dil] Wd[h'] over the rows of g that exist
     float* Wd = (float*)workspace;
     { ProfScope ps(TGCN_PROF_RELAYOUT, st);
-      hipLaunchKernelGGL(series_flip_weight_kernel, dim3(grid_1d(wf)), dim3(kBlock), 0, st, W, Wd, (int)K, (int)H, (int)f, (int)N, 1); }
-    SeriesGemmParams p;
-    memset(&p, 0, sizeof(p));
-    p.src = gc; p.W = Wd; p.bias = nullptr; p.bias_kind = 0; p.out = G;
-    p.src_ks = 0; p.src_ss = g_ss; p.src_is = g_is; p.src_ts = g_ws;
-    p.o_ss = n * Tf; p.o_is = Tf; p.o_ws = f; p.o_gs = S * n * Tf; p.ocg = f;      // columns (k, c) into the chunk-shaped (K, S, n, Tc*f)
+      X::flip(st, W, Wd, (int)K, (int)H, (int)f, (int)N, 1); }
     const int64_t left = (int64_t)g_T - g_t0;
-    p.n = n; p.Tin = (int32_t)(left < (int64_t)Tc + C ? left : (int64_t)Tc + C); p.padl = 0; p.nwin = Tc; p.H = H; p.f = N; p.N = K * f; p.nterms = 1;
-    if (int rc = series_gemm_launch(st, p, S, vecg, who, 1, dilation)) return rc;
+    // columns (k, c) into the chunk-shaped (K, S, n, Tc*f)
+    X::Params p = series_over_g<X::Params>(gc, g_ss, g_is, g_ws, (int32_t)(left < (int64_t)Tc + C ? left : (int64_t)Tc + C), S, n, Tf, f, N, K);
+    p.W = Wd; p.out = G; p.o_ws = f;
+    p.padl = 0; p.nwin = Tc; p.H = H;
+    if (int rc = X::launch(st, p, S, vecg, true, who, 1, dilation, false, 0)) return rc;
   }
-  if (dW) {
-    SeriesWgradParams q;
-    memset(&q, 0, sizeof(q));
-    q.stack = stack; q.g = gc; q.partial = (float*)((char*)workspace + align_up((size_t)wf * sizeof(float), 256));
-    q.st_ks = S * n * Tf; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
-    q.M = M; q.rows_per_block = rpb; q.n = n;
-    q.Tf = (int32_t)Tf; q.f = f; q.nwin = Tc; q.J = H * f; q.N = N; q.K = K;
-    q.stride = 1; q.padl = C; q.T = Tc; q.dil = dilation;
-    q.ring = ring; q.ring_ks = S * n * ring_ld; q.ring_is = ring_ld; q.C = C; q.head = head;
-    { ProfScope ps(TGCN_PROF_WGRAD, st);
-      const dim3 grid((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups));
-      if (C == 0) hipLaunchKernelGGL(series_wgrad_partial_kernel<false>, grid, dim3(64), 0, st, q);      // one tap: the window is its own row
-      else if (dilation > 1) hipLaunchKernelGGL((series_wgrad_partial_kernel<true, true, true>), grid, dim3(64), 0, st, q);
-      else hipLaunchKernelGGL((series_wgrad_partial_kernel<true, false, true>), grid, dim3(64), 0, st, q); }
-    WgradParams r;
-    memset(&r, 0, sizeof(r));
-    r.partial = q.partial; r.dW = dW; r.Kc = q.J; r.N = N; r.nterms = K; r.nblocks = (int32_t)nblocks;
-    { ProfScope ps(TGCN_PROF_WGRAD, st);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
-  }
-  if (carried) {      // behind both on the same stream: the weight gradient has read the old ring
-    const bool vec = (f % 4 == 0) && (((uintptr_t)stack & 15) == 0) && (ring_ld % 4 == 0) && (((uintptr_t)ring & 15) == 0);
-    series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, vec, Tc, C, head, nullptr);
-  }
-  TGCN_CHECK_LAUNCH("tgcn_cheb_series_chunk_backward_f32");
-  return TGCN_OK;
+  // one tap (C == 0): the window is its own row, the plain form; else the window that ends at each chunk row, its early rows from the ring
+  if (dW)
+    if (int rc = series_wgrad_launch<X>(st, who, S, n, Tc, f, H, N, K, stack, Tf, gc, g_ss, g_is, g_ws, Tc, dW, workspace, 1, C, dilation, C > 0, true,
+                                        ring, ring_ld, C, head)) return rc;
+  if (carried)       // behind both on the same stream: the weight gradient has read the old ring
+    series_ring_update_launch(st, stack, ring, K * S * n, Tf, ring_ld, f, 4, series_vec<X>(f, stack, Tf, ring, ring_ld), Tc, C, head, nullptr);
+  return series_launched(who, X::kSuffix);
 }
 
-// ---- streaming time windows on bf16 tensors (windows_bf16.h): one entry family, the general geometry; (1, 0, 0) is its default
-// series_gemm_lds's three regimes on bf16 span bytes: the weight tile is NT*16 columns of kPbLd bf16
-static int series_gemm_bf16_lds(int H, int f, int NT, bool vec, int stride, int* hc_out) {
-  auto bytes = [&](int hc) { return ((size_t)NT * 16 * kPbLd + 4 * (size_t)series_bf16_span_elems(hc, f, vec, stride)) * sizeof(hbf16); };   // 64-bit
-  const size_t limits[2] = {64 * 1024, (size_t)lds_optin_limit()};
-  for (size_t lim : limits)
-    for (int hc = H; hc >= 1; --hc)
-      if (bytes(hc) <= lim) { *hc_out = hc; return (int)bytes(hc); }
-  return 0;
-}
-
-int tgcn_series_conv_plan_bf16(int32_t H, int32_t f, int32_t N, int32_t vec, int32_t stride, int32_t* hc, int32_t* lds_bytes) {
-  if (H < 1 || f < 1 || N < 1 || stride < 1 || !hc || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_conv_plan_bf16: bad argument");
-  int h = 0;
-  const int lds = series_gemm_bf16_lds(H, f, series_gemm_nt(N), vec != 0 && f % 8 == 0, stride, &h);
-  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_conv_plan_bf16: %d channels per time row do not fit the LDS span", f);
-  *hc = h; *lds_bytes = lds;
-  return TGCN_OK;
-}
-
-// out_f32: the input gradient's fp32 columns; otherwise bf16 output.  stride >= 2 takes the STRIDED instantiations, dil >= 2 (at step 1) the
-// DILATED ones, planned as step 1.
-static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride = 1,
-                                   int dil = 1, bool carry = false) {
-  p.tpv = (p.nwin + kSgWin - 1) / kSgWin;
-  p.dil = dil;
-  if (dil > 1) series_dilated_tiles(p.nwin, dil, &p.tpp, &p.tpv);
-  p.ntiles = S * p.n * p.tpv;
-  const int64_t gx = (p.ntiles + 3) / 4;
-  const int NT = series_gemm_nt(p.N);
-  const int64_t gy = (p.N + NT * 16 - 1) / (NT * 16);
-  if (gx > (int64_t)INT32_MAX || gy > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: grid too large", who);
-  int hc = 0;
-  const int lds = series_gemm_bf16_lds(p.H, p.f, NT, vec, stride, &hc);
-  if (!lds) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, p.f);
-  p.HC = hc;
-  p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = vec ? series_bf16_row_elems(p.f, p.lst) : p.f;
-  const dim3 grid((unsigned)gx, (unsigned)gy);
-  ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_GEMM_B(NT_, VEC_, STR_, OUT_, DIL_, ...)                                                                      \
-  do {                                                                                                                            \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>, lds);  \
-    hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>), grid, dim3(kBlock), lds, st, p);    \
-  } while (0)
-#define TGCN_SERIES_GEMM_B_NT(VEC_, STR_, OUT_, DIL_, ...)                                                                        \
-  do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                                 \
-       else if (NT == 2) TGCN_SERIES_GEMM_B(2, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                            \
-       else TGCN_SERIES_GEMM_B(4, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__); } while (0)
-  if (carry) {          // the stream entries: bf16 out, the time rows before the chunk from p.ring (a window step: STRIDED && CARRY)
-    if (stride > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16, false, true); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16, false, true); }
-    else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true, true); }
-    else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, false, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, false, true); }
-  } else if (dil > 1) {        // dilated taps at step 1: the forward, and the input gradient in one launch
-    if (out_f32) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, true); else TGCN_SERIES_GEMM_B_NT(false, false, float, true); }
-    else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true); }
-  } else if (out_f32) {        // the input gradient: one launch per phase, each at step 1
-    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, false); else TGCN_SERIES_GEMM_B_NT(false, false, float, false);
-  } else if (stride == 1) {
-    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, false); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, false);
-  } else {
-    if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16, false); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16, false);
-  }
-#undef TGCN_SERIES_GEMM_B_NT
-#undef TGCN_SERIES_GEMM_B
-  return TGCN_OK;
-}
-
-static bool series_stack_ld_ok(int32_t T, int32_t f, int64_t stack_ld) { return stack_ld >= (int64_t)T * f && stack_ld < (int64_t)INT32_MAX; }
-
-// The bf16 forward after the geometry check (dil > 1: stride == 1); who names the entry in messages
-static int project_series_bf16_impl(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                    const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype, int32_t bias_kind,
-                                    int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dil, const char* who) {
-  if (!stack || !W || !out || !series_stack_ld_ok(T, f, stack_ld)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
-  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "%s: dtype code %d", who, bias_dtype);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
-  stride = series_conv_stride(T, stride, pad_left, pad_right);
-  const int64_t n = n_vertices, nwin = series_conv_nwin(T, (H - 1) * dil + 1, stride, pad_left, pad_right);
-  SeriesGemmBf16Params p;
-  memset(&p, 0, sizeof(p));
-  p.src = (const hbf16*)stack; p.W = (const hbf16*)W; p.bias = bias; p.out = out;
-  p.src_ks = S * n * stack_ld; p.src_ss = n * stack_ld; p.src_is = stack_ld; p.src_ts = f;
-  if (as_series) { p.o_ss = n * nwin * N; p.o_is = nwin * N; p.o_ws = N; }      // (S, n, nwin, N)
-  else { p.o_ss = nwin * n * N; p.o_is = N; p.o_ws = n * N; }                     // (S, nwin, n, N)
-  p.o_gs = 0; p.ocg = N;
-  p.n = n; p.Tin = T; p.padl = pad_left; p.nwin = (int32_t)nwin; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
-  p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
-  const bool vec = (f % 8 == 0) && (stack_ld % 8 == 0) && (((uintptr_t)stack & 15) == 0);
-  return series_gemm_bf16_launch((hipStream_t)stream, p, S, vec, false, who, stride, dil);
-}
-
-int tgcn_cheb_project_series_conv_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                       const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
-                                       int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right) {
-  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_conv_bf16: bad argument");
-  if (int rc = project_series_bf16_impl(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, as_series, out, stride,
-                                        pad_left, pad_right, 1, "project_series_conv_bf16")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_conv_bf16");
-  return TGCN_OK;
-}
-
-int tgcn_cheb_project_series_dilated_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                          const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
-                                          int32_t bias_kind, int32_t as_series, void* out, int32_t stride, int32_t pad_left, int32_t pad_right,
-                                          int32_t dilation) {
-  if (series_dilation_is_one(H, stride, dilation))
-    return tgcn_cheb_project_series_conv_bf16(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, as_series, out,
-                                              stride, pad_left, pad_right);
-  int32_t He = 0;
-  const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
-  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "project_series_dilated_bf16: dilation %d with stride %d is not built", dilation, stride);
-  if (grc) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_dilated_bf16: bad argument");
-  if (int rc = project_series_bf16_impl(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, as_series, out, 1,
-                                        pad_left, pad_right, dilation, "project_series_dilated_bf16")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_dilated_bf16");
-  return TGCN_OK;
-}
-
-// Both bf16 stream entries (project_series_stream_impl's rule for head and pos)
-static int project_series_stream_bf16_impl(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
-                                           const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
-                                           int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation,
-                                           const char* who) {
-  int32_t C = 0;
-  if (series_stream_check(S, n_vertices, Tc, f, H, N, K, dilation, ring_ld, head, &C) || !stack || !W || !out || !ring ||
-      !series_stack_ld_ok(Tc, f, stack_ld))
-    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
-  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "%s: dtype code %d", who, bias_dtype);
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t n = n_vertices;
-  SeriesGemmBf16Params p;
-  memset(&p, 0, sizeof(p));
-  p.src = (const hbf16*)stack; p.W = (const hbf16*)W; p.bias = bias; p.out = out;
-  p.src_ks = S * n * stack_ld; p.src_ss = n * stack_ld; p.src_is = stack_ld; p.src_ts = f;
-  p.o_ss = n * Tc * N; p.o_is = (int64_t)Tc * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, Tc, N)
-  p.n = n; p.Tin = Tc; p.padl = C; p.nwin = Tc; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
-  p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
-  p.ring = (const hbf16*)ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
-  const bool vec = (f % 8 == 0) && (stack_ld % 8 == 0) && (((uintptr_t)stack & 15) == 0) && (ring_ld % 8 == 0) && (((uintptr_t)ring & 15) == 0);
-  if (int rc = series_gemm_bf16_launch(st, p, S, vec, false, who, 1, dilation, true)) return rc;
-  series_ring_update_launch(st, stack, ring, K * S * n, stack_ld, ring_ld, f, 2, vec, Tc, C, head, pos);
-  if (pos) series_stream_advance_launch(st, pos, Tc, C);
-  return TGCN_OK;
-}
-
-int tgcn_cheb_project_series_stream_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
-                                         const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
-                                         int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int32_t dilation) {
-  if (int rc = project_series_stream_bf16_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, out, ring,
-                                               ring_ld, head, nullptr, dilation, "project_series_stream_bf16")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_bf16");
-  return TGCN_OK;
-}
-
-int tgcn_cheb_project_series_stream_pos_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
-                                             const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
-                                             int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int64_t* pos, int32_t dilation) {
-  if (!pos) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_stream_pos_bf16: bad argument");
-  if (int rc = project_series_stream_bf16_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, out, ring,
-                                               ring_ld, 0, pos, dilation, "project_series_stream_pos_bf16")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_pos_bf16");
-  return TGCN_OK;
-}
-
-// The bf16 _stream_strided entry: tgcn_cheb_project_series_stream_strided_f32's contract on bf16 tensors with a row leading dimension
-int tgcn_cheb_project_series_stream_strided_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
-                                                 const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype,
-                                                 int32_t bias_kind, void* out, void* ring, int64_t ring_ld, int32_t head, int64_t* pos,
-                                                 int32_t stride, int32_t win_off) {
-  const char* who = "project_series_stream_strided_bf16";
-  int32_t C = 0, m = 0, sc = 1;
-  if (series_stream_strided_check(S, n_vertices, Tc, f, H, N, K, ring_ld, head, pos != nullptr, stride, win_off, &C, &m, &sc) || !stack || !W ||
-      (m > 0 && !out) || (C > 0 && !ring) || !series_stack_ld_ok(Tc, f, stack_ld))
-    TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-  if (stride == 1 && C > 0) {        // step 1 on a ring: the stream entries' own launches
-    if (int rc = project_series_stream_bf16_impl(stream, S, n_vertices, Tc, f, H, N, K, stack, stack_ld, W, bias, bias_dtype, bias_kind, out, ring,
-                                                 ring_ld, pos ? 0 : head, pos, 1, who)) return rc;
-    TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_strided_bf16");
-    return TGCN_OK;
-  }
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
-  if (bias_dtype != TGCN_DTYPE_F32 && bias_dtype != TGCN_DTYPE_BF16) TGCN_FAIL(TGCN_ERR_INVALID, "%s: dtype code %d", who, bias_dtype);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t n = n_vertices;
-  const bool vec = (f % 8 == 0) && (stack_ld % 8 == 0) && (((uintptr_t)stack & 15) == 0) &&
-                   (C == 0 || ((ring_ld % 8 == 0) && (((uintptr_t)ring & 15) == 0)));
-  int hc = 0;
-  if (!series_gemm_bf16_lds(H, f, series_gemm_nt(N), vec, sc, &hc))       // the plan's refusal comes before the first launch
-    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: %d channels per time row do not fit the LDS span", who, f);
-  if (m > 0) {
-    if (int drc = check_pointer_device(out, st, who)) return drc;
-    SeriesGemmBf16Params p;
-    memset(&p, 0, sizeof(p));
-    p.src = (const hbf16*)stack; p.W = (const hbf16*)W; p.bias = bias; p.out = out;
-    p.src_ks = S * n * stack_ld; p.src_ss = n * stack_ld; p.src_is = stack_ld; p.src_ts = f;
-    p.o_ss = n * (int64_t)m * N; p.o_is = (int64_t)m * N; p.o_ws = N; p.o_gs = 0; p.ocg = N;      // (S, n, m, N)
-    p.n = n; p.Tin = Tc; p.padl = C; p.nwin = m; p.H = H; p.f = f; p.N = N; p.nterms = K; p.bias_kind = bias_kind;
-    p.bias_bf16 = bias_dtype == TGCN_DTYPE_BF16;
-    if (C > 0) {
-      p.ring = (const hbf16*)ring; p.ring_ks = S * n * ring_ld; p.ring_ss = n * ring_ld; p.ring_is = ring_ld; p.C = C; p.head = head; p.pos = pos;
-      p.win_off = win_off;
-    } else {       // one tap: the chunk from row win_off on through the instantiations without a ring
-      p.src = (const hbf16*)stack + (int64_t)win_off * f; p.Tin = Tc - win_off;
-    }
-    if (int rc = series_gemm_bf16_launch(st, p, S, vec, false, who, sc, 1, C > 0)) return rc;
-  }
-  if (C > 0) series_ring_update_launch(st, stack, ring, K * S * n, stack_ld, ring_ld, f, 2, vec, Tc, C, head, pos);
-  if (pos) series_stream_advance_launch(st, pos, Tc, C);
-  TGCN_CHECK_LAUNCH("tgcn_cheb_project_series_stream_strided_bf16");
-  return TGCN_OK;
-}
-
-size_t tgcn_cheb_series_conv_backward_bf16_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                                           int32_t stride, int32_t pad_left, int32_t pad_right) {
-  // the flipped weight (bf16, in the fp32 entries' slot) and the fp32 partials: the fp32 entries' size and 256 MB cap
-  return tgcn_cheb_series_conv_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
-}
-
-// Both bf16 gradients after the geometry check (dil > 1: stride == 1); need: the entry's own workspace size
-static int series_backward_bf16_impl(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                     const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G, float* dW,
-                                     void* workspace, size_t workspace_bytes, size_t need, int32_t stride, int32_t pad_left, int32_t pad_right,
-                                     int32_t dil, const char* who) {
-  if (!g) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
-  if (int drc = check_pointer_device(g, (hipStream_t)stream, who)) return drc;
-  if (!workspace || workspace_bytes < need || ((uintptr_t)workspace & 15)) TGCN_FAIL(TGCN_ERR_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
-  stride = series_conv_stride(T, stride, pad_left, pad_right);
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t n = n_vertices, Tf = (int64_t)T * f, nwin = series_conv_nwin(T, (H - 1) * dil + 1, stride, pad_left, pad_right),
-                wf = (int64_t)K * H * f * N;
-  const int32_t pl = pad_left;
-  const bool conv = stride != 1 || pad_left != 0 || pad_right != 0;
-  int64_t g_ss, g_is, g_ws;
-  if (g_as_series) { g_ss = n * nwin * N; g_is = nwin * N; g_ws = N; }
-  else { g_ss = nwin * n * N; g_is = N; g_ws = n * N; }
-  if (G) {      // the forward's kernel over g as a series of N channels, columns (k, c), fp32 out; per phase of the window step, each at step 1
-    if (!W) TGCN_FAIL(TGCN_ERR_INVALID, "%s: the input gradient needs W", who);
-    hbf16* Wd = (hbf16*)workspace;
-    { ProfScope ps(TGCN_PROF_RELAYOUT, st);
-      hipLaunchKernelGGL(series_flip_weight_bf16_kernel, dim3(grid_1d(wf)), dim3(kBlock), 0, st, (const hbf16*)W, Wd, (int)K, (int)H, (int)f, (int)N,
-                         (int)stride); }
-    // the time rows of the phases ph >= H (a step longer than the window) lie between the windows: exact zeros
-    if (stride > H && hipMemsetAsync(G, 0, (size_t)K * S * n * Tf * sizeof(float), st) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "%s: memset failed", who);
-    // 16-byte loads of g's time rows: N % 8 makes every stride of either layout a multiple of 8 elements.  The phases' weights start at
-    // rows of N*K*f elements: any alignment, the weight tile is loaded element by element.
-    const bool vec = (N % 8 == 0) && (((uintptr_t)g & 15) == 0);
-    SeriesGemmBf16Params over_g;      // what every launch over g shares (as in series_backward_impl)
-    memset(&over_g, 0, sizeof(over_g));
-    over_g.src = (const hbf16*)g; over_g.bias = nullptr; over_g.bias_kind = 0;
-    over_g.src_ks = 0; over_g.src_ss = g_ss; over_g.src_is = g_is; over_g.src_ts = g_ws;
-    over_g.o_ss = n * Tf; over_g.o_is = Tf; over_g.o_gs = S * n * Tf; over_g.ocg = f;
-    over_g.n = n; over_g.Tin = (int32_t)nwin; over_g.f = N; over_g.N = K * f; over_g.nterms = 1;
-    if (dil > 1) {      // dilated taps (step 1): all T time rows in one launch of the DILATED kernel over g, reaching (H - 1) * dil - pl rows back
-      SeriesGemmBf16Params p = over_g;
-      p.W = Wd; p.out = G; p.o_ws = f;
-      p.padl = (H - 1) * dil - pl; p.nwin = T; p.H = H;
-      if (int rc = series_gemm_bf16_launch(st, p, S, vec, true, who, 1, dil)) return rc;
-    } else {
-      for (int ph = 0; ph < stride && ph < H; ++ph) {
-        const int Hp = series_phase_rows(H, stride, ph);
-        if ((int64_t)T - 1 + pl - ph < 0) continue;
-        const int64_t u0 = ph >= pl ? 0 : (pl - ph + stride - 1) / stride, u1 = ((int64_t)T - 1 + pl - ph) / stride;
-        if (u1 < u0) continue;
-        SeriesGemmBf16Params p = over_g;
-        p.W = Wd + (int64_t)series_phase_row0(H, stride, ph) * N * K * f;
-        p.out = G + (u0 * stride + ph - pl) * f; p.o_ws = (int64_t)stride * f;
-        p.padl = (int32_t)(Hp - 1 - u0); p.nwin = (int32_t)(u1 - u0 + 1); p.H = Hp;
-        if (int rc = series_gemm_bf16_launch(st, p, S, vec, true, who)) return rc;
-      }
-    }
-  }
-  if (dW) {
-    if (!stack || !series_stack_ld_ok(T, f, stack_ld)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: the weight gradient needs the hop tensors", who);
-    const int64_t M = S * n * nwin;
-    SeriesWgradBf16Params q;
-    memset(&q, 0, sizeof(q));
-    q.stack = (const hbf16*)stack; q.g = (const hbf16*)g; q.partial = (float*)((char*)workspace + align_up((size_t)wf * sizeof(float), 256));
-    q.st_ks = S * n * stack_ld; q.st_is = stack_ld; q.g_ss = g_ss; q.g_is = g_is; q.g_ws = g_ws;
-    q.M = M; q.rows_per_block = series_wgrad_rows_per_block(M, wf); q.n = n;
-    q.f = f; q.nwin = (int32_t)nwin; q.J = H * f; q.N = N; q.K = K;
-    q.stride = stride; q.padl = pl; q.T = T; q.dil = dil;
-    const int64_t nblocks = (M + q.rows_per_block - 1) / q.rows_per_block;
-    const int64_t jtiles = (q.J + 15) / 16, tgroups = (K + kWgTerms - 1) / kWgTerms;
-    if (q.rows_per_block + nwin >= (int64_t)INT32_MAX || q.rows_per_block / nwin + n >= (int64_t)INT32_MAX || nblocks > (int64_t)INT32_MAX ||
-        (N + 63) / 64 > 65535 || jtiles * tgroups > 65535)
-      TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: weight gradient shape too large", who);
-    { ProfScope ps(TGCN_PROF_WGRAD, st);
-      const dim3 grid((unsigned)nblocks, (unsigned)((N + 63) / 64), (unsigned)(jtiles * tgroups));
-      if (dil > 1) hipLaunchKernelGGL((series_wgrad_bf16_partial_kernel<true, true>), grid, dim3(64), 0, st, q);
-      else if (conv) hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<true>, grid, dim3(64), 0, st, q);
-      else hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<false>, grid, dim3(64), 0, st, q); }
-    WgradParams r;
-    memset(&r, 0, sizeof(r));
-    r.partial = q.partial; r.dW = dW; r.Kc = q.J; r.N = N; r.nterms = K; r.nblocks = (int32_t)nblocks;
-    { ProfScope ps(TGCN_PROF_WGRAD, st);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((wf + 63) / 64)), dim3(1024), 0, st, r); }
-  }
-  return TGCN_OK;
-}
-
-int tgcn_cheb_series_conv_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                        const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
-                                        float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right) {
-  if (!series_conv_shape_ok(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right)) TGCN_FAIL(TGCN_ERR_INVALID, "series_conv_backward_bf16: bad argument");
-  const size_t need = tgcn_cheb_series_conv_backward_bf16_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right);
-  if (int rc = series_backward_bf16_impl(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, g, g_as_series, W, G, dW, workspace, workspace_bytes,
-                                         need, stride, pad_left, pad_right, 1, "series_conv_backward_bf16")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_series_conv_backward_bf16");
-  return TGCN_OK;
-}
-
-size_t tgcn_cheb_series_dilated_backward_bf16_workspace_bytes(int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                                              int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation) {
-  return tgcn_cheb_series_dilated_backward_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation);
-}
-
-int tgcn_cheb_series_dilated_backward_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
-                                           const void* stack, int64_t stack_ld, const void* g, int32_t g_as_series, const void* W, float* G,
-                                           float* dW, void* workspace, size_t workspace_bytes, int32_t stride, int32_t pad_left, int32_t pad_right,
-                                           int32_t dilation) {
-  if (series_dilation_is_one(H, stride, dilation))
-    return tgcn_cheb_series_conv_backward_bf16(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, g, g_as_series, W, G, dW, workspace,
-                                               workspace_bytes, stride, pad_left, pad_right);
-  int32_t He = 0;
-  const int grc = series_dilated_check(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation, &He);
-  if (grc == TGCN_ERR_UNSUPPORTED) TGCN_FAIL(grc, "series_dilated_backward_bf16: dilation %d with stride %d is not built", dilation, stride);
-  if (grc) TGCN_FAIL(TGCN_ERR_INVALID, "series_dilated_backward_bf16: bad argument");
-  const size_t need = tgcn_cheb_series_dilated_backward_bf16_workspace_bytes(S, n_vertices, T, f, H, N, K, stride, pad_left, pad_right, dilation);
-  if (int rc = series_backward_bf16_impl(stream, S, n_vertices, T, f, H, N, K, stack, stack_ld, g, g_as_series, W, G, dW, workspace, workspace_bytes,
-                                         need, 1, pad_left, pad_right, dilation, "series_dilated_backward_bf16")) return rc;
-  TGCN_CHECK_LAUNCH("tgcn_cheb_series_dilated_backward_bf16");
-  return TGCN_OK;
-}
+extern "C" {
 
 int tgcn_fold_weight_f32(void* stream, int32_t K, int64_t CN, const float* fold, const float* W, float* out, int32_t transpose) {
   if (K < 1 || K > 4096 || CN < 1 || !fold || !W || !out || W == out) TGCN_FAIL(TGCN_ERR_INVALID, "fold_weight: bad argument");

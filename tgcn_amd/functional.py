@@ -332,7 +332,7 @@ def _windows_forward(op, x3, W, bias, bias_kind, mode):
     K, H, N = W.shape
     nwin = T - H + 1
     # x3 is in the operand's labels already (cheb_time_windows relabelled it): cheb_stack must not relabel it again
-    stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)   # (K, S, n, T)
+    stack = _series_stack(op, x3, K, mode)   # (K, S, n, T)
     out = torch.empty((S * nwin, n, N), dtype=torch.float32, device=x3.device)
     W2 = W.reshape(K * H, N).contiguous()
     b = bias.contiguous() if bias is not None else None
@@ -430,6 +430,24 @@ def _geom4(geom):
     return (tuple(geom) + (1,))[:4]
 
 
+def _series_stack(op, x3, K, mode):
+    """the K hop tensors of a series' rows in the operand's labels: the monomial stack (power mode) or the Chebyshev recurrence"""
+    return _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)
+
+
+def _series_bias_grad(g, as_series, bias_kind, bias_shape):
+    """the bias gradient of a time-window layer from its fp32 output gradient g: (S, n, nwin, N) as a series, else (S*nwin, n, N)"""
+    if as_series:
+        return (g.sum(dim=(0, 1, 2)) if bias_kind == BIAS_CHANNEL else g.sum(dim=(0, 2))).reshape(bias_shape)
+    return _bias_grad(g, bias_kind, bias_shape, True)
+
+
+def _bf16_row_ld(Tf):
+    """elements between the vertex rows of a bf16 hop stack (the trailing-element row padding): T*f rounded up to whole 16-byte units, so
+    that every row starts aligned; rows of fewer than 7 elements stay packed"""
+    return Tf if (Tf % 8 == 0 or Tf < 7) else Tf + (-Tf) % 8
+
+
 def check_series_bf16(f, as_series, geom, series_dtype):
     """what a streaming call with bfloat16 parameters needs, checked before an operand is built: not the scalar-load form (ChebWindowsFn: one
     channel, window-major, default geometry), and a series that is bfloat16 already -- a streaming chain is bf16 from end to end (an
@@ -470,7 +488,7 @@ class ChebSeriesFn(torch.autograd.Function):
         fold = _power_fold(mode, W)
         Wt = _working_weight(fold, W)
         # the series is in the operand's labels already (cheb_time_windows relabelled it)
-        stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)   # (K, S, n, T*f)
+        stack = _series_stack(op, x3, K, mode)   # (K, S, n, T*f)
         out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=torch.float32, device=x3.device)
         b = bias.contiguous() if bias is not None else None
         args = (_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(out))
@@ -528,10 +546,7 @@ def _series_backward(ctx, Wt, g):
             dW = dW.view(K, H, f, N)
     gb = None
     if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
-        if ctx.as_series:
-            gb = (g.sum(dim=(0, 1, 2)) if ctx.bias_kind == BIAS_CHANNEL else g.sum(dim=(0, 2))).reshape(ctx.bias_shape)
-        else:
-            gb = _bias_grad(g, ctx.bias_kind, ctx.bias_shape, True)
+        gb = _series_bias_grad(g, ctx.as_series, ctx.bias_kind, ctx.bias_shape)
     return gx, dW, gb
 
 
@@ -580,7 +595,7 @@ class ChebSeriesReluPoolFn(torch.autograd.Function):
         W = weight_khfg.float().contiguous().view(K, H * f, N)
         fold = _power_fold(mode, W)
         Wt = _working_weight(fold, W)
-        stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)   # (K, S, n, T*f)
+        stack = _series_stack(op, x3, K, mode)   # (K, S, n, T*f)
         shape = (S, n // pool, nwin, N) if as_series else (S * nwin, n // pool, N)
         z = torch.empty(shape, dtype=torch.float32, device=x3.device)
         idx = torch.empty(shape, dtype=torch.uint8, device=x3.device) if need_idx else None
@@ -675,7 +690,7 @@ def _chunk_stack(op, x, t0, tc, K, mode):
     of tc*f floats, as _stream_chunk's"""
     S, n, _, f = x.shape
     x3 = x[:, :, t0:t0 + tc].reshape(S, n, tc * f)       # a view (time and channel merge); the stack's term 0 is the contiguous copy
-    return _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)
+    return _series_stack(op, x3, K, mode)
 
 
 class ChebSeriesChunkFn(torch.autograd.Function):
@@ -756,10 +771,7 @@ class ChebSeriesChunkFn(torch.autograd.Function):
                 dW = dW.view(K, H, f, N)
         gb = None
         if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
-            if ctx.as_series:
-                gb = (g.sum(dim=(0, 1, 2)) if ctx.bias_kind == BIAS_CHANNEL else g.sum(dim=(0, 2))).reshape(ctx.bias_shape)
-            else:
-                gb = _bias_grad(g, ctx.bias_kind, ctx.bias_shape, True)
+            gb = _series_bias_grad(g, ctx.as_series, ctx.bias_kind, ctx.bias_shape)
         return gx, dW, gb, None, None, None, None, None, None
 
 
@@ -2012,7 +2024,7 @@ class ChebSeriesBf16Fn(torch.autograd.Function):
             st = min(stride, T + left + right)      # (dilated: stride 1, all H weight time rows in the one launch)
             _lib.check(L.tgcn_series_conv_plan_bf16(-(-H // st), N, K * f, int(N % 8 == 0), 1, C.byref(hc), C.byref(lds)))
         Tf = T * f
-        ld = Tf if (Tf % 8 == 0 or Tf < 7) else Tf + (-Tf) % 8
+        ld = _bf16_row_ld(Tf)
         x3 = series.to(BF16).contiguous().view(S, n, Tf)      # bf16 already, or its bf16 values in fp32 behind a reordered operand's relabelling
         if ld != Tf:
             x3 = torch.nn.functional.pad(x3, (0, ld - Tf))
@@ -2064,12 +2076,7 @@ class ChebSeriesBf16Fn(torch.autograd.Function):
                 dW = dW.view(K, H, f, N).to(ctx.dtypes[1])
         gb = None
         if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
-            g32 = g.float()
-            if ctx.as_series:
-                gb = (g32.sum(dim=(0, 1, 2)) if ctx.bias_kind == BIAS_CHANNEL else g32.sum(dim=(0, 2))).reshape(ctx.bias_shape)
-            else:
-                gb = _bias_grad(g32, ctx.bias_kind, ctx.bias_shape, True)
-            gb = gb.to(ctx.dtypes[2])
+            gb = _series_bias_grad(g.float(), ctx.as_series, ctx.bias_kind, ctx.bias_shape).to(ctx.dtypes[2])
         return gx, dW, gb, None, None, None, None, None
 
 
@@ -2175,7 +2182,7 @@ def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state, pool=0):
     Wt = _working_weight_bf16(fold, W) if bf16 else _working_weight(fold, W)      # folded on every call, as forward_series does
     Tf = Tc * f
     if bf16:
-        ld = Tf if (Tf % 8 == 0 or Tf < 7) else Tf + (-Tf) % 8      # ChebSeriesBf16Fn's trailing-element row padding
+        ld = _bf16_row_ld(Tf)
         x3 = chunk.to(BF16).contiguous().view(S, n, Tf)
         if ld != Tf:
             x3 = torch.nn.functional.pad(x3, (0, ld - Tf))
@@ -2183,7 +2190,7 @@ def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state, pool=0):
         _basis_bf16(op, x3, K, mode, out=stack)
     else:
         x3 = _aligned_input(chunk.float().contiguous().view(S, n, Tf))
-        stack = _monomial_stack(op, x3, K) if mode == MODE_POWER else cheb_stack(op, x3, K, MODE_CHEBYSHEV, _operand_labels=True)
+        stack = _series_stack(op, x3, K, mode)
     # a capturable state takes only chunks of Tc % step == 0 (stream_precheck): off = 0 and m = Tc / step whatever the device position holds
     m, off = (Tc, 0) if step == 1 else ((Tc // step, 0) if state.capturable else stream_windows(state.seen, Tc, step))
     out = torch.empty((S, n // pool if pool else n, m, N), dtype=state.dtype, device=x3.device)

@@ -4,6 +4,7 @@
 Usage (from anywhere, reference mounted read-only at /root/reference):
 
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [--ref /root/reference] [--out tests/golden]
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py --series-refusals      (tests/test_series_refusal_table.py; needs no reference)
 
 What is executed from the reference (nothing is copied; only inputs/outputs are stored):
   * gcn.graph            grid / distance_sklearn_metrics / adjacency / laplacian / rescale_L / chebyshev
@@ -82,9 +83,21 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"))
+    ap.add_argument("--series-refusals", action="store_true",
+                    help="only record tests/golden/series_refusals_abi8.json from the built library (no reference, no device)")
     args = ap.parse_args()
     out_dir = os.path.abspath(args.out)
     os.makedirs(out_dir, exist_ok=True)
+    if args.series_refusals:       # the grid is tests/test_series_refusal_table.py's; the answers are the loaded library's
+        import json
+        root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+        sys.path[:0] = [root, os.path.join(root, "tests")]
+        import test_series_refusal_table as rt
+        from tgcn_amd import _lib
+        assert _lib.ABI_VERSION == 8, "the recording belongs to the ABI 8 library"
+        with open(os.path.join(out_dir, "series_refusals_abi8.json"), "w") as f:
+            json.dump(rt.table(_lib.lib()), f, separators=(",", ":"))
+        return
 
     sys.dont_write_bytecode = True
     sys.path.insert(0, args.ref)
