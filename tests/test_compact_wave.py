@@ -166,7 +166,8 @@ def test_offsets_beyond_2_31_elements(gpu_device):
     t * 640 M floats into x and out).  Size-independent properties, all compared on the device:
       * the last sample computed inside the batch == the same sample computed alone at offset 0 (bitwise: same kernels, samples
         are independent), for the plain and for the compacted forward;
-      * plain and compacted forward agree; linearity of the layer without bias on the last sample."""
+      * plain and compacted forward agree; linearity of the layer without bias on the last sample.
+    (The streaming time-window entries beyond 2^31 and 2^32 elements: tests/test_series_large_offsets.py.)"""
     from tgcn_amd import functional as F, graph, _lib
     g = torch.Generator(device="cuda").manual_seed(9)
     q, n, C, N, K = 9, 4_000_000, 64, 64, 3

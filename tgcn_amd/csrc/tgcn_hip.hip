@@ -1427,6 +1427,15 @@ static void series_dilated_tiles(int32_t nwin, int32_t dil, int32_t* tpp, int32_
 // Everything about one GEMM launch that can refuse: the tiles and the grid's limits, then the plan.  Both launchers start here, and so does
 // the chunk backward, which has to know before its first launch.
 struct SeriesLaunchPlan { int32_t tpp, tpv, hc, lds, NT; int64_t nq, ntiles, gx, gy; };
+// A launch holds fewer than 2^32 threads along x.  The runtime this was met on (ROCm 7.2, gfx950) counts a grid's work-items in 32 bits and runs a
+// larger grid only modulo 2^32, without an error: 16 one-window phase tiles per vertex on 4.2 M vertex rows are 16.8 M workgroups of 256, and
+// only (16.8 M * 256) mod 2^32 threads ran.  Another runtime may refuse such a grid instead; either way no launch here asks for one.  The
+// launchers issue the grid in parts of kSeriesGridPart workgroups, each told its first workgroup (blk0); the parts write disjoint tiles.
+// A launch error of any part is what every driver ends on (series_launched: hipGetLastError after its last launch).
+constexpr int64_t kSeriesGridPart = (int64_t)UINT32_MAX / kBlock;
+static dim3 series_grid_part(const SeriesLaunchPlan& lp, int64_t blk0) {
+  return dim3((unsigned)std::min<int64_t>(kSeriesGridPart, lp.gx - blk0), (unsigned)lp.gy);
+}
 static int series_launch_plan(SeriesLdsFn lds_of, int64_t S, int64_t n, int32_t nwin, int32_t H, int32_t f, int32_t N, bool vec, int stride, int dil,
                               int pool, const char* who, SeriesLaunchPlan* o) {
   o->tpp = 0; o->tpv = (nwin + kSgWin - 1) / kSgWin;
@@ -1459,12 +1468,12 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
   const int NT = lp.NT, hc = lp.hc, lds = pool ? series_pool_lds(lp.lds, NT) : lp.lds;
   p.HC = hc;
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = series_row_floats(hc, p.f, vec, stride);
-  const dim3 grid((unsigned)lp.gx, (unsigned)lp.gy);
   ProfScope ps(TGCN_PROF_PROJECT, st);
 #define TGCN_SERIES_GEMM(NT_, VEC_, STR_, DIL_, ...)                                                                      \
   do {                                                                                                                    \
     if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_kernel<NT_, VEC_, STR_, DIL_, ##__VA_ARGS__>, lds);     \
-    hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_, STR_, DIL_, ##__VA_ARGS__>), grid, dim3(kBlock), lds, st, p);       \
+    for (p.blk0 = 0; p.blk0 < lp.gx; p.blk0 += kSeriesGridPart)                                                           \
+      hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_, STR_, DIL_, ##__VA_ARGS__>), series_grid_part(lp, p.blk0), dim3(kBlock), lds, st, p); \
   } while (0)
 #define TGCN_SERIES_GEMM_NT(VEC_, STR_, DIL_, ...)                                                                        \
   do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_, DIL_, ##__VA_ARGS__); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_, DIL_, ##__VA_ARGS__);   \
@@ -1499,12 +1508,12 @@ static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int6
   const int NT = lp.NT, hc = lp.hc, lds = lp.lds;
   p.HC = hc;
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = vec ? series_bf16_row_elems(p.f, p.lst) : p.f;
-  const dim3 grid((unsigned)lp.gx, (unsigned)lp.gy);
   ProfScope ps(TGCN_PROF_PROJECT, st);
 #define TGCN_SERIES_GEMM_B(NT_, VEC_, STR_, OUT_, DIL_, ...)                                                                      \
   do {                                                                                                                            \
     if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>, lds);  \
-    hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>), grid, dim3(kBlock), lds, st, p);    \
+    for (p.blk0 = 0; p.blk0 < lp.gx; p.blk0 += kSeriesGridPart)                                                                   \
+      hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>), series_grid_part(lp, p.blk0), dim3(kBlock), lds, st, p); \
   } while (0)
 #define TGCN_SERIES_GEMM_B_NT(VEC_, STR_, OUT_, DIL_, ...)                                                                        \
   do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                                 \

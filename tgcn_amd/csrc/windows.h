@@ -25,6 +25,7 @@ struct SeriesGemmParams {
   int64_t src_ks, src_ss, src_is, src_ts;
   int64_t o_ss, o_is, o_ws, o_gs;   // output strides: recording, vertex, window, column group (column col lives at (col / ocg) * o_gs + col % ocg)
   int64_t n, ntiles;                // vertices per recording; wave tiles = S * n * tpv
+  int64_t blk0;                     // the launch's first workgroup: a grid of 2^32 threads or more is issued in parts (kSeriesGridPart)
   int32_t Tin, padl, nwin, H, f, N, nterms, ocg, bias_kind, tpv, HC;
   int32_t stride, lst, fp;          // STRIDED only: window step in time rows, window distance in span rows, floats per span row
   int32_t dil, tpp;                 // DILATED only: time rows between two taps, tiles of 32 windows per phase
@@ -112,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
   float* span = sg_lds + kSgKT * NS + wave * (int)(STRIDED ? series_span_floats(p.HC, p.f, VEC, p.stride) : series_span_floats(p.HC, p.f, VEC));
   static_assert(!(STRIDED && DILATED), "a window step with dilated taps is not built");
   static_assert(!(POOLED && STRIDED && CARRY), "a pooled window step on a chunk is not built");
-  const int64_t tile = POOLED ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + wave;
+  const int64_t tile = POOLED ? p.blk0 + blockIdx.x : (p.blk0 + blockIdx.x) * 4 + wave;
   bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
   int w0 = live ? (int)(tile % p.tpv) * kSgWin : 0;      // DILATED: the first window's index v0 inside its phase

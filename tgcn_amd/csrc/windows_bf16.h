@@ -38,6 +38,7 @@ struct SeriesGemmBf16Params {
   int64_t src_ks, src_ss, src_is, src_ts;   // in elements
   int64_t o_ss, o_is, o_ws, o_gs;
   int64_t n, ntiles;
+  int64_t blk0;                     // the launch's first workgroup (windows.h)
   int32_t Tin, padl, nwin, H, f, N, nterms, ocg, bias_kind, bias_bf16, tpv, HC;
   int32_t stride, lst, fp;
   int32_t dil, tpp;                 // DILATED only (windows.h)
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(kBlock) void series_gemm_bf16_kernel(const SeriesGe
   hbf16* span = Ws + NW * kPbLd + wave * (int)series_bf16_span_elems(p.HC, p.f, VEC8, stride);
   const uint16_t* span16 = reinterpret_cast<const uint16_t*>(span);
   static_assert(!(STRIDED && DILATED), "a window step with dilated taps is not built");
-  const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
+  const int64_t tile = (p.blk0 + blockIdx.x) * 4 + wave;
   bool live = tile < p.ntiles;
   const int64_t si = live ? tile / p.tpv : 0;
   int w0 = live ? (int)(tile % p.tpv) * kSgWin : 0;      // DILATED: the first window's index v0 inside its phase
