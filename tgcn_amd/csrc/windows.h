@@ -232,23 +232,33 @@ __global__ __launch_bounds__(kBlock) void series_gemm_kernel(const SeriesGemmPar
         }
         __syncthreads();                        // weight tile (and, first time round, the span) visible
         const int ksteps = min(kSgKT, jn - j0 + 3) >> 2;
-        for (int ks = 0; ks < ksteps; ++ks) {
+        // steps whose four k are all weight rows; the scalar-load form has at most one more, the ragged last step of a chunk (jn % 4 != 0).
+        // There k >= jn lies in the first floats of time row r + hcn of the span, which belongs to LATER windows; its zero weight row
+        // cancels a finite value only (0 * Inf = NaN), so that one step reads zero on the A side as well -- peeled, the loop is untouched
+        const int kfull = VEC ? ksteps : min(kSgKT, jn - j0) >> 2;
+        auto kstep = [&](const int ks, auto ragged) {
           int aoff;
+          bool kin = true;
           if constexpr (VEC) {
             aoff = ((STRIDED ? r * lst : r) + hh) * fp + cc + kq;
             cc += 4;
             if (cc >= p.f) { cc = 0; ++hh; }
           } else {
             aoff = (STRIDED ? r * lst : r) * p.f + j0 + ks * 4 + kq;  // < 31 * lst * f + jn + 3: inside the zero-tailed span
+            if constexpr (decltype(ragged)::value) kin = j0 + ks * 4 + kq < jn;
           }
-          const float a0 = span[aoff];
-          const float a1 = span[aoff + (STRIDED ? 16 * lst : 16) * fp];
+          const float a0 = kin ? span[aoff] : 0.f;
+          const float a1 = kin ? span[aoff + (STRIDED ? 16 * lst : 16) * fp] : 0.f;
 #pragma unroll
           for (int nt = 0; nt < NT; ++nt) {
             const float bv = Ws[(ks * 4 + kq) * NS + nt * 16 + r];
             acc[0][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, bv, acc[0][nt], 0, 0, 0);
             acc[1][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, bv, acc[1][nt], 0, 0, 0);
           }
+        };
+        for (int ks = 0; ks < kfull; ++ks) kstep(ks, std::false_type{});
+        if constexpr (!VEC) {
+          if (kfull < ksteps) kstep(kfull, std::true_type{});
         }
       }
       __syncthreads();                          // span and weight tile are free again
