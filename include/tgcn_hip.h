@@ -566,6 +566,31 @@ int tgcn_cheb_stream_small_f32(void* stream, const tgcn_csr* A, int32_t mode, in
                                const float* chunk, const float* W, const float* bias, int32_t bias_kind, float* out, float* ring,
                                int64_t ring_ld, int32_t head, const int64_t* pos, int32_t dilation);
 
+/* A whole-series time-window layer in ONE launch, for operands that fit in LDS ("One launch per series"; fp32): the K - 1
+ * hops and the window projection of tgcn_cheb_project_series_dilated_f32 at stride 1, out of LDS.  series (S, n, T*f) is the INPUT of the
+ * layer in the operand's labels (not a hop stack: the terms are made here, mode 0 the monomials P_k = A P_{k-1}, mode 1 Chebyshev
+ * T_k = 2 A T_{k-1} - T_{k-2}); W (K, H*f, N) in the basis of that mode, bias / bias_kind, as_series, out ((S, n, nwin, N) or
+ * (S*nwin, n, N), nwin = T + left + right - (H-1)*dilation), the zero pads left / right and dilation as in that entry.  The grid is
+ * S * ceil(nwin / tb) independent workgroups: each owns tb windows of one recording, loads the tb + (H-1)*dilation time rows they touch and
+ * hops them itself, so no workgroup reads what another writes.  Sums: fp32 products and sums, terms ascending, (h, c) ascending within a
+ * term, bias last -- the series entries' order, the same at every tile; equal to hops + the _dilated entry up to the order in which a hop
+ * adds its neighbours.  stack non-null: the hop stack (K, S, n, T*f) the backward entries read is written too: the tiles partition the time
+ * rows [0, T) of a recording, and every element is written once, by the workgroup that owns its row, from values it computed itself; NULL:
+ * nothing of that size is touched.  Any f, H, N, K >= 1, no alignment asked.
+ * tgcn_cheb_series_small_plan is a host query: 0 with *tb (windows per workgroup), *dense (1: the dense n x (n|1) copy of the operand in
+ * LDS, 0: its CSR -- the smaller of the two) and *lds_bytes, or TGCN_ERR_UNSUPPORTED where nothing fits: n > 1024, more than 2^20 entries,
+ * N > 1024, or operand + span buffers (one in mode 0, two in mode 1) at tb = 1 above 160 KB of LDS; TGCN_ERR_INVALID for a non-positive
+ * n, f, H, N, K, T or dilation, a pad outside [0, (H-1)*dilation], a window longer than the padded recording, a mode other than 0 / 1 or a
+ * null result pointer.  A is square (the caller's check: tgcn_csr has no column count).
+ * _f32: the plan's codes, TGCN_ERR_INVALID for a null A, series, W or out, S < 1 or a bad bias_kind, TGCN_ERR_UNSUPPORTED where n*T*f,
+ * n*nwin*N, K*H*f*N or the workgroup count reach 2^31; nothing is launched in any of these cases.  One launch (a grid of 2^32 threads or
+ * more is issued in parts); the entry does not synchronise and does not allocate. */
+int tgcn_cheb_series_small_plan(int64_t n, int64_t nnz, int32_t mode, int32_t f, int32_t H, int32_t N, int32_t K, int32_t T, int32_t left,
+                                int32_t right, int32_t dilation, int32_t* tb, int32_t* dense, int32_t* lds_bytes);
+int tgcn_cheb_series_small_f32(void* stream, const tgcn_csr* A, int32_t mode, int64_t S, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                               const float* series, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
+                               float* stack /* nullable */, int32_t left, int32_t right, int32_t dilation);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

@@ -45,6 +45,7 @@ namespace {
 #include "windows.h"
 #include "windows_bf16.h"
 #include "stream_small.h"
+#include "series_small.h"
 #include "device_build.h"
 #include "graph_build.h"
 
@@ -2019,6 +2020,61 @@ int tgcn_cheb_stream_small_f32(void* stream, const tgcn_csr* A, int32_t mode, in
 #undef TGCN_STREAM_SMALL_NTW
 #undef TGCN_STREAM_SMALL
   TGCN_CHECK_LAUNCH("tgcn_cheb_stream_small_f32");
+  return TGCN_OK;
+}
+
+// ---- one launch per series (series_small.h): the hops and the window projection of a whole-series call out of LDS
+int tgcn_cheb_series_small_plan(int64_t n, int64_t nnz, int32_t mode, int32_t f, int32_t H, int32_t N, int32_t K, int32_t T, int32_t left,
+                                int32_t right, int32_t dilation, int32_t* tb, int32_t* dense, int32_t* lds_bytes) {
+  if (!tb || !dense || !lds_bytes) TGCN_FAIL(TGCN_ERR_INVALID, "series_small_plan: bad argument");
+  SeriesSmallPlan pl;
+  const int rc = series_small_plan(n, nnz, mode, f, H, N, K, T, left, right, dilation, &pl);
+  if (rc == TGCN_ERR_INVALID) TGCN_FAIL(rc, "series_small_plan: bad argument");
+  if (rc) TGCN_FAIL(rc, "series_small_plan: n=%lld nnz=%lld f=%d H=%d N=%d does not fit one workgroup", (long long)n, (long long)nnz, f, H, N);
+  *tb = pl.tb; *dense = pl.dense; *lds_bytes = pl.lds;
+  return TGCN_OK;
+}
+
+int tgcn_cheb_series_small_f32(void* stream, const tgcn_csr* A, int32_t mode, int64_t S, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                               const float* series, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
+                               float* stack, int32_t left, int32_t right, int32_t dilation) {
+  if (!A || !series || !W || !out || S < 1) TGCN_FAIL(TGCN_ERR_INVALID, "series_small: bad argument");
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "series_small: bias_kind %d", bias_kind);
+  SeriesSmallPlan pl;
+  const int prc = series_small_plan(A->n, A->nnz, mode, f, H, N, K, T, left, right, dilation, &pl);
+  if (prc == TGCN_ERR_INVALID) TGCN_FAIL(prc, "series_small: bad argument");
+  if (prc) TGCN_FAIL(prc, "series_small: n=%lld nnz=%lld f=%d H=%d N=%d does not fit one workgroup", (long long)A->n, (long long)A->nnz, f, H, N);
+  // the kernel's 32-bit offsets: one recording's rows of the series (and of a term of the stack) and of the output; the whole weight; the grid
+  const int64_t lim = (int64_t)INT32_MAX;
+  if (A->n * T * f > lim || A->n * pl.nwin * N > lim || (int64_t)K * H * f * N > lim || S * pl.ntiles > lim)
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_small: a recording's rows, the weight or the grid exceed 32-bit offsets");
+  if (!A->rowptr || !A->edges) TGCN_FAIL(TGCN_ERR_INVALID, "series_small: bad argument");
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, "series_small")) return drc;
+  SeriesSmallParams p;
+  memset(&p, 0, sizeof(p));
+  p.rowptr = A->rowptr; p.ev = A->edges; p.series = series; p.W = W; p.bias = bias; p.out = out; p.stack = stack;
+  p.S = (int32_t)S; p.n = (int32_t)A->n; p.nnz = (int32_t)A->nnz; p.T = T; p.f = f; p.H = H; p.N = N; p.K = K; p.bias_kind = bias_kind;
+  p.TB = pl.tb; p.ld = pl.ld; p.left = left; p.dil = dilation; p.nwin = pl.nwin; p.ntiles = pl.ntiles; p.as_series = as_series ? 1 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nblk = S * pl.ntiles, part = (int64_t)UINT32_MAX / kSrMaxThreads;      // fewer than 2^32 threads per launch (series_grid_part)
+  const dim3 block((unsigned)pl.nthr);
+  ProfScope ps(TGCN_PROF_PROJECT, st);
+#define TGCN_SERIES_SMALL(DENSE_, NTW_, MODE_)                                                                        \
+  do {                                                                                                                \
+    if (pl.lds > 64 * 1024) allow_large_lds((const void*)small_series_kernel<DENSE_, NTW_, MODE_>, pl.lds);           \
+    for (int64_t b0 = 0; b0 < nblk; b0 += part) {                                                                     \
+      p.blk0 = (int32_t)b0;                                                                                           \
+      hipLaunchKernelGGL((small_series_kernel<DENSE_, NTW_, MODE_>), dim3((unsigned)std::min<int64_t>(part, nblk - b0)), block, pl.lds, st, p); \
+    }                                                                                                                 \
+  } while (0)
+#define TGCN_SERIES_SMALL_NTW(DENSE_, MODE_)                                                                          \
+  do { if (pl.ntw == 4) TGCN_SERIES_SMALL(DENSE_, 4, MODE_); else if (pl.ntw == 2) TGCN_SERIES_SMALL(DENSE_, 2, MODE_); \
+       else TGCN_SERIES_SMALL(DENSE_, 1, MODE_); } while (0)
+  if (pl.dense) { if (mode == 0) TGCN_SERIES_SMALL_NTW(true, 0); else TGCN_SERIES_SMALL_NTW(true, 1); }
+  else { if (mode == 0) TGCN_SERIES_SMALL_NTW(false, 0); else TGCN_SERIES_SMALL_NTW(false, 1); }
+#undef TGCN_SERIES_SMALL_NTW
+#undef TGCN_SERIES_SMALL
+  TGCN_CHECK_LAUNCH("tgcn_cheb_series_small_f32");
   return TGCN_OK;
 }
 

@@ -775,7 +775,118 @@ class ChebSeriesChunkFn(torch.autograd.Function):
         return gx, dW, gb, None, None, None, None, None, None
 
 
-def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_series=False, stride=1, padding=0, dilation=1, time_chunk=None):
+# fused="auto" fuses the shape classes listed here.  A call's class is what its UNFUSED form would be: "windows_f1" -- a single channel,
+# window-major, stride 1, no padding, dilation 1: the scalar-load form (ChebWindowsFn) -- or "series", every other call (the MFMA series
+# kernels, ChebSeriesFn).  Set from profiles/r21_series_small.json (DESIGN.md 3.10 "One launch per series"): a class is listed only where the
+# fused median lies below the unfused median of the same commit by more than the larger of the two spreads.  "windows_f1" does on both
+# measured operands, forward and forward + backward (148 parcels: 0.498 against 0.572 ms and 1.01 against 15.0 ms; the 28 x 28 grid: 0.456
+# against 0.495 ms and 1.86 against 35.0 ms; spreads under 0.02 ms but the last, 0.45); "series" does not (148 parcels as a series: 0.497
+# against 0.273 ms).  () would be "never".
+SERIES_FUSED_AUTO = ("windows_f1",)
+
+
+def check_series_fused(fused, stride, time_chunk, bf16, who="cheb_time_windows"):
+    """what fused= asks of a whole-series call that needs no operand, checked before one is built: False, True or "auto"; fused=True runs in
+    float32 at stride=1 without time_chunk.  -> fused"""
+    if fused is not False and fused is not True and not (isinstance(fused, str) and fused == "auto"):
+        raise _lib.TgcnError("%s: fused is False, True or \"auto\", got %r" % (who, fused))
+    if fused is True:
+        if bf16:
+            raise _lib.TgcnError("%s: fused=True runs in float32 only -- the parameters are bfloat16 (fused=False or \"auto\")" % who)
+        if not isinstance(stride, numbers.Integral) or isinstance(stride, bool) or stride != 1:
+            raise _lib.TgcnError("%s: fused=True has no window step -- the one-launch layer runs at stride=1, got stride=%r (fused=False or "
+                                 "\"auto\")" % (who, stride))
+        if time_chunk is not None:
+            raise _lib.TgcnError("%s: fused=True does not walk time chunks (time_chunk=%r): a workgroup keeps its span in LDS and nothing of "
+                                 "the stack's size exists unless the weight trains (fused=False or \"auto\")" % (who, time_chunk))
+    return fused
+
+
+def _series_small_plan(op, f, H, N, K, T, left, right, dilation, mode):
+    """tgcn_cheb_series_small_plan on a square operand -> (rc, tb, dense, lds_bytes)"""
+    tb, dense, lds = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    rc = _lib.lib().tgcn_cheb_series_small_plan(op.n, op.nnz, int(mode), int(f), int(H), int(N), int(K), int(T), int(left), int(right),
+                                                int(dilation), C.byref(tb), C.byref(dense), C.byref(lds))
+    return rc, tb.value, dense.value, lds.value
+
+
+def series_fused_supported(op, f, H, N, K, T, padding, dilation, mode):
+    """True where cheb_time_windows(..., fused=True) runs a float32 series of T time rows on this operand at stride 1: a square operand in
+    its own labels (op.perm is None), a legal padding / dilation and a plan that accepts (tgcn_cheb_series_small_plan: operand and span
+    buffers in one workgroup's LDS).  A host query: nothing launches."""
+    if op.n_cols != op.n or op.perm is not None or min(f, H, N, K, T) < 1:
+        return False
+    try:
+        _, left, right, _ = series_geometry(T, H, 1, padding, "series_fused_supported", dilation)
+    except _lib.TgcnError:
+        return False
+    return _series_small_plan(op, f, H, N, K, T, left, right, series_dilation(H, dilation), mode)[0] == 0
+
+
+def _series_fused_auto(f, as_series, geom):
+    """the measured rule of fused="auto": the class of the call's unfused form is listed in SERIES_FUSED_AUTO"""
+    return ("windows_f1" if (f == 1 and not as_series and tuple(geom) == (1, 0, 0, 1)) else "series") in SERIES_FUSED_AUTO
+
+
+def _series_fused_route(op, fused, bf16, time_chunk, geom, as_series, f, H, N, K, T, mode):
+    """whether a call with fused=True / "auto" takes the one-launch layer.  True: TgcnError for an operand or a plan that cannot; "auto":
+    False for those, for what check_series_fused refuses and outside the measured rule (asked first: no query is made for a class that never
+    fuses)"""
+    stride, left, right, dil = geom
+    if fused is True:
+        if op.n_cols != op.n:
+            raise _lib.TgcnError("cheb_time_windows: fused=True needs a square operand, got %d x %d" % (op.n, op.n_cols))
+        if op.perm is not None:
+            raise _lib.TgcnError("cheb_time_windows: fused=True runs in the operand's own labels -- a reordered operand is not supported "
+                                 "(fused=False or \"auto\")")
+        if _series_small_plan(op, f, H, N, K, T, left, right, dil, mode)[0] != 0:
+            raise _lib.TgcnError("cheb_time_windows: fused=True, but n = %d, nnz = %d, f = %d, H = %d, N = %d do not fit the one-launch layer "
+                                 "(series_fused_supported; fused=False or \"auto\")" % (op.n, op.nnz, f, H, N))
+        return True
+    return (not bf16 and time_chunk is None and stride == 1 and op.n_cols == op.n and op.perm is None and _series_fused_auto(f, as_series, geom)
+            and _series_small_plan(op, f, H, N, K, T, left, right, dil, mode)[0] == 0)
+
+
+class ChebSeriesSmallFn(torch.autograd.Function):
+    """ChebSeriesFn at stride 1 on an operand that fits in LDS, the forward in ONE launch (tgcn_cheb_series_small_f32, csrc/series_small.h;
+    DESIGN.md 3.10 "One launch per series"): the fold in power mode with K > 2, then the fused entry on the series itself -- hops, window
+    projection and bias of a tile of windows per workgroup.  The hop stack (K, S, n, T*f) is allocated and written by that launch only when
+    the weight needs a gradient (need_stack, the caller's look at grad mode); otherwise nothing of size K*T exists.  The backward is ChebSeriesFn's (_series_backward: the existing
+    backward entry of the geometry on the fused forward's stack, _adjoint_hops for the input gradient).  geom = (1, left, right, dilation)."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, need_stack):
+        L = _lib.lib()
+        S, n, T, f = series.shape
+        K, H, _, N = weight_khfg.shape
+        _, left, right, dil = geom
+        nwin = T + left + right - (H - 1) * dil
+        x3 = series.float().contiguous().view(S, n, T * f)
+        W = weight_khfg.float().contiguous().view(K, H * f, N)
+        fold = _power_fold(mode, W)
+        Wt = _working_weight(fold, W)
+        out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=torch.float32, device=x3.device)
+        stack = torch.empty((K, S, n, T * f), dtype=torch.float32, device=x3.device) if need_stack else None
+        b = bias.float().contiguous() if bias is not None else None
+        _lib.check(L.tgcn_cheb_series_small_f32(_lib.stream_ptr(), C.byref(op.struct), int(mode), S, T, f, H, N, K, _lib.ptr(x3), _lib.ptr(Wt),
+                                                _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(out), _lib.ptr(stack), left, right, dil))
+        ctx.geom = (1, left, right, dil) if dil > 1 else ((1, left, right) if (left, right) != (0, 0) else None)
+        ctx.save_for_backward(Wt)
+        ctx.stack = stack
+        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
+        ctx.dims = (S, n, T, f, H, N, K)
+        ctx.bias_shape = None if bias is None else bias.shape
+        return out
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, g):
+        return _series_backward(ctx, ctx.saved_tensors[0], g) + (None,) * 6
+
+
+def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_series=False, stride=1, padding=0, dilation=1, time_chunk=None,
+                      fused=False):
     """Streaming form of TGCNCheb_H / ChebTimeConv on sliding windows: series (S, n, T) raw recordings with weight (K, H, N), or
     (S, n, T, f) with weight (K, H, f, N), in the reference basis.  Returns (S * (T-H+1), n, N), identical to running the layer on the
     windowed batch x[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c] (load/data_hcp.py:146-152), but the K-1 hops run once on the T time
@@ -798,8 +909,15 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     is one chunk): nothing of size K*T is allocated in the forward or the backward, at the price of a third hop pass when the weight trains.
     It runs the causal layer at step 1 -- padding="causal", stride=1, any dilation, float32 parameters, either layout, a single channel on
     the general kernels -- and anything else raises TgcnError before an operand is built (check_time_chunk).  The causal result holds a row
-    for every time step; the windows that lie wholly inside the recording (padding=0) are out[:, :, He-1:] of it."""
+    for every time step; the windows that lie wholly inside the recording (padding=0) are out[:, :, He-1:] of it.
+    fused=True runs the forward of a layer in ONE launch on an operand that fits in LDS (ChebSeriesSmallFn, tgcn_cheb_series_small_f32:
+    hops, window projection and bias per tile of windows; the stack for the backward is written by the same launch, and only when the weight
+    trains): float32 parameters, stride=1, no time_chunk, any legal padding and dilation, either layout, a single channel included.  It
+    raises TgcnError before anything launches for bfloat16 parameters, stride > 1, a time_chunk, a non-square or reordered operand and a
+    plan that refuses (series_fused_supported tells).  fused="auto" fuses where all of that holds and SERIES_FUSED_AUTO says it pays, and
+    is the fused=False call everywhere else.  Fused and unfused results agree to rounding (a hop adds its neighbours in another order)."""
     bf16 = param_dtype(weight, bias, "cheb_time_windows") == BF16
+    fused = check_series_fused(fused, stride, time_chunk, bf16)
     time_chunk = check_time_chunk(time_chunk, stride, padding, bf16)
     if series.dim() not in (3, 4) or weight.dim() != series.dim():
         raise _lib.TgcnError("cheb_time_windows: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
@@ -810,7 +928,14 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     geom = series_geometry(series.shape[2], weight.shape[1], stride, padding, dilation=dilation)[:3] + (series_dilation(weight.shape[1], dilation),)
     if bf16:
         check_series_bf16(f, as_series, geom, series.dtype)
+    if fused is not False:
+        fused = _series_fused_route(op, fused, bf16, time_chunk, geom, bool(as_series), f, weight.shape[1], weight.shape[-1], weight.shape[0], series.shape[2], mode)
     _lib.require_device(series, weight, bias)
+    if fused:
+        if series.dim() == 3:
+            series, weight = series.unsqueeze(3), weight.unsqueeze(2)
+        need_stack = torch.is_grad_enabled() and weight.requires_grad       # the only reader of the stack is the weight gradient
+        return ChebSeriesSmallFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, need_stack)
     if bf16:
         if series.dim() == 3:
             series, weight = series.unsqueeze(3), weight.unsqueeze(2)

@@ -189,7 +189,7 @@ class TGCNCheb_H(_DenseLBase):
             X = X.unsqueeze(3)
         return self._stack(X)
 
-    def forward_series(self, series, as_series=False, stride=1, padding=0, dilation=1, time_chunk=None):
+    def forward_series(self, series, as_series=False, stride=1, padding=0, dilation=1, time_chunk=None, fused=False):
         """Additive API (not in the reference): series (S, n, T) or (S, n, T, f) raw recordings, f == in_channels -> the layer's output
         for all T-H+1 sliding windows of every recording without materialising the windows (load/data_hcp.py:116-154 builds them on
         the host and the hops then run H times too often): layer(xw) for xw[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c].
@@ -207,8 +207,14 @@ class TGCNCheb_H(_DenseLBase):
         follows the chunk and nothing of size K*T is allocated (F.ChebSeriesChunkFn; one more hop pass in the backward).  The causal
         layer at step 1 only: padding="causal", stride=1, any dilation, float32 parameters, either layout -- TgcnError before the operand
         is built for anything else.  The causal output has T rows; the windows that lie inside the recording are out[:, :, He-1:]
-        (as_series=True) of it."""
+        (as_series=True) of it.
+        fused=True runs the layer's forward in one launch on a graph that fits in LDS (float32, stride=1, no time_chunk, any legal
+        padding and dilation, either layout; the backward is the unfused one on a stack the same launch writes when the weight trains).
+        TgcnError where it cannot -- before the operand is built for bfloat16 parameters, stride > 1 and a time_chunk, before anything
+        launches for a reordered operand and a shape the plan refuses (F.series_fused_supported).  fused="auto" fuses where that is
+        measured to pay (F.SERIES_FUSED_AUTO) and is the fused=False call elsewhere."""
         bf16 = _compute_dtype(self) == torch.bfloat16      # F.cheb_time_windows routes it: every call but the scalar-load form
+        F.check_series_fused(fused, stride, time_chunk, bf16, "TGCNCheb_H.forward_series")
         series, W, geom = _series_args(self, series, stride, padding, dilation)
         F.check_time_chunk(time_chunk, stride, padding, bf16, "TGCNCheb_H.forward_series")
         if bf16:
@@ -217,7 +223,7 @@ class TGCNCheb_H(_DenseLBase):
                                    None if self.bias is None else self.bias.reshape(-1),
                                    F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series,
                                    stride=geom[0], padding=geom[1:3] if time_chunk is None else "causal", dilation=geom[3],
-                                   time_chunk=time_chunk)
+                                   time_chunk=time_chunk, fused=fused)
 
     def forward_stream(self, chunk, state=None, dilation=1, capturable=False, fused=False, stride=1):
         """Additive API, inference only: the causal layer on the next Tc time rows of S recordings.  chunk (S, n, Tc) or (S, n, Tc, f) ->
@@ -515,18 +521,21 @@ class ChebTimeConv(_EdgeBase):
         return F.cheb_layer(*args, values=self._values(x, edge_index, edge_weight, args[0]))
 
 
-    def forward_series(self, series, edge_index, edge_weight=None, as_series=False, stride=1, padding=0, dilation=1, time_chunk=None):
+    def forward_series(self, series, edge_index, edge_weight=None, as_series=False, stride=1, padding=0, dilation=1, time_chunk=None,
+                       fused=False):
         """Additive API: TGCNCheb_H.forward_series' contract for this class -- series (S, n, T) or (S, n, T, f), f == in_channels, ->
         forward(xw, edge_index, edge_weight) on the windowed batch xw[s*(T-H+1) + w, i, h, c] = series[s, i, w + h, c], as
         (S*(T-H+1), n, g) or, as_series=True, (S, n, T-H+1, g); true recurrence, per-channel bias.  The operand is the one forward builds
         and caches.  A learnable edge_weight (requires_grad) raises TgcnError: its gradient needs the basis of every window, which
         this entry exists not to form -- call forward on materialised windows to train edge weights.
         stride, padding, dilation and time_chunk as in TGCNCheb_H.forward_series (time_chunk: the causal layer at step 1 in float32, walked
-        Tc time rows at a time in both directions, out[:, :, He-1:] the windows inside the recording)."""
+        Tc time rows at a time in both directions, out[:, :, He-1:] the windows inside the recording).  fused: as in
+        TGCNCheb_H.forward_series (the true recurrence runs in the one-launch layer as it does in the hops)."""
         if edge_weight is not None and edge_weight.requires_grad:
             raise _lib.TgcnError("ChebTimeConv.forward_series: learnable edge weights (edge_weight.requires_grad) are not supported -- "
                                  "use forward on the windowed batch")
         bf16 = _compute_dtype(self, edge_weight) == torch.bfloat16      # as in TGCNCheb_H.forward_series
+        F.check_series_fused(fused, stride, time_chunk, bf16, "ChebTimeConv.forward_series")
         series, W, geom = _series_args(self, series, stride, padding, dilation)
         F.check_time_chunk(time_chunk, stride, padding, bf16, "ChebTimeConv.forward_series")
         if bf16:
@@ -535,7 +544,7 @@ class ChebTimeConv(_EdgeBase):
         return F.cheb_time_windows(op, series, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
                                    as_series=as_series,
                                    stride=geom[0], padding=geom[1:3] if time_chunk is None else "causal", dilation=geom[3],
-                                   time_chunk=time_chunk)
+                                   time_chunk=time_chunk, fused=fused)
 
     def forward_stream(self, chunk, edge_index, edge_weight=None, state=None, dilation=1, capturable=False, fused=False, stride=1):
         """Additive API, inference only: TGCNCheb_H.forward_stream's contract for this class -- chunk (S, n, Tc[, f]) -> (out (S, n, Tc, g),

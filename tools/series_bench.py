@@ -11,6 +11,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py --stream --fused [--include parent=FILE] [--out profiles/r14_series_stream_fused.json]
     python tools/series_bench.py --stream --stride 2,2,2 [--repeats 3] [--include parent=FILE] [--out profiles/r16_series_stream_stride.json]
     python tools/series_bench.py --time-chunk 64,256 [--repeats 3] [--include parent=FILE] [--out profiles/r17_series_time_chunk.json]
+    python tools/series_bench.py --fused-series --steps 200 --warmup 20 [--repeats 3] [--include parent=FILE] [--out profiles/r21_series_small.json]
     python tools/series_bench.py --relu-pool 4 [--repeats 3] [--out profiles/r18_series_relu_pool.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
@@ -54,7 +55,13 @@ On a tree whose forward_series has no `time_chunk` keyword only the unchunked co
 gcn_pool_4(relu(layer.forward_series(series))) (P = 2: gcn_pool; on the series layout through the (S, n, nwin*g) view) on the same commit:
 case (a) at 1 -> 32 window-major and at 32 -> 64 in the series layout, and case (b), forward and forward + backward.  The two sides
 alternate within the run, --repeats event timings each (median and spread); per side the peak of max_memory_allocated above the pre-call
-level, and torch.equal of the results and of every gradient; default --out profiles/r18_series_relu_pool.json."""
+level, and torch.equal of the results and of every gradient; default --out profiles/r18_series_relu_pool.json.
+--fused-series: the one-launch whole-series layer (forward_series(fused=True), DESIGN.md 3.10 "One launch per series") on the graphs that fit
+in LDS: the (a) layers of the r08 table on the 148 parcels (1 -> 32 window-major and as_series=True; 32 -> 64, which the plan refuses) and
+TGCNCheb_H(L, 1, 64, 5, 28) on the 28 x 28 grid, S = 8, T = 128.  Columns per case, forward and forward + backward: unfused and fused
+forward_series and forward on the materialised windows, alternating within the run, --repeats event timings of --steps calls each (median
+and max - min).  On a commit without the keyword only the unfused and the materialised column are timed, which is how the parent commit's file
+for --include LABEL=FILE is made; default --out profiles/r21_series_small.json."""
 import argparse
 import json
 import os
@@ -683,6 +690,87 @@ def main_relu_pool(args):
         json.dump(res, f, indent=1)
 
 
+def main_fused_series(args):
+    import inspect
+    dev = torch.device("cuda:0")
+    has_kw = "fused" in inspect.signature(tgcn_amd.TGCNCheb_H.forward_series).parameters
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, repeats=args.repeats,
+               has_fused_keyword=has_kw, cases={})
+    torch.manual_seed(0)
+
+    def case(name, desc, layer, series, as_series):
+        S, n, T, f = series.shape
+        K, H, _, N = layer.weight.shape
+        x = (series[..., 0] if f == 1 else series).contiguous().requires_grad_(True)       # a single channel is given as a 3-D series
+        xw = windows(series, H).requires_grad_(True)         # the windows exist beforehand: cutting them is not timed
+        entry = dict(desc=desc)
+        fusable = False
+        if has_kw:
+            op = layer._operand(dev)
+            fusable = F.series_fused_supported(op, f, H, N, K, T, 0, 1, F.MODE_POWER)
+            rc, tb, dense, lds = F._series_small_plan(op, f, H, N, K, T, 0, 0, 1, F.MODE_POWER)
+            entry["plan"] = dict(rc=rc, tb=tb, dense=dense, lds_bytes=lds, workgroups=S * -(-(T - H + 1) // tb) if rc == 0 else 0)
+        columns = ["unfused"] + (["fused"] if fusable else []) + ["materialised"]
+
+        def forward(col):
+            if col == "materialised":
+                return layer(xw)
+            return layer.forward_series(x, as_series=as_series, **(dict(fused=True) if col == "fused" else {}))
+
+        def step_of(col, train):
+            def step():
+                if not train:
+                    with torch.no_grad():
+                        forward(col)
+                    return
+                layer.zero_grad(set_to_none=True)
+                x.grad = xw.grad = None
+                out = forward(col)
+                out.backward(torch.ones_like(out))
+            return step
+
+        if fusable:
+            with torch.no_grad():
+                a, b = forward("fused"), forward("unfused")
+            entry["fused_vs_unfused_max_rel"] = float((a - b).abs().max() / b.abs().max())
+        for train in (False, True):
+            ms = {c: [] for c in columns}
+            for _ in range(args.repeats):               # alternating: every column once per repeat
+                for c in columns:
+                    ms[c].append(events_ms(step_of(c, train), args.steps, args.warmup))
+            entry["forward_backward" if train else "forward"] = {
+                c: dict(ms_per_call=ms[c], median=sorted(ms[c])[len(ms[c]) // 2], spread=round(max(ms[c]) - min(ms[c]), 4)) for c in columns}
+        res["cases"][name] = entry
+        print(json.dumps({name: entry}), flush=True)
+        layer.zero_grad(set_to_none=True)
+        torch.cuda.empty_cache()
+
+    op = dti148(dev)
+    l1 = tgcn_amd.TGCNCheb_H(op, 1, 32, 10, 15).to(dev)
+    l2 = tgcn_amd.TGCNCheb_H(op, 32, 64, 10, 15).to(dev)
+    x1, x32 = torch.randn(8, op.n, 284, 1, device=dev), torch.randn(8, op.n, 284, 32, device=dev)
+    for as_series in (False, True):
+        tag = "series" if as_series else "windows"
+        case("a_dti148_1to32_" + tag, "dti148 S=8 T=284 H=15 K=10 f=1 -> g=32, as_series=%s" % as_series, l1, x1, as_series)
+        case("a_dti148_32to64_" + tag, "dti148 S=8 T=284 H=15 K=10 f=32 -> g=64, as_series=%s" % as_series, l2, x32, as_series)
+    del l1, l2, x1, x32
+    n, row, col, val = synth.grid_knn(28, device=dev)
+    opg = GraphOperand.from_coo(n, row, col, val, dev)
+    lg = tgcn_amd.TGCNCheb_H(opg, 1, 64, 5, 28).to(dev)
+    case("g_grid784_1to64", "grid_knn(28) n=784 S=8 T=128 H=28 K=5 f=1 -> g=64, window-major", lg, torch.randn(8, n, 128, 1, device=dev), False)
+    for item in args.include:
+        label, path = item.split("=", 1)
+        with open(path) as f:
+            other = json.load(f)
+        rel = {name: {m: round(entry[m]["unfused"]["median"] / res["cases"][name][m]["unfused"]["median"], 3) for m in ("forward", "forward_backward")}
+               for name, entry in other["cases"].items() if name in res["cases"]}
+        res.setdefault("runs", {})[label] = dict(run=other, unfused_ms_over_this_run=rel)
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r21_series_small.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def stride_arg(text):
     parts = tuple(int(v) for v in text.split(","))
     return parts[0] if len(parts) == 1 else parts
@@ -705,6 +793,8 @@ def main():
                     help="a training step on T = 1200, unchunked against each time_chunk (profiles/r17_series_time_chunk.json)")
     ap.add_argument("--relu-pool", type=int, choices=(2, 4), default=None, metavar="P",
                     help="cheb_series_relu_pool against gcn_pool_4(relu(forward_series)) on the same commit (profiles/r18_series_relu_pool.json)")
+    ap.add_argument("--fused-series", action="store_true",
+                    help="forward_series(fused=True) next to the unfused call and the materialised windows (profiles/r21_series_small.json)")
     ap.add_argument("--include", action="append", default=[], metavar="LABEL=FILE",
                     help="put another run's --out file (the parent commit's, a repeat of this one) into this one under runs[LABEL], with "
                          "each shared case's ms per call relative to this run")
@@ -712,6 +802,10 @@ def main():
     args = ap.parse_args()
     if args.dtype == "bf16":
         return main_bf16(args)
+    if args.fused_series:
+        if args.relu_pool is not None or args.time_chunk is not None or args.stream or args.dilation or args.conv:
+            ap.error("--fused-series runs alone")
+        return main_fused_series(args)
     if args.relu_pool is not None:
         if args.time_chunk is not None or args.stream or args.dilation or args.conv:
             ap.error("--relu-pool P runs alone")
