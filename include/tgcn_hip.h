@@ -488,6 +488,31 @@ int tgcn_cheb_project_series_stream_pool_f32(void* stream, int64_t S, int64_t n_
                                              const float* stack, const float* W, const float* bias, int32_t bias_kind, float* z, int32_t pool,
                                              float* ring, int64_t ring_ld, int32_t head, int64_t* pos, int32_t dilation);
 
+/* Dropout between relu and the pool ("dropout in the relu + pool epilogue"; fp32): the mask is a pure function of
+ * (seed, element index e), never stored.  Philox4x32-10 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments 0x9E3779B9 / 0xBB67AE85)
+ * on the counter (lo32(e >> 2), hi32(e >> 2), 0, 0) under the key (lo32(seed), hi32(seed)); element e is kept iff output word e & 3 is
+ * >= thr, thr = min(floor(p * 2^32 + 0.5), 2^32 - 1); a kept value is multiplied by scale = 1 / (1 - p) (fp32), a dropped one by 0 (a
+ * dropped +Inf is NaN, NaN stays NaN).  e counts the layer's output in the caller's vertex labels whatever the layout:
+ * ((s * nwin + w) * n + v) * N + c for the streaming layers, (q * n + v) * N + c for the batch layers.  seed points to ONE int64 in device
+ * memory, 0 <= seed < 2^62, read by the kernels: a captured step that rewrites it draws a new mask on every replay.
+ * tgcn_cheb_project_series_pool_dropout_f32: tgcn_cheb_project_series_pool_f32 with t = relu(y) * mask in relu(y)'s place -- the same
+ * arguments, layouts, plan (tgcn_series_pool_plan: the dropout adds no LDS) and refusals with the same codes, then seed, thr, scale.
+ * z is bit-identical to tgcn_relu_dropout_pool_f32 on the unfused output; idx is the arg-max over the dropped values.  The backward is
+ * tgcn_relu_pool_bwd_f32 on grad_z * scale: z > 0 implies the arg-max was kept.
+ * tgcn_relu_dropout_pool_f32: tgcn_relu_pool_f32 with the mask, as its own pass over y (q, n, f) with f = nw * N columns per vertex row --
+ * column cc is window cc / N, channel cc % N, e = ((q_row * nw + cc / N) * n + v) * N + cc % N: (S*nwin, n, N) with nw = 1, the
+ * (S, n, nwin*N) view of a series, and the batch layers' (q, n, N).
+ * tgcn_dropout_keep_u8: out[i] = 1 where element e0 + i is kept, else 0, i < count.
+ * TGCN_ERR_INVALID before any launch: a null seed, a scale that is not finite or below 1, f % N != 0, e0 < 0, count < 1, and everything
+ * the entries they extend refuse. */
+int tgcn_cheb_project_series_pool_dropout_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                              const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* z,
+                                              uint8_t* idx, int32_t pool, int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation,
+                                              const int64_t* seed, uint32_t thr, float scale);
+int tgcn_relu_dropout_pool_f32(void* stream, const float* y, float* out, uint8_t* idx, int64_t q, int64_t n, int32_t f, int32_t pool, int32_t N,
+                               const int64_t* seed, uint32_t thr, float scale);
+int tgcn_dropout_keep_u8(void* stream, const int64_t* seed, int64_t e0, int64_t count, uint32_t thr, uint8_t* out);
+
 /* Time chunks of the causal layer with a backward ("Time chunks"; fp32, step 1, the host's head): forward_series walks a
  * recording chunk by chunk through the ring in both directions, so nothing of the hop stack's whole size is ever held.
  * tgcn_cheb_project_series_stream_at_f32 is tgcn_cheb_project_series_stream_f32 writing its Tc rows into rows [out_t0, out_t0 + Tc) of

@@ -42,6 +42,7 @@ namespace {
 #include "wgrad.h"
 #include "small_graph.h"
 #include "pool_relayout.h"
+#include "dropout.h"
 #include "windows.h"
 #include "windows_bf16.h"
 #include "stream_small.h"
@@ -1238,6 +1239,26 @@ int tgcn_relu_pool_f32(void* stream, const float* x, float* out, uint8_t* idx, i
   return TGCN_OK;
 }
 
+int tgcn_relu_dropout_pool_f32(void* stream, const float* y, float* out, uint8_t* idx, int64_t q, int64_t n, int32_t f, int32_t pool, int32_t N,
+                               const int64_t* seed, uint32_t thr, float scale) {
+  if (!y || !out || q <= 0 || n <= 0 || f <= 0 || pool <= 0 || pool > 255 || n % pool != 0 || N <= 0 || f % N != 0 || !seed ||
+      !dropout_scale_ok(scale))
+    TGCN_FAIL(TGCN_ERR_INVALID, "relu_dropout_pool: bad argument");
+  const int64_t total = q * (n / pool) * f;
+  const DropoutParams d{seed, thr, scale};
+  hipLaunchKernelGGL(relu_dropout_pool_kernel, dim3(grid_1d(total)), dim3(kBlock), 0, (hipStream_t)stream, y, out, idx, total, n, (int)f, (int)pool,
+                     (int)N, d);
+  TGCN_CHECK_LAUNCH("tgcn_relu_dropout_pool_f32");
+  return TGCN_OK;
+}
+
+int tgcn_dropout_keep_u8(void* stream, const int64_t* seed, int64_t e0, int64_t count, uint32_t thr, uint8_t* out) {
+  if (!seed || !out || e0 < 0 || count <= 0 || e0 > INT64_MAX - count) TGCN_FAIL(TGCN_ERR_INVALID, "dropout_keep: bad argument");
+  hipLaunchKernelGGL(dropout_keep_kernel, dim3(grid_1d(count)), dim3(kBlock), 0, (hipStream_t)stream, seed, (uint64_t)e0, count, thr, out);
+  TGCN_CHECK_LAUNCH("tgcn_dropout_keep_u8");
+  return TGCN_OK;
+}
+
 int tgcn_relu_pool_bwd_f32(void* stream, const float* grad_z, const float* z, const uint8_t* idx, float* grad_y, int64_t q,
                            int64_t n, int32_t f, int32_t p) {
   if (!grad_z || !z || !idx || !grad_y || q <= 0 || n <= 0 || f <= 0 || p <= 0 || n % p != 0) TGCN_FAIL(TGCN_ERR_INVALID, "relu_pool_bwd: bad argument");
@@ -1458,11 +1479,13 @@ static int series_launch_plan(SeriesLdsFn lds_of, int64_t S, int64_t n, int32_t 
 // not), or STRIDED && CARRY for a window step on a chunk (the _stream_strided entry, p.win_off)
 // pool (2 / 4; 0: none): the POOLED instantiations of the same form -- one workgroup per (recording, vertex quad, window block), the
 // scratch's bytes where they exceed the GEMM's; not built with a window step on a chunk
+// drop (with pool, on a whole series): series_gemm_pool_dropout_kernel in the pooled form's place, on the same plan -- the dropout adds no LDS
 static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1, int dil = 1,
-                              bool carry = false, int pool = 0) {
+                              bool carry = false, int pool = 0, const DropoutParams* drop = nullptr) {
   SeriesLaunchPlan lp;
   if (int rc = series_launch_plan(series_gemm_lds, S, p.n, p.nwin, p.H, p.f, p.N, vec, stride, dil, pool, who, &lp)) return rc;
   if (pool && carry && stride > 1) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a pooled window step on a chunk is not built", who);
+  if (drop && (!pool || carry)) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: dropout is built into the pooled epilogue of a whole series", who);
   p.tpv = lp.tpv; p.dil = dil; p.ntiles = lp.ntiles; p.pool = pool;
   if (dil > 1) p.tpp = lp.tpp;
   if (pool) p.nq = lp.nq;
@@ -1479,7 +1502,20 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
 #define TGCN_SERIES_GEMM_NT(VEC_, STR_, DIL_, ...)                                                                        \
   do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_, DIL_, ##__VA_ARGS__); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_, DIL_, ##__VA_ARGS__);   \
        else TGCN_SERIES_GEMM(4, VEC_, STR_, DIL_, ##__VA_ARGS__); } while (0)
-  if (pool) {
+#define TGCN_SERIES_DROP(NT_, VEC_, STR_, DIL_)                                                                            \
+  do {                                                                                                                    \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_pool_dropout_kernel<NT_, VEC_, STR_, DIL_>, lds);       \
+    for (p.blk0 = 0; p.blk0 < lp.gx; p.blk0 += kSeriesGridPart)                                                           \
+      hipLaunchKernelGGL((series_gemm_pool_dropout_kernel<NT_, VEC_, STR_, DIL_>), series_grid_part(lp, p.blk0), dim3(kBlock), lds, st, p, *drop); \
+  } while (0)
+#define TGCN_SERIES_DROP_NT(VEC_, STR_, DIL_)                                                                             \
+  do { if (NT == 1) TGCN_SERIES_DROP(1, VEC_, STR_, DIL_); else if (NT == 2) TGCN_SERIES_DROP(2, VEC_, STR_, DIL_);       \
+       else TGCN_SERIES_DROP(4, VEC_, STR_, DIL_); } while (0)
+  if (drop) {
+    if (dil > 1) { if (vec) TGCN_SERIES_DROP_NT(true, false, true); else TGCN_SERIES_DROP_NT(false, false, true); }
+    else if (stride == 1) { if (vec) TGCN_SERIES_DROP_NT(true, false, false); else TGCN_SERIES_DROP_NT(false, false, false); }
+    else { if (vec) TGCN_SERIES_DROP_NT(true, true, false); else TGCN_SERIES_DROP_NT(false, true, false); }
+  } else if (pool) {
     if (carry) {
       if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, true, true); else TGCN_SERIES_GEMM_NT(false, false, true, true, true); }
       else { if (vec) TGCN_SERIES_GEMM_NT(true, false, false, true, true); else TGCN_SERIES_GEMM_NT(false, false, false, true, true); }
@@ -1493,6 +1529,8 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
   } else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true); else TGCN_SERIES_GEMM_NT(false, false, true); }
   else if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, false); else TGCN_SERIES_GEMM_NT(false, false, false); }
   else { if (vec) TGCN_SERIES_GEMM_NT(true, true, false); else TGCN_SERIES_GEMM_NT(false, true, false); }
+#undef TGCN_SERIES_DROP_NT
+#undef TGCN_SERIES_DROP
 #undef TGCN_SERIES_GEMM_NT
 #undef TGCN_SERIES_GEMM
   return TGCN_OK;
@@ -1547,8 +1585,9 @@ struct SeriesF32 {
   static constexpr int kUnit = 4;                    // elements per 16-byte access
   static constexpr const char* kSuffix = "_f32";     // "tgcn_cheb_" + who + kSuffix is the entry's name
   static constexpr SeriesLdsFn lds = series_gemm_lds;
-  static int launch(hipStream_t st, Params& p, int64_t S, bool vec, bool, const char* who, int stride, int dil, bool carry, int pool) {
-    return series_gemm_launch(st, p, S, vec, who, stride, dil, carry, pool);
+  static int launch(hipStream_t st, Params& p, int64_t S, bool vec, bool, const char* who, int stride, int dil, bool carry, int pool,
+                    const DropoutParams* drop = nullptr) {
+    return series_gemm_launch(st, p, S, vec, who, stride, dil, carry, pool, drop);
   }
   static void set_bias(Params& p, const void* bias, int32_t kind, int32_t) { p.bias = (const float*)bias; p.bias_kind = kind; }
   static void flip(hipStream_t st, const float* W, float* Wd, int K, int H, int f, int N, int stride) {
@@ -1576,7 +1615,8 @@ struct SeriesBf16 {
   static constexpr int kUnit = 8;
   static constexpr const char* kSuffix = "";         // who ends in _bf16
   static constexpr SeriesLdsFn lds = series_gemm_bf16_lds;
-  static int launch(hipStream_t st, Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride, int dil, bool carry, int) {
+  static int launch(hipStream_t st, Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride, int dil, bool carry, int,
+                    const DropoutParams* = nullptr) {      // no bf16 dropout
     return series_gemm_bf16_launch(st, p, S, vec, out_f32, who, stride, dil, carry);
   }
   static void set_bias(Params& p, const void* bias, int32_t kind, int32_t dtype) { p.bias = bias; p.bias_kind = kind; p.bias_bf16 = dtype == TGCN_DTYPE_BF16; }
@@ -1732,11 +1772,13 @@ static bool series_vec(int32_t f, const void* stack, int64_t ld, const void* rin
 }
 
 // ---- driver 1, a whole series: the _series, _conv, _dilated and _pool entries of both element types.  stack_ld: elements between vertex
-// rows (fp32: T * f).  pool 0: none (the _pool entry has checked its own).
+// rows (fp32: T * f).  pool 0: none (the _pool entry has checked its own).  drop (fp32, with pool; the _pool_dropout entry has checked it):
+// dropout between relu and the pool.
 template <class X>
 static int series_forward(const char* who, void* stream, SeriesRule rule, int64_t S, int64_t n, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
                           const void* stack, int64_t stack_ld, const void* W, const void* bias, int32_t bias_dtype, int32_t bias_kind,
-                          int32_t as_series, void* out, uint8_t* idx, int32_t pool, int32_t stride, int32_t pl, int32_t pr, int32_t dil) {
+                          int32_t as_series, void* out, uint8_t* idx, int32_t pool, int32_t stride, int32_t pl, int32_t pr, int32_t dil,
+                          const DropoutParams* drop = nullptr) {
   typedef typename X::Elem E;
   SeriesGeom ge;
   const int grc = series_geom(rule, S, n, T, f, H, N, K, stride, pl, pr, dil, &ge);
@@ -1750,7 +1792,7 @@ static int series_forward(const char* who, void* stream, SeriesRule rule, int64_
   X::set_bias(p, bias, bias_kind, bias_dtype);
   series_out(p, (E*)out, pool ? n / pool : n, ge.nwin, N, as_series);      // pooled: out and idx hold n / pool vertices
   if constexpr (std::is_same<E, float>::value) p.idx = idx;
-  if (int rc = X::launch((hipStream_t)stream, p, S, series_vec<X>(f, stack, stack_ld), false, who, ge.stride, ge.dil, false, pool)) return rc;
+  if (int rc = X::launch((hipStream_t)stream, p, S, series_vec<X>(f, stack, stack_ld), false, who, ge.stride, ge.dil, false, pool, drop)) return rc;
   return series_launched(who, X::kSuffix);
 }
 
@@ -1781,6 +1823,20 @@ int tgcn_cheb_project_series_pool_f32(void* stream, int64_t S, int64_t n_vertice
   if (!series_pool_ok(n_vertices, pool)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_pool: pool %d of %lld vertices", pool, (long long)n_vertices);
   return series_forward<SeriesF32>("project_series_pool", stream, kSeriesDilated, S, n_vertices, T, f, H, N, K, stack, (int64_t)T * f, W, bias,
                                    TGCN_DTYPE_F32, bias_kind, as_series, z, idx, pool, stride, pad_left, pad_right, dilation);
+}
+
+// dropout between relu and the pool of the entry above ("dropout in the relu + pool epilogue"): the mask's own rules, then
+// that entry's driver with its checks and codes; all of them before a pointer is read
+int tgcn_cheb_project_series_pool_dropout_f32(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                              const float* stack, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* z,
+                                              uint8_t* idx, int32_t pool, int32_t stride, int32_t pad_left, int32_t pad_right, int32_t dilation,
+                                              const int64_t* seed, uint32_t thr, float scale) {
+  if (!series_pool_ok(n_vertices, pool))
+    TGCN_FAIL(TGCN_ERR_INVALID, "project_series_pool_dropout: pool %d of %lld vertices", pool, (long long)n_vertices);
+  if (!seed || !dropout_scale_ok(scale)) TGCN_FAIL(TGCN_ERR_INVALID, "project_series_pool_dropout: a null seed or a scale that is not finite and >= 1");
+  const DropoutParams drop{seed, thr, scale};
+  return series_forward<SeriesF32>("project_series_pool_dropout", stream, kSeriesDilated, S, n_vertices, T, f, H, N, K, stack, (int64_t)T * f, W, bias,
+                                   TGCN_DTYPE_F32, bias_kind, as_series, z, idx, pool, stride, pad_left, pad_right, dilation, &drop);
 }
 
 int tgcn_cheb_project_series_conv_bf16(void* stream, int64_t S, int64_t n_vertices, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,

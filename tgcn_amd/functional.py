@@ -6,7 +6,9 @@ memory, the stream and autograd bookkeeping.  There is no CPU fallback.
 import ctypes as C
 import dataclasses
 import functools
+import math
 import numbers
+import struct
 import threading
 
 import torch
@@ -583,46 +585,60 @@ class ChebSeriesReluPoolFn(torch.autograd.Function):
     @staticmethod
     @_on_device
     def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx):
-        L = _lib.lib()
-        S, n, T, f = series.shape
-        K, H, _, N = weight_khfg.shape
-        stride, left, right, dil = _geom4(geom)
-        conv = (stride, left, right) != (1, 0, 0)
-        nwin = (T + left + right - (H - 1) * dil - 1) // stride + 1
-        hc, lds = C.c_int32(0), C.c_int32(0)
-        _lib.check(L.tgcn_series_pool_plan(H, f, N, int(f % 4 == 0), stride, pool, C.byref(hc), C.byref(lds)))
-        x3 = _aligned_input(series.float().contiguous().view(S, n, T * f))
-        W = weight_khfg.float().contiguous().view(K, H * f, N)
-        fold = _power_fold(mode, W)
-        Wt = _working_weight(fold, W)
-        stack = _series_stack(op, x3, K, mode)   # (K, S, n, T*f)
-        shape = (S, n // pool, nwin, N) if as_series else (S * nwin, n // pool, N)
-        z = torch.empty(shape, dtype=torch.float32, device=x3.device)
-        idx = torch.empty(shape, dtype=torch.uint8, device=x3.device) if need_idx else None
-        b = bias.contiguous() if bias is not None else None
-        _lib.check(L.tgcn_cheb_project_series_pool_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind,
-                                                       1 if as_series else 0, _lib.ptr(z), _lib.ptr(idx), pool, stride, left, right, dil))
-        ctx.geom = (stride, left, right, dil) if dil > 1 else ((stride, left, right) if conv else None)
-        ctx.save_for_backward(Wt, z, idx)
-        ctx.stack = stack if ctx.needs_input_grad[1] else None
-        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.pool = op, mode, fold, bias_kind, as_series, pool
-        ctx.dims = (S, n, T, f, H, N, K)
-        ctx.nwin = nwin
-        ctx.bias_shape = None if bias is None else bias.shape
-        return z
+        return _series_pool_forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx)
 
     @staticmethod
     @_on_device
     def backward(ctx, gz):
-        Wt, z, idx = ctx.saved_tensors
-        S, n, T, f, H, N, K = ctx.dims
-        if idx is None:
-            raise _lib.TgcnError("cheb_time_windows_relu_pool: the forward ran without grad mode and kept no arg-max")
-        gy = torch.empty((S, n, ctx.nwin, N) if ctx.as_series else (S * ctx.nwin, n, N), dtype=torch.float32, device=gz.device)
-        q, fN = (S, ctx.nwin * N) if ctx.as_series else (S * ctx.nwin, N)
-        _lib.check(_lib.lib().tgcn_relu_pool_bwd_f32(_lib.stream_ptr(), _lib.ptr(gz.float().contiguous()), _lib.ptr(z), _lib.ptr(idx), _lib.ptr(gy),
-                                                     q, n, fN, ctx.pool))
-        return _series_backward(ctx, Wt, gy) + (None,) * 7
+        return _series_pool_backward(ctx, gz, "cheb_time_windows_relu_pool") + (None,) * 7
+
+
+def _series_pool_forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx, drop=None):
+    """the forward ChebSeriesReluPoolFn and ChebSeriesReluDropoutPoolFn share; drop = (seed tensor, thr, scale) calls the _pool_dropout entry"""
+    L = _lib.lib()
+    S, n, T, f = series.shape
+    K, H, _, N = weight_khfg.shape
+    stride, left, right, dil = _geom4(geom)
+    conv = (stride, left, right) != (1, 0, 0)
+    nwin = (T + left + right - (H - 1) * dil - 1) // stride + 1
+    hc, lds = C.c_int32(0), C.c_int32(0)
+    _lib.check(L.tgcn_series_pool_plan(H, f, N, int(f % 4 == 0), stride, pool, C.byref(hc), C.byref(lds)))
+    x3 = _aligned_input(series.float().contiguous().view(S, n, T * f))
+    W = weight_khfg.float().contiguous().view(K, H * f, N)
+    fold = _power_fold(mode, W)
+    Wt = _working_weight(fold, W)
+    stack = _series_stack(op, x3, K, mode)   # (K, S, n, T*f)
+    shape = (S, n // pool, nwin, N) if as_series else (S * nwin, n // pool, N)
+    z = torch.empty(shape, dtype=torch.float32, device=x3.device)
+    idx = torch.empty(shape, dtype=torch.uint8, device=x3.device) if need_idx else None
+    b = bias.contiguous() if bias is not None else None
+    args = (_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(z),
+            _lib.ptr(idx), pool, stride, left, right, dil)
+    if drop is None:
+        _lib.check(L.tgcn_cheb_project_series_pool_f32(*args))
+    else:
+        _lib.check(L.tgcn_cheb_project_series_pool_dropout_f32(*args, _lib.ptr(drop[0]), drop[1], drop[2]))
+    ctx.geom = (stride, left, right, dil) if dil > 1 else ((stride, left, right) if conv else None)
+    ctx.save_for_backward(Wt, z, idx)
+    ctx.stack = stack if ctx.needs_input_grad[1] else None
+    ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.pool = op, mode, fold, bias_kind, as_series, pool
+    ctx.dims = (S, n, T, f, H, N, K)
+    ctx.nwin = nwin
+    ctx.bias_shape = None if bias is None else bias.shape
+    return z
+
+
+def _series_pool_backward(ctx, gz, who):
+    """(d series, dW, d bias) behind the pooled forward above: gz to the arg-max vertex where z > 0, then ChebSeriesFn's backward body"""
+    Wt, z, idx = ctx.saved_tensors
+    S, n, T, f, H, N, K = ctx.dims
+    if idx is None:
+        raise _lib.TgcnError("%s: the forward ran without grad mode and kept no arg-max" % who)
+    gy = torch.empty((S, n, ctx.nwin, N) if ctx.as_series else (S * ctx.nwin, n, N), dtype=torch.float32, device=gz.device)
+    q, fN = (S, ctx.nwin * N) if ctx.as_series else (S * ctx.nwin, N)
+    _lib.check(_lib.lib().tgcn_relu_pool_bwd_f32(_lib.stream_ptr(), _lib.ptr(gz.float().contiguous()), _lib.ptr(z), _lib.ptr(idx), _lib.ptr(gy),
+                                                 q, n, fN, ctx.pool))
+    return _series_backward(ctx, Wt, gy)
 
 
 def _relu_pool_view(y, pool):
@@ -641,8 +657,8 @@ def cheb_time_windows_relu_pool(op, series, weight, bias, bias_kind, mode, pool,
     gradient are bit-identical to the hand-written composition.  as_series, stride, padding, dilation: cheb_time_windows'.
     A single-channel series runs the MFMA kernels (ChebSeriesFn's) in every geometry -- the scalar-load form has no pooled epilogue.
     A reordered operand runs the unfused composition (series_pool_is_fused): the layer, relabelled back, then tgcn_relu_pool_f32 on a view.
-    Dropout between relu and pool, as the reference's training script has it, is not this function: call the layer, relu, dropout and
-    gcn_pool_4 one after the other.
+    Dropout between relu and pool, as the reference's training script has it, is cheb_time_windows_relu_dropout_pool (below): the same
+    epilogue with a counter-based mask, so the full output stays unallocated in training too.
     TgcnError before anything is built or launched: bfloat16 parameters, pool outside {2, 4}, n % pool != 0, and every refusal
     cheb_time_windows makes for the same arguments.  There is no time_chunk."""
     who = "cheb_time_windows_relu_pool"
@@ -665,6 +681,159 @@ def cheb_time_windows_relu_pool(op, series, weight, bias, bias_kind, mode, pool,
         return _relu_pool_view(y if op.perm is None else relabel_rows(y, op.inv_perm, op.perm), pool)
     need_idx = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (series, weight, bias))
     return ChebSeriesReluPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, pool, need_idx)
+
+
+# ---- dropout between relu and the pool ("dropout in the relu + pool epilogue")
+def _f32(v):
+    """v rounded to float32, as a Python float"""
+    return struct.unpack("f", struct.pack("f", v))[0]
+
+
+def dropout_params(p, who="dropout"):
+    """(thr, scale) of the mask for a drop probability p, a real number in [0, 1): element e is kept iff its Philox word is >= thr =
+    min(floor(p * 2^32 + 0.5), 2^32 - 1), and a kept value is multiplied by scale = float32(1) / (float32(1) - float32(p)) -- the float32
+    operations, carried out in double precision and rounded once each (a difference of two float32 is exact there, and a quotient of two
+    float32 rounds to float32 the same way from 53 bits as from the exact value)."""
+    if not isinstance(p, numbers.Real) or isinstance(p, bool) or not 0.0 <= p < 1.0 or _f32(p) >= 1.0:      # float32(p) == 1: no finite scale
+        raise _lib.TgcnError("%s: p is a real number in [0, 1) (in float32), got %r" % (who, p))
+    p = float(p)
+    thr = min(int(math.floor(p * 4294967296.0 + 0.5)), 4294967295)
+    return thr, _f32(1.0 / _f32(1.0 - _f32(p)))
+
+
+def dropout_seed(seed, device, who="dropout", draw=True):
+    """the mask's seed as the kernels read it -- a one-element int64 tensor on `device` holding 0 <= seed < 2^62: None draws one there with
+    torch.randint (it follows torch.manual_seed and is legal inside a hipGraph capture; draw=False only checks and returns None), an int is
+    copied there, a tensor is checked (int64, one element, on the device; its VALUE is the caller's to keep in range -- reading it would
+    synchronise) and used as it is.  TgcnError for anything else."""
+    if seed is None:
+        return torch.randint(0, 2 ** 62, (1,), dtype=torch.int64, device=device) if draw else None
+    if isinstance(seed, torch.Tensor):
+        if seed.dtype != torch.int64 or seed.numel() != 1 or seed.device != torch.device(device):
+            raise _lib.TgcnError("%s: a seed tensor is one int64 element on the input's device %s, got %s %s on %s"
+                                 % (who, device, tuple(seed.shape), seed.dtype, seed.device))
+        return seed.reshape(1) if draw else None
+    if not isinstance(seed, numbers.Integral) or isinstance(seed, bool) or not 0 <= seed < 2 ** 62:
+        raise _lib.TgcnError("%s: seed is None, an integer in [0, 2^62) or a one-element int64 tensor, got %r" % (who, seed))
+    return torch.tensor([int(seed)], dtype=torch.int64, device=device) if draw else None
+
+
+@_on_device
+def _dropout_keep(seed_t, e0, count, thr):
+    out = torch.empty(count, dtype=torch.uint8, device=seed_t.device)
+    _lib.check(_lib.lib().tgcn_dropout_keep_u8(_lib.stream_ptr(), _lib.ptr(seed_t), e0, count, thr, _lib.ptr(out)))
+    return out.bool()
+
+
+def dropout_keep_mask(seed, e0, count, p, device):
+    """bool tensor of `count` elements on `device`: True where the elements e0 .. e0 + count - 1 are kept at drop probability p under `seed`
+    (tgcn_dropout_keep_u8) -- the mask cheb_series_relu_dropout_pool and cheb_relu_dropout_pool apply, by element index in the caller's
+    vertex labels: ((s * nwin + w) * n + v) * N + c for the streaming layers, (q * n + v) * N + c for the batch layers."""
+    who = "dropout_keep_mask"
+    thr, _ = dropout_params(p, who)
+    if not all(isinstance(v, numbers.Integral) and not isinstance(v, bool) for v in (e0, count)) or e0 < 0 or count < 1 or e0 + count > 2 ** 63 - 1:
+        raise _lib.TgcnError("%s: e0 >= 0 and count >= 1 are integers below 2^63, got %r and %r" % (who, e0, count))
+    seed_t = dropout_seed(seed, torch.device(device), who)
+    _lib.require_device(seed_t)
+    return _dropout_keep(seed_t, int(e0), int(count), thr)
+
+
+class ChebSeriesReluDropoutPoolFn(torch.autograd.Function):
+    """ChebSeriesReluPoolFn with dropout between relu and the pool (tgcn_cheb_project_series_pool_dropout_f32, csrc/windows.h DROP): z =
+    max over `pool` consecutive vertices of relu(y) * m, m = scale where dropout.h's mask keeps the element and 0 elsewhere, bit-identical to
+    tgcn_relu_dropout_pool_f32 on the unfused output; neither y nor a mask is ever allocated.  The backward needs no mask: z > 0 implies
+    the arg-max was kept, so gy[arg-max] = z > 0 ? gz * scale : 0 -- gz * scale (fp32), then ChebSeriesReluPoolFn's backward.
+    As with ChebSeriesReluPoolFn, one channel runs the MFMA kernels in every geometry: where forward_series itself runs the scalar-load
+    form (ChebWindowsFn: one channel, window-major, default geometry) the bits are those of forward_series(..., as_series=True), permuted.
+    Saves z, idx, the working weight, and the stack only if the weight trains; ctx.seed is the seed's tensor (z.grad_fn.seed: what a
+    captured step with seed=None drew)."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx, seed_t, thr, scale):
+        ctx.scale, ctx.seed = scale, seed_t
+        return _series_pool_forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx, drop=(seed_t, thr, scale))
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, gz):
+        return _series_pool_backward(ctx, gz.float() * ctx.scale, "cheb_time_windows_relu_dropout_pool") + (None,) * 10
+
+
+class ReluDropoutPoolFn(torch.autograd.Function):
+    """z = max over `pool` consecutive vertices of relu(y) * mask as its own pass (tgcn_relu_dropout_pool_f32 / tgcn_relu_pool_bwd_f32 on
+    gz * scale): y (q, n, f) with f = nw * N columns per vertex, column cc = window cc / N, channel cc % N."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, y, pool, N, seed_t, thr, scale):
+        _lib.require_device(y, seed_t)
+        y = y.float().contiguous()
+        q, n, f = y.shape
+        assert n % pool == 0 and f % N == 0, "pooling needs n divisible by the pool size and whole windows of N columns"
+        z = torch.empty((q, n // pool, f), dtype=torch.float32, device=y.device)
+        idx = torch.empty((q, n // pool, f), dtype=torch.uint8, device=y.device)
+        _lib.check(_lib.lib().tgcn_relu_dropout_pool_f32(_lib.stream_ptr(), _lib.ptr(y), _lib.ptr(z), _lib.ptr(idx), q, n, f, pool, N,
+                                                         _lib.ptr(seed_t), thr, scale))
+        ctx.save_for_backward(z, idx)
+        ctx.shape, ctx.pool, ctx.scale = (q, n, f), pool, scale
+        return z
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, gz):
+        z, idx = ctx.saved_tensors
+        q, n, f = ctx.shape
+        gy = torch.empty((q, n, f), dtype=torch.float32, device=gz.device)
+        _lib.check(_lib.lib().tgcn_relu_pool_bwd_f32(_lib.stream_ptr(), _lib.ptr((gz.float() * ctx.scale).contiguous()), _lib.ptr(z), _lib.ptr(idx),
+                                                     _lib.ptr(gy), q, n, f, ctx.pool))
+        return gy, None, None, None, None, None
+
+
+def _relu_dropout_pool_view(y, pool, seed_t, thr, scale):
+    """_relu_pool_view with the mask: (q, n, N) as it is, (S, n, nwin, N) through its (S, n, nwin*N) view -- one element index for both"""
+    if y.dim() == 3:
+        return ReluDropoutPoolFn.apply(y, pool, y.shape[2], seed_t, thr, scale)
+    S, n, nwin, N = y.shape
+    return ReluDropoutPoolFn.apply(y.reshape(S, n, nwin * N), pool, N, seed_t, thr, scale).view(S, n // pool, nwin, N)
+
+
+@_on_device
+def cheb_time_windows_relu_dropout_pool(op, series, weight, bias, bias_kind, mode, pool, p, seed, as_series=False, stride=1, padding=0, dilation=1):
+    """gcn_pool_4(dropout(relu(cheb_time_windows(...)), p)) -- the reference's training pattern -- with relu, the dropout and the max over
+    `pool` consecutive vertices in the projection's epilogue: cheb_time_windows_relu_pool's arguments, shapes and refusals, then
+    p, a real number in [0, 1), and seed: None (drawn on the series' device with torch.randint: follows torch.manual_seed, legal in a
+    capture), an integer in [0, 2^62) or a one-element int64 tensor on the series' device (read by the kernel: rewrite it between the
+    replays of a captured step).  The mask is a pure function of (seed, element index in the caller's vertex labels) -- dropout_keep_mask
+    reproduces it -- so nothing of the full output's size is allocated, no mask is stored, and both layouts and a reordered operand drop the
+    same elements; values and gradients are bit-identical to ReluPoolFn on relu(y) * mask.  p == 0 is cheb_time_windows_relu_pool itself.
+    A reordered operand runs the layer, relabels back, then tgcn_relu_dropout_pool_f32 on a view."""
+    who = "cheb_time_windows_relu_dropout_pool"
+    thr, scale = dropout_params(p, who)
+    dropout_seed(seed, series.device, who, draw=False)
+    if p == 0:
+        return cheb_time_windows_relu_pool(op, series, weight, bias, bias_kind, mode, pool, as_series=as_series, stride=stride, padding=padding,
+                                           dilation=dilation)
+    if param_dtype(weight, bias, who) == BF16:
+        raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
+    if series.dim() not in (3, 4) or weight.dim() != series.dim():
+        raise _lib.TgcnError("%s: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
+                             "(got %s and %s)" % (who, tuple(series.shape), tuple(weight.shape)))
+    f = series.shape[3] if series.dim() == 4 else 1
+    if series.dim() == 4 and weight.shape[2] != f:
+        raise _lib.TgcnError("%s: the series has %d channels, the weight %d" % (who, f, weight.shape[2]))
+    pool = check_pool(pool, series.shape[1], who)
+    geom = series_geometry(series.shape[2], weight.shape[1], stride, padding, who, dilation)[:3] + (series_dilation(weight.shape[1], dilation),)
+    _lib.require_device(series, weight, bias)
+    if series.dim() == 3:
+        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
+    seed_t = dropout_seed(seed, series.device, who)
+    if not series_pool_is_fused(op, pool):
+        s2, b2 = _to_operand_labels(op, series, bias, bias_kind)
+        y = ChebSeriesFn.apply(s2, weight, b2, op, mode, bias_kind, bool(as_series), geom)
+        return _relu_dropout_pool_view(y if op.perm is None else relabel_rows(y, op.inv_perm, op.perm), pool, seed_t, thr, scale)
+    need_idx = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (series, weight, bias))
+    return ChebSeriesReluDropoutPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, pool, need_idx, seed_t, thr, scale)
 
 
 def check_time_chunk(time_chunk, stride, padding, bf16, who="cheb_time_windows"):

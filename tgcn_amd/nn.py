@@ -676,8 +676,8 @@ def cheb_series_relu_pool(layer, series, *graph_args, pool=4, as_series=False, s
     vertices run in the projection's epilogue, so the layer's full output -- the large tensor of this path, g/f times the series -- is never
     allocated, in inference or in training; values and all gradients are bit-identical to the hand-written composition
     (F.cheb_time_windows_relu_pool).  A single channel runs the MFMA kernels in every geometry; an operand the layer keeps reordered runs
-    the unfused calls.  Dropout between relu and pool, as in the reference's training script, means the unfused calls: forward_series,
-    relu, dropout, gcn_pool_4.
+    the unfused calls.  Dropout between relu and pool, as in the reference's training script, is cheb_series_relu_dropout_pool: the same
+    epilogue with a counter-based mask (cheb_relu_dropout_pool for the batch layers).
     TgcnError before an operand is built: bfloat16 parameters, pool outside {2, 4}, n % pool != 0, a learnable edge_weight, and every
     refusal forward_series makes for the same arguments.  No time_chunk."""
     who = "cheb_series_relu_pool"
@@ -689,6 +689,57 @@ def cheb_series_relu_pool(layer, series, *graph_args, pool=4, as_series=False, s
     bias, bias_kind, mode = _series_pool_bias(layer)
     return F.cheb_time_windows_relu_pool(op, series, W, bias, bias_kind, mode, pool, as_series=as_series, stride=geom[0], padding=geom[1:3],
                                          dilation=geom[3])
+
+
+def cheb_series_relu_dropout_pool(layer, series, *graph_args, p=0.5, pool=4, training=True, seed=None, as_series=False, stride=1, padding=0,
+                                  dilation=1):
+    """gcn_pool_4(F.dropout(F.relu(layer.forward_series(series, ...)), p, training))  (pool=4; pool=2: gcn_pool)  in one fused op -- the
+    training pattern of examples/pytorch_based/pytorch_hcp_tgcn.py:134-137 on the streaming layers.  cheb_series_relu_pool's arguments,
+    shapes and refusals; relu, the dropout and the pool run in the projection's epilogue, so the layer's full output, its relu, a mask and
+    the dropped copy are never allocated, in the forward or the backward.
+    The mask is not torch's: element e = ((s * nwin + w) * n + v) * N + c of the layer's output, in the caller's vertex labels, is kept iff
+    word e & 3 of Philox4x32-10 on the counter e >> 2 under the key `seed` is >= p * 2^32, and a kept value is multiplied by 1 / (1 - p)
+    (F.dropout_params, F.dropout_keep_mask).  It does not depend on as_series, the tile or the operand's ordering, the
+    backward regenerates nothing (a positive pooled value was kept), and values and gradients are bit-identical to the composition with
+    that mask.  seed=None draws a seed on the series' device (torch.randint: follows torch.manual_seed, legal inside a hipGraph capture,
+    a new mask on every replay); an integer in [0, 2^62) or a one-element int64 tensor on the series' device fixes it.
+    training=False or p == 0 is cheb_series_relu_pool, launch for launch.  An operand the layer keeps reordered runs the unpooled layer,
+    relabels back, then one relu + dropout + pool pass -- the same mask.
+    TgcnError before an operand is built: p outside [0, 1), a seed outside [0, 2^62), a seed tensor that is not one int64 element on the
+    series' device, and everything cheb_series_relu_pool refuses."""
+    who = "cheb_series_relu_dropout_pool"
+    F.dropout_params(p, who)
+    if isinstance(series, torch.Tensor):
+        F.dropout_seed(seed, series.device, who, draw=False)
+    if not training or p == 0:
+        return cheb_series_relu_pool(layer, series, *graph_args, pool=pool, as_series=as_series, stride=stride, padding=padding, dilation=dilation)
+    edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
+    if series.dim() in (3, 4):
+        F.check_pool(pool, series.shape[1], who)
+    series, W, geom = _series_args(layer, series, stride, padding, dilation)
+    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
+    bias, bias_kind, mode = _series_pool_bias(layer)
+    return F.cheb_time_windows_relu_dropout_pool(op, series, W, bias, bias_kind, mode, pool, p, seed, as_series=as_series, stride=geom[0],
+                                                 padding=geom[1:3], dilation=geom[3])
+
+
+def cheb_relu_dropout_pool(layer, x, *graph_args, p=0.5, pool=4, training=True, seed=None):
+    """gcn_pool_4(F.dropout(F.relu(layer(x, ...)), p, training))  (pool=4; pool=2: gcn_pool)  for the batch layers -- any of the five
+    modules, graph_args as in cheb_relu_pool: the layer, then ONE relu + dropout + pool pass (tgcn_relu_dropout_pool_f32) in place of three
+    torch passes and a stored mask.  The mask is cheb_series_relu_dropout_pool's on the element index e = (q * n + v) * N + c of the layer's
+    (q, n, N) output; seed as there.  training=False or p == 0 is cheb_relu_pool.  Not fused into the layer's own kernels.
+    TgcnError before anything launches: p outside [0, 1), a bad seed, bfloat16 parameters, pool outside {2, 4}, n % pool != 0."""
+    who = "cheb_relu_dropout_pool"
+    thr, scale = F.dropout_params(p, who)
+    F.dropout_seed(seed, x.device, who, draw=False)
+    if not training or p == 0:
+        return cheb_relu_pool(layer, x, *graph_args, pool=pool)
+    if _compute_dtype(layer) != torch.float32:
+        raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
+    if x.dim() >= 2:
+        F.check_pool(pool, x.shape[1], who)
+    y = layer(x, *graph_args)
+    return F.ReluDropoutPoolFn.apply(y, pool, y.shape[2], F.dropout_seed(seed, y.device, who), thr, scale)
 
 
 def cheb_stream_relu_pool(layer, chunk, *graph_args, pool=4, state=None, dilation=1, capturable=False):

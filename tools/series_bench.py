@@ -13,6 +13,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py --time-chunk 64,256 [--repeats 3] [--include parent=FILE] [--out profiles/r17_series_time_chunk.json]
     python tools/series_bench.py --fused-series --steps 200 --warmup 20 [--repeats 3] [--include parent=FILE] [--out profiles/r21_series_small.json]
     python tools/series_bench.py --relu-pool 4 [--repeats 3] [--out profiles/r18_series_relu_pool.json]
+    python tools/series_bench.py --relu-pool 4 --dropout 0.1 [--repeats 3] [--out profiles/r22_series_relu_dropout_pool.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -56,6 +57,11 @@ gcn_pool_4(relu(layer.forward_series(series))) (P = 2: gcn_pool; on the series l
 case (a) at 1 -> 32 window-major and at 32 -> 64 in the series layout, and case (b), forward and forward + backward.  The two sides
 alternate within the run, --repeats event timings each (median and spread); per side the peak of max_memory_allocated above the pre-call
 level, and torch.equal of the results and of every gradient; default --out profiles/r18_series_relu_pool.json.
+--relu-pool P --dropout PROB (0 < PROB < 1) puts dropout between relu and the pool on the same cases: (a) the fused call
+tgcn_amd.cheb_series_relu_dropout_pool(layer, series, p=PROB, pool=P) with seed=None, (b) the composition forward_series -> relu ->
+torch's F.dropout -> gcn_pool_4 and (c) cheb_series_relu_pool without dropout -- the column to hold against a --relu-pool P run of the
+parent commit, whose code it shares.  The three alternate within the run; medians, spreads and peaks as above.  The masks of (a) and (b)
+are different generators', so no equality is recorded; default --out profiles/r22_series_relu_dropout_pool.json.
 --fused-series: the one-launch whole-series layer (forward_series(fused=True), DESIGN.md 3.10 "One launch per series") on the graphs that fit
 in LDS: the (a) layers of the r08 table on the 148 parcels (1 -> 32 window-major and as_series=True; 32 -> 64, which the plan refuses) and
 TGCNCheb_H(L, 1, 64, 5, 28) on the 28 x 28 grid, S = 8, T = 128.  Columns per case, forward and forward + backward: unfused and fused
@@ -607,17 +613,27 @@ def main_relu_pool(args):
     pool = args.relu_pool
     res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, repeats=args.repeats,
                pool=pool, cases={})
+    drop = args.dropout
+    if drop is not None:
+        res["dropout"] = drop
     torch.manual_seed(0)
     pool_fn = tgcn_amd.gcn_pool_4 if pool == 4 else tgcn_amd.gcn_pool
 
     def case(name, desc, layer, series, as_series):
         series = series.requires_grad_(True)
 
-        def fused():
+        def undropped():
             return tgcn_amd.cheb_series_relu_pool(layer, series, pool=pool, as_series=as_series)
+
+        def fused():
+            if drop is None:
+                return undropped()
+            return tgcn_amd.cheb_series_relu_dropout_pool(layer, series, p=drop, pool=pool, as_series=as_series)
 
         def composition():
             out = torch.relu(layer.forward_series(series, as_series=as_series))
+            if drop is not None:
+                out = torch.nn.functional.dropout(out, drop, True)
             if not as_series:
                 return pool_fn(out)
             S, n, nwin, g = out.shape
@@ -638,7 +654,7 @@ def main_relu_pool(args):
                         fn()
             return step
 
-        sides = (("fused", fused), ("composition", composition))
+        sides = (("fused", fused), ("composition", composition)) + ((("undropped", undropped),) if drop is not None else ())
         entry = dict(desc=desc, fused_by_predicate=bool(F.series_pool_is_fused(layer._operand(dev), pool)), series_bytes=series.numel() * 4)
         grads = {}
         for train in (False, True):
@@ -663,9 +679,10 @@ def main_relu_pool(args):
             col["fused_over_composition_ms"] = round(col["fused"]["median"] / col["composition"]["median"], 3)
             col["fused_over_composition_peak"] = round(peak["fused"] / peak["composition"], 3)
             entry["forward_backward" if train else "forward"] = col
-        with torch.no_grad():
-            entry["results_equal"] = bool(torch.equal(fused(), composition()))
-        entry["gradients_equal"] = all(bool(torch.equal(a, b)) for a, b in zip(grads["fused"], grads["composition"]))
+        if drop is None:
+            with torch.no_grad():
+                entry["results_equal"] = bool(torch.equal(fused(), composition()))
+            entry["gradients_equal"] = all(bool(torch.equal(a, b)) for a, b in zip(grads["fused"], grads["composition"]))
         res["cases"][name] = entry
         print(json.dumps({name: entry}), flush=True)
         grads.clear()
@@ -684,7 +701,8 @@ def main_relu_pool(args):
     opm = GraphOperand.from_coo(n, row, col, val, dev)
     lm = tgcn_amd.TGCNCheb_H(opm, 4, 32, 5, 15).to(dev)
     case("b_mesh90k_4to32", "sheet_mesh(300) n=%d S=1 T=75 H=15 K=5 f=4 -> g=32, window-major" % n, lm, torch.randn(1, n, 75, 4, device=dev), False)
-    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r18_series_relu_pool.json")
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
+                                   "r18_series_relu_pool.json" if drop is None else "r22_series_relu_dropout_pool.json")
     os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
     with open(out, "w") as f:
         json.dump(res, f, indent=1)
@@ -793,6 +811,9 @@ def main():
                     help="a training step on T = 1200, unchunked against each time_chunk (profiles/r17_series_time_chunk.json)")
     ap.add_argument("--relu-pool", type=int, choices=(2, 4), default=None, metavar="P",
                     help="cheb_series_relu_pool against gcn_pool_4(relu(forward_series)) on the same commit (profiles/r18_series_relu_pool.json)")
+    ap.add_argument("--dropout", type=float, default=None, metavar="PROB",
+                    help="with --relu-pool P: cheb_series_relu_dropout_pool against forward_series -> relu -> dropout -> pool and against "
+                         "cheb_series_relu_pool (profiles/r22_series_relu_dropout_pool.json)")
     ap.add_argument("--fused-series", action="store_true",
                     help="forward_series(fused=True) next to the unfused call and the materialised windows (profiles/r21_series_small.json)")
     ap.add_argument("--include", action="append", default=[], metavar="LABEL=FILE",
@@ -800,6 +821,8 @@ def main():
                          "each shared case's ms per call relative to this run")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.dropout is not None and (args.relu_pool is None or not 0.0 < args.dropout < 1.0):
+        ap.error("--dropout PROB (0 < PROB < 1) goes with --relu-pool P")
     if args.dtype == "bf16":
         return main_bf16(args)
     if args.fused_series:
