@@ -55,6 +55,8 @@ typedef struct tgcn_csr {
  *   longer rows: segments of bounded length, STORED IN ORDER OF THEIR FIRST COLUMN so that the groups in flight
  *   gather from the same region of the dense operand at about the same time (hub columns then hit in L2).
  *   16-lane schedules: rows of more than row_thresh but at most 128 entries are one whole-row segment handled by ONE WAVE (nwseg);
+ *   where the partial rows of the longer rows would not fit the Infinity Cache (npartial * lanes_per_row * 16 B > 256 MiB), rows of more
+ *   than 512 entries ("hub rows") are cut into wave segments of 64 consecutive entries, one WAVE and one scratch slot each (nwseg too).
  *   A segment that is its whole row writes the row directly (seg_slot = -1); rows cut into several segments
  *   ("long rows") sum them through numbered scratch slots that a fix-up launch folds in slot order, so results
  *   do not depend on timing.  The first nhuge long rows (most slots) get a whole workgroup each in the fix-up.
@@ -73,16 +75,18 @@ typedef struct tgcn_csr_sched {
   int32_t row_mix;  /* 1: row blocks dealt evenly among the segment blocks instead of all in front -- set by the builders for operands with
                        >= 1/8 structurally empty rows, whose row blocks are mostly streaming zero writes that fill the gaps of the
                        gather-bound segments (uncompacted R-MAT: 4.25 -> 3.95 ms per launch); 0 otherwise (it costs 2.5 % there) */
-  int32_t nwseg;    /* leading entries of the seg_* arrays that are WHOLE rows of row_thresh < entries <= 32 * (64 / lanes_per_row) (the builders
-                       use them for 16-lane schedules only), in
-                       order of their first column: one wave each (its lane groups take consecutive pieces, folded inside the wave), written
-                       directly -- no partial rows, no fix-up for them.  The remaining nseg - nwseg entries are the lane-group segments
-                       of the longer rows.  0 for 64-lane schedules */
+  int32_t nwseg;    /* leading entries of the seg_* arrays that are handled by ONE WAVE each (its lane groups take consecutive quarters of the
+                       segment, folded inside the wave; the builders use them for 16-lane schedules only).  Two runs, each in order of first
+                       column: first the WHOLE rows of row_thresh < entries <= 32 * (64 / lanes_per_row), seg_slot = -1, written directly -- no
+                       partial rows, no fix-up for them; behind them the hub rows' wave segments, seg_slot >= 0, one partial row per wave.  The
+                       kernel asks nothing of the order or the lengths: any segment among the first nwseg is folded inside its wave and goes
+                       where its seg_slot says.  The remaining nseg - nwseg entries are the lane-group segments of the other long rows.
+                       0 for 64-lane schedules */
   const int32_t* blk_row;   /* [nblk+1] first row of each block; blk_row[nblk] == n */
   const int32_t* seg_row;   /* [nseg] */
   const int32_t* seg_e0;    /* [nseg] first entry */
   const int32_t* seg_e1;    /* [nseg] one past last entry */
-  const int32_t* seg_slot;  /* [nseg] scratch slot, or -1: whole row, written directly */
+  const int32_t* seg_slot;  /* [nseg] scratch slot (slots of one row are consecutive, in entry order, whichever kind of segment holds them), or -1: whole row, written directly */
   const int32_t* long_row;  /* [nlong] */
   const int32_t* long_slot; /* [nlong+1] first slot of each long row (slots of a row are consecutive, in column order) */
 } tgcn_csr_sched;
@@ -208,7 +212,11 @@ int tgcn_profile_stop(int32_t* kinds, float* ms, int32_t capacity, int32_t* coun
  *   "compact_overlap" 1 (default): the compacted fp32 layer runs projections on the library's side stream beside its hop launches
  *                     where that pays; 0: everything on the caller's stream, one kernel after the other
  *   "compact_overlap_group"   time steps per group (default 3): a group's projection runs beside the next group's hops
- *   "compact_overlap_min_mb"  ... only when one time step's compact hop tensor is larger than this (default 256, the Infinity Cache) */
+ *   "compact_overlap_min_mb"  ... only when one time step's compact hop tensor is larger than this (default 256, the Infinity Cache)
+ *   "sched_hub_min"   tgcn_sched_build*, 16-lane schedules: rows of more entries are hub rows, cut into wave segments (default 512; 0: none) ...
+ *   "sched_hub_seg"   ... of this many entries (default 64; at least 32 and at most sched_hub_min, else no hub rows) ...
+ *   "sched_hub_gate_mb"  ... where the partial rows of the schedule without hub rows take more than this many MiB (default 256, the
+ *                     Infinity Cache; 0: always).  Read when a schedule is built; tgcn_amd/graph.py: HUB_MIN, HUB_SEG, HUB_GATE_BYTES */
 int tgcn_set_tuning(const char* key, int32_t value);
 /* Every switch above back to its default, for the calling thread (ABI v5; thread-local since v7).  A harness that sets one restores
  * them with this call in its teardown, whatever happened in between (tests/conftest.py does after every test). */

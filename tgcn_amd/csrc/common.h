@@ -101,6 +101,9 @@ thread_local TuneInt g_hop_seg_remap{0};    // hop_kernel: segment blocks in XCD
 thread_local TuneInt g_hop_mix{0};          // hop_kernel: row blocks dealt evenly among the segment blocks (1) or all in front (0)
 thread_local TuneInt g_hop_stream{1};       // hop_kernel: non-temporal entries / stores / partial rows when the output exceeds the Infinity Cache (0: never)
 thread_local TuneInt g_hop_lds_pad{0};      // hop_kernel: bytes of unused dynamic LDS per workgroup (occupancy limiter, developer A/B)
+thread_local TuneInt g_sched_hub_min{512};     // tgcn_sched_build, 16-lane schedules: rows of more entries are cut into wave segments (0: never) ...
+thread_local TuneInt g_sched_hub_seg{64};      // ... of this many entries ...
+thread_local TuneInt g_sched_hub_gate_mb{256};  // ... where the plain schedule's partial rows take more than this many MiB (tgcn_amd/graph.py: HUB_MIN, HUB_SEG, HUB_GATE_BYTES)
 thread_local TuneInt g_proj_variant{0};     // 1: force the streaming-W kernel
 thread_local TuneInt g_x3_form{2};          // bf16x3 projection, aligned operands, >= 96 output columns: 2 = A fragments from registers (+20 %), 1 = both operands through LDS
 thread_local TuneInt g_x3_tail{1};          // project_x3v2_kernel: rows of a thinly filled last round as 128-row tiles (0: 256-row tiles throughout)

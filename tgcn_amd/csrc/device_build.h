@@ -464,16 +464,39 @@ __global__ void sched_marks_kernel(const int64_t* __restrict__ cum, int64_t n, i
   }
 }
 
+// Segment length of a row of d entries that is cut into segments: hub rows (d > hub_min; hub_min < 0: there are none) take wave segments of
+// hub_seg entries, the others lane-group segments of seg_len
+__device__ __forceinline__ int64_t sched_row_seg_len(int64_t d, int seg_len, int64_t hub_min, int hub_seg) {
+  return (hub_min >= 0 && d > hub_min) ? hub_seg : seg_len;
+}
+
+// what the hub rule needs before anything is laid out: out2[0] = partial rows of the plain schedule (segments of rows with more than one),
+// out2[1] = hub wave segments under (hub_min, hub_seg).  Integer sums: order-independent
+__global__ void sched_hub_counts_kernel(const int32_t* __restrict__ rowptr, int64_t n, const int64_t* __restrict__ is_seg, int seg_len, int64_t hub_min,
+                                        int hub_seg, unsigned long long* __restrict__ out2) {
+  unsigned long long plain = 0, hub = 0;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    if (!is_seg[i]) continue;
+    const int64_t d = rowptr[i + 1] - rowptr[i];
+    const int64_t ns = (d + seg_len - 1) / seg_len;
+    if (ns > 1) plain += (unsigned long long)ns;
+    if (d > hub_min) hub += (unsigned long long)((d + hub_seg - 1) / hub_seg);
+  }
+  if (plain) atomicAdd(out2, plain);
+  if (hub) atomicAdd(out2 + 1, hub);
+}
+
 // rows cut into segments, in row order: seg_rows[pos[i]] = i; key = max_key - nsegs (ascending key = decreasing segment count)
 __global__ void sched_longrows_kernel(const int32_t* __restrict__ rowptr, int64_t n, const int64_t* __restrict__ is_seg,
-                                      const int64_t* __restrict__ pos, int seg_len, uint32_t max_key, uint32_t* __restrict__ seg_rows,
+                                      const int64_t* __restrict__ pos, int seg_len, int64_t hub_min, int hub_seg, uint32_t max_key, uint32_t* __restrict__ seg_rows,
                                       uint32_t* __restrict__ key) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     if (!is_seg[i]) continue;
     const int64_t d = rowptr[i + 1] - rowptr[i];
     const int64_t o = pos[i];
+    const int64_t len = sched_row_seg_len(d, seg_len, hub_min, hub_seg);
     seg_rows[o] = (uint32_t)i;
-    key[o] = max_key - (uint32_t)((d + seg_len - 1) / seg_len);
+    key[o] = max_key - (uint32_t)((d + len - 1) / len);
   }
 }
 
@@ -501,22 +524,24 @@ __global__ void sched_nsegs_kernel(const uint32_t* __restrict__ key, uint32_t ma
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) nsegs[i] = max_key - key[i];
 }
 
-// segment s belongs to the sorted long row j with first[j] <= s < first[j+1] (first = exclusive scan of nsegs, first[m] = nseg)
+// segment s belongs to the sorted long row j with first[j] <= s < first[j+1] (first = exclusive scan of nsegs, first[m] = nseg).
+// key = first column, lane-group segments lifted by lane_key_base (n_cols under the hub rule, else 0): the hub wave segments sort in front
 __global__ void sched_segments_kernel(const int32_t* __restrict__ rowptr, const tgcn_edge* __restrict__ edges, const uint32_t* __restrict__ seg_rows,
-                                      const int64_t* __restrict__ first, int64_t m, int64_t nseg, int64_t npartial, int seg_len,
-                                      int32_t* __restrict__ seg_row, int32_t* __restrict__ seg_e0, int32_t* __restrict__ seg_e1,
+                                      const int64_t* __restrict__ first, int64_t m, int64_t nseg, int64_t npartial, int seg_len, int64_t hub_min, int hub_seg,
+                                      uint32_t lane_key_base, int32_t* __restrict__ seg_row, int32_t* __restrict__ seg_e0, int32_t* __restrict__ seg_e1,
                                       int32_t* __restrict__ seg_slot, uint32_t* __restrict__ key, uint32_t* __restrict__ ident) {
   for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < nseg; s += (int64_t)gridDim.x * blockDim.x) {
     int64_t lo = 0, hi = m;                       // last j with first[j] <= s
     while (lo + 1 < hi) { const int64_t mid = (lo + hi) >> 1; if (first[mid] <= s) lo = mid; else hi = mid; }
     const int64_t r = seg_rows[lo];
-    const int64_t e0 = (int64_t)rowptr[r] + (s - first[lo]) * seg_len;
-    const int64_t e1 = (e0 + seg_len < (int64_t)rowptr[r + 1]) ? e0 + seg_len : (int64_t)rowptr[r + 1];
+    const int64_t len = sched_row_seg_len((int64_t)rowptr[r + 1] - rowptr[r], seg_len, hub_min, hub_seg);
+    const int64_t e0 = (int64_t)rowptr[r] + (s - first[lo]) * len;
+    const int64_t e1 = (e0 + len < (int64_t)rowptr[r + 1]) ? e0 + len : (int64_t)rowptr[r + 1];
     seg_row[s] = (int32_t)r;
     seg_e0[s] = (int32_t)e0;
     seg_e1[s] = (int32_t)e1;
     seg_slot[s] = s < npartial ? (int32_t)s : -1;
-    key[s] = (uint32_t)edges[e0].col;
+    key[s] = (uint32_t)edges[e0].col + (len == seg_len ? lane_key_base : 0u);
     ident[s] = (uint32_t)s;
   }
 }

@@ -207,14 +207,26 @@ int tgcn_sched_build_csr(const tgcn_csr* A, int64_t n_cols, int32_t C, int align
   hipLaunchKernelGGL(sched_marks_kernel, dim3(grid_1d(nblk + 1)), dim3(kBlock), 0, st, (const int64_t*)cost.p, n, target, nblk, (int32_t*)sc->blk_row.p);
   // ---- longest rows: lane-group segments; rows with several segments ("long") first, by decreasing segment count (stable)
   int64_t nlong = 0, nhuge = 0, npartial = 0, nsegl = 0;
-  DeviceBuf seg_rows, key, sortws, nsegs, first, cnt2;
+  // hub rows (16-lane schedules whose plain partial rows do not fit the Infinity Cache): wave segments of hub_seg entries, one slot each,
+  // stored behind the whole-row wave segments (tgcn_amd/graph.py: HUB_MIN, HUB_SEG, HUB_GATE_BYTES -- the same rule, array for array)
+  int64_t hub_min = -1, nhub = 0;
+  const int hub_seg = g_sched_hub_seg.load();
+  DeviceBuf seg_rows, key, sortws, nsegs, first, cnt2, hubcnt;
+  if (m > 0 && lanes == 16 && g_sched_hub_min.load() > 0 && g_sched_hub_min.load() >= hub_seg && hub_seg >= seg_len) {
+    unsigned long long hc[2] = {0, 0};
+    if (hubcnt.zero(16)) TGCN_SCHED_FAIL("sched_build: device allocation failed");
+    hipLaunchKernelGGL(sched_hub_counts_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, st, A->rowptr, n, (const int64_t*)is_seg.p, (int)seg_len,
+                       (int64_t)g_sched_hub_min.load(), hub_seg, (unsigned long long*)hubcnt.p);
+    if (hipMemcpy(hc, hubcnt.p, 16, hipMemcpyDeviceToHost) != hipSuccess) TGCN_SCHED_FAIL("sched_build: device read failed");
+    if ((int64_t)hc[0] * lanes * 16 > ((int64_t)g_sched_hub_gate_mb.load() << 20) && hc[1] > 0) { hub_min = g_sched_hub_min.load(); nhub = (int64_t)hc[1]; }
+  }
   if (m > 0) {
     const uint32_t max_key = (uint32_t)((A->nnz + seg_len - 1) / seg_len + 1);
     if (seg_rows.alloc((size_t)m * 4) || key.alloc((size_t)m * 4) || sortws.alloc(sort_ws_bytes(m)) || nsegs.zero((size_t)(m + 1) * 8) ||
         first.alloc((size_t)(m + 1) * 8) || cnt2.alloc(16))
       TGCN_SCHED_FAIL("sched_build: device allocation failed");
     hipLaunchKernelGGL(sched_longrows_kernel, dim3(grid_1d(n)), dim3(kBlock), 0, st, A->rowptr, n, (const int64_t*)is_seg.p, (const int64_t*)pos.p,
-                       (int)seg_len, max_key, (uint32_t*)seg_rows.p, (uint32_t*)key.p);
+                       (int)seg_len, hub_min, hub_seg, max_key, (uint32_t*)seg_rows.p, (uint32_t*)key.p);
     radix_sort_pairs(st, (uint32_t*)key.p, (uint32_t*)seg_rows.p, m, bits_for((int64_t)max_key + 1), (char*)sortws.p);
     hipLaunchKernelGGL(sched_nsegs_kernel, dim3(grid_1d(m)), dim3(kBlock), 0, st, (const uint32_t*)key.p, max_key, m, (int64_t*)nsegs.p);
     hipLaunchKernelGGL(sched_counts_kernel, dim3(1), dim3(64), 0, st, (const int64_t*)nsegs.p, m, (int)huge_slots, (int64_t*)cnt2.p);
@@ -224,7 +236,7 @@ int tgcn_sched_build_csr(const tgcn_csr* A, int64_t n_cols, int32_t C, int align
     nlong = h2[0]; nhuge = h2[1];
     if (nlong > 0 && read_back(&npartial, (const int64_t*)first.p + nlong)) TGCN_SCHED_FAIL("sched_build: device read failed");
   }
-  const int64_t nseg = mw + nsegl;               // whole-row wave segments first, then the lane-group segments
+  const int64_t nseg = mw + nsegl;               // whole-row wave segments first, then the hub rows' wave segments, then the lane-group segments
   if (nseg >= (int64_t)INT32_MAX) TGCN_SCHED_FAIL("sched_build: too many segments");
   const size_t sball = (size_t)(nseg > 0 ? nseg : 1) * 4;
   if (sc->seg_row.zero(sball) || sc->seg_e0.zero(sball) || sc->seg_e1.zero(sball) || sc->seg_slot.zero(sball) || sc->long_row.zero((size_t)(nlong ? nlong : 1) * 4) ||
@@ -244,9 +256,9 @@ int tgcn_sched_build_csr(const tgcn_csr* A, int64_t n_cols, int32_t C, int align
     if (u_row.alloc(sb) || u_e0.alloc(sb) || u_e1.alloc(sb) || u_slot.alloc(sb) || key2.alloc(sb) || ident.alloc(sb) || sortws2.alloc(sort_ws_bytes(nsegl)))
       TGCN_SCHED_FAIL("sched_build: device allocation failed");
     hipLaunchKernelGGL(sched_segments_kernel, dim3(grid_1d(nsegl)), dim3(kBlock), 0, st, A->rowptr, A->edges, (const uint32_t*)seg_rows.p, (const int64_t*)first.p, m,
-                       nsegl, npartial, (int)seg_len, (int32_t*)u_row.p, (int32_t*)u_e0.p, (int32_t*)u_e1.p, (int32_t*)u_slot.p, (uint32_t*)key2.p, (uint32_t*)ident.p);
-    // processing order: by first column (stable)
-    radix_sort_pairs(st, (uint32_t*)key2.p, (uint32_t*)ident.p, nsegl, bits_for(n_cols), (char*)sortws2.p);
+                       nsegl, npartial, (int)seg_len, hub_min, hub_seg, (uint32_t)(nhub > 0 ? n_cols : 0), (int32_t*)u_row.p, (int32_t*)u_e0.p, (int32_t*)u_e1.p, (int32_t*)u_slot.p, (uint32_t*)key2.p, (uint32_t*)ident.p);
+    // processing order: by first column (stable); under the hub rule the hub wave segments in front, a run of their own
+    radix_sort_pairs(st, (uint32_t*)key2.p, (uint32_t*)ident.p, nsegl, bits_for(nhub > 0 ? 2 * n_cols : n_cols), (char*)sortws2.p);
     const unsigned gs = grid_1d(nsegl);
     hipLaunchKernelGGL(permute_i32_kernel, dim3(gs), dim3(kBlock), 0, st, (const int32_t*)u_row.p, (const uint32_t*)ident.p, (int32_t*)sc->seg_row.p + mw, nsegl);
     hipLaunchKernelGGL(permute_i32_kernel, dim3(gs), dim3(kBlock), 0, st, (const int32_t*)u_e0.p, (const uint32_t*)ident.p, (int32_t*)sc->seg_e0.p + mw, nsegl);
@@ -261,7 +273,7 @@ int tgcn_sched_build_csr(const tgcn_csr* A, int64_t n_cols, int32_t C, int align
   memset(&sc->s, 0, sizeof(sc->s));
   sc->s.lanes_per_row = lanes; sc->s.row_thresh = row_thresh; sc->s.nblk = (int32_t)nblk; sc->s.nseg = (int32_t)nseg;
   sc->s.nlong = (int32_t)nlong; sc->s.nhuge = (int32_t)nhuge; sc->s.npartial = (int32_t)npartial; sc->s.seg_mode = seg_mode;
-  sc->s.nwseg = (int32_t)mw;
+  sc->s.nwseg = (int32_t)(mw + nhub);            // one wave each: the whole rows, then the hub rows' segments
   sc->s.row_mix = (n_empty * 8 >= n) ? 1 : 0;            // many empty rows: their blocks among the segment blocks (tgcn_csr_sched.row_mix)
   sc->s.blk_row = (const int32_t*)sc->blk_row.p; sc->s.seg_row = (const int32_t*)sc->seg_row.p; sc->s.seg_e0 = (const int32_t*)sc->seg_e0.p;
   sc->s.seg_e1 = (const int32_t*)sc->seg_e1.p; sc->s.seg_slot = (const int32_t*)sc->seg_slot.p; sc->s.long_row = (const int32_t*)sc->long_row.p;

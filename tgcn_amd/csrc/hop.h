@@ -25,7 +25,8 @@ struct HopParams {
   float alpha, beta, gamma;
   int32_t nblk, nseg, nlong, nhuge, row_thresh;
   int32_t C, nb, nchunks, cpad, remap;
-  int32_t nwseg;                 // leading segments that are whole rows of up to 32 * (64 / LPR) entries, one WAVE each (no partial rows)
+  int32_t nwseg;                 // leading segments handled by one WAVE each: whole rows of up to 32 * (64 / LPR) entries (seg_slot < 0: written directly),
+                                 // then the hub rows' wave segments (seg_slot >= 0: one partial row per wave)
   int32_t mix_period;            // kernel: > 1 one row block every mix_period block ids, < 0 segment blocks first, 0 / 1 row blocks first (host: the request, see launch_hop)
   int32_t stream_out;            // the output tensor is larger than the Infinity Cache: entries, results and partial rows with non-temporal hints
   int32_t seg_mode, seg_remap;   // seg_mode 1: one WAVE per segment (tgcn_csr_sched.seg_mode); seg_remap: XCD-contiguous segment ranges
@@ -351,11 +352,12 @@ __global__ __launch_bounds__(kBlock) void hop_kernel(const HopParams p) {
     int sbid = bid - p.nblk;
     if (p.seg_remap) sbid = xcd_remap(sbid, (int)gridDim.x - p.nblk);
     if constexpr (LPR < 64 && R == 1) {
-      const int nwblk = (p.nwseg + kBlock / 64 - 1) / (kBlock / 64);     // workgroups of the whole-row wave segments (hybrid schedule)
+      const int nwblk = (p.nwseg + kBlock / 64 - 1) / (kBlock / 64);     // workgroups of the wave-handled segments (hybrid schedule)
       if (p.seg_mode == 1 || sbid < nwblk) {
-        // One wave per segment of up to 32 * (64 / LPR) entries: its lane groups take consecutive pieces of the segment and the
-        // pieces are folded inside the wave (fixed order: neighbours first), so a row of up to that many entries is written
-        // directly and longer rows leave one partial row per wave instead of one per lane group.
+        // One wave per segment: its lane groups take consecutive pieces of the segment and the pieces are folded inside the wave
+        // (fixed order: neighbours first), so a whole row (seg_slot < 0, up to 32 * (64 / LPR) entries) is written directly and a
+        // longer row's wave segment (seg_mode 1, or a hub row's among the first nwseg) leaves one partial row per wave instead of
+        // one per lane group.
         constexpr int GPW = 64 / LPR;
         const int s = sbid * (kBlock / 64) + (tid >> 6);
         const int gw = (tid & 63) / LPR;
@@ -380,7 +382,9 @@ __global__ __launch_bounds__(kBlock) void hop_kernel(const HopParams p) {
         if (slot < 0) {
           if (cact) finish_row<VEC, NTM, T>(p, b, p.seg_row[s], c0, acc[0]);
         } else {
-          store_vec<VEC>(p.partial + ((int64_t)slot * p.nb + b) * p.cpad + (chunk * LPR + t) * VEC, acc[0]);
+          float* dst = p.partial + ((int64_t)slot * p.nb + b) * p.cpad + (chunk * LPR + t) * VEC;
+          if constexpr (NTM & kNtPartials) store_vec_nt<VEC>(dst, acc[0]);
+          else store_vec<VEC>(dst, acc[0]);
         }
         return;
       }

@@ -64,6 +64,7 @@ void tgcn_reset_tuning(void) {
   g_hop_variant.store(0); g_hop_remap.store(1); g_hop_seg_remap.store(0); g_hop_mix.store(0); g_hop_stream.store(1); g_hop_lds_pad.store(0);
   g_proj_variant.store(0); g_small_dense.store(2); g_small_narrow.store(1); g_x3_form.store(2); g_x3_tail.store(1);
   g_x3_stream_cap.store(0); g_overlap.store(1); g_overlap_group.store(3); g_overlap_min_mb.store(256);
+  g_sched_hub_min.store(512); g_sched_hub_seg.store(64); g_sched_hub_gate_mb.store(256);
 }
 
 int tgcn_set_tuning(const char* key, int32_t value) {
@@ -82,6 +83,9 @@ int tgcn_set_tuning(const char* key, int32_t value) {
   if (key && strcmp(key, "compact_overlap") == 0) { g_overlap.store(value != 0); return TGCN_OK; }
   if (key && strcmp(key, "compact_overlap_group") == 0) { if (value < 1) TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: compact_overlap_group %d", value); g_overlap_group.store(value); return TGCN_OK; }
   if (key && strcmp(key, "compact_overlap_min_mb") == 0) { if (value < 0) TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: compact_overlap_min_mb %d", value); g_overlap_min_mb.store(value); return TGCN_OK; }
+  if (key && strcmp(key, "sched_hub_min") == 0) { if (value < 0) TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: sched_hub_min %d", value); g_sched_hub_min.store(value); return TGCN_OK; }
+  if (key && strcmp(key, "sched_hub_seg") == 0) { if (value < 1) TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: sched_hub_seg %d", value); g_sched_hub_seg.store(value); return TGCN_OK; }
+  if (key && strcmp(key, "sched_hub_gate_mb") == 0) { if (value < 0) TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: sched_hub_gate_mb %d", value); g_sched_hub_gate_mb.store(value); return TGCN_OK; }
   TGCN_FAIL(TGCN_ERR_INVALID, "set_tuning: unknown key");
 }
 

@@ -13,12 +13,19 @@ import torch
 from . import _lib
 
 ROW_THRESH = 32         # rows with more stored entries are processed as column-ordered segments
-SEG_LEN = 32            # stored entries per segment (measured on cfg5: 32 beats 16/64/128/256, tools/hop_bench.py)
+SEG_LEN = 32            # stored entries per lane-group segment (measured on cfg5: 32 beats 16/64/128/256, tools/hop_bench.py); hub rows: HUB_SEG
 SEG_MODE = 0            # 0: one lane group per segment (shipped); 1: one WAVE per segment of SEG_LEN * (64 / lanes) entries, pieces folded in
                         # the wave -- 4.7x fewer partial rows but the column-ordered sweep loses its locality: cfg5 hop 3.82 -> 4.44 ms (docs/EXPERIMENTS.md A.3)
 SEG_KEY = "first"       # column of the segment used as its place in the processing order
 WAVE_ROWS = True        # 16-lane schedules: rows with ROW_THRESH < entries <= 128 are whole-row segments of one WAVE each (its lane groups fold inside the
                         # wave: no partial rows, no fix-up for them; cfg5: fix-up 0.216 -> 0.155 ms per launch, hop unchanged); False: lane-group segments
+                        # (and no hub rows: their wave segments live in the same leading run of the seg_* arrays, Schedule.nwseg)
+HUB_MIN = 512           # 16-lane schedules whose plain partial rows exceed HUB_GATE_BYTES: rows with more entries ("hub rows") are cut into wave segments of
+HUB_SEG = 64            # HUB_SEG consecutive entries (one WAVE each, 16 entries per lane group, folded inside the wave: one partial row per HUB_SEG entries
+                        # instead of one per SEG_LEN); rows of 129 .. HUB_MIN entries stay lane-group segments, whose pieces must travel with the column-ordered
+                        # sweep.  cfg5: partial rows 3.47 M -> 2.23 M, hop + fix-up 3.833 -> 3.762 ms per launch; 128-entry wave segments and thresholds
+                        # of 128 / 2048 / 4096 lose or gain nothing (docs/EXPERIMENTS.md A.9).  HUB_MIN = 0: no hub rows
+HUB_GATE_BYTES = 256 << 20   # ... the rule applies only where the plain schedule's partial rows (npartial * lanes * 16 B) do not fit the Infinity Cache
 HUGE_SLOTS = 64         # long rows with more segments than this get a whole workgroup in the fix-up
 ROW_COST = 4            # per-row overhead of the balance model, in entry equivalents
 DENSE_MAX_N = 256       # operands up to this size that store >= 1/4 of their entries also keep a dense copy
@@ -28,6 +35,7 @@ COMPACT_MIN_EMPTY = 0.125      # ... with at least this share of structurally em
 BUILDER = "library"     # operands / schedules of device tensors: "library" = the HIP kernels of libtgcn_hip.so (csrc/device_build.h: own stable
                         # radix sort, prefix sums, marks); "torch" = the torch index ops below (always for CPU tensors; the cross-check)
 BLOCK_ROWS_MAX = None   # cost of a row block at most this many entry-equivalents per lane group (None: 64 for rows up to 64 floats, else 256)
+_HUB_DEFAULTS = (HUB_MIN, HUB_SEG, HUB_GATE_BYTES)     # what tgcn_sched_build applies (csrc/graph_build.h); anything else builds with the torch ops below
 
 
 def _as_i32(t):
@@ -45,7 +53,8 @@ class Schedule:
 
     def __init__(self, rowptr, n, lanes_per_row, edges=None, row_thresh=None, seg_len=None, seg_mode=None, n_cols=None, builder=None):
         defaults = (row_thresh is None and seg_len is None and seg_mode is None and ROW_THRESH == 32 and SEG_LEN == 32 and SEG_MODE == 0
-                    and SEG_KEY == "first" and WAVE_ROWS and BLOCK_ROWS_MAX is None and ROW_COST == 4 and HUGE_SLOTS == 64 and MAX_BLOCKS_HINT == 2048)
+                    and SEG_KEY == "first" and WAVE_ROWS and BLOCK_ROWS_MAX is None and ROW_COST == 4 and HUGE_SLOTS == 64 and MAX_BLOCKS_HINT == 2048
+                    and (HUB_MIN, HUB_SEG, HUB_GATE_BYTES) == _HUB_DEFAULTS)
         builder = BUILDER if builder is None else builder
         if builder == "library" and rowptr.is_cuda and edges is not None and defaults:
             self._build_library(rowptr, n, lanes_per_row, edges, n if n_cols is None else n_cols)
@@ -79,7 +88,7 @@ class Schedule:
         self.blk_row = _as_i32(torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), inner,
                                           torch.full((1,), n, dtype=torch.int64, device=dev)]))
         self.nblk = nblk
-        # ---- longer rows: segments, long rows (several segments) first by decreasing segment count
+        # ---- longer rows: segments, long rows (several segments) first by decreasing segment (= slot) count
         self.nwseg = 0
         wave_rows = None
         # 16-lane groups only: with 4-lane groups (cfg5n) a wave is 16 groups and a 40-entry row leaves most of them idle (hop +8 %)
@@ -94,18 +103,26 @@ class Schedule:
         self.nseg = self.nlong = self.nhuge = self.npartial = 0
         self.seg_row = self.seg_e0 = self.seg_e1 = self.seg_slot = self.long_row = z1
         self.long_slot = torch.zeros(2, dtype=torch.int32, device=dev)
+        hub = None                                  # per seg row: segment length (HUB_SEG for hub rows), once the rule applies
+        if wave_rows is not None and HUB_MIN and HUB_MIN >= HUB_SEG >= seg_len and seg_rows.numel():
+            plain = (deg[seg_rows] + seg_len - 1) // seg_len
+            if int(plain[plain > 1].sum().item()) * lanes_per_row * 16 > HUB_GATE_BYTES and bool((deg[seg_rows] > HUB_MIN).any()):
+                hub = torch.where(deg[seg_rows] > HUB_MIN, HUB_SEG, seg_len)
+        nhub = 0
         if seg_rows.numel():
-            nsegs = (deg[seg_rows] + seg_len - 1) // seg_len
+            rlen = hub if hub is not None else torch.full_like(seg_rows, seg_len)
+            nsegs = (deg[seg_rows] + rlen - 1) // rlen
             order = torch.argsort(nsegs, descending=True, stable=True)
-            seg_rows, nsegs = seg_rows[order], nsegs[order]
+            seg_rows, nsegs, rlen = seg_rows[order], nsegs[order], rlen[order]
             self.nlong = int((nsegs > 1).sum().item())
             self.nhuge = int((nsegs > HUGE_SLOTS).sum().item())
             self.nseg = int(nsegs.sum().item())
             first = torch.cumsum(nsegs, 0) - nsegs
             row_of = torch.repeat_interleave(seg_rows, nsegs)
             within = torch.arange(self.nseg, device=dev, dtype=torch.int64) - torch.repeat_interleave(first, nsegs)
-            e0 = rowptr[row_of].to(torch.int64) + within * seg_len
-            e1 = torch.minimum(e0 + seg_len, rowptr[row_of + 1].to(torch.int64))
+            len_of = torch.repeat_interleave(rlen, nsegs)
+            e0 = rowptr[row_of].to(torch.int64) + within * len_of
+            e1 = torch.minimum(e0 + len_of, rowptr[row_of + 1].to(torch.int64))
             # slots: segments of long rows are numbered consecutively per row (long rows come first in `seg_rows`)
             self.npartial = int(nsegs[: self.nlong].sum().item())
             slot = torch.arange(self.nseg, device=dev, dtype=torch.int64)
@@ -123,6 +140,11 @@ class Schedule:
                     key = edges[e0, 0].to(torch.int64) * (n + 1) + edges[e1 - 1, 0].to(torch.int64)
                 else:
                     key = edges[e0, 0].to(torch.int64)
+                if hub is not None:
+                    # hub wave segments first (they join the wave-handled run below), lane-group segments behind them; each run by first column
+                    is_lane = (len_of == seg_len).to(torch.int64)
+                    nhub = int((deg[row_of] > HUB_MIN).sum().item())
+                    key = key + is_lane * (int(key.max().item()) + 1)
                 perm = torch.argsort(key, stable=True)
                 row_of, e0, e1, slot = row_of[perm], e0[perm], e1[perm], slot[perm]
             self.seg_row, self.seg_e0, self.seg_e1, self.seg_slot = _as_i32(row_of), _as_i32(e0), _as_i32(e1), _as_i32(slot)
@@ -138,6 +160,7 @@ class Schedule:
             self.seg_row, self.seg_e0, self.seg_e1 = cat(wr, self.seg_row), cat(w0, self.seg_e0), cat(w1, self.seg_e1)
             self.seg_slot = cat(torch.full_like(wr, -1), self.seg_slot)
             self.nseg = had + self.nwseg
+        self.nwseg += nhub                           # the hub wave segments: a run of their own behind the whole rows, one wave each as well
         self.lanes_per_row = lanes_per_row
         self.row_thresh = row_thresh
         self.seg_len = seg_len
