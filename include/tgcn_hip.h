@@ -760,6 +760,27 @@ int tgcn_cheb_basis_small_supported(int64_t n, int64_t nnz, int32_t C, int32_t m
 int tgcn_cheb_basis_small_f32(void* stream, const tgcn_csr* A, int32_t mode, int32_t K, int64_t q, int32_t C,
                               const float* x, float* stack);
 
+/* Host query (ABI 8, additive): the kernel and launch configuration that tgcn_cheb_forward_small_pool_f32 (basis = 0; pool as passed
+ * there, 0 for tgcn_cheb_forward_small_f32) or tgcn_cheb_basis_small_f32 (basis != 0; N and pool are not read) takes for an operand of n
+ * vertices and nnz entries (has_dense_copy: tgcn_csr.dense is non-null), input rows of C floats, N output channels and a batch of q.  The
+ * launch entries get their configuration from this very function, so what it reports is what runs; it honours the small_dense and
+ * small_narrow tuning switches as they do.  Nothing is launched.
+ *   form       0 small_forward_kernel (recursion on the output side), 1 small_narrow_kernel (C <= 4, recursion on the input side),
+ *              2 small_basis_kernel, 3 fp32 matrix pipe (small_dense_kernel), 4 bf16x3 matrix pipe (small_dense_x3_kernel)
+ *   tile       channels per workgroup: NTC (form 0), NT (form 1), CT (form 2), 16 (forms 3, 4)
+ *   cp         floats of the input row a thread of form 0 keeps in registers (4 / 16 / 32); 0 for the other forms
+ *   spw        samples per workgroup (forms 3, 4: their S); the last workgroup has q % spw live samples when that is not 0
+ *   dense_lds  1: the operand lies in LDS as a dense n x (n|1) matrix, 0: as its CSR (forms 3, 4: 0, L is held in registers)
+ *   threads, lds_bytes, grid_x, grid_y   the launch
+ * Returns 0, or the code the launch entry returns for the same arguments: TGCN_ERR_INVALID for q < 1, N < 1 (forward), C < 1 (basis), a
+ * pool outside [0, 255] or one that does not divide n, or a null plan; TGCN_ERR_UNSUPPORTED where the operand and buffers do not fit
+ * (n > 1024, more than 2^20 entries, C > 128 in the forward, above 160 KB of LDS, a mode other than 0 / 1) or the grid is too large. */
+typedef struct tgcn_small_plan {
+  int32_t form, tile, cp, spw, dense_lds, threads, lds_bytes, grid_x, grid_y;
+} tgcn_small_plan;
+int tgcn_cheb_small_plan(int64_t n, int64_t nnz, int32_t has_dense_copy, int32_t mode, int32_t C, int32_t N, int64_t q, int32_t pool,
+                         int32_t basis, tgcn_small_plan* plan);
+
 /* Fused epilogue of the callers' pattern  x = gcn_pool_4(F.relu(layer(x)))  (examples/pytorch_based/
  * pytorch_hcp_tgcn.py:134-141): out (q, n/pool, N) = max over `pool` consecutive vertices of
  * relu(layer output); pool_idx (nullable, uint8) receives the arg-max offset for the backward.

@@ -27,6 +27,10 @@ class SchedStruct(C.Structure):
                 ("seg_slot", C.c_void_p), ("long_row", C.c_void_p), ("long_slot", C.c_void_p)]
 
 
+class SmallPlanStruct(C.Structure):       # tgcn_small_plan
+    _fields_ = [(k, C.c_int32) for k in ("form", "tile", "cp", "spw", "dense_lds", "threads", "lds_bytes", "grid_x", "grid_y")]
+
+
 class DenseStruct(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("batch_stride", C.c_int64), ("row_stride", C.c_int64)]
 
@@ -123,6 +127,8 @@ SIGNATURES = {
     "tgcn_cheb_forward_small_supported": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "tgcn_cheb_basis_small_supported": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
     "tgcn_cheb_forward_small_pool_supported": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "tgcn_cheb_small_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,
+                                       C.POINTER(SmallPlanStruct)]),
     "tgcn_cheb_basis_small_f32": (C.c_int, [C.c_void_p, C.POINTER(CsrStruct), C.c_int32, C.c_int32, C.c_int64, C.c_int32,
                                            C.c_void_p, C.c_void_p]),
     "tgcn_cheb_forward_small_f32": (C.c_int, [_P, C.POINTER(CsrStruct), C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32,

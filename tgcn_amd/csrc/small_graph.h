@@ -942,13 +942,18 @@ inline int dense_mfma_config(int64_t n, int64_t nnz, int32_t C, int32_t mode, in
   return 0;
 }
 
+inline size_t dense_lds_bytes(int n, int S, int mode, bool basis) {
+  const int npad = (n + 15) / 16 * 16;
+  return ((size_t)(basis ? 0 : kDenseWFloats) + (size_t)(mode == 0 ? 2 : 3) * npad * (S * 16 + 16)) * sizeof(float);
+}
+
 template <bool BASIS>
-inline void launch_small_dense(hipStream_t st, const SmallParams& p, int S, int64_t col_tiles) {
+inline void launch_small_dense(hipStream_t st, const SmallParams& p, const tgcn_small_plan& pl) {
   const int npad = (p.n + 15) / 16 * 16;
-  const int nbuf = p.mode == 0 ? 2 : 3;
-  const size_t lds = ((size_t)(BASIS ? 0 : kDenseWFloats) + (size_t)nbuf * npad * (S * 16 + 16)) * sizeof(float);
-  const dim3 grid((unsigned)((p.q + S - 1) / S), (unsigned)col_tiles);
-  const dim3 block((unsigned)(npad / 16 * 64));
+  const int S = pl.spw;
+  const size_t lds = (size_t)pl.lds_bytes;
+  const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
+  const dim3 block((unsigned)pl.threads);
 #define TGCN_DENSE(SV, NWV, XKV)                                                                   \
   {                                                                                                \
     allow_large_lds((const void*)small_dense_kernel<SV, BASIS, NWV, XKV>, 160 * 1024);             \
@@ -989,11 +994,12 @@ inline int dense_x3_config(int64_t n, int64_t nnz, int32_t C, int32_t mode, int6
 }
 
 template <bool BASIS>
-inline void launch_small_dense_x3(hipStream_t st, const SmallParams& p, int S, int64_t col_tiles) {
+inline void launch_small_dense_x3(hipStream_t st, const SmallParams& p, const tgcn_small_plan& pl) {
   const int npad = (p.n + 15) / 16 * 16;
-  const size_t lds = dense_x3_lds_bytes(p.n, S, p.mode, BASIS);
-  const dim3 grid((unsigned)((p.q + S - 1) / S), (unsigned)col_tiles);
-  const dim3 block((unsigned)(npad / 16 * 64));
+  const int S = pl.spw;
+  const size_t lds = (size_t)pl.lds_bytes;
+  const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
+  const dim3 block((unsigned)pl.threads);
 #define TGCN_DX3(SV, NWV, XKV)                                                                       \
   {                                                                                                  \
     allow_large_lds((const void*)small_dense_x3_kernel<SV, BASIS, NWV, XKV>, 160 * 1024);            \
@@ -1010,4 +1016,86 @@ inline void launch_small_dense_x3(hipStream_t st, const SmallParams& p, int S, i
 #undef TGCN_DX3_S
 #undef TGCN_DX3_X
 #undef TGCN_DX3
+}
+
+// ---- the one place that picks the kernel and launch configuration of tgcn_cheb_forward_small_pool_f32 (basis false) and
+// tgcn_cheb_basis_small_f32 (basis true) from the shape and the batch; tgcn_cheb_small_plan reports it, the launch entries run it.
+// -> TGCN_OK with *pl filled, or the entry's code with *why set to the rest of its message.
+inline void small_plan_matrix_pipe(int64_t n, int32_t mode, int64_t q, int64_t tiles16, int S, int S3, bool basis, tgcn_small_plan* pl) {
+  const int s = S3 ? S3 : S;
+  pl->form = S3 ? 4 : 3; pl->tile = 16; pl->cp = 0; pl->spw = s; pl->dense_lds = 0;
+  pl->threads = (int32_t)((n + 15) / 16 * 64);
+  pl->lds_bytes = (int32_t)(S3 ? dense_x3_lds_bytes((int)n, s, mode, basis) : dense_lds_bytes((int)n, s, mode, basis));
+  pl->grid_x = (int32_t)((q + s - 1) / s); pl->grid_y = (int32_t)tiles16;
+}
+
+inline int small_plan(int64_t n, int64_t nnz, bool has_dense, int32_t mode, int32_t C, int32_t N, int64_t q, int32_t pool, bool basis,
+                      tgcn_small_plan* pl, const char** why) {
+  const int sd = g_small_dense.load();
+  int dense = 0;
+  *why = "does not fit in LDS";
+  if (basis) {
+    const int ct = basis_config(n, nnz, C, mode, &dense);
+    if (!ct && !(sd && dense_mfma_config(n, nnz, C, mode, 1, 1, true))) return TGCN_ERR_UNSUPPORTED;
+    if (q > 2147483647LL || C > 16 * 65535) { *why = "grid too large"; return TGCN_ERR_UNSUPPORTED; }
+    if (has_dense && sd) {
+      const int64_t tiles16 = (C + 15) / 16;
+      const int S = dense_mfma_config(n, nnz, C, mode, q, tiles16, true);
+      if (S) {
+        small_plan_matrix_pipe(n, mode, q, tiles16, S, sd >= 2 ? dense_x3_config(n, nnz, C, mode, q, tiles16, true) : 0, true, pl);
+        return TGCN_OK;
+      }
+    }
+    if (!ct) return TGCN_ERR_UNSUPPORTED;
+    const int npad = ((int)n + 63) / 64 * 64;
+    const int64_t col_tiles = (C + ct - 1) / ct;
+    int spw = 1;
+    while ((spw + 1) * npad <= kSmallMaxN && basis_lds_bytes((int)n, (int)nnz, ct, mode, dense, spw + 1) <= 160 * 1024 &&
+           (q + spw) / (spw + 1) * col_tiles >= 512)
+      ++spw;
+    pl->form = 2; pl->tile = ct; pl->cp = 0; pl->spw = spw; pl->dense_lds = dense; pl->threads = npad * spw;
+    pl->lds_bytes = (int32_t)basis_lds_bytes((int)n, (int)nnz, ct, mode, dense, spw);
+    pl->grid_x = (int32_t)((q + spw - 1) / spw); pl->grid_y = (int32_t)col_tiles;
+    return TGCN_OK;
+  }
+  if (q > 2147483647LL) { *why = "grid too large"; return TGCN_ERR_UNSUPPORTED; }
+  if (pool == 0 && has_dense && sd) {   // dense operand (e.g. the 148-parcel DTI graph): matrix pipe
+    const int64_t tiles16 = (N + 15) / 16;
+    const int S = dense_mfma_config(n, nnz, C, mode, q, tiles16, false);
+    if (S && tiles16 <= 65535) {
+      // S3: L . Y on the bf16 matrix pipe, three-way split
+      small_plan_matrix_pipe(n, mode, q, tiles16, S, sd >= 2 ? dense_x3_config(n, nnz, C, mode, q, tiles16, false) : 0, false, pl);
+      return TGCN_OK;
+    }
+  }
+  const int ntc = small_config(n, nnz, C, mode, &dense);
+  if (!ntc) return TGCN_ERR_UNSUPPORTED;
+  if ((N + ntc - 1) / ntc > 65535) { *why = "grid too large"; return TGCN_ERR_UNSUPPORTED; }
+  const int npad = ((int)n + 63) / 64 * 64;
+  if (C <= 4 && g_small_narrow.load() && (pool == 0 || (pool <= 64 && (64 % pool) == 0))) {
+    // first layers: recursion on the 4-float input side, all of NT output channels per workgroup (small_narrow_kernel)
+    int nt = N > 32 ? 64 : (N > 16 ? 32 : 16);
+    while (nt > 16 && q * ((N + nt - 1) / nt) < 256) nt /= 2;            // fill the chip before widening the tile
+    int spw = 1;
+    const int64_t tiles = (N + nt - 1) / nt;
+    while ((spw + 1) * npad <= kSmallMaxN && narrow_lds_bytes((int)n, (int)nnz, nt, mode, dense, spw + 1) <= 160 * 1024 &&
+           (q + spw) / (spw + 1) * tiles >= 512)
+      ++spw;
+    if (narrow_lds_bytes((int)n, (int)nnz, nt, mode, dense, spw) <= 160 * 1024) {
+      pl->form = 1; pl->tile = nt; pl->cp = 0; pl->spw = spw; pl->dense_lds = dense; pl->threads = npad * spw;
+      pl->lds_bytes = (int32_t)narrow_lds_bytes((int)n, (int)nnz, nt, mode, dense, spw);
+      pl->grid_x = (int32_t)((q + spw - 1) / spw); pl->grid_y = (int32_t)tiles;
+      return TGCN_OK;
+    }
+  }
+  // samples per workgroup: as many as fit the 1024-thread / 160 KB budget, but keep >= 512 workgroups in the grid
+  int spw = 1;
+  const int64_t col_tiles = (N + ntc - 1) / ntc;
+  while ((spw + 1) * npad <= kSmallMaxN && small_lds_bytes((int)n, (int)nnz, C, ntc, mode, dense, spw + 1) <= 160 * 1024 &&
+         (q + spw) / (spw + 1) * col_tiles >= 512)
+    ++spw;
+  pl->form = 0; pl->tile = ntc; pl->cp = C <= 4 ? 4 : (C <= 16 ? 16 : 32); pl->spw = spw; pl->dense_lds = dense; pl->threads = npad * spw;
+  pl->lds_bytes = (int32_t)small_lds_bytes((int)n, (int)nnz, C, ntc, mode, dense, spw);
+  pl->grid_x = (int32_t)((q + spw - 1) / spw); pl->grid_y = (int32_t)col_tiles;
+  return TGCN_OK;
 }

@@ -767,80 +767,65 @@ int tgcn_cheb_forward_small_pool_f32(void* stream, const tgcn_csr* A, int32_t mo
   if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "forward_small: bias_kind %d", bias_kind);
   if (fold && mode != 0) TGCN_FAIL(TGCN_ERR_INVALID, "forward_small: fold is for mode 0");
   if (q > 2147483647LL) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "forward_small: grid too large");
-  int dense = 0;
   SmallParams p;
   p.rowptr = A->rowptr; p.ev = A->edges; p.x = x; p.W = W; p.fold = fold; p.bias = bias; p.out = out;
   p.n = (int32_t)A->n; p.nnz = (int32_t)A->nnz; p.q = (int32_t)q; p.K = K; p.C = C; p.N = N; p.mode = mode; p.bias_kind = bias_kind; p.dense = 0; p.relu = relu; p.pool = pool; p.pool_idx = pool_idx;
   p.npad = 0; p.spw = 1;
   p.Ld = A->dense;
-  if (pool == 0 && A->dense && g_small_dense.load()) {   // dense operand (e.g. the 148-parcel DTI graph): fp32 matrix pipe
-    const int64_t tiles16 = (N + 15) / 16;
-    const int S = dense_mfma_config(A->n, A->nnz, C, mode, q, tiles16, false);
-    if (S && tiles16 <= 65535) {
-      hipStream_t st = (hipStream_t)stream;
-      ProfScope ps(TGCN_PROF_SMALL, st);
-      const int S3 = g_small_dense.load() >= 2 ? dense_x3_config(A->n, A->nnz, C, mode, q, tiles16, false) : 0;
-      p.npad = 0; p.spw = S3 ? S3 : S;
-      if (S3) launch_small_dense_x3<false>(st, p, S3, tiles16);     // L . Y on the bf16 matrix pipe, three-way split
-      else launch_small_dense<false>(st, p, S, tiles16);
-      TGCN_CHECK_LAUNCH("tgcn_cheb_forward_small_f32 (dense)");
-      return TGCN_OK;
-    }
+  tgcn_small_plan pl;     // kernel form, tile, samples per workgroup, grid, block and LDS: small_plan (small_graph.h), also behind tgcn_cheb_small_plan
+  const char* why = "";
+  if (const int prc = small_plan(A->n, A->nnz, A->dense != nullptr, mode, C, N, q, pool, false, &pl, &why)) {
+    if (why[0] == 'g') TGCN_FAIL(prc, "forward_small: grid too large");
+    TGCN_FAIL(prc, "forward_small: n=%lld nnz=%lld C=%d does not fit in LDS", (long long)A->n, (long long)A->nnz, C);
   }
-  const int ntc = small_config(A->n, A->nnz, C, mode, &dense);
-  if (!ntc) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "forward_small: n=%lld nnz=%lld C=%d does not fit in LDS", (long long)A->n, (long long)A->nnz, C);
-  if ((N + ntc - 1) / ntc > 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "forward_small: grid too large");
-  p.dense = dense;
-  if (C <= 4 && g_small_narrow.load() && (pool == 0 || (pool <= 64 && (64 % pool) == 0))) {
-    // first layers: recursion on the 4-float input side, all of NT output channels per workgroup (small_narrow_kernel)
-    p.npad = (p.n + 63) / 64 * 64;
-    int nt = N > 32 ? 64 : (N > 16 ? 32 : 16);
-    while (nt > 16 && q * ((N + nt - 1) / nt) < 256) nt /= 2;            // fill the chip before widening the tile
-    int spw = 1;
-    const int64_t tiles = (N + nt - 1) / nt;
-    while ((spw + 1) * p.npad <= kSmallMaxN && narrow_lds_bytes(p.n, p.nnz, nt, mode, dense, spw + 1) <= 160 * 1024 &&
-           (q + spw) / (spw + 1) * tiles >= 512)
-      ++spw;
-    if (narrow_lds_bytes(p.n, p.nnz, nt, mode, dense, spw) <= 160 * 1024) {
-      p.spw = spw;
-      const size_t lds = narrow_lds_bytes(p.n, p.nnz, nt, mode, dense, spw);
-      const dim3 grid((unsigned)((q + spw - 1) / spw), (unsigned)tiles);
-      hipStream_t st = (hipStream_t)stream;
-      const unsigned nthreads = (unsigned)(p.npad * spw);
-      ProfScope ps(TGCN_PROF_SMALL, st);
+  hipStream_t st = (hipStream_t)stream;
+  p.spw = pl.spw;
+  if (pl.form >= 3) {   // dense operand (e.g. the 148-parcel DTI graph) on the matrix pipe: fp32, or bf16 with the three-way split
+    ProfScope ps(TGCN_PROF_SMALL, st);
+    if (pl.form == 4) launch_small_dense_x3<false>(st, p, pl);
+    else launch_small_dense<false>(st, p, pl);
+    TGCN_CHECK_LAUNCH("tgcn_cheb_forward_small_f32 (dense)");
+    return TGCN_OK;
+  }
+  p.dense = pl.dense_lds;
+  p.npad = (p.n + 63) / 64 * 64;
+  const size_t lds = (size_t)pl.lds_bytes;
+  const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
+  const unsigned nthreads = (unsigned)pl.threads;
+  ProfScope ps(TGCN_PROF_SMALL, st);
+  if (pl.form == 1) {   // first layers: recursion on the 4-float input side, all of NT output channels per workgroup (small_narrow_kernel)
 #define TGCN_NARROW(NTV)                                                                     \
   {                                                                                          \
     allow_large_lds((const void*)small_narrow_kernel<NTV>, 160 * 1024);                      \
     hipLaunchKernelGGL((small_narrow_kernel<NTV>), grid, dim3(nthreads), lds, st, p);        \
   }
-      if (nt == 64) TGCN_NARROW(64) else if (nt == 32) TGCN_NARROW(32) else TGCN_NARROW(16)
+    if (pl.tile == 64) TGCN_NARROW(64) else if (pl.tile == 32) TGCN_NARROW(32) else TGCN_NARROW(16)
 #undef TGCN_NARROW
-      TGCN_CHECK_LAUNCH("tgcn_cheb_forward_small_f32 (narrow input)");
-      return TGCN_OK;
-    }
+    TGCN_CHECK_LAUNCH("tgcn_cheb_forward_small_f32 (narrow input)");
+    return TGCN_OK;
   }
-  // samples per workgroup: as many as fit the 1024-thread / 160 KB budget, but keep >= 512 workgroups in the grid
-  p.npad = (p.n + 63) / 64 * 64;
-  int spw = 1;
-  const int64_t col_tiles = (N + ntc - 1) / ntc;
-  while ((spw + 1) * p.npad <= kSmallMaxN && small_lds_bytes(p.n, p.nnz, C, ntc, mode, dense, spw + 1) <= 160 * 1024 &&
-         (q + spw) / (spw + 1) * col_tiles >= 512)
-    ++spw;
-  p.spw = spw;
-  const size_t lds = small_lds_bytes(p.n, p.nnz, C, ntc, mode, dense, spw);
-  const dim3 grid((unsigned)((q + spw - 1) / spw), (unsigned)col_tiles);
-  hipStream_t st = (hipStream_t)stream;
-  const unsigned nthreads = (unsigned)(p.npad * p.spw);
-  ProfScope ps(TGCN_PROF_SMALL, st);
 #define TGCN_SMALL(NTCV, CPV)                                                                                     \
   {                                                                                                               \
     allow_large_lds((const void*)small_forward_kernel<NTCV, CPV>, 160 * 1024);                                      \
     hipLaunchKernelGGL((small_forward_kernel<NTCV, CPV>), grid, dim3(nthreads), lds, st, p);                      \
   }
-  if (ntc == 16) { if (C <= 4) TGCN_SMALL(16, 4) else if (C <= 16) TGCN_SMALL(16, 16) else TGCN_SMALL(16, 32) }
-  else { if (C <= 4) TGCN_SMALL(8, 4) else if (C <= 16) TGCN_SMALL(8, 16) else TGCN_SMALL(8, 32) }
+  if (pl.tile == 16) { if (pl.cp == 4) TGCN_SMALL(16, 4) else if (pl.cp == 16) TGCN_SMALL(16, 16) else TGCN_SMALL(16, 32) }
+  else { if (pl.cp == 4) TGCN_SMALL(8, 4) else if (pl.cp == 16) TGCN_SMALL(8, 16) else TGCN_SMALL(8, 32) }
 #undef TGCN_SMALL
   TGCN_CHECK_LAUNCH("tgcn_cheb_forward_small_f32");
+  return TGCN_OK;
+}
+
+int tgcn_cheb_small_plan(int64_t n, int64_t nnz, int32_t has_dense_copy, int32_t mode, int32_t C, int32_t N, int64_t q, int32_t pool,
+                         int32_t basis, tgcn_small_plan* plan) {
+  if (!plan || q < 1) TGCN_FAIL(TGCN_ERR_INVALID, "small_plan: bad argument");
+  if (basis ? C < 1 : N < 1) TGCN_FAIL(TGCN_ERR_INVALID, "small_plan: bad argument");
+  if (!basis && (pool < 0 || pool > 255 || (pool > 0 && n % pool != 0))) TGCN_FAIL(TGCN_ERR_INVALID, "small_plan: pool=%d n=%lld", pool, (long long)n);
+  const char* why = "";
+  tgcn_small_plan pl;
+  if (const int rc = small_plan(n, nnz, has_dense_copy != 0, mode, C, N, q, pool, basis != 0, &pl, &why))
+    TGCN_FAIL(rc, "small_plan: n=%lld nnz=%lld C=%d N=%d q=%lld: %s", (long long)n, (long long)nnz, C, N, (long long)q, why);
+  *plan = pl;
   return TGCN_OK;
 }
 
@@ -857,48 +842,37 @@ int tgcn_cheb_basis_small_f32(void* stream, const tgcn_csr* A, int32_t mode, int
   if (!tgcn_cheb_basis_small_supported(A->n, A->nnz, C, mode))
     TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "basis_small: n=%lld nnz=%lld does not fit in LDS", (long long)A->n, (long long)A->nnz);
   if (K == 1) return TGCN_OK;
-  if (q > 2147483647LL || C > 16 * 65535) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "basis_small: grid too large");
   SmallParams p;
   memset(&p, 0, sizeof(p));
   p.rowptr = A->rowptr; p.ev = A->edges; p.x = x; p.out = stack;
   p.n = (int32_t)A->n; p.nnz = (int32_t)A->nnz; p.q = (int32_t)q; p.K = K; p.C = C; p.mode = mode;
   p.Ld = A->dense;
-  if (A->dense && g_small_dense.load()) {
-    const int64_t tiles16 = (C + 15) / 16;
-    const int S = dense_mfma_config(A->n, A->nnz, C, mode, q, tiles16, true);
-    if (S) {
-      hipStream_t st = (hipStream_t)stream;
-      ProfScope ps(TGCN_PROF_SMALL_BASIS, st);
-      const int S3 = g_small_dense.load() >= 2 ? dense_x3_config(A->n, A->nnz, C, mode, q, tiles16, true) : 0;
-      p.spw = S3 ? S3 : S;
-      if (S3) launch_small_dense_x3<true>(st, p, S3, tiles16);
-      else launch_small_dense<true>(st, p, S, tiles16);
-      TGCN_CHECK_LAUNCH("tgcn_cheb_basis_small_f32 (dense)");
-      return TGCN_OK;
-    }
+  tgcn_small_plan pl;     // small_plan (small_graph.h), also behind tgcn_cheb_small_plan
+  const char* why = "";
+  if (const int prc = small_plan(A->n, A->nnz, A->dense != nullptr, mode, C, 0, q, 0, true, &pl, &why)) {
+    if (why[0] == 'g') TGCN_FAIL(prc, "basis_small: grid too large");
+    TGCN_FAIL(prc, "basis_small: n=%lld nnz=%lld does not fit in LDS", (long long)A->n, (long long)A->nnz);
   }
-  int dense = 0;
-  const int ct = basis_config(A->n, A->nnz, C, mode, &dense);
-  if (!ct) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "basis_small: n=%lld nnz=%lld does not fit in LDS", (long long)A->n, (long long)A->nnz);
-  const int64_t col_tiles = (C + ct - 1) / ct;
-  p.dense = dense;
-  p.npad = (p.n + 63) / 64 * 64;
-  int spw = 1;
-  while ((spw + 1) * p.npad <= kSmallMaxN && basis_lds_bytes(p.n, p.nnz, ct, mode, dense, spw + 1) <= 160 * 1024 &&
-         (q + spw) / (spw + 1) * col_tiles >= 512)
-    ++spw;
-  p.spw = spw;
-  const size_t lds = basis_lds_bytes(p.n, p.nnz, ct, mode, dense, spw);
-  const dim3 grid((unsigned)((q + spw - 1) / spw), (unsigned)col_tiles);
   hipStream_t st = (hipStream_t)stream;
-  const unsigned nthreads = (unsigned)(p.npad * p.spw);
+  p.spw = pl.spw;
   ProfScope ps(TGCN_PROF_SMALL_BASIS, st);
+  if (pl.form >= 3) {
+    if (pl.form == 4) launch_small_dense_x3<true>(st, p, pl);
+    else launch_small_dense<true>(st, p, pl);
+    TGCN_CHECK_LAUNCH("tgcn_cheb_basis_small_f32 (dense)");
+    return TGCN_OK;
+  }
+  p.dense = pl.dense_lds;
+  p.npad = (p.n + 63) / 64 * 64;
+  const size_t lds = (size_t)pl.lds_bytes;
+  const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
+  const unsigned nthreads = (unsigned)pl.threads;
 #define TGCN_BASIS(CTV)                                                                    \
   {                                                                                        \
     allow_large_lds((const void*)small_basis_kernel<CTV>, 160 * 1024);                     \
     hipLaunchKernelGGL((small_basis_kernel<CTV>), grid, dim3(nthreads), lds, st, p);       \
   }
-  if (ct == 16) TGCN_BASIS(16) else if (ct == 8) TGCN_BASIS(8) else TGCN_BASIS(4)
+  if (pl.tile == 16) TGCN_BASIS(16) else if (pl.tile == 8) TGCN_BASIS(8) else TGCN_BASIS(4)
 #undef TGCN_BASIS
   TGCN_CHECK_LAUNCH("tgcn_cheb_basis_small_f32");
   return TGCN_OK;

@@ -1514,6 +1514,17 @@ def cheb_forward_small(op, x3, W_kcn, fold, bias, bias_kind, mode):
     return out
 
 
+def small_plan(op, C_row, N, q, mode, pool=0, basis=False):
+    """The kernel and launch configuration cheb_forward_small / the fused small-pool call (basis=False) or cheb_basis_small (basis=True) takes
+    for this operand, row length, width and batch (tgcn_cheb_small_plan: the function the launch entries get it from), as a dict: form
+    (0 output-side, 1 narrow input-side, 2 basis, 3 fp32 matrix pipe, 4 bf16x3 matrix pipe), tile, cp, spw, dense_lds, threads, lds_bytes,
+    grid_x, grid_y.  A host query: nothing launches; raises TgcnError where the launch entry would refuse."""
+    pl = _lib.SmallPlanStruct()
+    _lib.check(_lib.lib().tgcn_cheb_small_plan(op.n, op.nnz, 1 if op.dense is not None else 0, int(mode), int(C_row), int(N), int(q), int(pool),
+                                               1 if basis else 0, C.byref(pl)))
+    return {k: int(getattr(pl, k)) for k, _ in _lib.SmallPlanStruct._fields_}
+
+
 def small_basis_tile(op, C_row, mode):
     """Channel tile of the one-launch basis kernel (weight gradient on small graphs), or 0 when the operand does not fit."""
     if op.n_cols != op.n or not SMALL_PATH:
