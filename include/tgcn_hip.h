@@ -553,6 +553,35 @@ int tgcn_cheb_series_chunk_backward_f32(void* stream, int64_t S, int64_t n_verti
                                         int32_t g_t0, int32_t g_as_series, const float* W, float* G, float* dW, void* workspace,
                                         size_t workspace_bytes, int32_t dilation);
 
+/* Time chunks through the relu + dropout + pool epilogue ("Time chunks through the pooled epilogue"; fp32, step 1, the
+ * host's head): the chunked walk above with the pooled epilogue in the projection's place, so neither the hop stack nor the layer's output
+ * nor that output's gradient is ever held whole.
+ * tgcn_cheb_project_series_stream_pool_at_f32 is the step of tgcn_cheb_project_series_stream_pool_f32 (pos == NULL) writing its Tc pooled
+ * rows into rows [out_t0, out_t0 + Tc) of a whole z of out_T time rows, (S, n/pool, out_T, N) for out_as_series != 0 and
+ * (S*out_T, n/pool, N) otherwise; idx (nullable) receives the arg-max bytes in the same layout and rows.  seed == NULL: no dropout (thr
+ * and scale unused) -- that entry's kernels, ring update included, so on one stack and ring the rows and the ring afterwards are
+ * bit-identical to it.  seed non-null: t = relu(y) * mask in relu(y)'s place by the rules of the dropout entries above, the mask's element
+ * index taken at the ABSOLUTE window, e = ((s * out_T + out_t0 + w) * n + v) * N + c -- what tgcn_relu_dropout_pool_f32 gives on the
+ * _stream_at entry's rows inside a whole output of out_T rows, bit for bit, whatever the chunking.  H == 1 is admitted: no ring (NULL,
+ * ring_ld and head unused), the pooled forms of a whole series on the chunk, nothing to update.  The caller sets head = (head + Tc) mod C.
+ * TGCN_ERR_INVALID before any launch: pool outside {2, 4}, n_vertices % pool != 0, a seed with a scale that is not finite or below 1,
+ * out_T < 1, out_t0 < 0, out_t0 + Tc > out_T, a null stack, W, z (or ring for H > 1), and everything the _stream_at entry refuses;
+ * TGCN_ERR_UNSUPPORTED where tgcn_series_pool_plan(H, f, N, vec, 1, pool) or a grid limit refuses.
+ * tgcn_relu_pool_bwd_rows_f32: tgcn_relu_pool_bwd_f32's routing for the time rows [t0, t0 + rows) of whole pooled tensors grad_z, z, idx
+ * of out_T time rows -- (S, n/pool, out_T, N) for as_series != 0 and (S*out_T, n/pool, N) otherwise -- into the dense slab grad_y of those
+ * rows alone, (S, n, rows, N) or (S*rows, n, N), every element written:
+ *   grad_y[s, v, r, c] = (z > 0 && idx == v % pool) ? grad_z * scale : 0      at (s, v / pool, t0 + r, c),
+ * grad_z * scale one fp32 multiply (the dropout's 1 / (1 - p), or 1).  The slab is what tgcn_cheb_series_chunk_backward_f32 reads with
+ * g_T = rows and g_t0 = 0.  Grid-stride with 64-bit offsets.  TGCN_ERR_INVALID: a null pointer, S, n, N < 1, pool outside [1, 255],
+ * n % pool != 0, out_T < 1, t0 < 0, rows < 1, t0 + rows > out_T, a scale that is not finite.
+ * Nothing is launched on any error; the entries do not synchronise and do not allocate. */
+int tgcn_cheb_project_series_stream_pool_at_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                const float* stack, const float* W, const float* bias, int32_t bias_kind, float* z, uint8_t* idx,
+                                                int32_t pool, int32_t out_T, int32_t out_t0, int32_t out_as_series, float* ring, int64_t ring_ld,
+                                                int32_t head, int32_t dilation, const int64_t* seed, uint32_t thr, float scale);
+int tgcn_relu_pool_bwd_rows_f32(void* stream, const float* grad_z, const float* z, const uint8_t* idx, float* grad_y, int64_t S, int64_t n,
+                                int32_t out_T, int32_t t0, int32_t rows, int32_t N, int32_t pool, int32_t as_series, float scale);
+
 /* A window step on the streaming state ("Window step"): the stream entries' chunk, ring and position at dilation 1, with
  * only every stride-th window projected.  pos == NULL: head is the host's (0 <= head < C); pos non-null: the _pos entries' device position
  * {head, seen} and defensive read (the head argument is unused).  win_off (0 <= win_off < stride) is the chunk row at which the chunk's

@@ -202,6 +202,11 @@ SIGNATURES = {
     "tgcn_cheb_project_series_pool_dropout_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
                                                             _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                             _P, C.c_uint32, C.c_float]),
+    "tgcn_cheb_project_series_stream_pool_at_f32": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P,
+                                                              _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64,
+                                                              C.c_int32, C.c_int32, _P, C.c_uint32, C.c_float]),
+    "tgcn_relu_pool_bwd_rows_f32": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                              C.c_int32, C.c_float]),
     "tgcn_relu_dropout_pool_f32": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _P, C.c_uint32, C.c_float]),
     "tgcn_dropout_keep_u8": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_uint32, _P]),
     "tgcn_cheb_stream_small_plan": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -63,6 +63,27 @@ __global__ __launch_bounds__(kBlock) void relu_pool_bwd_kernel(const float* __re
   }
 }
 
+// the same routing for time rows [t0, t0 + rows) of whole pooled tensors -- (S, n/p, T, N) as a series, else (S*T, n/p, N) -- into a dense slab
+// of those rows only, (S, n, rows, N) or (S*rows, n, N): one thread per element of the slab, so every element is written,
+//   gy[s, v, r, c] = (z > 0 && idx == v % p) ? gz * scale : 0      at (s, v / p, t0 + r, c)
+// with gz * scale one fp32 multiply (the dropout's 1 / (1 - p); 1 without).  64-bit offsets throughout.
+__global__ __launch_bounds__(kBlock) void relu_pool_bwd_rows_kernel(const float* __restrict__ gz, const float* __restrict__ z,
+                                                                    const uint8_t* __restrict__ idx, float* __restrict__ gy, int64_t total,
+                                                                    int64_t n, int64_t T, int64_t t0, int64_t rows, int N, int p, bool as_series,
+                                                                    float scale) {
+  const int64_t nout = n / p;
+  for (int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x; o < total; o += (int64_t)gridDim.x * kBlock) {
+    const int64_t row = o / N;            // (s, v, r) as a series, else (s, r, v)
+    const int c = (int)(o - row * N);
+    int64_t s, v, r;
+    if (as_series) { const int64_t sv = row / rows; r = row - sv * rows; s = sv / n; v = sv - s * n; }
+    else { const int64_t sr = row / n; v = row - sr * n; s = sr / rows; r = sr - s * rows; }
+    const int64_t vo = v / p;
+    const int64_t src = (as_series ? (s * nout + vo) * T + t0 + r : (s * T + t0 + r) * nout + vo) * N + c;
+    gy[o] = (z[src] > 0.f && (int64_t)idx[src] == v - vo * p) ? gz[src] * scale : 0.f;
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void pool_max_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                           int32_t* __restrict__ idx, int64_t total, int f, int p) {
   for (int64_t o = (int64_t)blockIdx.x * kBlock + threadIdx.x; o < total; o += (int64_t)gridDim.x * kBlock) {

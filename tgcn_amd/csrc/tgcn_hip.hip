@@ -1246,6 +1246,20 @@ int tgcn_relu_pool_bwd_f32(void* stream, const float* grad_z, const float* z, co
   return TGCN_OK;
 }
 
+// tgcn_relu_pool_bwd_f32's routing for time rows [t0, t0 + rows) of whole pooled tensors into a dense slab (pool_relayout.h)
+int tgcn_relu_pool_bwd_rows_f32(void* stream, const float* grad_z, const float* z, const uint8_t* idx, float* grad_y, int64_t S, int64_t n,
+                                int32_t out_T, int32_t t0, int32_t rows, int32_t N, int32_t pool, int32_t as_series, float scale) {
+  if (!grad_z || !z || !idx || !grad_y || S <= 0 || n <= 0 || N <= 0 || pool <= 0 || pool > 255 || n % pool != 0 || out_T < 1 || t0 < 0 || rows < 1 ||
+      (int64_t)t0 + rows > (int64_t)out_T || !isfinite(scale))
+    TGCN_FAIL(TGCN_ERR_INVALID, "relu_pool_bwd_rows: bad argument");
+  if (S > INT64_MAX / n || S * n > INT64_MAX / out_T || S * n * out_T > INT64_MAX / N) TGCN_FAIL(TGCN_ERR_INVALID, "relu_pool_bwd_rows: bad argument");
+  const int64_t total = S * n * rows * N;
+  hipLaunchKernelGGL(relu_pool_bwd_rows_kernel, dim3(grid_1d(total)), dim3(kBlock), 0, (hipStream_t)stream, grad_z, z, idx, grad_y, total, n, (int64_t)out_T,
+                     (int64_t)t0, (int64_t)rows, (int)N, (int)pool, as_series != 0, scale);
+  TGCN_CHECK_LAUNCH("tgcn_relu_pool_bwd_rows_f32");
+  return TGCN_OK;
+}
+
 // Workspace of the project-first path: Z (q*n x K*N) + 3 result buffers (q*n x N) + hop scratch.
 static void pf_ws_layout(const tgcn_csr_sched* S, int32_t K, int64_t q, int64_t n, int32_t N, size_t* z_bytes, size_t* y_bytes,
                          size_t* off_part, size_t* total) {
@@ -1458,12 +1472,14 @@ static int series_launch_plan(SeriesLdsFn lds_of, int64_t S, int64_t n, int32_t 
 // pool (2 / 4; 0: none): the POOLED instantiations of the same form -- one workgroup per (recording, vertex quad, window block), the
 // scratch's bytes where they exceed the GEMM's; not built with a window step on a chunk
 // drop (with pool, on a whole series): series_gemm_pool_dropout_kernel in the pooled form's place, on the same plan -- the dropout adds no LDS
+// at (with drop, at step 1; a chunk's place in the whole series): series_gemm_chunk_pool_dropout_kernel, behind the ring (carry) or without one
 static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1, int dil = 1,
-                              bool carry = false, int pool = 0, const DropoutParams* drop = nullptr) {
+                              bool carry = false, int pool = 0, const DropoutParams* drop = nullptr, const SeriesDropAt* at = nullptr) {
   SeriesLaunchPlan lp;
   if (int rc = series_launch_plan(series_gemm_lds, S, p.n, p.nwin, p.H, p.f, p.N, vec, stride, dil, pool, who, &lp)) return rc;
   if (pool && carry && stride > 1) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a pooled window step on a chunk is not built", who);
-  if (drop && (!pool || carry)) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: dropout is built into the pooled epilogue of a whole series", who);
+  if (drop && (!pool || (carry && !at))) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: dropout is built into the pooled epilogue of a whole series", who);
+  if (at && (!drop || stride > 1)) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a chunk's mask is built at step 1 with dropout", who);
   p.tpv = lp.tpv; p.dil = dil; p.ntiles = lp.ntiles; p.pool = pool;
   if (dil > 1) p.tpp = lp.tpp;
   if (pool) p.nq = lp.nq;
@@ -1489,7 +1505,21 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
 #define TGCN_SERIES_DROP_NT(VEC_, STR_, DIL_)                                                                             \
   do { if (NT == 1) TGCN_SERIES_DROP(1, VEC_, STR_, DIL_); else if (NT == 2) TGCN_SERIES_DROP(2, VEC_, STR_, DIL_);       \
        else TGCN_SERIES_DROP(4, VEC_, STR_, DIL_); } while (0)
-  if (drop) {
+#define TGCN_SERIES_DROP_AT(NT_, VEC_, DIL_, CARRY_)                                                                       \
+  do {                                                                                                                    \
+    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_chunk_pool_dropout_kernel<NT_, VEC_, DIL_, CARRY_>, lds); \
+    for (p.blk0 = 0; p.blk0 < lp.gx; p.blk0 += kSeriesGridPart)                                                           \
+      hipLaunchKernelGGL((series_gemm_chunk_pool_dropout_kernel<NT_, VEC_, DIL_, CARRY_>), series_grid_part(lp, p.blk0), dim3(kBlock), lds, st, p, \
+                         *drop, *at);                                                                                     \
+  } while (0)
+#define TGCN_SERIES_DROP_AT_NT(VEC_, DIL_, CARRY_)                                                                        \
+  do { if (NT == 1) TGCN_SERIES_DROP_AT(1, VEC_, DIL_, CARRY_); else if (NT == 2) TGCN_SERIES_DROP_AT(2, VEC_, DIL_, CARRY_); \
+       else TGCN_SERIES_DROP_AT(4, VEC_, DIL_, CARRY_); } while (0)
+  if (at) {
+    if (!carry) { if (vec) TGCN_SERIES_DROP_AT_NT(true, false, false); else TGCN_SERIES_DROP_AT_NT(false, false, false); }      // one tap: dil == 1
+    else if (dil > 1) { if (vec) TGCN_SERIES_DROP_AT_NT(true, true, true); else TGCN_SERIES_DROP_AT_NT(false, true, true); }
+    else { if (vec) TGCN_SERIES_DROP_AT_NT(true, false, true); else TGCN_SERIES_DROP_AT_NT(false, false, true); }
+  } else if (drop) {
     if (dil > 1) { if (vec) TGCN_SERIES_DROP_NT(true, false, true); else TGCN_SERIES_DROP_NT(false, false, true); }
     else if (stride == 1) { if (vec) TGCN_SERIES_DROP_NT(true, false, false); else TGCN_SERIES_DROP_NT(false, false, false); }
     else { if (vec) TGCN_SERIES_DROP_NT(true, true, false); else TGCN_SERIES_DROP_NT(false, true, false); }
@@ -1507,6 +1537,8 @@ static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bo
   } else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true); else TGCN_SERIES_GEMM_NT(false, false, true); }
   else if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, false); else TGCN_SERIES_GEMM_NT(false, false, false); }
   else { if (vec) TGCN_SERIES_GEMM_NT(true, true, false); else TGCN_SERIES_GEMM_NT(false, true, false); }
+#undef TGCN_SERIES_DROP_AT_NT
+#undef TGCN_SERIES_DROP_AT
 #undef TGCN_SERIES_DROP_NT
 #undef TGCN_SERIES_DROP
 #undef TGCN_SERIES_GEMM_NT
@@ -1564,8 +1596,8 @@ struct SeriesF32 {
   static constexpr const char* kSuffix = "_f32";     // "tgcn_cheb_" + who + kSuffix is the entry's name
   static constexpr SeriesLdsFn lds = series_gemm_lds;
   static int launch(hipStream_t st, Params& p, int64_t S, bool vec, bool, const char* who, int stride, int dil, bool carry, int pool,
-                    const DropoutParams* drop = nullptr) {
-    return series_gemm_launch(st, p, S, vec, who, stride, dil, carry, pool, drop);
+                    const DropoutParams* drop = nullptr, const SeriesDropAt* at = nullptr) {
+    return series_gemm_launch(st, p, S, vec, who, stride, dil, carry, pool, drop, at);
   }
   static void set_bias(Params& p, const void* bias, int32_t kind, int32_t) { p.bias = (const float*)bias; p.bias_kind = kind; }
   static void flip(hipStream_t st, const float* W, float* Wd, int K, int H, int f, int N, int stride) {
@@ -1594,7 +1626,7 @@ struct SeriesBf16 {
   static constexpr const char* kSuffix = "";         // who ends in _bf16
   static constexpr SeriesLdsFn lds = series_gemm_bf16_lds;
   static int launch(hipStream_t st, Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride, int dil, bool carry, int,
-                    const DropoutParams* = nullptr) {      // no bf16 dropout
+                    const DropoutParams* = nullptr, const SeriesDropAt* = nullptr) {      // no bf16 dropout
     return series_gemm_bf16_launch(st, p, S, vec, out_f32, who, stride, dil, carry);
   }
   static void set_bias(Params& p, const void* bias, int32_t kind, int32_t dtype) { p.bias = bias; p.bias_kind = kind; p.bias_bf16 = dtype == TGCN_DTYPE_BF16; }
@@ -1870,6 +1902,8 @@ struct SeriesChunkAsk {
   bool one_tap = false;          // H == 1 admitted: no ring (null allowed), nothing to update
   bool stepped = false;          // the _stream_strided entries (DESIGN.md 3.10 "Window step"): windows end at chunk rows win_off + r * stride;
   int32_t stride = 1, win_off = 0;     // a chunk may end no window (out null allowed), and the position advances all the same
+  uint8_t* idx = nullptr;        // the _stream_pool_at entry: sliced and pooled -- arg-max bytes in z's layout (null: not stored) and the
+  const DropoutParams* drop = nullptr;       // optional mask, counted at window out_t0 + w of out_T (series_gemm_chunk_pool_dropout_kernel)
 };
 
 // ---- driver 2, a chunk of Tc time rows behind the ring of the C rows before it: the _stream, _pos, _stream_pool, _at and _stream_strided
@@ -1908,11 +1942,14 @@ static int series_chunk_forward(const char* who, void* stream, int64_t S, int64_
     series_src_stack(p, (const E*)stack, S, n, stack_ld, f);
     p.W = (const E*)W;
     X::set_bias(p, bias, bias_kind, bias_dtype);
-    if (ask.sliced) series_out(p, (E*)out, n, ask.out_T, N, ask.out_as_series, ask.out_t0);
+    if (ask.sliced) series_out(p, (E*)out, ask.pool ? n / ask.pool : n, ask.out_T, N, ask.out_as_series, ask.out_t0);
     else series_out(p, (E*)out, ask.pool ? n / ask.pool : n, m, N, 1);      // (S, n, m, N); pooled: n / pool
     if (carry) series_ring(p, (const E*)ring, S, n, ring_ld, C, head, pos, win_off);
     else { p.src += (int64_t)win_off * f; p.Tin = Tc - win_off; }           // one tap reads no row before the chunk
-    if (int rc = X::launch(st, p, S, vec, false, who, sc, dil, carry, ask.pool)) return rc;
+    const SeriesDropAt at{ask.out_t0, ask.out_T};
+    if constexpr (std::is_same<E, float>::value)
+      if (ask.idx) p.idx = ask.idx + (int64_t)ask.out_t0 * p.o_ws;          // the same rows of the same layout
+    if (int rc = X::launch(st, p, S, vec, false, who, sc, dil, carry, ask.pool, ask.drop, ask.drop ? &at : nullptr)) return rc;
   }
   if (carry) series_ring_update_launch(st, stack, ring, K * S * n, stack_ld, ring_ld, f, (int)sizeof(E), vec, Tc, C, head, pos);
   if (pos) series_stream_advance_launch(st, pos, Tc, C);
@@ -1954,6 +1991,24 @@ int tgcn_cheb_project_series_stream_pool_f32(void* stream, int64_t S, int64_t n_
   ask.dil = dilation; ask.pool = pool;
   return series_chunk_forward<SeriesF32>(who, stream, S, n_vertices, Tc, f, H, N, K, stack, (int64_t)Tc * f, W, bias, TGCN_DTYPE_F32, bias_kind, z, ring,
                                          ring_ld, head, pos, ask);
+}
+
+// The _stream_pool entry's step (host head) into rows [out_t0, out_t0 + Tc) of a whole z of out_T time rows, in either layout, with the
+// arg-max bytes and an optional mask ("Time chunks through the pooled epilogue").  seed null: the _stream_pool entry's own
+// kernels, only the output's strides differ; else the chunk form of the dropout epilogue.  H == 1: no ring, the non-carry pooled forms.
+int tgcn_cheb_project_series_stream_pool_at_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,
+                                                const float* stack, const float* W, const float* bias, int32_t bias_kind, float* z, uint8_t* idx,
+                                                int32_t pool, int32_t out_T, int32_t out_t0, int32_t out_as_series, float* ring, int64_t ring_ld,
+                                                int32_t head, int32_t dilation, const int64_t* seed, uint32_t thr, float scale) {
+  const char* who = "project_series_stream_pool_at";
+  if (!series_pool_ok(n_vertices, pool)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: pool %d of %lld vertices", who, pool, (long long)n_vertices);
+  if (seed && !dropout_scale_ok(scale)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: a scale that is not finite and >= 1", who);
+  const DropoutParams drop{seed, thr, scale};
+  SeriesChunkAsk ask;
+  ask.dil = dilation; ask.pool = pool; ask.one_tap = true; ask.sliced = true; ask.out_T = out_T; ask.out_t0 = out_t0; ask.out_as_series = out_as_series;
+  ask.idx = idx; ask.drop = seed ? &drop : nullptr;
+  return series_chunk_forward<SeriesF32>(who, stream, S, n_vertices, Tc, f, H, N, K, stack, (int64_t)Tc * f, W, bias, TGCN_DTYPE_F32, bias_kind, z, ring,
+                                         ring_ld, head, nullptr, ask);
 }
 
 int tgcn_cheb_project_series_stream_at_f32(void* stream, int64_t S, int64_t n_vertices, int32_t Tc, int32_t f, int32_t H, int32_t N, int32_t K,

@@ -127,6 +127,21 @@ __global__ __launch_bounds__(kBlock) void series_gemm_pool_dropout_kernel(const 
 #include "windows_gemm_body.inc"
 #undef TGCN_SERIES_GEMM_DROP
 }
+// DROP on a CHUNK (series_gemm_chunk_pool_dropout_kernel: POOLED with the mask on one chunk of a longer series, behind the ring -- CARRY -- or,
+// for a one-tap layer, without one; at step 1, DILATED or not): the chunk's window w is window at.w0 + w of the at.nwin windows of the whole
+// series, and that is the window the mask counts: e = ((s * at.nwin + at.w0 + w) * n + iv) * N + col.  Nothing else differs from DROP, and
+// only this template reads `at`, so every other instantiation keeps its parameters and its code.  e & 3 == col & 3 needs N % 4 == 0 only
+// (the window term is a multiple of N), so the quad exchange holds whatever the base.
+struct SeriesDropAt {
+  int64_t w0, nwin;       // the chunk's first window in the whole series, and the whole series' windows
+};
+template <int NT, bool VEC, bool DILATED, bool CARRY>
+__global__ __launch_bounds__(kBlock) void series_gemm_chunk_pool_dropout_kernel(const SeriesGemmParams p, const DropoutParams dp, const SeriesDropAt at) {
+  constexpr bool STRIDED = false, POOLED = true;
+#define TGCN_SERIES_GEMM_DROP 2
+#include "windows_gemm_body.inc"
+#undef TGCN_SERIES_GEMM_DROP
+}
 
 // Ring update of the CARRY form, after the projection: the m = min(Tc, C) newest time rows j0 .. j0 + m - 1 (j0 = Tc - m) of every (term,
 // recording, vertex) row of the chunk's stack go to the slots (head + j) mod C of the ring's row; the host then moves head by Tc (mod C).

@@ -1,5 +1,5 @@
-// windows_gemm_body.inc -- the body of series_gemm_kernel and of series_gemm_pool_dropout_kernel (windows.h), included once in each with
-// TGCN_SERIES_GEMM_DROP 0 / 1.  Textual on purpose: behind a shared __forceinline__ function the instantiations without dropout came out
+// windows_gemm_body.inc -- the body of series_gemm_kernel, of series_gemm_pool_dropout_kernel and of series_gemm_chunk_pool_dropout_kernel
+// (windows.h), included once in each with TGCN_SERIES_GEMM_DROP 0 / 1 / 2 (2: 1 with the mask's window taken from `at`).  Textual on purpose: behind a shared __forceinline__ function the instantiations without dropout came out
 // with other register counts and schedules than before (DESIGN.md 3.10, "dropout in the relu + pool epilogue"); included with 0, the
 // compiler sees the tokens the kernel always had.  Names from the including kernel: NT, VEC, STRIDED, DILATED, CARRY, POOLED, p, and -- with
 // TGCN_SERIES_GEMM_DROP -- dp.
@@ -187,7 +187,11 @@
           for (int i = 0; i < 4; ++i) {
             const int wl = rt * 16 + kq * 4 + i;
             const int64_t w = DILATED ? ph + (int64_t)(w0 + wl) * p.dil : w0 + wl;
+#if TGCN_SERIES_GEMM_DROP == 2  // a chunk: the window's place in the whole series (windows.h, DROP on a CHUNK)
+            e[i] = (uint64_t)(((s * at.nwin + at.w0 + w) * p.n + iv) * p.N + col);
+#else
             e[i] = (uint64_t)(((s * p.nwin + w) * p.n + iv) * p.N + col);
+#endif
           }
           bool keep[4];
           if (quad) {

@@ -660,7 +660,8 @@ def cheb_time_windows_relu_pool(op, series, weight, bias, bias_kind, mode, pool,
     Dropout between relu and pool, as the reference's training script has it, is cheb_time_windows_relu_dropout_pool (below): the same
     epilogue with a counter-based mask, so the full output stays unallocated in training too.
     TgcnError before anything is built or launched: bfloat16 parameters, pool outside {2, 4}, n % pool != 0, and every refusal
-    cheb_time_windows makes for the same arguments.  There is no time_chunk."""
+    cheb_time_windows makes for the same arguments.  There is no time_chunk: the causal layer in time chunks through this epilogue is
+    cheb_time_windows_relu_pool_chunked."""
     who = "cheb_time_windows_relu_pool"
     if param_dtype(weight, bias, who) == BF16:
         raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
@@ -942,6 +943,159 @@ class ChebSeriesChunkFn(torch.autograd.Function):
         if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
             gb = _series_bias_grad(g, ctx.as_series, ctx.bias_kind, ctx.bias_shape)
         return gx, dW, gb, None, None, None, None, None, None
+
+
+class ChebSeriesChunkReluPoolFn(torch.autograd.Function):
+    """ChebSeriesChunkFn's walk with relu, dropout and the vertex max-pool in the projection's epilogue (DESIGN.md 3.10 "Time chunks through
+    the pooled epilogue"): z = max over `pool` consecutive vertices of relu(y) * mask of the causal layer at step 1, time_chunk rows at a time
+    in both directions.  Neither the hop stack (K, S, n, T*f) nor the layer's output (S, n, T, N) nor that output's gradient is ever
+    allocated: the step holds z, idx and chunk-sized buffers.
+    forward: tgcn_series_pool_plan once, a zero ring, then per chunk the K - 1 hops and tgcn_cheb_project_series_stream_pool_at_f32, which
+    writes the chunk's pooled rows (and arg-max bytes, need_idx) into rows [t0, t0 + Tc) of the whole z and updates the ring.  seed_t None:
+    no mask.  The mask's element index is taken at the absolute window, so the chunking does not change which elements drop.
+    backward, per chunk in forward time order, C = (H-1)*dilation: ONE slab of rows = min(Tc + C, T - t0) time rows of the output gradient
+    (tgcn_relu_pool_bwd_rows_f32: gz * scale to the arg-max vertex where z > 0), the hops again if the weight trains, one
+    tgcn_cheb_series_chunk_backward_f32 call on the slab (g_T = rows, g_t0 = 0: the same launch over the same rows as ChebSeriesChunkFn's on
+    the whole gradient), the ring's advance, the adjoint hops into d series[:, :, t0:t0 + Tc].  dW is summed in chunk order and un-folded
+    once.  The bias gradient is summed per chunk from slab rows [0, Tc) only -- the C halo rows are the next chunk's first rows and are
+    counted there.  The one-sided forms skip what ChebSeriesChunkFn's skip.  Saves the series (only if the weight trains), the working
+    weight, z and idx."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, dil, time_chunk, pool, need_idx, seed_t, thr, scale):
+        L = _lib.lib()
+        S, n, T, f = series.shape
+        K, H, _, N = weight_khfg.shape
+        hc, lds = C.c_int32(0), C.c_int32(0)
+        _lib.check(L.tgcn_series_pool_plan(H, f, N, int(f % 4 == 0), 1, pool, C.byref(hc), C.byref(lds)))
+        x = series.float().contiguous()
+        W = weight_khfg.float().contiguous().view(K, H * f, N)
+        fold = _power_fold(mode, W)
+        Wt = _working_weight(fold, W)
+        state = SeriesStreamState(op, torch.float32, S, n, f, K, H, dil, x.device)
+        shape = (S, n // pool, T, N) if as_series else (S * T, n // pool, N)
+        z = torch.empty(shape, dtype=torch.float32, device=x.device)
+        idx = torch.empty(shape, dtype=torch.uint8, device=x.device) if need_idx else None
+        b = bias.contiguous() if bias is not None else None
+        for t0 in range(0, T, time_chunk):
+            tc = min(time_chunk, T - t0)
+            stack = _chunk_stack(op, x, t0, tc, K, mode)
+            _lib.check(L.tgcn_cheb_project_series_stream_pool_at_f32(_lib.stream_ptr(), S, n, tc, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b),
+                                                                     bias_kind, _lib.ptr(z), _lib.ptr(idx), pool, T, t0, 1 if as_series else 0,
+                                                                     _lib.ptr(state.ring), state.ring_ld, state.head, dil, _lib.ptr(seed_t), thr, scale))
+            state.advance(tc)
+            stack = None        # released before the next chunk's is allocated: one chunk tensor at a time
+        ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, Wt, z, idx)
+        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.pool = op, mode, fold, bias_kind, as_series, pool
+        ctx.dims = (S, n, T, f, H, N, K, dil, time_chunk)
+        ctx.scale, ctx.seed = scale, seed_t
+        ctx.bias_shape = None if bias is None else bias.shape
+        return z
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, gz):
+        x, Wt, z, idx = ctx.saved_tensors
+        S, n, T, f, H, N, K, dil, time_chunk = ctx.dims
+        if idx is None:
+            raise _lib.TgcnError("cheb_time_windows_relu_pool_chunked: the forward ran without grad mode and kept no arg-max")
+        L = _lib.lib()
+        gz = gz.float().contiguous()
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
+        Cr = (H - 1) * dil
+        gx = dW = gb = None
+        opT = ctx.op.transpose() if need_x else None
+        state = SeriesStreamState(ctx.op, torch.float32, S, n, f, K, H, dil, gz.device) if need_w else None
+        if need_x:
+            gx = torch.empty((S, n, T, f), dtype=torch.float32, device=gz.device)
+        for t0 in range(0, T, time_chunk):
+            tc = min(time_chunk, T - t0)
+            rows = min(tc + Cr, T - t0)
+            slab = torch.empty((S, n, rows, N) if ctx.as_series else (S * rows, n, N), dtype=torch.float32, device=gz.device)
+            _lib.check(L.tgcn_relu_pool_bwd_rows_f32(_lib.stream_ptr(), _lib.ptr(gz), _lib.ptr(z), _lib.ptr(idx), _lib.ptr(slab), S, n, T, t0, rows, N,
+                                                     ctx.pool, 1 if ctx.as_series else 0, ctx.scale))
+            if need_x or need_w:
+                stack = _chunk_stack(ctx.op, x, t0, tc, K, ctx.mode) if need_w else None
+                G = torch.empty((K, S, n, tc * f), dtype=torch.float32, device=gz.device) if need_x else None
+                dWc = torch.empty((K, H * f, N), dtype=torch.float32, device=gz.device) if need_w else None
+                ws = _workspace(L.tgcn_cheb_series_chunk_backward_workspace_bytes(S, n, tc, f, H, N, K, dil), gz.device, floor=16)
+                _lib.check(L.tgcn_cheb_series_chunk_backward_f32(_lib.stream_ptr(), S, n, tc, f, H, N, K, _lib.ptr(stack),
+                                                                 _lib.ptr(state.ring) if need_w else None, state.ring_ld if need_w else 0,
+                                                                 state.head if need_w else 0, _lib.ptr(slab), rows, 0, 1 if ctx.as_series else 0,
+                                                                 _lib.ptr(Wt) if need_x else None, _lib.ptr(G), _lib.ptr(dWc), _lib.ptr(ws),
+                                                                 ws.numel(), dil))
+                if need_w:
+                    state.advance(tc)
+                    dW = dWc if dW is None else dW.add_(dWc)        # fp32, in chunk order
+                if need_x:
+                    gx[:, :, t0:t0 + tc] = _adjoint_hops(opT, G, ctx.mode).view(S, n, tc, f)
+                stack = G = None
+            if need_b:      # rows [0, tc) only: the halo rows are the next chunk's own
+                own = slab[:, :, :tc] if ctx.as_series else slab.view(S, rows, n, N)[:, :tc]
+                if ctx.bias_kind == BIAS_CHANNEL:
+                    part = own.sum(dim=(0, 1, 2))
+                else:
+                    part = own.sum(dim=(0, 2)) if ctx.as_series else own.sum(dim=(0, 1))
+                gb = part if gb is None else gb.add_(part)
+            slab = own = ws = None      # released before the next chunk's are allocated: one slab at a time (own is a view of it)
+        if need_w:
+            if ctx.fold is not None:
+                dW = fold_weight(ctx.fold, dW, transpose=True)      # the sum un-folded once
+            dW = dW.view(K, H, f, N)
+        if gb is not None:
+            gb = gb.reshape(ctx.bias_shape)
+        return (gx, dW, gb) + (None,) * 11
+
+
+@_on_device
+def cheb_time_windows_relu_pool_chunked(op, series, weight, bias, bias_kind, mode, pool, time_chunk, p=0.0, seed=None, as_series=False, dilation=1):
+    """gcn_pool_4(dropout(relu(cheb_time_windows(..., padding="causal", dilation=dilation, time_chunk=time_chunk)), p)) with relu, the dropout
+    and the max over `pool` consecutive vertices in the projection's epilogue AND the walk in time chunks (ChebSeriesChunkReluPoolFn): the
+    two memory features of the streaming layers in one call.  series (S, n, T) with weight (K, H, N), or (S, n, T, f) with (K, H, f, N)
+    -> z (S*T, n/pool, N) or, as_series=True, (S, n/pool, T, N).  The geometry is always the causal layer at step 1 -- what the streaming
+    ring implements -- so there is no stride and no padding.  Nothing of the size of the hop stack, of the layer's output or of that
+    output's gradient is allocated in either direction; the price is time_chunk's own (a second hop pass when the weight trains, and
+    (H-1)*dilation re-routed gradient rows per chunk).
+    p == 0: relu + pool without a mask.  Otherwise the mask, its seed and its element index are cheb_time_windows_relu_dropout_pool's with
+    nwin = T, e = ((s*T + t)*n + v)*N + c in the caller's vertex labels: dropout_keep_mask reproduces it, and the chunk length does not
+    change which elements drop.  z, d series and dW are bit-identical to the composition at the same time_chunk; d bias is summed chunk by
+    chunk and agrees to rounding.
+    A reordered operand (series_pool_is_fused(op) False) runs cheb_time_windows(time_chunk=...), relabels back, then the relu (+ dropout) +
+    pool pass: the same values and the same mask, but the layer's output is allocated -- the memory saving is absent there.
+    TgcnError before an operand is built: bfloat16 parameters, a bad pool, p, seed or time_chunk, n % pool != 0."""
+    who = "cheb_time_windows_relu_pool_chunked"
+    thr, scale = dropout_params(p, who)
+    dropout_seed(seed, series.device, who, draw=False)
+    bf16 = param_dtype(weight, bias, who) == BF16
+    if bf16:
+        raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
+    if time_chunk is None:
+        raise _lib.TgcnError("%s: time_chunk is None or an integer >= 1, got None -- without chunks this is cheb_time_windows_relu_pool / "
+                             "cheb_time_windows_relu_dropout_pool" % who)
+    time_chunk = check_time_chunk(time_chunk, 1, "causal", bf16, who)
+    if series.dim() not in (3, 4) or weight.dim() != series.dim():
+        raise _lib.TgcnError("%s: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
+                             "(got %s and %s)" % (who, tuple(series.shape), tuple(weight.shape)))
+    f = series.shape[3] if series.dim() == 4 else 1
+    if series.dim() == 4 and weight.shape[2] != f:
+        raise _lib.TgcnError("%s: the series has %d channels, the weight %d" % (who, f, weight.shape[2]))
+    pool = check_pool(pool, series.shape[1], who)
+    series_geometry(series.shape[2], weight.shape[1], 1, "causal", who, dilation)
+    dil = series_dilation(weight.shape[1], dilation)
+    _lib.require_device(series, weight, bias)
+    if series.dim() == 3:
+        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
+    seed_t = dropout_seed(seed, series.device, who) if p != 0 else None
+    if not series_pool_is_fused(op, pool):
+        s2, b2 = _to_operand_labels(op, series, bias, bias_kind)
+        y = ChebSeriesChunkFn.apply(s2, weight, b2, op, mode, bias_kind, bool(as_series), dil, time_chunk)
+        y = y if op.perm is None else relabel_rows(y, op.inv_perm, op.perm)
+        return _relu_pool_view(y, pool) if seed_t is None else _relu_dropout_pool_view(y, pool, seed_t, thr, scale)
+    need_idx = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (series, weight, bias))
+    return ChebSeriesChunkReluPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), dil, time_chunk, pool, need_idx, seed_t,
+                                           thr if seed_t is not None else 0, scale if seed_t is not None else 1.0)
 
 
 # fused="auto" fuses the shape classes listed here.  A call's class is what its UNFUSED form would be: "windows_f1" -- a single channel,

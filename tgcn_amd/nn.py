@@ -679,7 +679,8 @@ def cheb_series_relu_pool(layer, series, *graph_args, pool=4, as_series=False, s
     the unfused calls.  Dropout between relu and pool, as in the reference's training script, is cheb_series_relu_dropout_pool: the same
     epilogue with a counter-based mask (cheb_relu_dropout_pool for the batch layers).
     TgcnError before an operand is built: bfloat16 parameters, pool outside {2, 4}, n % pool != 0, a learnable edge_weight, and every
-    refusal forward_series makes for the same arguments.  No time_chunk."""
+    refusal forward_series makes for the same arguments.  No time_chunk: the causal layer in time chunks through this epilogue is
+    cheb_series_relu_pool_chunked."""
     who = "cheb_series_relu_pool"
     edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
     if series.dim() in (3, 4):
@@ -706,7 +707,8 @@ def cheb_series_relu_dropout_pool(layer, series, *graph_args, p=0.5, pool=4, tra
     training=False or p == 0 is cheb_series_relu_pool, launch for launch.  An operand the layer keeps reordered runs the unpooled layer,
     relabels back, then one relu + dropout + pool pass -- the same mask.
     TgcnError before an operand is built: p outside [0, 1), a seed outside [0, 2^62), a seed tensor that is not one int64 element on the
-    series' device, and everything cheb_series_relu_pool refuses."""
+    series' device, and everything cheb_series_relu_pool refuses.  No time_chunk: cheb_series_relu_pool_chunked walks the causal layer in
+    time chunks through this epilogue, with the same mask."""
     who = "cheb_series_relu_dropout_pool"
     F.dropout_params(p, who)
     if isinstance(series, torch.Tensor):
@@ -721,6 +723,39 @@ def cheb_series_relu_dropout_pool(layer, series, *graph_args, p=0.5, pool=4, tra
     bias, bias_kind, mode = _series_pool_bias(layer)
     return F.cheb_time_windows_relu_dropout_pool(op, series, W, bias, bias_kind, mode, pool, p, seed, as_series=as_series, stride=geom[0],
                                                  padding=geom[1:3], dilation=geom[3])
+
+
+def cheb_series_relu_pool_chunked(layer, series, *graph_args, time_chunk, pool=4, p=0.0, training=True, seed=None, as_series=False, dilation=1):
+    """gcn_pool_4(F.dropout(F.relu(layer.forward_series(series, ..., padding="causal", dilation=dilation, time_chunk=time_chunk)), p, training))
+    (pool=4; pool=2: gcn_pool)  in one op that uses BOTH memory features of the streaming layers: relu, the dropout and the pool run in the
+    projection's epilogue, and the recording is walked time_chunk rows at a time through the streaming ring in both directions.  Neither the
+    hop stack (K times the series), nor the layer's output (g/f times the series), nor that output's gradient is ever allocated: a training
+    step holds the pooled tensors and chunk-sized buffers.  layer is a TGCNCheb_H or a ChebTimeConv, graph_args are ChebTimeConv's
+    (edge_index[, edge_weight]).  -> z (S*T, n/pool, g) or, as_series=True, (S, n/pool, T, g).
+    The geometry is always the causal layer at step 1 (what the ring implements): no stride and no padding keyword.  p == 0 or
+    training=False is relu + pool without a mask.  Otherwise the mask is cheb_series_relu_dropout_pool's with nwin = T: element
+    e = ((s*T + t)*n + v)*g + c of the layer's output in the caller's vertex labels, reproduced by F.dropout_keep_mask, the same for every
+    time_chunk; seed as there.  z, d series and dW are bit-identical to the hand-written composition at the same time_chunk; d bias is
+    summed chunk by chunk (agrees to rounding).  float32 only.
+    An operand the layer keeps reordered runs forward_series(time_chunk=...), then one relu (+ dropout) + pool pass: the same values and
+    mask, but the layer's output is allocated there -- the memory saving is absent.
+    TgcnError before an operand is built: bfloat16 parameters, a learnable edge_weight, a bad pool, p, seed or time_chunk, n % pool != 0."""
+    who = "cheb_series_relu_pool_chunked"
+    F.dropout_params(p, who)
+    if isinstance(series, torch.Tensor):
+        F.dropout_seed(seed, series.device, who, draw=False)
+    edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
+    if time_chunk is None:
+        raise _lib.TgcnError("%s: time_chunk is an integer >= 1, got None -- without chunks this is cheb_series_relu_pool / "
+                             "cheb_series_relu_dropout_pool" % who)
+    F.check_time_chunk(time_chunk, 1, "causal", False, who)
+    if series.dim() in (3, 4):
+        F.check_pool(pool, series.shape[1], who)
+    series, W, geom = _series_args(layer, series, 1, "causal", dilation)
+    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
+    bias, bias_kind, mode = _series_pool_bias(layer)
+    return F.cheb_time_windows_relu_pool_chunked(op, series, W, bias, bias_kind, mode, pool, time_chunk, p=p if training else 0.0, seed=seed,
+                                                 as_series=as_series, dilation=geom[3])
 
 
 def cheb_relu_dropout_pool(layer, x, *graph_args, p=0.5, pool=4, training=True, seed=None):

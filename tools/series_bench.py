@@ -14,6 +14,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py --fused-series --steps 200 --warmup 20 [--repeats 3] [--include parent=FILE] [--out profiles/r21_series_small.json]
     python tools/series_bench.py --relu-pool 4 [--repeats 3] [--out profiles/r18_series_relu_pool.json]
     python tools/series_bench.py --relu-pool 4 --dropout 0.1 [--repeats 3] [--out profiles/r22_series_relu_dropout_pool.json]
+    python tools/series_bench.py --time-chunk 32,64 --relu-pool 4 [--dropout 0.1] [--repeats 3] [--out profiles/r23_series_chunk_relu_pool.json]
 
 Cases: (a) the 148-parcel DTI graph, S = 8 recordings of T = 284, H = 15, K = 10, the two layers of the reference's HCP net (1 -> 32 and
 32 -> 64 channels); (b) the 90 k-vertex sheet mesh, S = 1, T = 75, H = 15, 4 -> 32 channels, K = 5; (c) the two layers of (a) chained:
@@ -62,6 +63,13 @@ tgcn_amd.cheb_series_relu_dropout_pool(layer, series, p=PROB, pool=P) with seed=
 torch's F.dropout -> gcn_pool_4 and (c) cheb_series_relu_pool without dropout -- the column to hold against a --relu-pool P run of the
 parent commit, whose code it shares.  The three alternate within the run; medians, spreads and peaks as above.  The masks of (a) and (b)
 are different generators', so no equality is recorded; default --out profiles/r22_series_relu_dropout_pool.json.
+--time-chunk Tc[,Tc...] --relu-pool P [--dropout PROB] times a training step (forward + backward, all three gradients) of the causal layer
+followed by relu (+ dropout) + pool on the three cases of --relu-pool (DESIGN.md 3.10 "Time chunks through the pooled epilogue"), three forms
+in one run, alternating: (a) the fused unchunked call, cheb_series_relu_pool / cheb_series_relu_dropout_pool(..., padding="causal"); and
+per Tc (b) forward_series(..., padding="causal", time_chunk=Tc) followed by the stand-alone relu (+ dropout) + pool pass and (c)
+cheb_series_relu_pool_chunked(..., time_chunk=Tc).  One seed for the three, so they compute the same z.  Per column --repeats event
+timings of --steps steps each (median and spread) and the peak of max_memory_allocated above the pre-step level, also in units of the
+layer's full output; default --out profiles/r23_series_chunk_relu_pool.json.
 --fused-series: the one-launch whole-series layer (forward_series(fused=True), DESIGN.md 3.10 "One launch per series") on the graphs that fit
 in LDS: the (a) layers of the r08 table on the 148 parcels (1 -> 32 window-major and as_series=True; 32 -> 64, which the plan refuses) and
 TGCNCheb_H(L, 1, 64, 5, 28) on the 28 x 28 grid, S = 8, T = 128.  Columns per case, forward and forward + backward: unfused and fused
@@ -708,6 +716,96 @@ def main_relu_pool(args):
         json.dump(res, f, indent=1)
 
 
+def main_chunk_relu_pool(args):
+    dev = torch.device("cuda:0")
+    pool, drop = args.relu_pool, args.dropout or 0.0
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, repeats=args.repeats,
+               pool=pool, dropout=drop, time_chunks=list(args.time_chunk), cases={})
+    torch.manual_seed(0)
+    seed = torch.tensor([0x2468ACE13579BDF], dtype=torch.int64, device=dev)
+    thr, scale = F.dropout_params(drop)
+
+    def case(name, desc, layer, series, as_series):
+        series = series.requires_grad_(True)
+        N = layer.weight.shape[-1]
+
+        def pool_pass(y):
+            y3 = y if y.dim() == 3 else y.reshape(y.shape[0], y.shape[1], -1)
+            z = F.ReluDropoutPoolFn.apply(y3, pool, N, seed, thr, scale) if drop else F.ReluPoolFn.apply(y3, pool)
+            return z if y.dim() == 3 else z.view(y.shape[0], y.shape[1] // pool, y.shape[2], N)
+
+        def fused_unchunked():
+            if drop:
+                return tgcn_amd.cheb_series_relu_dropout_pool(layer, series, p=drop, pool=pool, seed=seed, as_series=as_series, padding="causal")
+            return tgcn_amd.cheb_series_relu_pool(layer, series, pool=pool, as_series=as_series, padding="causal")
+
+        columns = [("fused_unchunked", fused_unchunked)]
+        for tc in args.time_chunk:
+            columns.append(("time_chunk_%d_then_pool_pass" % tc,
+                            lambda tc=tc: pool_pass(layer.forward_series(series, as_series=as_series, padding="causal", time_chunk=tc))))
+            columns.append(("chunked_pooled_%d" % tc,
+                            lambda tc=tc: tgcn_amd.cheb_series_relu_pool_chunked(layer, series, time_chunk=tc, pool=pool, p=drop, seed=seed,
+                                                                                 as_series=as_series)))
+
+        def clear():
+            layer.zero_grad(set_to_none=True)
+            series.grad = None
+
+        def step_of(fn):
+            def step():
+                clear()
+                z = fn()
+                z.backward(torch.ones_like(z))
+            return step
+
+        ms, peak = {k: [] for k, _ in columns}, {}
+        for _ in range(args.repeats):               # alternating: every column once per repeat
+            for k, fn in columns:
+                step = step_of(fn)
+                ms[k].append(events_ms(step, args.steps, args.warmup))
+                clear()
+                torch.cuda.synchronize()
+                torch.cuda.reset_peak_memory_stats()
+                base = torch.cuda.memory_allocated()
+                step()
+                torch.cuda.synchronize()
+                peak[k] = torch.cuda.max_memory_allocated() - base
+        with torch.no_grad():
+            zs = [fn() for _, fn in columns]
+        S, n, T = series.shape[:3]
+        full = 4 * S * n * T * N
+        entry = dict(desc=desc, fused_by_predicate=bool(F.series_pool_is_fused(layer._operand(dev), pool)), series_bytes=series.numel() * 4,
+                     full_output_bytes=full, results_equal_to_fused_unchunked=[bool(torch.equal(z, zs[0])) for z in zs[1:]])
+        for k, _ in columns:
+            entry[k] = dict(ms_per_step=ms[k], median=sorted(ms[k])[len(ms[k]) // 2], spread=round(max(ms[k]) - min(ms[k]), 4),
+                            peak_bytes_above_baseline=peak[k], peak_over_full_output=round(peak[k] / full, 4),
+                            ms_over_fused_unchunked=round(sorted(ms[k])[len(ms[k]) // 2] / sorted(ms["fused_unchunked"])[len(ms[k]) // 2], 3))
+        res["cases"][name] = entry
+        print(json.dumps({name: entry}), flush=True)
+        del zs
+        clear()
+        torch.cuda.empty_cache()
+
+    op = dti148(dev)
+    S, T, H, K = 8, 284, 15, 10
+    l1 = tgcn_amd.TGCNCheb_H(op, 1, 32, K, H).to(dev)
+    case("a_dti148_1to32", "dti148 S=8 T=284 H=15 K=10 f=1 -> g=32 causal, window-major, forward + backward", l1, torch.randn(S, op.n, T, device=dev), False)
+    del l1
+    l2 = tgcn_amd.TGCNCheb_H(op, 32, 64, K, H).to(dev)
+    case("a_dti148_32to64_series", "dti148 S=8 T=284 H=15 K=10 f=32 -> g=64 causal, series layout, forward + backward", l2,
+         torch.randn(S, op.n, T, 32, device=dev), True)
+    del l2
+    n, row, col, val = synth.sheet_mesh(300, device=dev)
+    opm = GraphOperand.from_coo(n, row, col, val, dev)
+    lm = tgcn_amd.TGCNCheb_H(opm, 4, 32, 5, 15).to(dev)
+    case("b_mesh90k_4to32", "sheet_mesh(300) n=%d S=1 T=75 H=15 K=5 f=4 -> g=32 causal, window-major, forward + backward" % n, lm,
+         torch.randn(1, n, 75, 4, device=dev), False)
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r23_series_chunk_relu_pool.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def main_fused_series(args):
     import inspect
     dev = torch.device("cuda:0")
@@ -829,9 +927,13 @@ def main():
         if args.relu_pool is not None or args.time_chunk is not None or args.stream or args.dilation or args.conv:
             ap.error("--fused-series runs alone")
         return main_fused_series(args)
+    if args.relu_pool is not None and args.time_chunk is not None:
+        if min(args.time_chunk) < 1 or args.stream or args.dilation or args.conv:
+            ap.error("--time-chunk Tc[,Tc...] (integers >= 1) --relu-pool P [--dropout PROB] run without the other case switches")
+        return main_chunk_relu_pool(args)
     if args.relu_pool is not None:
-        if args.time_chunk is not None or args.stream or args.dilation or args.conv:
-            ap.error("--relu-pool P runs alone")
+        if args.stream or args.dilation or args.conv:
+            ap.error("--relu-pool P runs alone or with --time-chunk")
         return main_relu_pool(args)
     if args.time_chunk is not None:
         if min(args.time_chunk) < 1 or args.stream or args.dilation or args.conv:
