@@ -653,6 +653,24 @@ int tgcn_cheb_series_small_f32(void* stream, const tgcn_csr* A, int32_t mode, in
                                const float* series, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
                                float* stack /* nullable */, int32_t left, int32_t right, int32_t dilation);
 
+/* tgcn_cheb_series_small_f32 with relu, an optional dropout and the max over `pool` (2 or 4) consecutive vertices as its epilogue (DESIGN.md
+ * 3.10, "relu + pool in the one-launch series layer"; fp32): still ONE launch, and the layer's (S, n, nwin, N) output is never written.  The
+ * four accumulator floats of a lane are four consecutive vertices from a multiple of 4 on -- one group of 4 or two pairs -- so the pool runs in
+ * registers.  Per element of the unpooled output: t = acc + bias; with seed non-null t = relu(t) * m, m = scale where dropout.h's mask keeps
+ * element e = ((s * nwin + w) * n + v) * N + c (Philox4x32-10 on e >> 2 under *seed, word e & 3 >= thr -- tgcn_dropout_keep_u8 reproduces it)
+ * and 0 elsewhere; then tgcn_relu_pool_f32's rules: members ascending, the first maximum wins, a NaN wins over a number,
+ * z = best > 0 ? best : (NaN ? NaN : 0).  z is (S, n/pool, nwin, N) as_series, else (S*nwin, n/pool, N); idx (nullable) holds the arg-max
+ * member of every element in z's layout, what tgcn_relu_pool_bwd_f32 reads.  z and idx have the bits of tgcn_relu_pool_f32 /
+ * tgcn_relu_dropout_pool_f32 on tgcn_cheb_series_small_f32's output.  stack (nullable) as there.  seed NULL: no dropout, thr and scale unread.
+ * The plan is tgcn_cheb_series_small_plan: the pool adds no LDS and no threads.
+ * Codes: tgcn_cheb_series_small_f32's own, then TGCN_ERR_INVALID for a pool outside {2, 4}, n % pool != 0, and a non-null seed with a scale
+ * that is not finite and >= 1; nothing is launched and no pointer is read in any of these cases.  The grid is issued in parts as there;
+ * the entry does not synchronise and does not allocate. */
+int tgcn_cheb_series_small_pool_f32(void* stream, const tgcn_csr* A, int32_t mode, int64_t S, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                    const float* series, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* z,
+                                    uint8_t* idx /* nullable */, int32_t pool, float* stack /* nullable */, int32_t left, int32_t right,
+                                    int32_t dilation, const int64_t* seed /* NULL: no dropout */, uint32_t thr, float scale);
+
 /* Weight gradient of the projection (backward of gcn.py:39,113,194 w.r.t. weight):
  *   dW[t*Kc + c, n] = sum_m A_t[m, c] * G[m, n]
  * A_t as in tgcn_cheb_project_f32 (host arrays of nterms <= 32 pointers / strides), G: M x N with row stride ldg,

@@ -8,7 +8,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.path.join(_HERE, "lib", "libtgcn_hip.so")
 SOURCES = [os.path.join(_HERE, "csrc", "tgcn_hip.hip")]      # one translation unit; the kernels are in csrc/*.h
-HEADERS = [os.path.join(_HERE, "csrc", h) for h in ("common.h", "hop.h", "project.h", "wgrad.h", "small_graph.h", "pool_relayout.h", "dropout.h", "windows.h", "windows_gemm_body.inc", "windows_bf16.h", "stream_small.h", "series_small.h", "device_build.h", "graph_build.h")]
+HEADERS = [os.path.join(_HERE, "csrc", h) for h in ("common.h", "hop.h", "project.h", "wgrad.h", "small_graph.h", "pool_relayout.h", "dropout.h", "windows.h", "windows_gemm_body.inc", "windows_bf16.h", "stream_small.h", "series_small.h", "series_small_body.inc", "device_build.h", "graph_build.h")]
 INCLUDE = os.path.join(ROOT, "include")
 
 
@@ -217,6 +217,9 @@ SIGNATURES = {
                                               C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "tgcn_cheb_series_small_f32": (C.c_int, [_P, C.POINTER(CsrStruct), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                              _P, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32]),
+    "tgcn_cheb_series_small_pool_f32": (C.c_int, [_P, C.POINTER(CsrStruct), C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                  C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, _P, C.c_int32, C.c_int32,
+                                                  C.c_int32, _P, C.c_uint32, C.c_float]),
     "tgcn_fold_weight_f32": (C.c_int, [_P, C.c_int32, C.c_int64, _P, _P, _P, C.c_int32]),
     "tgcn_weight_layout_f32": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_int32]),
     "tgcn_csr_hop_f64": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, C.c_double, C.c_double, _P, _P]),

@@ -2124,26 +2124,41 @@ int tgcn_cheb_series_small_plan(int64_t n, int64_t nnz, int32_t mode, int32_t f,
   return TGCN_OK;
 }
 
+// the checks and the kernel parameters the two one-launch entries share: the plan's codes, then the entry's own; nothing is launched here
+static int series_small_setup(const char* who, void* stream, const tgcn_csr* A, int32_t mode, int64_t S, int32_t T, int32_t f, int32_t H, int32_t N,
+                              int32_t K, const float* series, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
+                              float* stack, int32_t left, int32_t right, int32_t dilation, bool pooled, int32_t pool, const int64_t* seed,
+                              float scale, SeriesSmallPlan* pl, SeriesSmallParams* p) {
+  if (!A || !series || !W || !out || S < 1) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bias_kind %d", who, bias_kind);
+  const int prc = series_small_plan(A->n, A->nnz, mode, f, H, N, K, T, left, right, dilation, pl);
+  if (prc == TGCN_ERR_INVALID) TGCN_FAIL(prc, "%s: bad argument", who);
+  if (prc) TGCN_FAIL(prc, "%s: n=%lld nnz=%lld f=%d H=%d N=%d does not fit one workgroup", who, (long long)A->n, (long long)A->nnz, f, H, N);
+  if (pooled) {           // the pooled entry's own: pool 2 or 4 dividing the graph, and the dropout's scale
+    if ((pool != 2 && pool != 4) || A->n % pool) TGCN_FAIL(TGCN_ERR_INVALID, "%s: pool %d on %lld vertices (2 or 4, dividing n)", who, pool, (long long)A->n);
+    if (seed && !dropout_scale_ok(scale)) TGCN_FAIL(TGCN_ERR_INVALID, "%s: a scale that is not finite and >= 1", who);
+  }
+  // the kernel's 32-bit offsets: one recording's rows of the series (and of a term of the stack) and of the output; the whole weight; the grid
+  const int64_t lim = (int64_t)INT32_MAX;
+  if (A->n * T * f > lim || A->n * pl->nwin * N > lim || (int64_t)K * H * f * N > lim || S * pl->ntiles > lim)
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a recording's rows, the weight or the grid exceed 32-bit offsets", who);
+  if (!A->rowptr || !A->edges) TGCN_FAIL(TGCN_ERR_INVALID, "%s: bad argument", who);
+  if (int drc = check_pointer_device(out, (hipStream_t)stream, who)) return drc;
+  memset(p, 0, sizeof(*p));
+  p->rowptr = A->rowptr; p->ev = A->edges; p->series = series; p->W = W; p->bias = bias; p->out = out; p->stack = stack;
+  p->S = (int32_t)S; p->n = (int32_t)A->n; p->nnz = (int32_t)A->nnz; p->T = T; p->f = f; p->H = H; p->N = N; p->K = K; p->bias_kind = bias_kind;
+  p->TB = pl->tb; p->ld = pl->ld; p->left = left; p->dil = dilation; p->nwin = pl->nwin; p->ntiles = pl->ntiles; p->as_series = as_series ? 1 : 0;
+  return TGCN_OK;
+}
+
 int tgcn_cheb_series_small_f32(void* stream, const tgcn_csr* A, int32_t mode, int64_t S, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
                                const float* series, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* out,
                                float* stack, int32_t left, int32_t right, int32_t dilation) {
-  if (!A || !series || !W || !out || S < 1) TGCN_FAIL(TGCN_ERR_INVALID, "series_small: bad argument");
-  if (bias_kind < 0 || bias_kind > 2 || (bias_kind && !bias)) TGCN_FAIL(TGCN_ERR_INVALID, "series_small: bias_kind %d", bias_kind);
   SeriesSmallPlan pl;
-  const int prc = series_small_plan(A->n, A->nnz, mode, f, H, N, K, T, left, right, dilation, &pl);
-  if (prc == TGCN_ERR_INVALID) TGCN_FAIL(prc, "series_small: bad argument");
-  if (prc) TGCN_FAIL(prc, "series_small: n=%lld nnz=%lld f=%d H=%d N=%d does not fit one workgroup", (long long)A->n, (long long)A->nnz, f, H, N);
-  // the kernel's 32-bit offsets: one recording's rows of the series (and of a term of the stack) and of the output; the whole weight; the grid
-  const int64_t lim = (int64_t)INT32_MAX;
-  if (A->n * T * f > lim || A->n * pl.nwin * N > lim || (int64_t)K * H * f * N > lim || S * pl.ntiles > lim)
-    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "series_small: a recording's rows, the weight or the grid exceed 32-bit offsets");
-  if (!A->rowptr || !A->edges) TGCN_FAIL(TGCN_ERR_INVALID, "series_small: bad argument");
-  if (int drc = check_pointer_device(out, (hipStream_t)stream, "series_small")) return drc;
   SeriesSmallParams p;
-  memset(&p, 0, sizeof(p));
-  p.rowptr = A->rowptr; p.ev = A->edges; p.series = series; p.W = W; p.bias = bias; p.out = out; p.stack = stack;
-  p.S = (int32_t)S; p.n = (int32_t)A->n; p.nnz = (int32_t)A->nnz; p.T = T; p.f = f; p.H = H; p.N = N; p.K = K; p.bias_kind = bias_kind;
-  p.TB = pl.tb; p.ld = pl.ld; p.left = left; p.dil = dilation; p.nwin = pl.nwin; p.ntiles = pl.ntiles; p.as_series = as_series ? 1 : 0;
+  if (int rc = series_small_setup("series_small", stream, A, mode, S, T, f, H, N, K, series, W, bias, bias_kind, as_series, out, stack, left, right,
+                                  dilation, false, 0, nullptr, 1.f, &pl, &p))
+    return rc;
   hipStream_t st = (hipStream_t)stream;
   const int64_t nblk = S * pl.ntiles, part = (int64_t)UINT32_MAX / kSrMaxThreads;      // fewer than 2^32 threads per launch (series_grid_part)
   const dim3 block((unsigned)pl.nthr);
@@ -2164,6 +2179,49 @@ int tgcn_cheb_series_small_f32(void* stream, const tgcn_csr* A, int32_t mode, in
 #undef TGCN_SERIES_SMALL_NTW
 #undef TGCN_SERIES_SMALL
   TGCN_CHECK_LAUNCH("tgcn_cheb_series_small_f32");
+  return TGCN_OK;
+}
+
+// the one-launch layer with relu (+ dropout) + pool as its epilogue (series_small.h, small_series_pool_kernel): the same plan and grid
+int tgcn_cheb_series_small_pool_f32(void* stream, const tgcn_csr* A, int32_t mode, int64_t S, int32_t T, int32_t f, int32_t H, int32_t N, int32_t K,
+                                    const float* series, const float* W, const float* bias, int32_t bias_kind, int32_t as_series, float* z,
+                                    uint8_t* idx, int32_t pool, float* stack, int32_t left, int32_t right, int32_t dilation, const int64_t* seed,
+                                    uint32_t thr, float scale) {
+  SeriesSmallPlan pl;
+  SeriesSmallParams p;
+  if (int rc = series_small_setup("series_small_pool", stream, A, mode, S, T, f, H, N, K, series, W, bias, bias_kind, as_series, z, stack, left,
+                                  right, dilation, true, pool, seed, scale, &pl, &p))
+    return rc;
+  SeriesSmallPoolParams pp;
+  memset(&pp, 0, sizeof(pp));
+  pp.idx = idx; pp.drop.seed = seed; pp.drop.thr = thr; pp.drop.scale = scale;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nblk = S * pl.ntiles, part = (int64_t)UINT32_MAX / kSrMaxThreads;      // fewer than 2^32 threads per launch, as above
+  const dim3 block((unsigned)pl.nthr);
+  ProfScope ps(TGCN_PROF_PROJECT, st);
+#define TGCN_SERIES_POOL(DENSE_, NTW_, MODE_, POOL_, DROP_)                                                           \
+  do {                                                                                                                \
+    if (pl.lds > 64 * 1024) allow_large_lds((const void*)small_series_pool_kernel<DENSE_, NTW_, MODE_, POOL_, DROP_>, pl.lds); \
+    for (int64_t b0 = 0; b0 < nblk; b0 += part) {                                                                     \
+      p.blk0 = (int32_t)b0;                                                                                           \
+      hipLaunchKernelGGL((small_series_pool_kernel<DENSE_, NTW_, MODE_, POOL_, DROP_>), dim3((unsigned)std::min<int64_t>(part, nblk - b0)), block, \
+                         pl.lds, st, p, pp);                                                                          \
+    }                                                                                                                 \
+  } while (0)
+#define TGCN_SERIES_POOL_DROP(DENSE_, NTW_, MODE_, POOL_)                                                             \
+  do { if (seed) TGCN_SERIES_POOL(DENSE_, NTW_, MODE_, POOL_, true); else TGCN_SERIES_POOL(DENSE_, NTW_, MODE_, POOL_, false); } while (0)
+#define TGCN_SERIES_POOL_P(DENSE_, NTW_, MODE_)                                                                       \
+  do { if (pool == 4) TGCN_SERIES_POOL_DROP(DENSE_, NTW_, MODE_, 4); else TGCN_SERIES_POOL_DROP(DENSE_, NTW_, MODE_, 2); } while (0)
+#define TGCN_SERIES_POOL_NTW(DENSE_, MODE_)                                                                           \
+  do { if (pl.ntw == 4) TGCN_SERIES_POOL_P(DENSE_, 4, MODE_); else if (pl.ntw == 2) TGCN_SERIES_POOL_P(DENSE_, 2, MODE_); \
+       else TGCN_SERIES_POOL_P(DENSE_, 1, MODE_); } while (0)
+  if (pl.dense) { if (mode == 0) TGCN_SERIES_POOL_NTW(true, 0); else TGCN_SERIES_POOL_NTW(true, 1); }
+  else { if (mode == 0) TGCN_SERIES_POOL_NTW(false, 0); else TGCN_SERIES_POOL_NTW(false, 1); }
+#undef TGCN_SERIES_POOL_NTW
+#undef TGCN_SERIES_POOL_P
+#undef TGCN_SERIES_POOL_DROP
+#undef TGCN_SERIES_POOL
+  TGCN_CHECK_LAUNCH("tgcn_cheb_series_small_pool_f32");
   return TGCN_OK;
 }
 

@@ -1284,6 +1284,133 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)      # the vertex axis is dim 1 in both layouts
 
 
+# ---- relu (+ dropout) + pool in the one-launch series layer ("relu + pool in the one-launch series layer")
+# fused="auto" of cheb_time_windows_relu_pool_fused takes the one-launch form for the classes listed here: "pool" -- a call without a mask
+# (p == 0) -- and "pool_dropout".  Set from profiles/r24_series_small_pool.json by SERIES_FUSED_AUTO's rule: a class is listed only where
+# the new call's median lies below BOTH comparators' -- the general pooled epilogue and forward_series(fused=True) followed by the relu
+# (+ dropout) + pool pass -- by more than the largest of the spreads, on both measured operands, forward and forward + backward.
+# () is "never": "auto" is then cheb_time_windows_relu_pool / cheb_time_windows_relu_dropout_pool everywhere.
+SERIES_POOL_FUSED_AUTO = ()
+
+
+def series_pool_fused_supported(op, f, H, N, K, T, padding, dilation, mode, pool):
+    """True where cheb_time_windows_relu_pool_fused(..., fused=True) runs: series_fused_supported's rules plus the pool's -- 2 or 4
+    consecutive vertices, dividing the graph.  A host query: nothing launches."""
+    if not isinstance(pool, numbers.Integral) or isinstance(pool, bool) or pool not in (2, 4) or op.n % pool:
+        return False
+    return series_fused_supported(op, f, H, N, K, T, padding, dilation, mode)
+
+
+class ChebSeriesSmallReluPoolFn(torch.autograd.Function):
+    """z = max over `pool` consecutive vertices of relu(ChebSeriesSmallFn's output) -- with drop = (seed tensor, thr, scale), of
+    relu(y) * mask -- taken in the registers of the one-launch layer's epilogue (tgcn_cheb_series_small_pool_f32, csrc/series_small.h
+    small_series_pool_kernel): the fold in power mode with K > 2, then ONE launch; the (S, n, nwin, N) output is never allocated.  z is
+    (S*nwin, n/pool, N) or, as_series, (S, n/pool, nwin, N), bit-identical to _relu_pool_view / _relu_dropout_pool_view of
+    ChebSeriesSmallFn's output.  The hop stack is written by that launch only when the weight trains (need_stack), the arg-max bytes only
+    with need_idx (the caller's looks at grad mode).  The backward is _series_pool_backward: gz (times scale with dropout) through
+    tgcn_relu_pool_bwd_f32, then ChebSeriesFn's backward body on the stack the launch wrote.  ctx.seed is the seed's tensor.
+    geom = (1, left, right, dilation)."""
+
+    @staticmethod
+    @_on_device
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx, need_stack, drop):
+        L = _lib.lib()
+        S, n, T, f = series.shape
+        K, H, _, N = weight_khfg.shape
+        _, left, right, dil = geom
+        nwin = T + left + right - (H - 1) * dil
+        x3 = series.float().contiguous().view(S, n, T * f)
+        W = weight_khfg.float().contiguous().view(K, H * f, N)
+        fold = _power_fold(mode, W)
+        Wt = _working_weight(fold, W)
+        shape = (S, n // pool, nwin, N) if as_series else (S * nwin, n // pool, N)
+        z = torch.empty(shape, dtype=torch.float32, device=x3.device)
+        idx = torch.empty(shape, dtype=torch.uint8, device=x3.device) if need_idx else None
+        stack = torch.empty((K, S, n, T * f), dtype=torch.float32, device=x3.device) if need_stack else None
+        b = bias.float().contiguous() if bias is not None else None
+        seed_t, thr, scale = drop if drop is not None else (None, 0, 1.0)
+        _lib.check(L.tgcn_cheb_series_small_pool_f32(_lib.stream_ptr(), C.byref(op.struct), int(mode), S, T, f, H, N, K, _lib.ptr(x3), _lib.ptr(Wt),
+                                                     _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(z), _lib.ptr(idx), pool,
+                                                     _lib.ptr(stack), left, right, dil, _lib.ptr(seed_t), thr, scale))
+        ctx.geom = (1, left, right, dil) if dil > 1 else ((1, left, right) if (left, right) != (0, 0) else None)
+        ctx.save_for_backward(Wt, z, idx)
+        ctx.stack = stack
+        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.pool = op, mode, fold, bias_kind, as_series, pool
+        ctx.dims = (S, n, T, f, H, N, K)
+        ctx.nwin = nwin
+        ctx.bias_shape = None if bias is None else bias.shape
+        ctx.scale, ctx.seed = (None, None) if drop is None else (scale, seed_t)
+        return z
+
+    @staticmethod
+    @_on_device
+    def backward(ctx, gz):
+        if ctx.scale is not None:
+            gz = gz.float() * ctx.scale
+        return _series_pool_backward(ctx, gz, "cheb_time_windows_relu_pool_fused") + (None,) * 9
+
+
+@_on_device
+def cheb_time_windows_relu_pool_fused(op, series, weight, bias, bias_kind, mode, pool, p=0.0, seed=None, as_series=False, padding=0, dilation=1,
+                                      fused=True):
+    """gcn_pool_4(dropout(relu(cheb_time_windows(..., fused=True)), p)) (pool=4; pool=2: gcn_pool) in ONE launch on an operand that fits in
+    LDS: the hops, the window projection, the bias, relu, the dropout and the max over `pool` consecutive vertices
+    (ChebSeriesSmallReluPoolFn).  series (S, n, T) with weight (K, H, N), or (S, n, T, f) with (K, H, f, N) -> z (S*nwin, n/pool, N) or,
+    as_series=True, (S, n/pool, nwin, N).  The layer's full output is never allocated; z and every gradient are bit-identical to
+    _relu_pool_view / _relu_dropout_pool_view of cheb_time_windows(..., fused=True) under the same seed.  p == 0 runs the form without a
+    mask; otherwise p, seed and the element index are cheb_time_windows_relu_dropout_pool's (dropout_keep_mask reproduces the mask).
+    There is no stride and no time_chunk: the one-launch layer has neither.
+    fused=True raises TgcnError before an operand is touched or anything launches: bfloat16 parameters, a non-square or reordered
+    operand, a plan that refuses (series_pool_fused_supported tells), and everything check_pool, dropout_params, dropout_seed and
+    series_geometry refuse.  fused="auto" runs the one-launch form where it can and where SERIES_POOL_FUSED_AUTO lists the call's class
+    ("pool" at p == 0, else "pool_dropout"); everywhere else it is cheb_time_windows_relu_pool / cheb_time_windows_relu_dropout_pool with
+    the same arguments."""
+    who = "cheb_time_windows_relu_pool_fused"
+    if fused is not True and not (isinstance(fused, str) and fused == "auto"):
+        raise _lib.TgcnError("%s: fused is True or \"auto\", got %r" % (who, fused))
+    thr, scale = dropout_params(p, who)
+    dropout_seed(seed, series.device, who, draw=False)
+    bf16 = param_dtype(weight, bias, who) == BF16
+    if bf16 and fused is True:
+        raise _lib.TgcnError("%s: fused=True runs in float32 only -- the parameters are bfloat16" % who)
+    run = not bf16
+    if run:
+        if series.dim() not in (3, 4) or weight.dim() != series.dim():
+            raise _lib.TgcnError("%s: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
+                                 "(got %s and %s)" % (who, tuple(series.shape), tuple(weight.shape)))
+        f = series.shape[3] if series.dim() == 4 else 1
+        if series.dim() == 4 and weight.shape[2] != f:
+            raise _lib.TgcnError("%s: the series has %d channels, the weight %d" % (who, f, weight.shape[2]))
+        pool = check_pool(pool, series.shape[1], who)
+        K, H, N, T = weight.shape[0], weight.shape[1], weight.shape[-1], series.shape[2]
+        geom = series_geometry(T, H, 1, padding, who, dilation)[:3] + (series_dilation(H, dilation),)
+        if fused is True:
+            if op.n_cols != op.n:
+                raise _lib.TgcnError("%s: fused=True needs a square operand, got %d x %d" % (who, op.n, op.n_cols))
+            if op.perm is not None:
+                raise _lib.TgcnError("%s: fused=True runs in the operand's own labels -- a reordered operand is not supported (fused=\"auto\")" % who)
+            if _series_small_plan(op, f, H, N, K, T, geom[1], geom[2], geom[3], mode)[0] != 0:
+                raise _lib.TgcnError("%s: fused=True, but n = %d, nnz = %d, f = %d, H = %d, N = %d do not fit the one-launch layer "
+                                     "(series_pool_fused_supported; fused=\"auto\")" % (who, op.n, op.nnz, f, H, N))
+        else:       # the measured rule first: no query is made for a class that never fuses
+            run = (("pool" if p == 0 else "pool_dropout") in SERIES_POOL_FUSED_AUTO and op.n_cols == op.n and op.perm is None
+                   and _series_small_plan(op, f, H, N, K, T, geom[1], geom[2], geom[3], mode)[0] == 0)
+    if not run:
+        if p == 0:
+            return cheb_time_windows_relu_pool(op, series, weight, bias, bias_kind, mode, pool, as_series=as_series, padding=padding,
+                                               dilation=dilation)
+        return cheb_time_windows_relu_dropout_pool(op, series, weight, bias, bias_kind, mode, pool, p, seed, as_series=as_series, padding=padding,
+                                                   dilation=dilation)
+    _lib.require_device(series, weight, bias)
+    if series.dim() == 3:
+        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
+    drop = None if p == 0 else (dropout_seed(seed, series.device, who), thr, scale)
+    grad = torch.is_grad_enabled()
+    need_idx = grad and any(t is not None and t.requires_grad for t in (series, weight, bias))
+    return ChebSeriesSmallReluPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, pool, need_idx,
+                                           grad and weight.requires_grad, drop)
+
+
 @_on_device
 def cheb_wgrad(terms, g2d):
     """dW[t] = terms[t]^T @ g2d  ->  (T, Kc, N); terms: list of (M, Kc) views with contiguous rows, g2d: (M, N)."""

@@ -758,6 +758,36 @@ def cheb_series_relu_pool_chunked(layer, series, *graph_args, time_chunk, pool=4
                                                  as_series=as_series, dilation=geom[3])
 
 
+def cheb_series_relu_pool_fused(layer, series, *graph_args, pool=4, p=0.0, training=True, seed=None, as_series=False, padding=0, dilation=1,
+                                fused=True):
+    """gcn_pool_4(F.dropout(F.relu(layer.forward_series(series, ..., fused=True)), p, training))  (pool=4; pool=2: gcn_pool)  in ONE launch on
+    a graph that fits in LDS -- the opening block of the reference's HCP network (examples/pytorch_based/pytorch_hcp_tgcn.py:134-137) on the
+    148-parcel graph: the hops, the window projection, the bias, relu, the dropout and the pool of a tile of windows per workgroup, the
+    max taken in the accumulator registers (F.cheb_time_windows_relu_pool_fused, F.ChebSeriesSmallReluPoolFn).  layer is a TGCNCheb_H or a
+    ChebTimeConv, graph_args are ChebTimeConv's (edge_index[, edge_weight]); as_series, padding, dilation as in forward_series.
+    -> z (S*nwin, n/pool, g) or, as_series=True, (S, n/pool, nwin, g).  The layer's full output is never allocated; z and all gradients are
+    bit-identical to relu (+ dropout) + pool as their own pass behind forward_series(..., fused=True).  p == 0 or training=False runs
+    without a mask; otherwise the mask, p and seed are cheb_series_relu_dropout_pool's.  No stride and no time_chunk.
+    fused=True raises TgcnError where the one-launch layer cannot run -- before an operand is built: bfloat16 parameters, a learnable
+    edge_weight, a bad pool, p, seed, padding or dilation, n % pool != 0; before anything launches: an operand the layer keeps reordered
+    and a shape the plan refuses (F.series_pool_fused_supported).  fused="auto" runs it where F.SERIES_POOL_FUSED_AUTO says it pays and is
+    cheb_series_relu_pool / cheb_series_relu_dropout_pool elsewhere."""
+    who = "cheb_series_relu_pool_fused"
+    if fused is not True and not (isinstance(fused, str) and fused == "auto"):
+        raise _lib.TgcnError("%s: fused is True or \"auto\", got %r" % (who, fused))
+    F.dropout_params(p, who)
+    if isinstance(series, torch.Tensor):
+        F.dropout_seed(seed, series.device, who, draw=False)
+    edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
+    if series.dim() in (3, 4):
+        F.check_pool(pool, series.shape[1], who)
+    series, W, geom = _series_args(layer, series, 1, padding, dilation)
+    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
+    bias, bias_kind, mode = _series_pool_bias(layer)
+    return F.cheb_time_windows_relu_pool_fused(op, series, W, bias, bias_kind, mode, pool, p=p if training else 0.0, seed=seed, as_series=as_series,
+                                               padding=geom[1:3], dilation=geom[3], fused=fused)
+
+
 def cheb_relu_dropout_pool(layer, x, *graph_args, p=0.5, pool=4, training=True, seed=None):
     """gcn_pool_4(F.dropout(F.relu(layer(x, ...)), p, training))  (pool=4; pool=2: gcn_pool)  for the batch layers -- any of the five
     modules, graph_args as in cheb_relu_pool: the layer, then ONE relu + dropout + pool pass (tgcn_relu_dropout_pool_f32) in place of three

@@ -12,6 +12,7 @@ call, ms per call and per kernel kind (tgcn_profile_*), forward and forward + ba
     python tools/series_bench.py --stream --stride 2,2,2 [--repeats 3] [--include parent=FILE] [--out profiles/r16_series_stream_stride.json]
     python tools/series_bench.py --time-chunk 64,256 [--repeats 3] [--include parent=FILE] [--out profiles/r17_series_time_chunk.json]
     python tools/series_bench.py --fused-series --steps 200 --warmup 20 [--repeats 3] [--include parent=FILE] [--out profiles/r21_series_small.json]
+    python tools/series_bench.py --fused-series --relu-pool 4 [--dropout 0.5] --steps 200 --warmup 20 [--include LABEL=FILE] [--out profiles/r24_series_small_pool.json]
     python tools/series_bench.py --relu-pool 4 [--repeats 3] [--out profiles/r18_series_relu_pool.json]
     python tools/series_bench.py --relu-pool 4 --dropout 0.1 [--repeats 3] [--out profiles/r22_series_relu_dropout_pool.json]
     python tools/series_bench.py --time-chunk 32,64 --relu-pool 4 [--dropout 0.1] [--repeats 3] [--out profiles/r23_series_chunk_relu_pool.json]
@@ -75,7 +76,15 @@ in LDS: the (a) layers of the r08 table on the 148 parcels (1 -> 32 window-major
 TGCNCheb_H(L, 1, 64, 5, 28) on the 28 x 28 grid, S = 8, T = 128.  Columns per case, forward and forward + backward: unfused and fused
 forward_series and forward on the materialised windows, alternating within the run, --repeats event timings of --steps calls each (median
 and max - min).  On a commit without the keyword only the unfused and the materialised column are timed, which is how the parent commit's file
-for --include LABEL=FILE is made; default --out profiles/r21_series_small.json."""
+for --include LABEL=FILE is made; default --out profiles/r21_series_small.json.
+--fused-series --relu-pool P [--dropout PROB]: relu (+ dropout) + pool behind the one-launch layer (DESIGN.md 3.10 "relu + pool in the one-launch
+series layer") on the two fusable operands of r21 (148 parcels 1 -> 32, the 28 x 28 grid), window-major, forward and forward + backward:
+(a) tgcn_amd.cheb_series_relu_pool_fused, (b) cheb_series_relu_pool / cheb_series_relu_dropout_pool, the general pooled epilogue, and (c)
+forward_series(fused=True) followed by the relu (+ dropout) + pool pass -- alternating, --repeats event timings of --steps calls each.  One
+row per (case, direction) with its class ("pool" / "pool_dropout"); on a commit without (a) only (b) and (c) are timed, which is how the
+parent's file is made.  --include LABEL=FILE appends another run's rows under that label -- the parent's build, or this tool's run with the
+other --dropout setting under the label "this", so that one file holds both classes -- and "auto" is F.SERIES_POOL_FUSED_AUTO's rule over
+the rows labelled "this"; default --out profiles/r24_series_small_pool.json."""
 import argparse
 import json
 import os
@@ -887,6 +896,97 @@ def main_fused_series(args):
         json.dump(res, f, indent=1)
 
 
+def series_pool_auto_classes(rows):
+    """F.SERIES_POOL_FUSED_AUTO's rule on this run's rows: a class is listed only where the one-launch call's median lies below BOTH
+    comparators' by more than the largest of the three spreads, in every row of the class"""
+    out = []
+    for klass in ("pool", "pool_dropout"):
+        mine = [r for r in rows if r["class"] == klass and r.get("label") == "this" and "fused" in r]
+        if mine and all(r["fused"]["median_ms"] + max(r[c]["spread_ms"] for c in ("fused", "general", "composed"))
+                        < min(r["general"]["median_ms"], r["composed"]["median_ms"]) for r in mine):
+            out.append(klass)
+    return out
+
+
+def main_fused_series_pool(args):
+    """--fused-series --relu-pool P [--dropout PROB]: relu (+ dropout) + pool behind the one-launch series layer"""
+    dev = torch.device("cuda:0")
+    has_new = hasattr(tgcn_amd, "cheb_series_relu_pool_fused")
+    pool, drop = args.relu_pool, args.dropout or 0.0
+    klass = "pool_dropout" if drop else "pool"
+    res = dict(device=torch.cuda.get_device_name(0), lib_hash=_lib.binary_hash(), steps=args.steps, warmup=args.warmup, repeats=args.repeats,
+               pool=pool, dropout=drop, has_fused_pool_call=has_new, rows=[])
+    torch.manual_seed(0)
+    seed = torch.tensor([20240], dtype=torch.int64, device=dev)
+    thr, scale = F.dropout_params(drop)
+
+    def case(name, desc, layer, series):
+        x = series.contiguous().requires_grad_(True)
+
+        def forward(col):
+            if col == "fused":         # (a) the new call
+                return tgcn_amd.cheb_series_relu_pool_fused(layer, x, pool=pool, p=drop, seed=seed, fused=True)
+            if col == "general":       # (b) the general pooled epilogue
+                if drop:
+                    return tgcn_amd.cheb_series_relu_dropout_pool(layer, x, p=drop, pool=pool, seed=seed)
+                return tgcn_amd.cheb_series_relu_pool(layer, x, pool=pool)
+            y = layer.forward_series(x, fused=True)      # (c) the one-launch layer, then the relu (+ dropout) + pool pass
+            return F._relu_dropout_pool_view(y, pool, seed, thr, scale) if drop else F._relu_pool_view(y, pool)
+
+        def step_of(col, train):
+            def step():
+                if not train:
+                    with torch.no_grad():
+                        forward(col)
+                    return
+                layer.zero_grad(set_to_none=True)
+                x.grad = None
+                z = forward(col)
+                z.backward(torch.ones_like(z))
+            return step
+
+        columns = (["fused"] if has_new else []) + ["general", "composed"]
+        equal = None
+        if has_new:
+            with torch.no_grad():
+                equal = bool(torch.equal(forward("fused"), forward("composed")))
+        for train in (False, True):
+            ms = {c: [] for c in columns}
+            for _ in range(args.repeats):               # alternating: every column once per repeat
+                for c in columns:
+                    ms[c].append(events_ms(step_of(c, train), args.steps, args.warmup))
+            row = dict(case=name, desc=desc, direction="forward_backward" if train else "forward", label="this", fused_equals_composed=equal)
+            row["class"] = klass
+            for c in columns:
+                row[c] = dict(ms_per_call=ms[c], median_ms=sorted(ms[c])[len(ms[c]) // 2], spread_ms=round(max(ms[c]) - min(ms[c]), 4))
+            res["rows"].append(row)
+            print(json.dumps(row), flush=True)
+        layer.zero_grad(set_to_none=True)
+        torch.cuda.empty_cache()
+
+    op = dti148(dev)
+    l1 = tgcn_amd.TGCNCheb_H(op, 1, 32, 10, 15).to(dev)
+    case("a_dti148_1to32", "dti148 S=8 T=284 H=15 K=10 f=1 -> g=32, window-major, pool %d%s" % (pool, ", p=%g" % drop if drop else ""), l1,
+         torch.randn(8, op.n, 284, device=dev))
+    del l1
+    n, row, col, val = synth.grid_knn(28, device=dev)
+    opg = GraphOperand.from_coo(n, row, col, val, dev)
+    lg = tgcn_amd.TGCNCheb_H(opg, 1, 64, 5, 28).to(dev)
+    case("g_grid784_1to64", "grid_knn(28) n=784 S=8 T=128 H=28 K=5 f=1 -> g=64, window-major, pool %d%s" % (pool, ", p=%g" % drop if drop else ""), lg,
+         torch.randn(8, n, 128, device=dev))
+    for item in args.include:       # another run's file: its rows under LABEL (the parent's build: comparators only), and the rule over all
+        label, path = item.split("=", 1)
+        with open(path) as f:
+            other = json.load(f)
+        res["rows"] += [dict(r, label=label) if r.get("label") == "this" else r for r in other["rows"]]
+    res["auto"] = dict(rule="a class is listed only where fused.median_ms + max(spread_ms of fused, general, composed) < min(general.median_ms, "
+                            "composed.median_ms) in every row labelled 'this' of the class", classes=series_pool_auto_classes(res["rows"]))
+    out = args.out or os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "r24_series_small_pool.json")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+
+
 def stride_arg(text):
     parts = tuple(int(v) for v in text.split(","))
     return parts[0] if len(parts) == 1 else parts
@@ -924,9 +1024,9 @@ def main():
     if args.dtype == "bf16":
         return main_bf16(args)
     if args.fused_series:
-        if args.relu_pool is not None or args.time_chunk is not None or args.stream or args.dilation or args.conv:
-            ap.error("--fused-series runs alone")
-        return main_fused_series(args)
+        if args.time_chunk is not None or args.stream or args.dilation or args.conv:
+            ap.error("--fused-series runs alone or with --relu-pool P [--dropout PROB]")
+        return main_fused_series_pool(args) if args.relu_pool is not None else main_fused_series(args)
     if args.relu_pool is not None and args.time_chunk is not None:
         if min(args.time_chunk) < 1 or args.stream or args.dilation or args.conv:
             ap.error("--time-chunk Tc[,Tc...] (integers >= 1) --relu-pool P [--dropout PROB] run without the other case switches")
