@@ -464,6 +464,44 @@ def check_series_bf16(f, as_series, geom, series_dtype):
                              "(series.to(torch.bfloat16))" % series_dtype)
 
 
+def _series_operands(series, weight_khfg, bias, mode):
+    """what every float32 series Function launches with -> (series, fold, working weight, bias): the fp32 contiguous series (S, n, T, f), the
+    fold of the (K, H*f, N) weight view (_power_fold: None outside power mode with K > 2), that view in the kernels' basis (_working_weight:
+    at most one tgcn_fold_weight_f32) and the contiguous bias.  The bias goes through .float() at every site (the one-launch Functions did,
+    the others called .contiguous() alone): param_dtype has refused a bias of another dtype than the weight's, so on these float32 paths it
+    returns the tensor itself and launches nothing"""
+    K, H, f, N = weight_khfg.shape
+    W = weight_khfg.float().contiguous().view(K, H * f, N)
+    fold = power_fold_matrix(K, W.device) if (mode == MODE_POWER and K > 2) else None       # _power_fold and _working_weight, without their calls
+    return series.float().contiguous(), fold, W if fold is None else fold_weight(fold, W), None if bias is None else bias.float().contiguous()
+
+
+def _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, dims, geom=None, pooled=None):
+    """The fields a float32 series Function leaves for its backward, in one call per forward (these calls run at 0.3 ms, where a Python
+    call counts); dims starts (S, n, T, f, H, N, K).
+    geom = (stride, left, right, dilation) of a Function with a whole hop stack: ctx.geom is the backward's record of it -- the arguments
+    that follow the common ones in the entries of that geometry, which also names them (_series_backward): () the default geometry's,
+    (stride, left, right) the _conv entries', all four the _dilated ones'.
+    pooled = (Wt, z, idx, pool, nwin, drop) of a pooled one (_series_pool_backward): saved in that order, the pool, the window count, and
+    the mask's seed tensor and scale (None, None without one)."""
+    ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.dims = op, mode, fold, bias_kind, as_series, dims
+    ctx.bias_shape = None if bias is None else bias.shape
+    if geom is not None:
+        ctx.geom = geom if geom[3] > 1 else (geom[:3] if geom[:3] != (1, 0, 0) else ())
+    if pooled is not None:
+        Wt, z, idx, ctx.pool, ctx.nwin, drop = pooled
+        ctx.save_for_backward(Wt, z, idx)
+        ctx.seed, ctx.scale = (None, None) if drop is None else (drop[0], drop[2])
+
+
+def _series_dW(ctx, dW):
+    """the (K, H*f, N) weight gradient of the working weight -> the caller's (K, H, f, N): un-folded (once: a chunked walk passes its sum)"""
+    S, n, T, f, H, N, K = ctx.dims[:7]
+    if ctx.fold is not None:
+        dW = fold_weight(ctx.fold, dW, transpose=True)
+    return dW.view(K, H, f, N)
+
+
 class ChebSeriesFn(torch.autograd.Function):
     """Streaming time-window layer on a multi-channel series (S, n, T, f), weight (K, H, f, N): the hops run once on rows of T*f floats in
     both directions, the window projection and its two gradients are the sliding-window MFMA kernels of csrc/windows.h
@@ -480,32 +518,22 @@ class ChebSeriesFn(torch.autograd.Function):
         S, n, T, f = series.shape
         K, H, _, N = weight_khfg.shape
         stride, left, right, dil = _geom4(geom)
-        conv = (stride, left, right) != (1, 0, 0)
         nwin = (T + left + right - (H - 1) * dil - 1) // stride + 1
-        if conv or dil > 1:
+        if dil > 1 or (stride, left, right) != (1, 0, 0):
             hc, lds = C.c_int32(0), C.c_int32(0)
             _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), stride, C.byref(hc), C.byref(lds)))
-        x3 = _aligned_input(series.float().contiguous().view(S, n, T * f))
-        W = weight_khfg.float().contiguous().view(K, H * f, N)
-        fold = _power_fold(mode, W)
-        Wt = _working_weight(fold, W)
+        x, fold, Wt, b = _series_operands(series, weight_khfg, bias, mode)
+        _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, (S, n, T, f, H, N, K), (stride, left, right, dil))
+        x3 = _aligned_input(x.view(S, n, T * f))
         # the series is in the operand's labels already (cheb_time_windows relabelled it)
         stack = _series_stack(op, x3, K, mode)   # (K, S, n, T*f)
         out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=torch.float32, device=x3.device)
-        b = bias.contiguous() if bias is not None else None
-        args = (_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(out))
-        if dil > 1:
-            _lib.check(L.tgcn_cheb_project_series_dilated_f32(*args, stride, left, right, dil))
-        elif conv:
-            _lib.check(L.tgcn_cheb_project_series_conv_f32(*args, stride, left, right))
-        else:
-            _lib.check(L.tgcn_cheb_project_series_f32(*args))
-        ctx.geom = (stride, left, right, dil) if dil > 1 else ((stride, left, right) if conv else None)
+        entry = (L.tgcn_cheb_project_series_dilated_f32 if dil > 1 else L.tgcn_cheb_project_series_conv_f32 if ctx.geom
+                 else L.tgcn_cheb_project_series_f32)
+        _lib.check(entry(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind, 1 if as_series else 0,
+                         _lib.ptr(out), *ctx.geom))
         ctx.save_for_backward(Wt)
         ctx.stack = stack if ctx.needs_input_grad[1] else None       # the basis the weight gradient contracts with g
-        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
-        ctx.dims = (S, n, T, f, H, N, K)
-        ctx.bias_shape = None if bias is None else bias.shape
         return out
 
     @staticmethod
@@ -515,8 +543,8 @@ class ChebSeriesFn(torch.autograd.Function):
 
 
 def _series_backward(ctx, Wt, g):
-    """(d series, dW, d bias) of ChebSeriesFn from the gradient g of its output in the forward's layout -- the body ChebSeriesFn.backward and
-    ChebSeriesReluPoolFn.backward share; reads ctx.geom, stack, op, mode, fold, bias_kind, as_series, dims, bias_shape of the forward"""
+    """(d series, dW, d bias) of ChebSeriesFn from the gradient g of its output in the forward's layout -- the body every float32 series
+    Function with a whole hop stack shares; reads ctx.stack and _series_ctx's fields, ctx.geom among them, of the forward"""
     S, n, T, f, H, N, K = ctx.dims
     L = _lib.lib()
     g = _aligned_input(g.float().contiguous())
@@ -525,27 +553,17 @@ def _series_backward(ctx, Wt, g):
     if need_x or need_w:
         G = torch.empty((K, S, n, T * f), dtype=torch.float32, device=g.device) if need_x else None
         dW = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
-        if ctx.geom is None:
-            ws = _workspace(L.tgcn_cheb_series_backward_workspace_bytes(S, n, T, f, H, N, K), g.device, floor=16)
-            _lib.check(L.tgcn_cheb_series_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
-                                                       1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel()))
-        elif len(ctx.geom) == 4:
-            ws = _workspace(L.tgcn_cheb_series_dilated_backward_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
-            _lib.check(L.tgcn_cheb_series_dilated_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
-                                                               1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
-                                                               ws.numel(), *ctx.geom))
-        else:
-            ws = _workspace(L.tgcn_cheb_series_conv_backward_workspace_bytes(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
-            _lib.check(L.tgcn_cheb_series_conv_backward_f32(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g),
-                                                            1 if ctx.as_series else 0, _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws),
-                                                            ws.numel(), *ctx.geom))
+        query, entry = ((L.tgcn_cheb_series_dilated_backward_workspace_bytes, L.tgcn_cheb_series_dilated_backward_f32) if len(ctx.geom) == 4 else
+                        (L.tgcn_cheb_series_conv_backward_workspace_bytes, L.tgcn_cheb_series_conv_backward_f32) if ctx.geom else
+                        (L.tgcn_cheb_series_backward_workspace_bytes, L.tgcn_cheb_series_backward_f32))
+        ws = _workspace(query(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
+        _lib.check(entry(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g), 1 if ctx.as_series else 0, _lib.ptr(Wt),
+                         _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel(), *ctx.geom))
         ctx.stack = None
         if need_x:
             gx = _adjoint_hops(ctx.op.transpose(), G, ctx.mode).reshape(S, n, T, f)
         if need_w:
-            if ctx.fold is not None:
-                dW = fold_weight(ctx.fold, dW, transpose=True)
-            dW = dW.view(K, H, f, N)
+            dW = _series_dW(ctx, dW)
     gb = None
     if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
         gb = _series_bias_grad(g, ctx.as_series, ctx.bias_kind, ctx.bias_shape)
@@ -580,60 +598,58 @@ class ChebSeriesReluPoolFn(torch.autograd.Function):
     (S, n/pool, nwin, N), bit-identical to tgcn_relu_pool_f32 on the unfused output.  Asks tgcn_series_pool_plan before the hops.
     need_idx (the caller's: grad mode and a leaf that requires grad) stores the arg-max bytes; the backward routes gz through them
     (tgcn_relu_pool_bwd_f32 on the forward's layout: q = S*nwin, f = N window-major, q = S, f = nwin*N as a series) and runs ChebSeriesFn's
-    backward body on the result.  Saves z, idx, the working weight, and the stack only if the weight trains."""
+    backward body on the result.  Saves z, idx, the working weight, and the stack only if the weight trains.
+    drop = (seed tensor, thr, scale) puts dropout between relu and the pool (tgcn_cheb_project_series_pool_dropout_f32, csrc/windows.h DROP):
+    z = the max of relu(y) * m, m = scale where dropout.h's mask keeps the element and 0 elsewhere, bit-identical to
+    tgcn_relu_dropout_pool_f32 on the unfused output; neither y nor a mask is ever allocated.  The backward needs no mask: z > 0 implies
+    the arg-max was kept, so gy[arg-max] = z > 0 ? gz * scale : 0 -- gz * scale (fp32), then the backward without one.  ctx.seed is the
+    seed's tensor (z.grad_fn.seed: what a captured step with seed=None drew).
+    One channel runs the MFMA kernels in every geometry: where forward_series itself runs the scalar-load form (ChebWindowsFn: one channel,
+    window-major, default geometry) the bits are those of forward_series(..., as_series=True), permuted."""
 
     @staticmethod
     @_on_device
-    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx):
-        return _series_pool_forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx)
+    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx, drop=None):
+        L = _lib.lib()
+        S, n, T, f = series.shape
+        K, H, _, N = weight_khfg.shape
+        stride, left, right, dil = geom       # (the entries pass all four)
+        nwin = (T + left + right - (H - 1) * dil - 1) // stride + 1
+        hc, lds = C.c_int32(0), C.c_int32(0)
+        _lib.check(L.tgcn_series_pool_plan(H, f, N, int(f % 4 == 0), stride, pool, C.byref(hc), C.byref(lds)))
+        x, fold, Wt, b = _series_operands(series, weight_khfg, bias, mode)
+        x3 = _aligned_input(x.view(S, n, T * f))
+        stack = _series_stack(op, x3, K, mode)   # (K, S, n, T*f)
+        shape = (S, n // pool, nwin, N) if as_series else (S * nwin, n // pool, N)
+        z = torch.empty(shape, dtype=torch.float32, device=x3.device)
+        idx = torch.empty(shape, dtype=torch.uint8, device=x3.device) if need_idx else None
+        args = (_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(z),
+                _lib.ptr(idx), pool, stride, left, right, dil)
+        if drop is None:
+            _lib.check(L.tgcn_cheb_project_series_pool_f32(*args))
+        else:
+            _lib.check(L.tgcn_cheb_project_series_pool_dropout_f32(*args, _lib.ptr(drop[0]), drop[1], drop[2]))
+        ctx.stack = stack if ctx.needs_input_grad[1] else None
+        _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, (S, n, T, f, H, N, K), (stride, left, right, dil),
+                    (Wt, z, idx, pool, nwin, drop))
+        return z
 
     @staticmethod
     @_on_device
     def backward(ctx, gz):
-        return _series_pool_backward(ctx, gz, "cheb_time_windows_relu_pool") + (None,) * 7
-
-
-def _series_pool_forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx, drop=None):
-    """the forward ChebSeriesReluPoolFn and ChebSeriesReluDropoutPoolFn share; drop = (seed tensor, thr, scale) calls the _pool_dropout entry"""
-    L = _lib.lib()
-    S, n, T, f = series.shape
-    K, H, _, N = weight_khfg.shape
-    stride, left, right, dil = _geom4(geom)
-    conv = (stride, left, right) != (1, 0, 0)
-    nwin = (T + left + right - (H - 1) * dil - 1) // stride + 1
-    hc, lds = C.c_int32(0), C.c_int32(0)
-    _lib.check(L.tgcn_series_pool_plan(H, f, N, int(f % 4 == 0), stride, pool, C.byref(hc), C.byref(lds)))
-    x3 = _aligned_input(series.float().contiguous().view(S, n, T * f))
-    W = weight_khfg.float().contiguous().view(K, H * f, N)
-    fold = _power_fold(mode, W)
-    Wt = _working_weight(fold, W)
-    stack = _series_stack(op, x3, K, mode)   # (K, S, n, T*f)
-    shape = (S, n // pool, nwin, N) if as_series else (S * nwin, n // pool, N)
-    z = torch.empty(shape, dtype=torch.float32, device=x3.device)
-    idx = torch.empty(shape, dtype=torch.uint8, device=x3.device) if need_idx else None
-    b = bias.contiguous() if bias is not None else None
-    args = (_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(z),
-            _lib.ptr(idx), pool, stride, left, right, dil)
-    if drop is None:
-        _lib.check(L.tgcn_cheb_project_series_pool_f32(*args))
-    else:
-        _lib.check(L.tgcn_cheb_project_series_pool_dropout_f32(*args, _lib.ptr(drop[0]), drop[1], drop[2]))
-    ctx.geom = (stride, left, right, dil) if dil > 1 else ((stride, left, right) if conv else None)
-    ctx.save_for_backward(Wt, z, idx)
-    ctx.stack = stack if ctx.needs_input_grad[1] else None
-    ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.pool = op, mode, fold, bias_kind, as_series, pool
-    ctx.dims = (S, n, T, f, H, N, K)
-    ctx.nwin = nwin
-    ctx.bias_shape = None if bias is None else bias.shape
-    return z
+        who = "cheb_time_windows_relu_pool" if ctx.scale is None else "cheb_time_windows_relu_dropout_pool"
+        return _series_pool_backward(ctx, gz, who) + (None,) * 8
 
 
 def _series_pool_backward(ctx, gz, who):
-    """(d series, dW, d bias) behind the pooled forward above: gz to the arg-max vertex where z > 0, then ChebSeriesFn's backward body"""
+    """(d series, dW, d bias) behind a pooled forward: gz (times the mask's scale) to the arg-max vertex where z > 0, then ChebSeriesFn's
+    backward body; who names the public entry in the refusal of a forward that kept no arg-max"""
     Wt, z, idx = ctx.saved_tensors
     S, n, T, f, H, N, K = ctx.dims
     if idx is None:
         raise _lib.TgcnError("%s: the forward ran without grad mode and kept no arg-max" % who)
+    if ctx.scale is not None:
+        gz = gz.float() * ctx.scale
     gy = torch.empty((S, n, ctx.nwin, N) if ctx.as_series else (S * ctx.nwin, n, N), dtype=torch.float32, device=gz.device)
     q, fN = (S, ctx.nwin * N) if ctx.as_series else (S * ctx.nwin, N)
     _lib.check(_lib.lib().tgcn_relu_pool_bwd_f32(_lib.stream_ptr(), _lib.ptr(gz.float().contiguous()), _lib.ptr(z), _lib.ptr(idx), _lib.ptr(gy),
@@ -662,26 +678,70 @@ def cheb_time_windows_relu_pool(op, series, weight, bias, bias_kind, mode, pool,
     TgcnError before anything is built or launched: bfloat16 parameters, pool outside {2, 4}, n % pool != 0, and every refusal
     cheb_time_windows makes for the same arguments.  There is no time_chunk: the causal layer in time chunks through this epilogue is
     cheb_time_windows_relu_pool_chunked."""
-    who = "cheb_time_windows_relu_pool"
+    return _series_relu_pool("cheb_time_windows_relu_pool", op, series, weight, bias, bias_kind, mode, pool, as_series, stride, padding, dilation)
+
+
+def _series_relu_pool(who, op, series, weight, bias, bias_kind, mode, pool, as_series, stride, padding, dilation, seed=None, thr=None, scale=None):
+    """cheb_time_windows_relu_pool (thr None: no mask) and, behind its own checks of p and the seed, cheb_time_windows_relu_dropout_pool:
+    seed is the caller's (None, an integer or a tensor) -- the seed tensor of drop = (seed tensor, thr, scale) is made here, once the
+    arguments are accepted"""
     if param_dtype(weight, bias, who) == BF16:
-        raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
+        raise _lib.TgcnError(_POOL_F32_ONLY % who)
+    pool, geom = _series_pool_checks(who, series, weight, pool, stride, padding, dilation)
+    series, weight, need_idx = _series_pool_tensors(series, weight, bias)
+    drop = None if thr is None else (dropout_seed(seed, series.device, who), thr, scale)
+    if not series_pool_is_fused(op, pool):
+        return _series_pool_unfused(op, lambda s, b: ChebSeriesFn.apply(s, weight, b, op, mode, bias_kind, bool(as_series), geom), series, bias,
+                                    bias_kind, pool, drop)
+    return ChebSeriesReluPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, pool, need_idx, drop)
+
+
+def _series_shape_check(who, series, weight):
+    """the ranks and channels of a whole-series call -> f"""
     if series.dim() not in (3, 4) or weight.dim() != series.dim():
         raise _lib.TgcnError("%s: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
                              "(got %s and %s)" % (who, tuple(series.shape), tuple(weight.shape)))
     f = series.shape[3] if series.dim() == 4 else 1
     if series.dim() == 4 and weight.shape[2] != f:
         raise _lib.TgcnError("%s: the series has %d channels, the weight %d" % (who, f, weight.shape[2]))
+    return f
+
+
+_POOL_F32_ONLY = "%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)"     # the pooled entries' refusal
+
+
+def _series_pool_checks(who, series, weight, pool, stride, padding, dilation):
+    """what the four pooled entries ask of their arguments behind the parameters' dtype (_POOL_F32_ONLY; the one-launch entry has its own
+    rule), in this order, before anything is built or launched: ranks and channels, the pool, the geometry
+    -> (pool, (stride, left, right, dilation))"""
+    _series_shape_check(who, series, weight)
     pool = check_pool(pool, series.shape[1], who)
-    geom = series_geometry(series.shape[2], weight.shape[1], stride, padding, who, dilation)[:3] + (series_dilation(weight.shape[1], dilation),)
+    H = weight.shape[1]
+    return pool, series_geometry(series.shape[2], H, stride, padding, who, dilation)[:3] + (series_dilation(H, dilation),)
+
+
+def _series_pool_tensors(series, weight, bias):
+    """the accepted tensors of a pooled entry -> (series, weight) on the device and 4-D, and need_idx: grad mode and a leaf that trains"""
     _lib.require_device(series, weight, bias)
+    need_idx = torch.is_grad_enabled() and (series.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad))
     if series.dim() == 3:
         series, weight = series.unsqueeze(3), weight.unsqueeze(2)
-    if not series_pool_is_fused(op, pool):
-        s2, b2 = _to_operand_labels(op, series, bias, bias_kind)
-        y = ChebSeriesFn.apply(s2, weight, b2, op, mode, bias_kind, bool(as_series), geom)
-        return _relu_pool_view(y if op.perm is None else relabel_rows(y, op.inv_perm, op.perm), pool)
-    need_idx = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (series, weight, bias))
-    return ChebSeriesReluPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, pool, need_idx)
+    return series, weight, need_idx
+
+
+def _in_operand_labels(op, layer, series, bias, bias_kind):
+    """layer(series, bias) -> out around a reordered operand: the rows of the series and of a per-vertex bias to the operand's labels, the
+    output's back to the caller's (the vertex axis is dim 1 in every layout); a plain operand calls the layer as it is"""
+    series, bias = _to_operand_labels(op, series, bias, bias_kind)
+    out = layer(series, bias)
+    return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)
+
+
+def _series_pool_unfused(op, layer, series, bias, bias_kind, pool, drop):
+    """what a pooled entry runs where series_pool_is_fused says no: the unpooled layer in the operand's labels, relabelled back, then relu
+    (+ dropout, drop = (seed tensor, thr, scale)) + pool as one pass on a view"""
+    y = _in_operand_labels(op, layer, series, bias, bias_kind)
+    return _relu_pool_view(y, pool) if drop is None else _relu_dropout_pool_view(y, pool, *drop)
 
 
 # ---- dropout between relu and the pool (DESIGN.md 3.10, "dropout in the relu + pool epilogue")
@@ -739,28 +799,6 @@ def dropout_keep_mask(seed, e0, count, p, device):
     return _dropout_keep(seed_t, int(e0), int(count), thr)
 
 
-class ChebSeriesReluDropoutPoolFn(torch.autograd.Function):
-    """ChebSeriesReluPoolFn with dropout between relu and the pool (tgcn_cheb_project_series_pool_dropout_f32, csrc/windows.h DROP): z =
-    max over `pool` consecutive vertices of relu(y) * m, m = scale where dropout.h's mask keeps the element and 0 elsewhere, bit-identical to
-    tgcn_relu_dropout_pool_f32 on the unfused output; neither y nor a mask is ever allocated.  The backward needs no mask: z > 0 implies
-    the arg-max was kept, so gy[arg-max] = z > 0 ? gz * scale : 0 -- gz * scale (fp32), then ChebSeriesReluPoolFn's backward.
-    As with ChebSeriesReluPoolFn, one channel runs the MFMA kernels in every geometry: where forward_series itself runs the scalar-load
-    form (ChebWindowsFn: one channel, window-major, default geometry) the bits are those of forward_series(..., as_series=True), permuted.
-    Saves z, idx, the working weight, and the stack only if the weight trains; ctx.seed is the seed's tensor (z.grad_fn.seed: what a
-    captured step with seed=None drew)."""
-
-    @staticmethod
-    @_on_device
-    def forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx, seed_t, thr, scale):
-        ctx.scale, ctx.seed = scale, seed_t
-        return _series_pool_forward(ctx, series, weight_khfg, bias, op, mode, bias_kind, as_series, geom, pool, need_idx, drop=(seed_t, thr, scale))
-
-    @staticmethod
-    @_on_device
-    def backward(ctx, gz):
-        return _series_pool_backward(ctx, gz.float() * ctx.scale, "cheb_time_windows_relu_dropout_pool") + (None,) * 10
-
-
 class ReluDropoutPoolFn(torch.autograd.Function):
     """z = max over `pool` consecutive vertices of relu(y) * mask as its own pass (tgcn_relu_dropout_pool_f32 / tgcn_relu_pool_bwd_f32 on
     gz * scale): y (q, n, f) with f = nw * N columns per vertex, column cc = window cc / N, channel cc % N."""
@@ -815,26 +853,7 @@ def cheb_time_windows_relu_dropout_pool(op, series, weight, bias, bias_kind, mod
     if p == 0:
         return cheb_time_windows_relu_pool(op, series, weight, bias, bias_kind, mode, pool, as_series=as_series, stride=stride, padding=padding,
                                            dilation=dilation)
-    if param_dtype(weight, bias, who) == BF16:
-        raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
-    if series.dim() not in (3, 4) or weight.dim() != series.dim():
-        raise _lib.TgcnError("%s: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
-                             "(got %s and %s)" % (who, tuple(series.shape), tuple(weight.shape)))
-    f = series.shape[3] if series.dim() == 4 else 1
-    if series.dim() == 4 and weight.shape[2] != f:
-        raise _lib.TgcnError("%s: the series has %d channels, the weight %d" % (who, f, weight.shape[2]))
-    pool = check_pool(pool, series.shape[1], who)
-    geom = series_geometry(series.shape[2], weight.shape[1], stride, padding, who, dilation)[:3] + (series_dilation(weight.shape[1], dilation),)
-    _lib.require_device(series, weight, bias)
-    if series.dim() == 3:
-        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
-    seed_t = dropout_seed(seed, series.device, who)
-    if not series_pool_is_fused(op, pool):
-        s2, b2 = _to_operand_labels(op, series, bias, bias_kind)
-        y = ChebSeriesFn.apply(s2, weight, b2, op, mode, bias_kind, bool(as_series), geom)
-        return _relu_dropout_pool_view(y if op.perm is None else relabel_rows(y, op.inv_perm, op.perm), pool, seed_t, thr, scale)
-    need_idx = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (series, weight, bias))
-    return ChebSeriesReluDropoutPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, pool, need_idx, seed_t, thr, scale)
+    return _series_relu_pool(who, op, series, weight, bias, bias_kind, mode, pool, as_series, stride, padding, dilation, seed, thr, scale)
 
 
 def check_time_chunk(time_chunk, stride, padding, bf16, who="cheb_time_windows"):
@@ -884,15 +903,10 @@ class ChebSeriesChunkFn(torch.autograd.Function):
         K, H, _, N = weight_khfg.shape
         hc, lds = C.c_int32(0), C.c_int32(0)
         _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), 1, C.byref(hc), C.byref(lds)))
-        x = series.float().contiguous()
-        W = weight_khfg.float().contiguous().view(K, H * f, N)
-        fold = _power_fold(mode, W)
-        Wt = _working_weight(fold, W)
+        x, fold, Wt, b = _series_operands(series, weight_khfg, bias, mode)
         state = SeriesStreamState(op, torch.float32, S, n, f, K, H, dil, x.device)
         out = torch.empty((S, n, T, N) if as_series else (S * T, n, N), dtype=torch.float32, device=x.device)
-        b = bias.contiguous() if bias is not None else None
-        for t0 in range(0, T, time_chunk):
-            tc = min(time_chunk, T - t0)
+        for t0, tc in _time_chunks(T, time_chunk):
             stack = _chunk_stack(op, x, t0, tc, K, mode)
             _lib.check(L.tgcn_cheb_project_series_stream_at_f32(_lib.stream_ptr(), S, n, tc, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b),
                                                                 bias_kind, _lib.ptr(out), T, t0, 1 if as_series else 0, _lib.ptr(state.ring),
@@ -900,49 +914,65 @@ class ChebSeriesChunkFn(torch.autograd.Function):
             state.advance(tc)
             stack = None        # released before the next chunk's is allocated: one chunk tensor at a time
         ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, Wt)
-        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
-        ctx.dims = (S, n, T, f, H, N, K, dil, time_chunk)
-        ctx.bias_shape = None if bias is None else bias.shape
+        _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, (S, n, T, f, H, N, K, dil, time_chunk))
         return out
 
     @staticmethod
     @_on_device
     def backward(ctx, g):
         x, Wt = ctx.saved_tensors
-        S, n, T, f, H, N, K, dil, time_chunk = ctx.dims
-        L = _lib.lib()
+        T, time_chunk = ctx.dims[2], ctx.dims[8]
         g = _aligned_input(g.float().contiguous())
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         gx = dW = None
-        if need_x or need_w:
-            opT = ctx.op.transpose() if need_x else None
-            state = SeriesStreamState(ctx.op, torch.float32, S, n, f, K, H, dil, g.device) if need_w else None
-            gx = torch.empty((S, n, T, f), dtype=torch.float32, device=g.device) if need_x else None
-            for t0 in range(0, T, time_chunk):
-                tc = min(time_chunk, T - t0)
-                stack = _chunk_stack(ctx.op, x, t0, tc, K, ctx.mode) if need_w else None
-                G = torch.empty((K, S, n, tc * f), dtype=torch.float32, device=g.device) if need_x else None
-                dWc = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
-                ws = _workspace(L.tgcn_cheb_series_chunk_backward_workspace_bytes(S, n, tc, f, H, N, K, dil), g.device, floor=16)
-                _lib.check(L.tgcn_cheb_series_chunk_backward_f32(_lib.stream_ptr(), S, n, tc, f, H, N, K, _lib.ptr(stack),
-                                                                 _lib.ptr(state.ring) if need_w else None, state.ring_ld if need_w else 0,
-                                                                 state.head if need_w else 0, _lib.ptr(g), T, t0, 1 if ctx.as_series else 0,
-                                                                 _lib.ptr(Wt) if need_x else None, _lib.ptr(G), _lib.ptr(dWc), _lib.ptr(ws),
-                                                                 ws.numel(), dil))
-                if need_w:
-                    state.advance(tc)
-                    dW = dWc if dW is None else dW.add_(dWc)        # fp32, in chunk order
-                if need_x:
-                    gx[:, :, t0:t0 + tc] = _adjoint_hops(opT, G, ctx.mode).view(S, n, tc, f)
-                stack = G = None        # released before the next chunk's are allocated: two chunk tensors at a time
-            if need_w:
-                if ctx.fold is not None:
-                    dW = fold_weight(ctx.fold, dW, transpose=True)      # the sum un-folded once
-                dW = dW.view(K, H, f, N)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            opT, state, gx = _chunk_backward_start(ctx, g.device)
+            for t0, tc in _time_chunks(T, time_chunk):
+                dW = _chunk_backward_step(ctx, x, Wt, opT, state, g, T, t0, t0, tc, gx, dW)     # g rows [t0, t0 + tc + C) read in place
+            if dW is not None:
+                dW = _series_dW(ctx, dW)
         gb = None
         if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
             gb = _series_bias_grad(g, ctx.as_series, ctx.bias_kind, ctx.bias_shape)
         return gx, dW, gb, None, None, None, None, None, None
+
+
+def _time_chunks(T, time_chunk):
+    """(t0, tc) of the chunks a walk over T time rows takes, in time order: time_chunk rows each, the last one what is left"""
+    return ((t0, min(time_chunk, T - t0)) for t0 in range(0, T, time_chunk))
+
+
+def _chunk_backward_start(ctx, device):
+    """what a backward walk carries from chunk to chunk -> (the transposed operand, a zero ring, d series): the first and the last only
+    when the series needs a gradient, the ring only when the weight does (its dW reads the forward's ring)"""
+    S, n, T, f, H, N, K, dil, _ = ctx.dims
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    return (ctx.op.transpose() if need_x else None,
+            SeriesStreamState(ctx.op, torch.float32, S, n, f, K, H, dil, device) if need_w else None,
+            torch.empty((S, n, T, f), dtype=torch.float32, device=device) if need_x else None)
+
+
+def _chunk_backward_step(ctx, x, Wt, opT, state, g, g_T, g_t0, t0, tc, gx, dW):
+    """One chunk of a backward walk, rows [t0, t0 + tc) of the series x: the hops again if the weight trains (state is not None), one
+    tgcn_cheb_series_chunk_backward_f32 call on the output gradient g of g_T time rows with the chunk's first at row g_t0, the ring's
+    advance, and the adjoint hops into gx[:, :, t0:t0 + tc] if the series needs a gradient (opT is not None).  -> dW plus the chunk's, summed
+    in fp32 in chunk order.  The chunk's stack, G, dWc and workspace are this call's locals: none outlives its chunk."""
+    S, n, T, f, H, N, K, dil, _ = ctx.dims
+    L = _lib.lib()
+    need_x, need_w = opT is not None, state is not None
+    stack = _chunk_stack(ctx.op, x, t0, tc, K, ctx.mode) if need_w else None
+    G = torch.empty((K, S, n, tc * f), dtype=torch.float32, device=g.device) if need_x else None
+    dWc = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
+    ws = _workspace(L.tgcn_cheb_series_chunk_backward_workspace_bytes(S, n, tc, f, H, N, K, dil), g.device, floor=16)
+    _lib.check(L.tgcn_cheb_series_chunk_backward_f32(_lib.stream_ptr(), S, n, tc, f, H, N, K, _lib.ptr(stack),
+                                                     _lib.ptr(state.ring) if need_w else None, state.ring_ld if need_w else 0,
+                                                     state.head if need_w else 0, _lib.ptr(g), g_T, g_t0, 1 if ctx.as_series else 0,
+                                                     _lib.ptr(Wt) if need_x else None, _lib.ptr(G), _lib.ptr(dWc), _lib.ptr(ws), ws.numel(), dil))
+    if need_w:
+        state.advance(tc)
+        dW = dWc if dW is None else dW.add_(dWc)
+    if need_x:
+        gx[:, :, t0:t0 + tc] = _adjoint_hops(opT, G, ctx.mode).view(S, n, tc, f)
+    return dW
 
 
 class ChebSeriesChunkReluPoolFn(torch.autograd.Function):
@@ -969,17 +999,12 @@ class ChebSeriesChunkReluPoolFn(torch.autograd.Function):
         K, H, _, N = weight_khfg.shape
         hc, lds = C.c_int32(0), C.c_int32(0)
         _lib.check(L.tgcn_series_pool_plan(H, f, N, int(f % 4 == 0), 1, pool, C.byref(hc), C.byref(lds)))
-        x = series.float().contiguous()
-        W = weight_khfg.float().contiguous().view(K, H * f, N)
-        fold = _power_fold(mode, W)
-        Wt = _working_weight(fold, W)
+        x, fold, Wt, b = _series_operands(series, weight_khfg, bias, mode)
         state = SeriesStreamState(op, torch.float32, S, n, f, K, H, dil, x.device)
         shape = (S, n // pool, T, N) if as_series else (S * T, n // pool, N)
         z = torch.empty(shape, dtype=torch.float32, device=x.device)
         idx = torch.empty(shape, dtype=torch.uint8, device=x.device) if need_idx else None
-        b = bias.contiguous() if bias is not None else None
-        for t0 in range(0, T, time_chunk):
-            tc = min(time_chunk, T - t0)
+        for t0, tc in _time_chunks(T, time_chunk):
             stack = _chunk_stack(op, x, t0, tc, K, mode)
             _lib.check(L.tgcn_cheb_project_series_stream_pool_at_f32(_lib.stream_ptr(), S, n, tc, f, H, N, K, _lib.ptr(stack), _lib.ptr(Wt), _lib.ptr(b),
                                                                      bias_kind, _lib.ptr(z), _lib.ptr(idx), pool, T, t0, 1 if as_series else 0,
@@ -987,10 +1012,8 @@ class ChebSeriesChunkReluPoolFn(torch.autograd.Function):
             state.advance(tc)
             stack = None        # released before the next chunk's is allocated: one chunk tensor at a time
         ctx.save_for_backward(x if ctx.needs_input_grad[1] else None, Wt, z, idx)
-        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.pool = op, mode, fold, bias_kind, as_series, pool
-        ctx.dims = (S, n, T, f, H, N, K, dil, time_chunk)
-        ctx.scale, ctx.seed = scale, seed_t
-        ctx.bias_shape = None if bias is None else bias.shape
+        ctx.pool, ctx.scale, ctx.seed = pool, scale, seed_t
+        _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, (S, n, T, f, H, N, K, dil, time_chunk))
         return z
 
     @staticmethod
@@ -1002,36 +1025,17 @@ class ChebSeriesChunkReluPoolFn(torch.autograd.Function):
             raise _lib.TgcnError("cheb_time_windows_relu_pool_chunked: the forward ran without grad mode and kept no arg-max")
         L = _lib.lib()
         gz = gz.float().contiguous()
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         need_b = ctx.bias_shape is not None and ctx.needs_input_grad[2]
         Cr = (H - 1) * dil
-        gx = dW = gb = None
-        opT = ctx.op.transpose() if need_x else None
-        state = SeriesStreamState(ctx.op, torch.float32, S, n, f, K, H, dil, gz.device) if need_w else None
-        if need_x:
-            gx = torch.empty((S, n, T, f), dtype=torch.float32, device=gz.device)
-        for t0 in range(0, T, time_chunk):
-            tc = min(time_chunk, T - t0)
+        dW = gb = None
+        opT, state, gx = _chunk_backward_start(ctx, gz.device)
+        for t0, tc in _time_chunks(T, time_chunk):
             rows = min(tc + Cr, T - t0)
             slab = torch.empty((S, n, rows, N) if ctx.as_series else (S * rows, n, N), dtype=torch.float32, device=gz.device)
             _lib.check(L.tgcn_relu_pool_bwd_rows_f32(_lib.stream_ptr(), _lib.ptr(gz), _lib.ptr(z), _lib.ptr(idx), _lib.ptr(slab), S, n, T, t0, rows, N,
                                                      ctx.pool, 1 if ctx.as_series else 0, ctx.scale))
-            if need_x or need_w:
-                stack = _chunk_stack(ctx.op, x, t0, tc, K, ctx.mode) if need_w else None
-                G = torch.empty((K, S, n, tc * f), dtype=torch.float32, device=gz.device) if need_x else None
-                dWc = torch.empty((K, H * f, N), dtype=torch.float32, device=gz.device) if need_w else None
-                ws = _workspace(L.tgcn_cheb_series_chunk_backward_workspace_bytes(S, n, tc, f, H, N, K, dil), gz.device, floor=16)
-                _lib.check(L.tgcn_cheb_series_chunk_backward_f32(_lib.stream_ptr(), S, n, tc, f, H, N, K, _lib.ptr(stack),
-                                                                 _lib.ptr(state.ring) if need_w else None, state.ring_ld if need_w else 0,
-                                                                 state.head if need_w else 0, _lib.ptr(slab), rows, 0, 1 if ctx.as_series else 0,
-                                                                 _lib.ptr(Wt) if need_x else None, _lib.ptr(G), _lib.ptr(dWc), _lib.ptr(ws),
-                                                                 ws.numel(), dil))
-                if need_w:
-                    state.advance(tc)
-                    dW = dWc if dW is None else dW.add_(dWc)        # fp32, in chunk order
-                if need_x:
-                    gx[:, :, t0:t0 + tc] = _adjoint_hops(opT, G, ctx.mode).view(S, n, tc, f)
-                stack = G = None
+            if opT is not None or state is not None:
+                dW = _chunk_backward_step(ctx, x, Wt, opT, state, slab, rows, 0, t0, tc, gx, dW)      # the slab is the whole gradient it reads
             if need_b:      # rows [0, tc) only: the halo rows are the next chunk's own
                 own = slab[:, :, :tc] if ctx.as_series else slab.view(S, rows, n, N)[:, :tc]
                 if ctx.bias_kind == BIAS_CHANNEL:
@@ -1039,11 +1043,9 @@ class ChebSeriesChunkReluPoolFn(torch.autograd.Function):
                 else:
                     part = own.sum(dim=(0, 2)) if ctx.as_series else own.sum(dim=(0, 1))
                 gb = part if gb is None else gb.add_(part)
-            slab = own = ws = None      # released before the next chunk's are allocated: one slab at a time (own is a view of it)
-        if need_w:
-            if ctx.fold is not None:
-                dW = fold_weight(ctx.fold, dW, transpose=True)      # the sum un-folded once
-            dW = dW.view(K, H, f, N)
+            slab = own = None      # released before the next chunk's is allocated: one slab at a time (own is a view of it)
+        if dW is not None:
+            dW = _series_dW(ctx, dW)
         if gb is not None:
             gb = gb.reshape(ctx.bias_shape)
         return (gx, dW, gb) + (None,) * 11
@@ -1068,34 +1070,20 @@ def cheb_time_windows_relu_pool_chunked(op, series, weight, bias, bias_kind, mod
     who = "cheb_time_windows_relu_pool_chunked"
     thr, scale = dropout_params(p, who)
     dropout_seed(seed, series.device, who, draw=False)
-    bf16 = param_dtype(weight, bias, who) == BF16
-    if bf16:
-        raise _lib.TgcnError("%s: bfloat16 parameters are not supported (run the layer, then gcn_pool / gcn_pool_4)" % who)
+    if param_dtype(weight, bias, who) == BF16:
+        raise _lib.TgcnError(_POOL_F32_ONLY % who)
     if time_chunk is None:
         raise _lib.TgcnError("%s: time_chunk is None or an integer >= 1, got None -- without chunks this is cheb_time_windows_relu_pool / "
                              "cheb_time_windows_relu_dropout_pool" % who)
-    time_chunk = check_time_chunk(time_chunk, 1, "causal", bf16, who)
-    if series.dim() not in (3, 4) or weight.dim() != series.dim():
-        raise _lib.TgcnError("%s: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
-                             "(got %s and %s)" % (who, tuple(series.shape), tuple(weight.shape)))
-    f = series.shape[3] if series.dim() == 4 else 1
-    if series.dim() == 4 and weight.shape[2] != f:
-        raise _lib.TgcnError("%s: the series has %d channels, the weight %d" % (who, f, weight.shape[2]))
-    pool = check_pool(pool, series.shape[1], who)
-    series_geometry(series.shape[2], weight.shape[1], 1, "causal", who, dilation)
-    dil = series_dilation(weight.shape[1], dilation)
-    _lib.require_device(series, weight, bias)
-    if series.dim() == 3:
-        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
-    seed_t = dropout_seed(seed, series.device, who) if p != 0 else None
+    time_chunk = check_time_chunk(time_chunk, 1, "causal", False, who)
+    pool, geom = _series_pool_checks(who, series, weight, pool, 1, "causal", dilation)
+    series, weight, need_idx = _series_pool_tensors(series, weight, bias)
+    seed_t = dropout_seed(seed, series.device, who) if p != 0 else None       # (p == 0: thr = 0 and scale = 1 already)
     if not series_pool_is_fused(op, pool):
-        s2, b2 = _to_operand_labels(op, series, bias, bias_kind)
-        y = ChebSeriesChunkFn.apply(s2, weight, b2, op, mode, bias_kind, bool(as_series), dil, time_chunk)
-        y = y if op.perm is None else relabel_rows(y, op.inv_perm, op.perm)
-        return _relu_pool_view(y, pool) if seed_t is None else _relu_dropout_pool_view(y, pool, seed_t, thr, scale)
-    need_idx = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (series, weight, bias))
-    return ChebSeriesChunkReluPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), dil, time_chunk, pool, need_idx, seed_t,
-                                           thr if seed_t is not None else 0, scale if seed_t is not None else 1.0)
+        return _series_pool_unfused(op, lambda s, b: ChebSeriesChunkFn.apply(s, weight, b, op, mode, bias_kind, bool(as_series), geom[3], time_chunk),
+                                    series, bias, bias_kind, pool, None if seed_t is None else (seed_t, thr, scale))
+    return ChebSeriesChunkReluPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom[3], time_chunk, pool, need_idx, seed_t,
+                                           thr, scale)
 
 
 # fused="auto" fuses the shape classes listed here.  A call's class is what its UNFUSED form would be: "windows_f1" -- a single channel,
@@ -1185,21 +1173,14 @@ class ChebSeriesSmallFn(torch.autograd.Function):
         K, H, _, N = weight_khfg.shape
         _, left, right, dil = geom
         nwin = T + left + right - (H - 1) * dil
-        x3 = series.float().contiguous().view(S, n, T * f)
-        W = weight_khfg.float().contiguous().view(K, H * f, N)
-        fold = _power_fold(mode, W)
-        Wt = _working_weight(fold, W)
-        out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=torch.float32, device=x3.device)
-        stack = torch.empty((K, S, n, T * f), dtype=torch.float32, device=x3.device) if need_stack else None
-        b = bias.float().contiguous() if bias is not None else None
-        _lib.check(L.tgcn_cheb_series_small_f32(_lib.stream_ptr(), C.byref(op.struct), int(mode), S, T, f, H, N, K, _lib.ptr(x3), _lib.ptr(Wt),
+        x, fold, Wt, b = _series_operands(series, weight_khfg, bias, mode)
+        out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=torch.float32, device=x.device)
+        stack = torch.empty((K, S, n, T * f), dtype=torch.float32, device=x.device) if need_stack else None
+        _lib.check(L.tgcn_cheb_series_small_f32(_lib.stream_ptr(), C.byref(op.struct), int(mode), S, T, f, H, N, K, _lib.ptr(x), _lib.ptr(Wt),
                                                 _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(out), _lib.ptr(stack), left, right, dil))
-        ctx.geom = (1, left, right, dil) if dil > 1 else ((1, left, right) if (left, right) != (0, 0) else None)
         ctx.save_for_backward(Wt)
         ctx.stack = stack
-        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
-        ctx.dims = (S, n, T, f, H, N, K)
-        ctx.bias_shape = None if bias is None else bias.shape
+        _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, (S, n, T, f, H, N, K), (1, left, right, dil))
         return out
 
     @staticmethod
@@ -1242,46 +1223,30 @@ def cheb_time_windows(op, series, weight, bias, bias_kind, mode=MODE_POWER, as_s
     bf16 = param_dtype(weight, bias, "cheb_time_windows") == BF16
     fused = check_series_fused(fused, stride, time_chunk, bf16)
     time_chunk = check_time_chunk(time_chunk, stride, padding, bf16)
-    if series.dim() not in (3, 4) or weight.dim() != series.dim():
-        raise _lib.TgcnError("cheb_time_windows: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
-                             "(got %s and %s)" % (tuple(series.shape), tuple(weight.shape)))
-    f = series.shape[3] if series.dim() == 4 else 1
-    if series.dim() == 4 and weight.shape[2] != f:
-        raise _lib.TgcnError("cheb_time_windows: the series has %d channels, the weight %d" % (f, weight.shape[2]))
+    f = _series_shape_check("cheb_time_windows", series, weight)
     geom = series_geometry(series.shape[2], weight.shape[1], stride, padding, dilation=dilation)[:3] + (series_dilation(weight.shape[1], dilation),)
     if bf16:
         check_series_bf16(f, as_series, geom, series.dtype)
     if fused is not False:
         fused = _series_fused_route(op, fused, bf16, time_chunk, geom, bool(as_series), f, weight.shape[1], weight.shape[-1], weight.shape[0], series.shape[2], mode)
     _lib.require_device(series, weight, bias)
+    if not (fused or bf16) and time_chunk is None and f == 1 and not as_series and geom == (1, 0, 0, 1):      # the scalar-load form, on 3-D tensors
+        if series.dim() == 4:
+            series, weight = series.reshape(series.shape[:3]), weight.reshape(weight.shape[0], weight.shape[1], weight.shape[3])
+        return _in_operand_labels(op, lambda s, b: ChebWindowsFn.apply(s, weight, b, op, mode, bias_kind), series, bias, bias_kind)
+    if series.dim() == 3:
+        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
     if fused:
-        if series.dim() == 3:
-            series, weight = series.unsqueeze(3), weight.unsqueeze(2)
         need_stack = torch.is_grad_enabled() and weight.requires_grad       # the only reader of the stack is the weight gradient
         return ChebSeriesSmallFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, need_stack)
     if bf16:
-        if series.dim() == 3:
-            series, weight = series.unsqueeze(3), weight.unsqueeze(2)
-        series, bias = _to_operand_labels(op, series, bias, bias_kind)      # (the relabelling kernel is fp32: bf16 values pass through it exactly)
-        out = ChebSeriesBf16Fn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom)
-        return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm).to(BF16)
-    if time_chunk is not None:
-        if series.dim() == 3:
-            series, weight = series.unsqueeze(3), weight.unsqueeze(2)
-        series, bias = _to_operand_labels(op, series, bias, bias_kind)
-        out = ChebSeriesChunkFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom[3], time_chunk)
-        return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)
-    if f == 1 and not as_series and geom == (1, 0, 0, 1):
-        if series.dim() == 4:
-            series, weight = series.reshape(series.shape[:3]), weight.reshape(weight.shape[0], weight.shape[1], weight.shape[3])
-        series, bias = _to_operand_labels(op, series, bias, bias_kind)
-        out = ChebWindowsFn.apply(series, weight, bias, op, mode, bias_kind)
-        return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)
-    if series.dim() == 3:
-        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
-    series, bias = _to_operand_labels(op, series, bias, bias_kind)
-    out = ChebSeriesFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom)
-    return out if op.perm is None else relabel_rows(out, op.inv_perm, op.perm)      # the vertex axis is dim 1 in both layouts
+        layer = lambda s, b: ChebSeriesBf16Fn.apply(s, weight, b, op, mode, bias_kind, bool(as_series), geom)
+    elif time_chunk is not None:
+        layer = lambda s, b: ChebSeriesChunkFn.apply(s, weight, b, op, mode, bias_kind, bool(as_series), geom[3], time_chunk)
+    else:
+        layer = lambda s, b: ChebSeriesFn.apply(s, weight, b, op, mode, bias_kind, bool(as_series), geom)
+    out = _in_operand_labels(op, layer, series, bias, bias_kind)
+    return out.to(BF16) if bf16 and op.perm is not None else out      # (the relabelling kernel is fp32: bf16 values pass through it exactly)
 
 
 # ---- relu (+ dropout) + pool in the one-launch series layer ("relu + pool in the one-launch series layer")
@@ -1296,7 +1261,9 @@ SERIES_POOL_FUSED_AUTO = ()
 def series_pool_fused_supported(op, f, H, N, K, T, padding, dilation, mode, pool):
     """True where cheb_time_windows_relu_pool_fused(..., fused=True) runs: series_fused_supported's rules plus the pool's -- 2 or 4
     consecutive vertices, dividing the graph.  A host query: nothing launches."""
-    if not isinstance(pool, numbers.Integral) or isinstance(pool, bool) or pool not in (2, 4) or op.n % pool:
+    try:
+        check_pool(pool, op.n, "series_pool_fused_supported")
+    except _lib.TgcnError:
         return False
     return series_fused_supported(op, f, H, N, K, T, padding, dilation, mode)
 
@@ -1319,34 +1286,22 @@ class ChebSeriesSmallReluPoolFn(torch.autograd.Function):
         K, H, _, N = weight_khfg.shape
         _, left, right, dil = geom
         nwin = T + left + right - (H - 1) * dil
-        x3 = series.float().contiguous().view(S, n, T * f)
-        W = weight_khfg.float().contiguous().view(K, H * f, N)
-        fold = _power_fold(mode, W)
-        Wt = _working_weight(fold, W)
+        x, fold, Wt, b = _series_operands(series, weight_khfg, bias, mode)
         shape = (S, n // pool, nwin, N) if as_series else (S * nwin, n // pool, N)
-        z = torch.empty(shape, dtype=torch.float32, device=x3.device)
-        idx = torch.empty(shape, dtype=torch.uint8, device=x3.device) if need_idx else None
-        stack = torch.empty((K, S, n, T * f), dtype=torch.float32, device=x3.device) if need_stack else None
-        b = bias.float().contiguous() if bias is not None else None
+        z = torch.empty(shape, dtype=torch.float32, device=x.device)
+        idx = torch.empty(shape, dtype=torch.uint8, device=x.device) if need_idx else None
+        stack = torch.empty((K, S, n, T * f), dtype=torch.float32, device=x.device) if need_stack else None
         seed_t, thr, scale = drop if drop is not None else (None, 0, 1.0)
-        _lib.check(L.tgcn_cheb_series_small_pool_f32(_lib.stream_ptr(), C.byref(op.struct), int(mode), S, T, f, H, N, K, _lib.ptr(x3), _lib.ptr(Wt),
+        _lib.check(L.tgcn_cheb_series_small_pool_f32(_lib.stream_ptr(), C.byref(op.struct), int(mode), S, T, f, H, N, K, _lib.ptr(x), _lib.ptr(Wt),
                                                      _lib.ptr(b), bias_kind, 1 if as_series else 0, _lib.ptr(z), _lib.ptr(idx), pool,
                                                      _lib.ptr(stack), left, right, dil, _lib.ptr(seed_t), thr, scale))
-        ctx.geom = (1, left, right, dil) if dil > 1 else ((1, left, right) if (left, right) != (0, 0) else None)
-        ctx.save_for_backward(Wt, z, idx)
         ctx.stack = stack
-        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.pool = op, mode, fold, bias_kind, as_series, pool
-        ctx.dims = (S, n, T, f, H, N, K)
-        ctx.nwin = nwin
-        ctx.bias_shape = None if bias is None else bias.shape
-        ctx.scale, ctx.seed = (None, None) if drop is None else (scale, seed_t)
+        _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, (S, n, T, f, H, N, K), (1, left, right, dil), (Wt, z, idx, pool, nwin, drop))
         return z
 
     @staticmethod
     @_on_device
     def backward(ctx, gz):
-        if ctx.scale is not None:
-            gz = gz.float() * ctx.scale
         return _series_pool_backward(ctx, gz, "cheb_time_windows_relu_pool_fused") + (None,) * 9
 
 
@@ -1375,15 +1330,8 @@ def cheb_time_windows_relu_pool_fused(op, series, weight, bias, bias_kind, mode,
         raise _lib.TgcnError("%s: fused=True runs in float32 only -- the parameters are bfloat16" % who)
     run = not bf16
     if run:
-        if series.dim() not in (3, 4) or weight.dim() != series.dim():
-            raise _lib.TgcnError("%s: a (S, n, T) series takes a (K, H, N) weight and a (S, n, T, f) series a (K, H, f, N) weight "
-                                 "(got %s and %s)" % (who, tuple(series.shape), tuple(weight.shape)))
-        f = series.shape[3] if series.dim() == 4 else 1
-        if series.dim() == 4 and weight.shape[2] != f:
-            raise _lib.TgcnError("%s: the series has %d channels, the weight %d" % (who, f, weight.shape[2]))
-        pool = check_pool(pool, series.shape[1], who)
-        K, H, N, T = weight.shape[0], weight.shape[1], weight.shape[-1], series.shape[2]
-        geom = series_geometry(T, H, 1, padding, who, dilation)[:3] + (series_dilation(H, dilation),)
+        pool, geom = _series_pool_checks(who, series, weight, pool, 1, padding, dilation)
+        f, K, H, N, T = series.shape[3] if series.dim() == 4 else 1, weight.shape[0], weight.shape[1], weight.shape[-1], series.shape[2]
         if fused is True:
             if op.n_cols != op.n:
                 raise _lib.TgcnError("%s: fused=True needs a square operand, got %d x %d" % (who, op.n, op.n_cols))
@@ -1401,14 +1349,10 @@ def cheb_time_windows_relu_pool_fused(op, series, weight, bias, bias_kind, mode,
                                                dilation=dilation)
         return cheb_time_windows_relu_dropout_pool(op, series, weight, bias, bias_kind, mode, pool, p, seed, as_series=as_series, padding=padding,
                                                    dilation=dilation)
-    _lib.require_device(series, weight, bias)
-    if series.dim() == 3:
-        series, weight = series.unsqueeze(3), weight.unsqueeze(2)
+    series, weight, need_idx = _series_pool_tensors(series, weight, bias)
     drop = None if p == 0 else (dropout_seed(seed, series.device, who), thr, scale)
-    grad = torch.is_grad_enabled()
-    need_idx = grad and any(t is not None and t.requires_grad for t in (series, weight, bias))
     return ChebSeriesSmallReluPoolFn.apply(series, weight, bias, op, mode, bias_kind, bool(as_series), geom, pool, need_idx,
-                                           grad and weight.requires_grad, drop)
+                                           torch.is_grad_enabled() and weight.requires_grad, drop)
 
 
 @_on_device
@@ -1764,7 +1708,8 @@ def fold_weight(fold, W, transpose=False):
 
 
 def _power_fold(mode, W_kcn):
-    """fold matrix of a (K, C, N) reference-basis weight for MODE_POWER with K > 2, else None (the two bases agree)"""
+    """fold matrix of a (K, C, N) reference-basis weight for MODE_POWER with K > 2, else None (the two bases agree).  _series_operands
+    writes this rule and _working_weight's out in place (it runs at 0.3 ms per call): a change here is a change there"""
     return power_fold_matrix(W_kcn.shape[0], W_kcn.device) if (mode == MODE_POWER and W_kcn.shape[0] > 2) else None
 
 

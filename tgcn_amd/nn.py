@@ -668,6 +668,18 @@ def _series_pool_bias(layer):
     return layer.bias, F.BIAS_NONE if layer.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV
 
 
+def _series_pool_call(layer, series, graph_args, who, pool, stride, padding, dilation, edges=None):
+    """((op, series, weight, bias, bias_kind, mode), (stride, left, right, dilation)): how an F.cheb_time_windows_relu_* call begins, and the
+    checked geometry for its keywords -- behind the layer's, the pool's and forward_series' refusals, the operand built last; edges is
+    _series_pool_layer's answer where the wrapper has asked already"""
+    edge_index, edge_weight = edges if edges is not None else _series_pool_layer(layer, graph_args, who)
+    if series.dim() in (3, 4):
+        F.check_pool(pool, series.shape[1], who)
+    series, W, geom = _series_args(layer, series, stride, padding, dilation)
+    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
+    return (op, series, W) + _series_pool_bias(layer), geom
+
+
 def cheb_series_relu_pool(layer, series, *graph_args, pool=4, as_series=False, stride=1, padding=0, dilation=1):
     """gcn_pool_4(F.relu(layer.forward_series(series, ...)))  (pool=4; pool=2: gcn_pool)  in one fused op -- the caller pattern of
     cheb_relu_pool for the streaming time-window layers.  layer is a TGCNCheb_H or a ChebTimeConv, graph_args are ChebTimeConv's
@@ -681,15 +693,8 @@ def cheb_series_relu_pool(layer, series, *graph_args, pool=4, as_series=False, s
     TgcnError before an operand is built: bfloat16 parameters, pool outside {2, 4}, n % pool != 0, a learnable edge_weight, and every
     refusal forward_series makes for the same arguments.  No time_chunk: the causal layer in time chunks through this epilogue is
     cheb_series_relu_pool_chunked."""
-    who = "cheb_series_relu_pool"
-    edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
-    if series.dim() in (3, 4):
-        F.check_pool(pool, series.shape[1], who)
-    series, W, geom = _series_args(layer, series, stride, padding, dilation)
-    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
-    bias, bias_kind, mode = _series_pool_bias(layer)
-    return F.cheb_time_windows_relu_pool(op, series, W, bias, bias_kind, mode, pool, as_series=as_series, stride=geom[0], padding=geom[1:3],
-                                         dilation=geom[3])
+    args, geom = _series_pool_call(layer, series, graph_args, "cheb_series_relu_pool", pool, stride, padding, dilation)
+    return F.cheb_time_windows_relu_pool(*args, pool, as_series=as_series, stride=geom[0], padding=geom[1:3], dilation=geom[3])
 
 
 def cheb_series_relu_dropout_pool(layer, series, *graph_args, p=0.5, pool=4, training=True, seed=None, as_series=False, stride=1, padding=0,
@@ -715,14 +720,8 @@ def cheb_series_relu_dropout_pool(layer, series, *graph_args, p=0.5, pool=4, tra
         F.dropout_seed(seed, series.device, who, draw=False)
     if not training or p == 0:
         return cheb_series_relu_pool(layer, series, *graph_args, pool=pool, as_series=as_series, stride=stride, padding=padding, dilation=dilation)
-    edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
-    if series.dim() in (3, 4):
-        F.check_pool(pool, series.shape[1], who)
-    series, W, geom = _series_args(layer, series, stride, padding, dilation)
-    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
-    bias, bias_kind, mode = _series_pool_bias(layer)
-    return F.cheb_time_windows_relu_dropout_pool(op, series, W, bias, bias_kind, mode, pool, p, seed, as_series=as_series, stride=geom[0],
-                                                 padding=geom[1:3], dilation=geom[3])
+    args, geom = _series_pool_call(layer, series, graph_args, who, pool, stride, padding, dilation)
+    return F.cheb_time_windows_relu_dropout_pool(*args, pool, p, seed, as_series=as_series, stride=geom[0], padding=geom[1:3], dilation=geom[3])
 
 
 def cheb_series_relu_pool_chunked(layer, series, *graph_args, time_chunk, pool=4, p=0.0, training=True, seed=None, as_series=False, dilation=1):
@@ -744,18 +743,14 @@ def cheb_series_relu_pool_chunked(layer, series, *graph_args, time_chunk, pool=4
     F.dropout_params(p, who)
     if isinstance(series, torch.Tensor):
         F.dropout_seed(seed, series.device, who, draw=False)
-    edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
+    edges = _series_pool_layer(layer, graph_args, who)       # the layer's refusals come ahead of time_chunk's
     if time_chunk is None:
         raise _lib.TgcnError("%s: time_chunk is an integer >= 1, got None -- without chunks this is cheb_series_relu_pool / "
                              "cheb_series_relu_dropout_pool" % who)
     F.check_time_chunk(time_chunk, 1, "causal", False, who)
-    if series.dim() in (3, 4):
-        F.check_pool(pool, series.shape[1], who)
-    series, W, geom = _series_args(layer, series, 1, "causal", dilation)
-    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
-    bias, bias_kind, mode = _series_pool_bias(layer)
-    return F.cheb_time_windows_relu_pool_chunked(op, series, W, bias, bias_kind, mode, pool, time_chunk, p=p if training else 0.0, seed=seed,
-                                                 as_series=as_series, dilation=geom[3])
+    args, geom = _series_pool_call(layer, series, graph_args, who, pool, 1, "causal", dilation, edges)
+    return F.cheb_time_windows_relu_pool_chunked(*args, pool, time_chunk, p=p if training else 0.0, seed=seed, as_series=as_series,
+                                                 dilation=geom[3])
 
 
 def cheb_series_relu_pool_fused(layer, series, *graph_args, pool=4, p=0.0, training=True, seed=None, as_series=False, padding=0, dilation=1,
@@ -778,14 +773,9 @@ def cheb_series_relu_pool_fused(layer, series, *graph_args, pool=4, p=0.0, train
     F.dropout_params(p, who)
     if isinstance(series, torch.Tensor):
         F.dropout_seed(seed, series.device, who, draw=False)
-    edge_index, edge_weight = _series_pool_layer(layer, graph_args, who)
-    if series.dim() in (3, 4):
-        F.check_pool(pool, series.shape[1], who)
-    series, W, geom = _series_args(layer, series, 1, padding, dilation)
-    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
-    bias, bias_kind, mode = _series_pool_bias(layer)
-    return F.cheb_time_windows_relu_pool_fused(op, series, W, bias, bias_kind, mode, pool, p=p if training else 0.0, seed=seed, as_series=as_series,
-                                               padding=geom[1:3], dilation=geom[3], fused=fused)
+    args, geom = _series_pool_call(layer, series, graph_args, who, pool, 1, padding, dilation)
+    return F.cheb_time_windows_relu_pool_fused(*args, pool, p=p if training else 0.0, seed=seed, as_series=as_series, padding=geom[1:3],
+                                               dilation=geom[3], fused=fused)
 
 
 def cheb_relu_dropout_pool(layer, x, *graph_args, p=0.5, pool=4, training=True, seed=None):

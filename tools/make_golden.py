@@ -5,6 +5,7 @@ Usage (from anywhere, reference mounted read-only at /root/reference):
 
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [--ref /root/reference] [--out tests/golden]
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py --series-refusals      (tests/test_series_refusal_table.py; needs no reference)
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py --series-host-calls    (tests/test_series_host_table.py; no reference, no library)
 
 What is executed from the reference (nothing is copied; only inputs/outputs are stored):
   * gcn.graph            grid / distance_sklearn_metrics / adjacency / laplacian / rescale_L / chebyshev
@@ -85,6 +86,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden"))
     ap.add_argument("--series-refusals", action="store_true",
                     help="only record tests/golden/series_refusals_abi8.json from the built library (no reference, no device)")
+    ap.add_argument("--series-host-calls", action="store_true",
+                    help="only record tests/golden/series_host_calls.json: what the time-window host side logs (no reference, device or library)")
     args = ap.parse_args()
     out_dir = os.path.abspath(args.out)
     os.makedirs(out_dir, exist_ok=True)
@@ -97,6 +100,14 @@ def main():
         assert _lib.ABI_VERSION == 8, "the recording belongs to the ABI 8 library"
         with open(os.path.join(out_dir, "series_refusals_abi8.json"), "w") as f:
             json.dump(rt.table(_lib.lib()), f, separators=(",", ":"))
+        return
+    if args.series_host_calls:     # the grid and the recorder are tests/test_series_host_table.py's
+        import json
+        root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+        sys.path[:0] = [root, os.path.join(root, "tests")]
+        import test_series_host_table as ht
+        with open(os.path.join(out_dir, "series_host_calls.json"), "w") as f:
+            json.dump(ht.table(), f, separators=(",", ":"))
         return
 
     sys.dont_write_bytecode = True
