@@ -208,6 +208,15 @@ def _sched_build_library(self, rowptr, n, lanes_per_row, edges, n_cols):
 Schedule._build_library = _sched_build_library
 
 
+def _no_build_in_capture(what):
+    """TgcnError where an operand's lazily built part would be built while the current stream records a hipGraph: the build reads counts
+    back from the device, which a capture forbids.  Asked on a miss only, so a built part costs nothing."""
+    if torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing():
+        raise _lib.TgcnError("tgcn_amd: the operand's %s would have to be built while the current stream is capturing a hipGraph, and the "
+                             "build synchronises -- it has to be built by a warm-up step (forward and backward) on the same graph arguments "
+                             "before the capture begins" % what)
+
+
 def _spread_hot_block(perm, n_live):
     """Hub-first order without the hub pile-up: the first H = 2^floor(log2(n_live / 8)) positions of a degree-sorted order (the hot block: on the
     10 M / 160 M R-MAT 524,288 vertices that take 84 % of the gathers) are visited in BIT-REVERSED order, the rest stays sorted.  A plain
@@ -330,6 +339,7 @@ class GraphOperand:
             if kind not in self._compact:
                 plan = None
                 if self.n == self.n_cols and self.n >= COMPACT_MIN_ROWS and self.nnz > 0:
+                    _no_build_in_capture("compact plan")
                     keep = self.rowptr[1:] > self.rowptr[:-1]
                     shared = False
                     if kind == "closed":
@@ -595,6 +605,7 @@ class GraphOperand:
 
     def _transpose_locked(self):
         if self._transpose is None:
+            _no_build_in_capture("transpose (the backward's operand)")
             row, col, val = self.coo()
             # a rectangular operand (vertex shard: n owned rows x n_cols owned + halo columns) transposes to n_cols x n
             self._transpose = GraphOperand.from_coo(self.n_cols, col, row, val, self.device, n_cols=self.n)

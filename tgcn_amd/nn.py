@@ -66,12 +66,23 @@ class _OperandCache:
         with self._lock:
             hit = self._d.get(key)
             if hit is None:
+                if F.stream_is_capturing():       # a build synchronises (and allocates outside torch): not inside a hipGraph capture
+                    raise _lib.TgcnError(_BUILD_IN_CAPTURE)
                 hit = self._d[key] = (build(), tuple(sources))
                 while len(self._d) > self.MAX_ENTRIES:        # evict the least recently used entry only: the others keep their operands
                     self._d.popitem(last=False)
             else:
                 self._d.move_to_end(key)
             return hit[0]
+
+
+_BUILD_IN_CAPTURE = ("tgcn_amd: a graph operand would have to be built while the current stream is capturing a hipGraph, and the build "
+                     "synchronises -- the operand has to be built by a warm-up step on the same graph arguments (the same L / edge_index / "
+                     "edge_weight objects, unchanged) before the capture begins")
+_LEARNABLE_IN_CAPTURE = ("tgcn_amd: learnable edge weights (edge_weight.requires_grad) cannot run inside a hipGraph capture -- the operand's "
+                         "values are re-packed from the weight by host-driven passes that synchronise, and a replay would not repeat them; "
+                         "train edge weights with the eager step")
+_warmup_notes = None      # a list while a GraphedTrainStep warm-up runs: what the step did that a capture cannot (graphed.py reads it)
 
 
 def _np_fingerprint(L):
@@ -340,6 +351,10 @@ def _refresh_values(op, weight, make_vals):
     alive -- a freed weight's address can be handed to the next one, version 0 again -- so the operand holds the detached alias of the tensor it
     was packed from (shares storage and version counter, keeps no autograd graph): same address then means same storage, and its version counter
     says whether it was written."""
+    if _warmup_notes is not None:
+        _warmup_notes.append(_LEARNABLE_IN_CAPTURE)
+    if F.stream_is_capturing():
+        raise _lib.TgcnError(_LEARNABLE_IN_CAPTURE)
     stamp = _stamp(weight)
     if getattr(op, "_packed_stamp", None) != stamp:
         with op._lock:

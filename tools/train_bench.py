@@ -2,7 +2,7 @@
 """Forward + backward time of the small-graph configs (the shapes the reference trains on), with a breakdown of
 the kernels of one training step.  Developer tool.
 
-    python tools/train_bench.py [--workloads cfg3,cfg2,hcp148] [--steps 100]
+    python tools/train_bench.py [--workloads cfg3,cfg2,hcp148] [--steps 100] [--graph]
 """
 import argparse
 import collections
@@ -22,6 +22,7 @@ def main():
     ap.add_argument("--workloads", default="cfg3,cfg2,hcp148")
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--no-dx", action="store_true", help="input does not require a gradient (first layer of a model)")
+    ap.add_argument("--graph", action="store_true", help="also time the layer's training step eager against replayed (tgcn_amd.GraphedTrainStep)")
     args = ap.parse_args()
     from tgcn_amd import _lib
     dev = torch.device("cuda:0")
@@ -51,6 +52,36 @@ def main():
             step()
         torch.cuda.synchronize()
         tfb = (time.perf_counter() - t0) / args.steps
+        if args.graph:
+            # the layer's training step (forward, backward of sum(out * g), SGD) eager against replayed by tgcn_amd.GraphedTrainStep; the
+            # input takes no gradient here (a step's batch does not)
+            import tgcn_amd
+            opt = torch.optim.SGD(layer.parameters(), lr=0.0)
+            xb = x.detach()
+
+            def loss_fn(out, target):
+                return (out * target).sum()
+
+            def train_step():
+                opt.zero_grad(set_to_none=True)
+                loss_fn(layer(xb), g).backward()
+                opt.step()
+
+            def time_of(fn):
+                for _ in range(10):
+                    fn()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(args.steps):
+                    fn()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / args.steps
+            te = time_of(train_step)
+            gts = tgcn_amd.GraphedTrainStep(layer, opt, loss_fn, xb, g)
+            tg = time_of(lambda: gts(xb, g))
+            print("%s: training step (forward + backward + SGD) eager %.1f us, replayed by GraphedTrainStep %.1f us" % (wl, te * 1e6, tg * 1e6),
+                  flush=True)
+            layer.zero_grad(set_to_none=True)
         _lib.profile_start(4096)
         step()
         torch.cuda.synchronize()
