@@ -450,6 +450,18 @@ def _bf16_row_ld(Tf):
     return Tf if (Tf % 8 == 0 or Tf < 7) else Tf + (-Tf) % 8
 
 
+def _series_stack_bf16(op, rows, K, mode):
+    """the bf16 hop stack of a (S, n, T*f) block of bf16 rows in the operand's labels -> (stack (K, S, n, ld), ld): the rows padded with
+    trailing zeros to ld elements (_bf16_row_ld), then one bf16 hop per term written into its slice (_basis_bf16)"""
+    S, n, Tf = rows.shape
+    ld = _bf16_row_ld(Tf)
+    if ld != Tf:
+        rows = torch.nn.functional.pad(rows, (0, ld - Tf))
+    stack = torch.empty((K, S, n, ld), dtype=BF16, device=rows.device)
+    _basis_bf16(op, rows, K, mode, out=stack)
+    return stack, ld
+
+
 def check_series_bf16(f, as_series, geom, series_dtype):
     """what a streaming call with bfloat16 parameters needs, checked before an operand is built: not the scalar-load form (ChebWindowsFn: one
     channel, window-major, default geometry), and a series that is bfloat16 already -- a streaming chain is bf16 from end to end (an
@@ -476,15 +488,17 @@ def _series_operands(series, weight_khfg, bias, mode):
     return series.float().contiguous(), fold, W if fold is None else fold_weight(fold, W), None if bias is None else bias.float().contiguous()
 
 
-def _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, dims, geom=None, pooled=None):
+def _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, dims, geom=None, pooled=None, bf16=None):
     """The fields a float32 series Function leaves for its backward, in one call per forward (these calls run at 0.3 ms, where a Python
     call counts); dims starts (S, n, T, f, H, N, K).
     geom = (stride, left, right, dilation) of a Function with a whole hop stack: ctx.geom is the backward's record of it -- the arguments
     that follow the common ones in the entries of that geometry, which also names them (_series_backward): () the default geometry's,
     (stride, left, right) the _conv entries', all four the _dilated ones'.
     pooled = (Wt, z, idx, pool, nwin, drop) of a pooled one (_series_pool_backward): saved in that order, the pool, the window count, and
-    the mask's seed tensor and scale (None, None without one)."""
-    ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.dims = op, mode, fold, bias_kind, as_series, dims
+    the mask's seed tensor and scale (None, None without one).
+    bf16 = (ld, (series dtype, weight dtype, bias dtype)) of ChebSeriesBf16Fn -- the stack's row distance and what the gradients are cast
+    to; None marks a float32 Function for _series_backward."""
+    ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series, ctx.dims, ctx.bf16 = op, mode, fold, bias_kind, as_series, dims, bf16
     ctx.bias_shape = None if bias is None else bias.shape
     if geom is not None:
         ctx.geom = geom if geom[3] > 1 else (geom[:3] if geom[:3] != (1, 0, 0) else ())
@@ -543,21 +557,29 @@ class ChebSeriesFn(torch.autograd.Function):
 
 
 def _series_backward(ctx, Wt, g):
-    """(d series, dW, d bias) of ChebSeriesFn from the gradient g of its output in the forward's layout -- the body every float32 series
-    Function with a whole hop stack shares; reads ctx.stack and _series_ctx's fields, ctx.geom among them, of the forward"""
+    """(d series, dW, d bias) of ChebSeriesFn from the gradient g of its output in the forward's layout -- the body every series Function
+    with a whole hop stack shares; reads ctx.stack and _series_ctx's fields, ctx.geom among them, of the forward.
+    ctx.bf16 (ChebSeriesBf16Fn) picks the _bf16 workspace queries and entries, which take the stack's ld behind the stack and a bf16 g, and
+    casts the three results to the forward's dtypes; G, dW, the adjoint hops, the un-fold and the bias sum are fp32 either way."""
     S, n, T, f, H, N, K = ctx.dims
     L = _lib.lib()
-    g = _aligned_input(g.float().contiguous())
+    g = _aligned_input((g.float() if ctx.bf16 is None else g.to(BF16)).contiguous())
     need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
     gx = dW = None
     if need_x or need_w:
         G = torch.empty((K, S, n, T * f), dtype=torch.float32, device=g.device) if need_x else None
         dW = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
-        query, entry = ((L.tgcn_cheb_series_dilated_backward_workspace_bytes, L.tgcn_cheb_series_dilated_backward_f32) if len(ctx.geom) == 4 else
-                        (L.tgcn_cheb_series_conv_backward_workspace_bytes, L.tgcn_cheb_series_conv_backward_f32) if ctx.geom else
-                        (L.tgcn_cheb_series_backward_workspace_bytes, L.tgcn_cheb_series_backward_f32))
+        if ctx.bf16 is None:
+            stack = (_lib.ptr(ctx.stack),)
+            query, entry = ((L.tgcn_cheb_series_dilated_backward_workspace_bytes, L.tgcn_cheb_series_dilated_backward_f32) if len(ctx.geom) == 4 else
+                            (L.tgcn_cheb_series_conv_backward_workspace_bytes, L.tgcn_cheb_series_conv_backward_f32) if ctx.geom else
+                            (L.tgcn_cheb_series_backward_workspace_bytes, L.tgcn_cheb_series_backward_f32))
+        else:       # (no default-geometry entry: ctx.geom is never ())
+            stack = (_lib.ptr(ctx.stack), ctx.bf16[0])
+            query, entry = ((L.tgcn_cheb_series_dilated_backward_bf16_workspace_bytes, L.tgcn_cheb_series_dilated_backward_bf16)
+                            if len(ctx.geom) == 4 else (L.tgcn_cheb_series_conv_backward_bf16_workspace_bytes, L.tgcn_cheb_series_conv_backward_bf16))
         ws = _workspace(query(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
-        _lib.check(entry(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), _lib.ptr(g), 1 if ctx.as_series else 0, _lib.ptr(Wt),
+        _lib.check(entry(_lib.stream_ptr(), S, n, T, f, H, N, K, *stack, _lib.ptr(g), 1 if ctx.as_series else 0, _lib.ptr(Wt),
                          _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel(), *ctx.geom))
         ctx.stack = None
         if need_x:
@@ -566,7 +588,9 @@ def _series_backward(ctx, Wt, g):
             dW = _series_dW(ctx, dW)
     gb = None
     if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
-        gb = _series_bias_grad(g, ctx.as_series, ctx.bias_kind, ctx.bias_shape)
+        gb = _series_bias_grad(g if ctx.bf16 is None else g.float(), ctx.as_series, ctx.bias_kind, ctx.bias_shape)
+    if ctx.bf16 is not None:        # rounded once each: bf16, or fp32 for a series behind a reordered operand's relabelling
+        gx, dW, gb = (None if t is None else t.to(dt) for t, dt in zip((gx, dW, gb), ctx.bf16[1]))
     return gx, dW, gb
 
 
@@ -2554,18 +2578,12 @@ class ChebSeriesBf16Fn(torch.autograd.Function):
         if ctx.needs_input_grad[0]:       # the input gradient's own span (phase 0 at step 1 over g as a series of N channels): refused here, not in the backward
             st = min(stride, T + left + right)      # (dilated: stride 1, all H weight time rows in the one launch)
             _lib.check(L.tgcn_series_conv_plan_bf16(-(-H // st), N, K * f, int(N % 8 == 0), 1, C.byref(hc), C.byref(lds)))
-        Tf = T * f
-        ld = _bf16_row_ld(Tf)
-        x3 = series.to(BF16).contiguous().view(S, n, Tf)      # bf16 already, or its bf16 values in fp32 behind a reordered operand's relabelling
-        if ld != Tf:
-            x3 = torch.nn.functional.pad(x3, (0, ld - Tf))
         W = weight_khfg.to(BF16).contiguous().view(K, H * f, N)
         fold = _power_fold(mode, W)
         Wt = _working_weight_bf16(fold, W)
-        # the series is in the operand's labels already (cheb_time_windows relabelled it)
-        stack = torch.empty((K, S, n, ld), dtype=BF16, device=x3.device)
-        _basis_bf16(op, x3, K, mode, out=stack)
-        out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=BF16, device=x3.device)
+        # the series is in the operand's labels already (cheb_time_windows relabelled it): bf16, or its bf16 values in fp32 behind that relabelling
+        stack, ld = _series_stack_bf16(op, series.to(BF16).contiguous().view(S, n, T * f), K, mode)
+        out = torch.empty((S, n, nwin, N) if as_series else (S * nwin, n, N), dtype=BF16, device=stack.device)
         b = bias.to(BF16).contiguous() if bias is not None else None
         args = (_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(stack), ld, _lib.ptr(Wt), _lib.ptr(b), _lib.DTYPE_BF16, bias_kind,
                 1 if as_series else 0, _lib.ptr(out), stride, left, right)
@@ -2575,40 +2593,15 @@ class ChebSeriesBf16Fn(torch.autograd.Function):
             _lib.check(L.tgcn_cheb_project_series_conv_bf16(*args))
         ctx.save_for_backward(Wt)
         ctx.stack = stack if ctx.needs_input_grad[1] else None       # the basis the weight gradient contracts with g, 2 B per element
-        ctx.op, ctx.mode, ctx.fold, ctx.bias_kind, ctx.as_series = op, mode, fold, bias_kind, as_series
-        ctx.dims, ctx.ld, ctx.geom = (S, n, T, f, H, N, K), ld, ((stride, left, right, dil) if dil > 1 else (stride, left, right))
-        ctx.bias_shape = None if bias is None else bias.shape
-        ctx.dtypes = (series.dtype, weight_khfg.dtype, None if bias is None else bias.dtype)
+        _series_ctx(ctx, op, mode, fold, bias, bias_kind, as_series, (S, n, T, f, H, N, K),
+                    bf16=(ld, (series.dtype, weight_khfg.dtype, None if bias is None else bias.dtype)))
+        ctx.geom = (stride, left, right, dil) if dil > 1 else (stride, left, right)      # never (): there is no default-geometry bf16 entry
         return out
 
     @staticmethod
     @_on_device
     def backward(ctx, g):
-        Wt, = ctx.saved_tensors
-        S, n, T, f, H, N, K = ctx.dims
-        L = _lib.lib()
-        g = _aligned_input(g.to(BF16).contiguous())
-        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gx = dW = None
-        if need_x or need_w:
-            G = torch.empty((K, S, n, T * f), dtype=torch.float32, device=g.device) if need_x else None
-            dW = torch.empty((K, H * f, N), dtype=torch.float32, device=g.device) if need_w else None
-            query, entry = ((L.tgcn_cheb_series_dilated_backward_bf16_workspace_bytes, L.tgcn_cheb_series_dilated_backward_bf16)
-                            if len(ctx.geom) == 4 else (L.tgcn_cheb_series_conv_backward_bf16_workspace_bytes, L.tgcn_cheb_series_conv_backward_bf16))
-            ws = _workspace(query(S, n, T, f, H, N, K, *ctx.geom), g.device, floor=16)
-            _lib.check(entry(_lib.stream_ptr(), S, n, T, f, H, N, K, _lib.ptr(ctx.stack), ctx.ld, _lib.ptr(g), 1 if ctx.as_series else 0,
-                             _lib.ptr(Wt), _lib.ptr(G), _lib.ptr(dW), _lib.ptr(ws), ws.numel(), *ctx.geom))
-            ctx.stack = None
-            if need_x:
-                gx = _adjoint_hops(ctx.op.transpose(), G, ctx.mode).reshape(S, n, T, f).to(ctx.dtypes[0])      # bf16 (fp32 behind a relabelling)
-            if need_w:
-                if ctx.fold is not None:
-                    dW = fold_weight(ctx.fold, dW, transpose=True)
-                dW = dW.view(K, H, f, N).to(ctx.dtypes[1])
-        gb = None
-        if ctx.bias_shape is not None and ctx.needs_input_grad[2]:
-            gb = _series_bias_grad(g.float(), ctx.as_series, ctx.bias_kind, ctx.bias_shape).to(ctx.dtypes[2])
-        return gx, dW, gb, None, None, None, None, None
+        return _series_backward(ctx, ctx.saved_tensors[0], g) + (None,) * 5
 
 
 # ----------------------------------------------------------------------------------------- streaming state
@@ -2687,15 +2680,25 @@ def stream_windows(seen, Tc, stride):
     return -(-(seen + Tc) // stride) - -(-seen // stride), (-seen) % stride
 
 
+def _stream_weight(weight_khfg, bias, mode, dtype):
+    """(working weight, bias) of a streaming step in the state's dtype: the (K, H*f, N) view of the weight in the kernels' basis -- folded on
+    every call, as forward_series does: each chunk is projected with the weight of its own call -- and the contiguous bias"""
+    K, H, f, N = weight_khfg.shape
+    W = weight_khfg.to(dtype).contiguous().view(K, H * f, N)
+    fold = _power_fold(mode, W)
+    return (_working_weight_bf16 if dtype == BF16 else _working_weight)(fold, W), None if bias is None else bias.to(dtype).contiguous()
+
+
 @_on_device
 def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state, pool=0):
-    """one chunk (S, n, Tc, f) in the operand's labels through the ring of `state`: plan query, K-1 hops on rows of Tc*f, the stream entry (the
-    projection and the ring update), head and seen moved; H == 1: the _conv entry on the chunk.  A capturable state runs the _pos entries,
-    which read the head from state.pos and move it on the device (H == 1: the _conv entry, then tgcn_series_stream_advance).
-    state.stride > 1: the plan at that step and ONE call of the _stream_strided entry (H == 1 included) with the host's head or the device
-    position, the step and win_off; out is (S, n, m, N) (stream_windows), empty when no window ends inside the chunk.
-    pool = 2 / 4 (float32, step 1: cheb_time_stream_relu_pool): tgcn_series_pool_plan, then ONE call of the _stream_pool entry -- the same
-    projection and ring update with relu + pool as the epilogue, z (S, n/pool, Tc, N) -- or, H == 1, of the pooled entry on the chunk."""
+    """one chunk (S, n, Tc, f) in the operand's labels through the ring of `state`, in this order: the plan query; the working weight
+    (_stream_weight) and the K-1 hops on rows of Tc*f (_series_stack / _series_stack_bf16); the arguments every entry begins with; the ring's
+    position, the host's head or the device's pos; ONE entry -- the projection and the ring update; the position moved.  The entry:
+    state.stride > 1 (planned at that step): the _stream_strided entry, H == 1 included; out is (S, n, m, N) (stream_windows), empty when no
+    window ends inside the chunk.  H == 1 at step 1: no ring, the _conv entry on the chunk (pool: the pooled series entry), and for a
+    capturable state tgcn_series_stream_advance behind it.  pool = 2 / 4 (float32, step 1: cheb_time_stream_relu_pool; planned by
+    tgcn_series_pool_plan): the _stream_pool entry, relu + pool as the epilogue, z (S, n/pool, Tc, N).  Else the _stream entry, or for a
+    capturable state the _stream_pos entry, which like the strided and the pooled one reads state.pos and moves it on the device."""
     L = _lib.lib()
     S, n, Tc, f = chunk.shape
     K, H, _, N = weight_khfg.shape
@@ -2708,63 +2711,37 @@ def _stream_chunk(chunk, weight_khfg, bias, op, mode, bias_kind, state, pool=0):
         _lib.check(L.tgcn_series_conv_plan_bf16(H, f, N, int(f % 8 == 0), step, C.byref(hc), C.byref(lds)))
     else:
         _lib.check(L.tgcn_series_conv_plan(H, f, N, int(f % 4 == 0), step, C.byref(hc), C.byref(lds)))
-    W = weight_khfg.to(state.dtype).contiguous().view(K, H * f, N)
-    fold = _power_fold(mode, W)
-    Wt = _working_weight_bf16(fold, W) if bf16 else _working_weight(fold, W)      # folded on every call, as forward_series does
-    Tf = Tc * f
+    Wt, b = _stream_weight(weight_khfg, bias, mode, state.dtype)
     if bf16:
-        ld = _bf16_row_ld(Tf)
-        x3 = chunk.to(BF16).contiguous().view(S, n, Tf)
-        if ld != Tf:
-            x3 = torch.nn.functional.pad(x3, (0, ld - Tf))
-        stack = torch.empty((K, S, n, ld), dtype=BF16, device=x3.device)
-        _basis_bf16(op, x3, K, mode, out=stack)
+        stack, ld = _series_stack_bf16(op, chunk.to(BF16).contiguous().view(S, n, Tc * f), K, mode)
     else:
-        x3 = _aligned_input(chunk.float().contiguous().view(S, n, Tf))
-        stack = _series_stack(op, x3, K, mode)
+        stack = _series_stack(op, _aligned_input(chunk.float().contiguous().view(S, n, Tc * f)), K, mode)
     # a capturable state takes only chunks of Tc % step == 0 (stream_precheck): off = 0 and m = Tc / step whatever the device position holds
     m, off = (Tc, 0) if step == 1 else ((Tc // step, 0) if state.capturable else stream_windows(state.seen, Tc, step))
-    out = torch.empty((S, n // pool if pool else n, m, N), dtype=state.dtype, device=x3.device)
-    b = bias.to(state.dtype).contiguous() if bias is not None else None
-    head = (_lib.stream_ptr(), S, n, Tc, f, H, N, K, _lib.ptr(stack))
-    where = _lib.ptr(state.pos) if state.capturable else state.head      # the ring's position: device memory, or the host's scalar
-    if pool:
-        mid = (_lib.ptr(Wt), _lib.ptr(b), bias_kind)
-        if state.C:
-            _lib.check(L.tgcn_cheb_project_series_stream_pool_f32(*head, *mid, _lib.ptr(out), pool, _lib.ptr(state.ring), state.ring_ld,
-                                                                  0 if state.capturable else state.head,
-                                                                  _lib.ptr(state.pos) if state.capturable else None, state.dilation))
+    out = torch.empty((S, n // pool if pool else n, m, N), dtype=state.dtype, device=stack.device)
+    # what every entry begins with: the chunk's shape, its stack (bf16: and the stack's ld), the weight and the bias (bf16: and its dtype)
+    args = (_lib.stream_ptr(), S, n, Tc, f, H, N, K, _lib.ptr(stack)) + ((ld, _lib.ptr(Wt), _lib.ptr(b), _lib.DTYPE_BF16, bias_kind) if bf16 else
+                                                                          (_lib.ptr(Wt), _lib.ptr(b), bias_kind))
+    # the ring's position: the device's pos, or the host's head -- with seen above the only reads of a position, both of a host-head state alone
+    head, pos = (0, _lib.ptr(state.pos)) if state.capturable else (state.head, None)
+    ring = (_lib.ptr(state.ring), state.ring_ld)
+    if step > 1:        # H == 1 included; both positions, the step and the first window's row; it moves a device position itself
+        entry = L.tgcn_cheb_project_series_stream_strided_bf16 if bf16 else L.tgcn_cheb_project_series_stream_strided_f32
+        _lib.check(entry(*args, _lib.ptr(out) if m else None, *ring, head, pos, step, off))
+    elif not state.C:   # no ring: the series entry on the chunk itself as a series, at step 1 with no padding
+        if pool:
+            _lib.check(L.tgcn_cheb_project_series_pool_f32(*args, 1, _lib.ptr(out), None, pool, 1, 0, 0, 1))
         else:
-            _lib.check(L.tgcn_cheb_project_series_pool_f32(*head, *mid, 1, _lib.ptr(out), None, pool, 1, 0, 0, 1))
-            if state.capturable:
-                _lib.check(L.tgcn_series_stream_advance(_lib.stream_ptr(), where, Tc, 0))       # no ring, but seen still counts
-        state.advance(Tc)
-        return out
-    if step > 1:
-        tail = (_lib.ptr(out) if m else None, _lib.ptr(state.ring), state.ring_ld, 0 if state.capturable else state.head,
-                _lib.ptr(state.pos) if state.capturable else None, step, off)
-        if bf16:
-            _lib.check(L.tgcn_cheb_project_series_stream_strided_bf16(*head, ld, _lib.ptr(Wt), _lib.ptr(b), _lib.DTYPE_BF16, bias_kind, *tail))
-        else:
-            _lib.check(L.tgcn_cheb_project_series_stream_strided_f32(*head, _lib.ptr(Wt), _lib.ptr(b), bias_kind, *tail))
-        state.advance(Tc)
-        return out
-    if bf16:
-        mid = (ld, _lib.ptr(Wt), _lib.ptr(b), _lib.DTYPE_BF16, bias_kind)
-        if state.C:
-            entry = L.tgcn_cheb_project_series_stream_pos_bf16 if state.capturable else L.tgcn_cheb_project_series_stream_bf16
-            _lib.check(entry(*head, *mid, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld, where, state.dilation))
-        else:
-            _lib.check(L.tgcn_cheb_project_series_conv_bf16(*head, *mid, 1, _lib.ptr(out), 1, 0, 0))
-    else:
-        mid = (_lib.ptr(Wt), _lib.ptr(b), bias_kind)
-        if state.C:
-            entry = L.tgcn_cheb_project_series_stream_pos_f32 if state.capturable else L.tgcn_cheb_project_series_stream_f32
-            _lib.check(entry(*head, *mid, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld, where, state.dilation))
-        else:
-            _lib.check(L.tgcn_cheb_project_series_conv_f32(*head, *mid, 1, _lib.ptr(out), 1, 0, 0))
-    if state.capturable and not state.C:
-        _lib.check(L.tgcn_series_stream_advance(_lib.stream_ptr(), where, Tc, 0))       # no ring, but seen still counts
+            entry = L.tgcn_cheb_project_series_conv_bf16 if bf16 else L.tgcn_cheb_project_series_conv_f32
+            _lib.check(entry(*args, 1, _lib.ptr(out), 1, 0, 0))
+    elif pool:         # both positions, as the strided entries take them
+        _lib.check(L.tgcn_cheb_project_series_stream_pool_f32(*args, _lib.ptr(out), pool, *ring, head, pos, state.dilation))
+    else:               # a host-head entry and a _pos entry, each with the one position it reads
+        entry = ((L.tgcn_cheb_project_series_stream_pos_bf16 if bf16 else L.tgcn_cheb_project_series_stream_pos_f32) if state.capturable else
+                 (L.tgcn_cheb_project_series_stream_bf16 if bf16 else L.tgcn_cheb_project_series_stream_f32))
+        _lib.check(entry(*args, _lib.ptr(out), *ring, pos if state.capturable else head, state.dilation))
+    if state.capturable and not state.C and step == 1:      # no ring, but seen still counts: the series entries know no position
+        _lib.check(L.tgcn_series_stream_advance(_lib.stream_ptr(), pos, Tc, 0))
     state.advance(Tc)
     return out
 
@@ -2799,11 +2776,9 @@ def _stream_chunk_fused(chunk, weight_khfg, bias, op, mode, bias_kind, state):
     L = _lib.lib()
     S, n, Tc, f = chunk.shape
     K, H, _, N = weight_khfg.shape
-    W = weight_khfg.float().contiguous().view(K, H * f, N)
-    Wt = _working_weight(_power_fold(mode, W), W)       # folded on every call: each chunk is projected with the weight of its own call
+    Wt, b = _stream_weight(weight_khfg, bias, mode, torch.float32)
     x3 = chunk.float().contiguous().view(S, n, Tc * f)
     out = torch.empty((S, n, Tc, N), dtype=torch.float32, device=x3.device)
-    b = bias.float().contiguous() if bias is not None else None
     pos = _lib.ptr(state.pos) if state.capturable else None
     _lib.check(L.tgcn_cheb_stream_small_f32(_lib.stream_ptr(), C.byref(op.struct), int(mode), S, Tc, f, H, N, K, _lib.ptr(x3), _lib.ptr(Wt),
                                             _lib.ptr(b), bias_kind, _lib.ptr(out), _lib.ptr(state.ring), state.ring_ld,
@@ -2869,6 +2844,28 @@ def stream_precheck(chunk, weight, bias, state, dilation, who="cheb_time_stream"
     return dt, (S, n, f, K, H), dilation
 
 
+def _stream_enter(op, chunk, weight, bias, bias_kind, state, dt, dims, dilation, capturable, stride=1):
+    """what the two cheb_time_stream* functions do behind their refusals (stream_precheck's answers in dt, dims, dilation) and in front of
+    the step -> (chunk (S, n, Tc, f), weight (K, H, f, N), bias, state): tensors on one device, a new state where none came, a 3-D chunk
+    and weight unsqueezed, chunk and bias in the operand's labels -- the ring lives in them"""
+    _lib.require_device(chunk, weight, bias)
+    if state is None:
+        S, n, f, K, H = dims
+        state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device, capturable=capturable, stride=stride)
+    if chunk.dim() == 3:
+        chunk, weight = chunk.unsqueeze(3), weight.unsqueeze(2)
+    chunk, bias = _to_operand_labels(op, chunk, bias, bias_kind)
+    return chunk, weight, bias, state
+
+
+def _stream_leave(op, out, dt):
+    """a step's output back in the caller's labels (a reordered operand; an output without windows has nothing to relabel), in the layer's
+    dtype: the relabelling kernel is fp32, and bf16 values pass through it exactly"""
+    if op.perm is not None and out.shape[2]:
+        out = relabel_rows(out, op.inv_perm, op.perm).to(dt)
+    return out
+
+
 def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=None, dilation=1, capturable=False, fused=False, stride=1):
     """The causal streaming layer on the NEXT Tc time rows of S recordings (inference only): chunk (S, n, Tc) with weight (K, H, N), or
     (S, n, Tc, f) with weight (K, H, f, N) -> (out (S, n, Tc, N) contiguous, state).  out equals rows [state.seen, state.seen + Tc) of
@@ -2913,17 +2910,10 @@ def cheb_time_stream(op, chunk, weight, bias, bias_kind, mode=MODE_POWER, state=
         else:
             fused = (dt != BF16 and H >= 2 and Tc <= STREAM_FUSED_AUTO_MAX_TC and op.n_cols == op.n
                      and _stream_small_plan(op, f, H, N, K, Tc, dilation, mode)[0] == 0)
-    _lib.require_device(chunk, weight, bias)
-    if state is None:
-        state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device, capturable=capturable, stride=stride)
     with torch.no_grad():
-        if chunk.dim() == 3:
-            chunk, weight = chunk.unsqueeze(3), weight.unsqueeze(2)
-        chunk, bias = _to_operand_labels(op, chunk, bias, bias_kind)      # the ring lives in the operand's labels
+        chunk, weight, bias, state = _stream_enter(op, chunk, weight, bias, bias_kind, state, dt, (S, n, f, K, H), dilation, capturable, stride)
         out = (_stream_chunk_fused if fused else _stream_chunk)(chunk, weight, bias, op, mode, bias_kind, state)
-        if op.perm is not None and out.shape[2]:
-            out = relabel_rows(out, op.inv_perm, op.perm).to(dt)
-    return out, state
+        return _stream_leave(op, out, dt), state
 
 
 def cheb_time_stream_relu_pool(op, chunk, weight, bias, bias_kind, mode, pool, state=None, dilation=1, capturable=False):
@@ -2941,16 +2931,9 @@ def cheb_time_stream_relu_pool(op, chunk, weight, bias, bias_kind, mode, pool, s
     pool = check_pool(pool, n, who)
     if state is not None and state.op is not op:
         raise _lib.TgcnError("%s: the state was made for another operand -- one state per layer and graph" % who)
-    _lib.require_device(chunk, weight, bias)
-    if state is None:
-        state = SeriesStreamState(op, dt, S, n, f, K, H, dilation, chunk.device, capturable=capturable)
     with torch.no_grad():
-        if chunk.dim() == 3:
-            chunk, weight = chunk.unsqueeze(3), weight.unsqueeze(2)
-        chunk, bias = _to_operand_labels(op, chunk, bias, bias_kind)      # the ring lives in the operand's labels
+        chunk, weight, bias, state = _stream_enter(op, chunk, weight, bias, bias_kind, state, dt, (S, n, f, K, H), dilation, capturable)
         if series_pool_is_fused(op, pool, stream=True):
             return _stream_chunk(chunk, weight, bias, op, mode, bias_kind, state, pool=pool), state
         out = _stream_chunk(chunk, weight, bias, op, mode, bias_kind, state)
-        if op.perm is not None:
-            out = relabel_rows(out, op.inv_perm, op.perm)
-        return _relu_pool_view(out, pool), state
+        return _relu_pool_view(_stream_leave(op, out, dt), pool), state

@@ -224,17 +224,7 @@ class TGCNCheb_H(_DenseLBase):
         TgcnError where it cannot -- before the operand is built for bfloat16 parameters, stride > 1 and a time_chunk, before anything
         launches for a reordered operand and a shape the plan refuses (F.series_fused_supported).  fused="auto" fuses where that is
         measured to pay (F.SERIES_FUSED_AUTO) and is the fused=False call elsewhere."""
-        bf16 = _compute_dtype(self) == torch.bfloat16      # F.cheb_time_windows routes it: every call but the scalar-load form
-        F.check_series_fused(fused, stride, time_chunk, bf16, "TGCNCheb_H.forward_series")
-        series, W, geom = _series_args(self, series, stride, padding, dilation)
-        F.check_time_chunk(time_chunk, stride, padding, bf16, "TGCNCheb_H.forward_series")
-        if bf16:
-            F.check_series_bf16(self.weight.shape[2], as_series, geom, series.dtype)
-        return F.cheb_time_windows(self._operand(series.device), series, W,
-                                   None if self.bias is None else self.bias.reshape(-1),
-                                   F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, as_series=as_series,
-                                   stride=geom[0], padding=geom[1:3] if time_chunk is None else "causal", dilation=geom[3],
-                                   time_chunk=time_chunk, fused=fused)
+        return _forward_series(self, "TGCNCheb_H.forward_series", series, None, None, as_series, stride, padding, dilation, time_chunk, fused)
 
     def forward_stream(self, chunk, state=None, dilation=1, capturable=False, fused=False, stride=1):
         """Additive API, inference only: the causal layer on the next Tc time rows of S recordings.  chunk (S, n, Tc) or (S, n, Tc, f) ->
@@ -258,13 +248,7 @@ class TGCNCheb_H(_DenseLBase):
         empty chunk.  A capturable state takes chunks with Tc % s == 0 only (m = Tc/s on every step, so GraphedStream's next layer sees
         chunks of Tc/s rows).  TgcnError: stride > 1 with dilation > 1, with fused=True ("auto" runs unfused), with a state of another
         stride."""
-        _compute_dtype(self)
-        chunk, W = _stream_args(self, chunk)
-        F.stream_precheck(chunk, W, self.bias, state, dilation, "TGCNCheb_H.forward_stream", capturable, fused=fused, stride=stride)      # refusals come before the operand is built
-        _state_operand_check(self, state, self._operand_key(chunk.device))
-        return F.cheb_time_stream(self._operand(chunk.device), chunk, W, None if self.bias is None else self.bias.reshape(-1),
-                                  F.BIAS_NONE if self.bias is None else F.BIAS_VERTEX_CHANNEL, F.MODE_POWER, state=state, dilation=dilation,
-                                  capturable=capturable, fused=fused, stride=stride)
+        return _forward_stream(self, "TGCNCheb_H.forward_stream", chunk, None, None, state, dilation, capturable, fused, stride)
 
 
 def _state_operand_check(module, state, key):
@@ -300,6 +284,38 @@ def _series_args(module, series, stride=1, padding=0, dilation=1):
                              % (name, series.shape[3] if series.dim() == 4 else 1, f))
     stride, left, right, _ = F.series_geometry(series.shape[2], H, stride, padding, "%s.forward_series" % name, dilation)
     return series, (module.weight.reshape(K, H, g) if series.dim() == 3 else module.weight), (stride, left, right, F.series_dilation(H, dilation))
+
+
+def _time_operand(layer, x, edge_index, edge_weight, key=False):
+    """the operand a time layer runs the series or chunk x on -- TGCNCheb_H's L on x's device, ChebTimeConv's graph arguments on x's
+    vertices and device -- built and cached by the layer; key=True: only its key in the layer's cache, nothing is built"""
+    get = layer._operand_key if key else layer._operand
+    return get(x.device) if isinstance(layer, _DenseLBase) else get(x, edge_index, edge_weight)
+
+
+def _forward_series(layer, who, series, edge_index, edge_weight, as_series, stride, padding, dilation, time_chunk, fused):
+    """the two forward_series methods behind their own refusals: every refusal that needs no operand, the operand, F.cheb_time_windows"""
+    bf16 = _compute_dtype(layer, edge_weight) == torch.bfloat16      # F.cheb_time_windows routes it: every call but the scalar-load form
+    F.check_series_fused(fused, stride, time_chunk, bf16, who)
+    series, W, geom = _series_args(layer, series, stride, padding, dilation)
+    F.check_time_chunk(time_chunk, stride, padding, bf16, who)
+    if bf16:
+        F.check_series_bf16(layer.weight.shape[2], as_series, geom, series.dtype)
+    op = _time_operand(layer, series, edge_index, edge_weight)
+    return F.cheb_time_windows(op, series, W, *_series_pool_bias(layer), as_series=as_series, stride=geom[0],
+                               padding=geom[1:3] if time_chunk is None else "causal", dilation=geom[3], time_chunk=time_chunk, fused=fused)
+
+
+def _forward_stream(layer, who, chunk, edge_index, edge_weight, state, dilation, capturable, fused, stride):
+    """the two forward_stream methods behind their own refusals: every refusal that needs no operand -- a state made for another one
+    among them, by a look at the key -- then the operand and F.cheb_time_stream"""
+    _compute_dtype(layer, edge_weight)
+    chunk, W = _stream_args(layer, chunk)
+    F.stream_precheck(chunk, W, layer.bias, state, dilation, who, capturable, fused=fused, stride=stride)
+    _state_operand_check(layer, state, _time_operand(layer, chunk, edge_index, edge_weight, key=True))
+    op = _time_operand(layer, chunk, edge_index, edge_weight)
+    return F.cheb_time_stream(op, chunk, W, *_series_pool_bias(layer), state=state, dilation=dilation, capturable=capturable, fused=fused,
+                              stride=stride)
 
 
 class GCNCheb(_DenseLBase):
@@ -549,17 +565,8 @@ class ChebTimeConv(_EdgeBase):
         if edge_weight is not None and edge_weight.requires_grad:
             raise _lib.TgcnError("ChebTimeConv.forward_series: learnable edge weights (edge_weight.requires_grad) are not supported -- "
                                  "use forward on the windowed batch")
-        bf16 = _compute_dtype(self, edge_weight) == torch.bfloat16      # as in TGCNCheb_H.forward_series
-        F.check_series_fused(fused, stride, time_chunk, bf16, "ChebTimeConv.forward_series")
-        series, W, geom = _series_args(self, series, stride, padding, dilation)
-        F.check_time_chunk(time_chunk, stride, padding, bf16, "ChebTimeConv.forward_series")
-        if bf16:
-            F.check_series_bf16(self.weight.shape[2], as_series, geom, series.dtype)
-        op = self._operand(series, edge_index, edge_weight)
-        return F.cheb_time_windows(op, series, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
-                                   as_series=as_series,
-                                   stride=geom[0], padding=geom[1:3] if time_chunk is None else "causal", dilation=geom[3],
-                                   time_chunk=time_chunk, fused=fused)
+        return _forward_series(self, "ChebTimeConv.forward_series", series, edge_index, edge_weight, as_series, stride, padding, dilation,
+                               time_chunk, fused)
 
     def forward_stream(self, chunk, edge_index, edge_weight=None, state=None, dilation=1, capturable=False, fused=False, stride=1):
         """Additive API, inference only: TGCNCheb_H.forward_stream's contract for this class -- chunk (S, n, Tc[, f]) -> (out (S, n, Tc, g),
@@ -573,13 +580,7 @@ class ChebTimeConv(_EdgeBase):
         if edge_weight is not None and edge_weight.requires_grad:
             raise _lib.TgcnError("ChebTimeConv.forward_stream: learnable edge weights (edge_weight.requires_grad) are not supported -- "
                                  "streaming is inference only; detach() the weight")
-        _compute_dtype(self, edge_weight)
-        chunk, W = _stream_args(self, chunk)
-        F.stream_precheck(chunk, W, self.bias, state, dilation, "ChebTimeConv.forward_stream", capturable, fused=fused, stride=stride)      # refusals come before the operand is built
-        _state_operand_check(self, state, self._operand_key(chunk, edge_index, edge_weight))
-        op = self._operand(chunk, edge_index, edge_weight)
-        return F.cheb_time_stream(op, chunk, W, self.bias, F.BIAS_NONE if self.bias is None else F.BIAS_CHANNEL, F.MODE_CHEBYSHEV,
-                                  state=state, dilation=dilation, capturable=capturable, fused=fused, stride=stride)
+        return _forward_stream(self, "ChebTimeConv.forward_stream", chunk, edge_index, edge_weight, state, dilation, capturable, fused, stride)
 
 
 # ------------------------------------------------------------------------------------ a streaming chain as one hipGraph
@@ -691,8 +692,7 @@ def _series_pool_call(layer, series, graph_args, who, pool, stride, padding, dil
     if series.dim() in (3, 4):
         F.check_pool(pool, series.shape[1], who)
     series, W, geom = _series_args(layer, series, stride, padding, dilation)
-    op = layer._operand(series.device) if isinstance(layer, TGCNCheb_H) else layer._operand(series, edge_index, edge_weight)
-    return (op, series, W) + _series_pool_bias(layer), geom
+    return (_time_operand(layer, series, edge_index, edge_weight), series, W) + _series_pool_bias(layer), geom
 
 
 def cheb_series_relu_pool(layer, series, *graph_args, pool=4, as_series=False, stride=1, padding=0, dilation=1):
@@ -824,12 +824,7 @@ def cheb_stream_relu_pool(layer, chunk, *graph_args, pool=4, state=None, dilatio
     chunk, W = _stream_args(layer, chunk)
     F.check_pool(pool, chunk.shape[1], who)
     F.stream_precheck(chunk, W, layer.bias, state, dilation, who, capturable)      # refusals come before the operand is built
-    if isinstance(layer, TGCNCheb_H):
-        _state_operand_check(layer, state, layer._operand_key(chunk.device))
-        op = layer._operand(chunk.device)
-    else:
-        _state_operand_check(layer, state, layer._operand_key(chunk, edge_index, edge_weight))
-        op = layer._operand(chunk, edge_index, edge_weight)
-    bias, bias_kind, mode = _series_pool_bias(layer)
-    return F.cheb_time_stream_relu_pool(op, chunk, W, bias, bias_kind, mode, pool, state=state, dilation=dilation, capturable=capturable)
+    _state_operand_check(layer, state, _time_operand(layer, chunk, edge_index, edge_weight, key=True))
+    op = _time_operand(layer, chunk, edge_index, edge_weight)
+    return F.cheb_time_stream_relu_pool(op, chunk, W, *_series_pool_bias(layer), pool, state=state, dilation=dilation, capturable=capturable)
 

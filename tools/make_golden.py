@@ -6,6 +6,7 @@ Usage (from anywhere, reference mounted read-only at /root/reference):
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py [--ref /root/reference] [--out tests/golden]
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py --series-refusals      (tests/test_series_refusal_table.py; needs no reference)
     PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py --series-host-calls    (tests/test_series_host_table.py; no reference, no library)
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden.py --series-stream-host-calls    (tests/test_series_stream_host_table.py; likewise)
 
 What is executed from the reference (nothing is copied; only inputs/outputs are stored):
   * gcn.graph            grid / distance_sklearn_metrics / adjacency / laplacian / rescale_L / chebyshev
@@ -88,6 +89,9 @@ def main():
                     help="only record tests/golden/series_refusals_abi8.json from the built library (no reference, no device)")
     ap.add_argument("--series-host-calls", action="store_true",
                     help="only record tests/golden/series_host_calls.json: what the time-window host side logs (no reference, device or library)")
+    ap.add_argument("--series-stream-host-calls", action="store_true",
+                    help="only record tests/golden/series_stream_host_calls.json: what the streaming step's and the bf16 series Function's "
+                         "host side logs (no reference, device or library)")
     args = ap.parse_args()
     out_dir = os.path.abspath(args.out)
     os.makedirs(out_dir, exist_ok=True)
@@ -108,6 +112,14 @@ def main():
         import test_series_host_table as ht
         with open(os.path.join(out_dir, "series_host_calls.json"), "w") as f:
             json.dump(ht.table(), f, separators=(",", ":"))
+        return
+    if args.series_stream_host_calls:      # the grid is tests/test_series_stream_host_table.py's, the recorder test_series_host_table.py's
+        import json
+        root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+        sys.path[:0] = [root, os.path.join(root, "tests")]
+        import test_series_stream_host_table as st
+        with open(os.path.join(out_dir, "series_stream_host_calls.json"), "w") as f:
+            json.dump(st.table(), f, separators=(",", ":"))
         return
 
     sys.dont_write_bytecode = True
