@@ -58,6 +58,50 @@ inline void allow_large_lds(const void* fn, int bytes) {
   }
 }
 
+// ---- run-time values as compile-time constants: how a launcher picks a kernel's template instantiation.  f is a generic lambda; its
+// arguments carry the values in their types (std::true_type / std::false_type, std::integral_constant<int, V>) and convert back to them
+// in a constant expression, template arguments included: with_flags([&](auto vec) { launch_kernel(some_kernel<vec>, ...); }, is_vec).
+// A launcher that builds only some combinations guards the body with `if constexpr (..._form_built(flags))`: the others are never instantiated.
+template <class F>
+inline void with_flags(F&& f) { f(); }
+template <class F, class... B>
+inline void with_flags(F&& f, bool b, B... rest) {
+  if (b) with_flags([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_flags([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+// v out of the list Vs; a value that is not in it takes the last
+template <int V, int... Vs, class F>
+inline void with_one_of(int v, F&& f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+  else if (v == V) f(std::integral_constant<int, V>{});
+  else with_one_of<Vs...>(v, f);
+}
+
+// Dynamic LDS of a launch and what its kernel is opted in to first (allow_large_lds): the launch's own bytes where they exceed the 64 KB every
+// kernel may take, or the family's largest where a launcher names it.
+struct DynLds {
+  size_t bytes;
+  int optin;
+  DynLds(size_t b) : bytes(b), optin(b > 64 * 1024 ? (int)b : 0) {}
+  DynLds(size_t b, int most) : bytes(b), optin(most) {}
+};
+template <class... P, class... A>
+inline void launch_kernel(void (*kernel)(P...), dim3 grid, dim3 block, DynLds lds, hipStream_t st, const A&... args) {
+  if (lds.optin) allow_large_lds((const void*)kernel, lds.optin);
+  hipLaunchKernelGGL(kernel, grid, block, lds.bytes, st, args...);
+}
+// A grid of nblk x gy workgroups in launches of at most `part` along x (a launch holds fewer than 2^32 threads along x, tgcn_hip.hip
+// kSeriesGridPart); each part is told its first workgroup in p.blk0, the kernel's first argument.
+template <class... P, class Params, class... A>
+inline void launch_kernel_parts(void (*kernel)(P...), int64_t nblk, int64_t part, unsigned gy, dim3 block, DynLds lds, hipStream_t st, Params& p,
+                                const A&... extra) {
+  if (lds.optin) allow_large_lds((const void*)kernel, lds.optin);
+  for (int64_t b0 = 0; b0 < nblk; b0 += part) {
+    p.blk0 = (decltype(p.blk0))b0;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)std::min<int64_t>(part, nblk - b0), gy), block, lds.bytes, st, p, extra...);
+  }
+}
+
 // Compute units of the calling thread's current device (256 on MI355X), read once per device: round sizes of one-workgroup-per-CU
 // kernels follow from it instead of a literal.
 // Dynamic LDS a workgroup of the calling thread's current device can opt in to (163,840 B on gfx950; 65,536 on gfx942), read once per device:

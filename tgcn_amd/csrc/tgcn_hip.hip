@@ -2,7 +2,8 @@
 // See include/tgcn_hip.h for the contract and DESIGN.md for layout / roofline notes.
 //
 // One translation unit; the kernels live in topic headers included once inside the anonymous namespace below:
-//   common.h         error reporting, launch timing (tgcn_profile_*), tuning switches, LDS attribute bookkeeping
+//   common.h         error reporting, launch timing (tgcn_profile_*), tuning switches, LDS attribute bookkeeping, and how a launcher picks a
+//                    kernel's template instantiation: with_flags / with_one_of (run-time values as constants), launch_kernel(_parts)
 //   hop.h            hop_kernel<LPR,VEC,U,R> / hop_fixup_kernel: row-block + column-ordered-segment CSR x dense rows,
 //                    fused Y = alpha (L X) + beta Z (+ gamma Z2) (+ P = L X); deterministic segment fold
 //   project.h        out = sum_t A_t W_t + bias: exact fp32 MFMA (streaming / W-resident), bf16x3 (two forms), narrow VALU
@@ -445,17 +446,11 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
       if (hipMemsetAsync(claim, 0, sizeof(int32_t), st) != hipSuccess) TGCN_FAIL(TGCN_ERR_LAUNCH, "project: memset of the tile counter failed");
     }
     ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_PROJ_S(NTV, KTV)                                                                                              \
-  if (claim) {                                                                                                             \
-    allow_large_lds((const void*)project_x3_claim_kernel<NTV, KTV>, (int)kX3StreamMaxLds);                                 \
-    hipLaunchKernelGGL((project_x3_claim_kernel<NTV, KTV>), dim3((unsigned)gx), dim3(256), lds, st, p, ntiles, claim);     \
-  } else {                                                                                                                 \
-    allow_large_lds((const void*)project_x3_stream_kernel<NTV, KTV>, (int)kX3StreamMaxLds);                                \
-    hipLaunchKernelGGL((project_x3_stream_kernel<NTV, KTV>), dim3((unsigned)gx), dim3(1024), lds, st, p, ntiles);          \
-  }
-    if (Kc == 32) { if (snt == 1) TGCN_PROJ_S(1, 1) else if (snt == 2) TGCN_PROJ_S(2, 1) else TGCN_PROJ_S(4, 1) }
-    else { if (snt == 1) TGCN_PROJ_S(1, 2) else if (snt == 2) TGCN_PROJ_S(2, 2) else TGCN_PROJ_S(4, 2) }
-#undef TGCN_PROJ_S
+    const DynLds dl(lds, (int)kX3StreamMaxLds);
+    with_one_of<1, 2, 4>(snt, [&](auto NT) { with_one_of<1, 2>(Kc == 32 ? 1 : 2, [&](auto KT) {
+      if (claim) launch_kernel(project_x3_claim_kernel<NT, KT>, dim3((unsigned)gx), dim3(256), dl, st, p, ntiles, claim);
+      else launch_kernel(project_x3_stream_kernel<NT, KT>, dim3((unsigned)gx), dim3(1024), dl, st, p, ntiles);
+    }); });
     TGCN_CHECK_LAUNCH("tgcn_cheb_project_f32 (bf16x3 streaming)");
     return TGCN_OK;
   }
@@ -469,17 +464,12 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
     if (gx > cu_count()) gx = cu_count();    // one persistent workgroup per CU (LDS-limited residency)
     const dim3 grid((unsigned)gx, gy);
     ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_PROJ_R(NTV, V4)                                                                                  \
-  {                                                                                                           \
-    allow_large_lds((const void*)project_resident_kernel<NTV, V4, 1>, kResMaxWBytes + kResScratchFloats * (int)sizeof(float)); \
-    allow_large_lds((const void*)project_resident_kernel<NTV, V4, 2>, kResMaxWBytes + kResScratchFloats * (int)sizeof(float)); \
-    if (rt == 1) hipLaunchKernelGGL((project_resident_kernel<NTV, V4, 1>), grid, dim3(1024), lds, st, p, kc4, ntiles); \
-    else hipLaunchKernelGGL((project_resident_kernel<NTV, V4, 2>), grid, dim3(512), lds, st, p, kc4, ntiles);          \
-  }
-    if (nt == 1) { if (vec4) TGCN_PROJ_R(1, true) else TGCN_PROJ_R(1, false) }
-    else if (nt == 2) { if (vec4) TGCN_PROJ_R(2, true) else TGCN_PROJ_R(2, false) }
-    else { if (vec4) TGCN_PROJ_R(4, true) else TGCN_PROJ_R(4, false) }
-#undef TGCN_PROJ_R
+    const DynLds dl(lds, kResMaxWBytes + kResScratchFloats * (int)sizeof(float));
+    with_one_of<1, 2, 4>(nt, [&](auto NT) { with_flags([&](auto V4) {
+      const auto rt1 = project_resident_kernel<NT, V4, 1>, rt2 = project_resident_kernel<NT, V4, 2>;
+      allow_large_lds((const void*)(rt == 1 ? rt2 : rt1), dl.optin);      // both forms are opted in, whichever runs
+      launch_kernel(rt == 1 ? rt1 : rt2, grid, dim3(1024 / rt), dl, st, p, kc4, ntiles);
+    }, vec4); });
     TGCN_CHECK_LAUNCH("tgcn_cheb_project_f32 (resident)");
     return TGCN_OK;
   }
@@ -488,9 +478,6 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
   const int tiles = (N + 15) / 16, nts = choice.nts;
   const dim3 grid((unsigned)mb, (unsigned)((tiles + nts - 1) / nts));
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_PROJ(NTV)                                                                               \
-  if (vec4) hipLaunchKernelGGL((project_kernel<NTV, true>), grid, dim3(kBlock), 0, st, p);             \
-  else hipLaunchKernelGGL((project_kernel<NTV, false>), grid, dim3(kBlock), 0, st, p);
   if (use_x3) {      // bf16x3 products on the bf16 matrix pipe
     const int64_t gx3 = (M + 255) / 256 * p.nbatch;                   // sample-fastest: the nbatch workgroups of a tile are neighbours
     if (gx3 > (int64_t)INT32_MAX) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "project: grid too large");
@@ -504,31 +491,17 @@ static int project_impl(void* stream, int64_t M, int32_t Kc, int32_t N, int32_t 
       tail_blocks = (M - main_blocks * 256 + 127) / 128;
     }
     const dim3 grid3v2((unsigned)(main_blocks + tail_blocks), grid.y);
-#define TGCN_PROJ3(NTV)                                                                              \
-  if (NTV >= 6 && choice.kernel == kProjX3Wide) hipLaunchKernelGGL((project_x3v2_kernel<NTV>), grid3v2, dim3(512), 0, st, p, (int)main_blocks); /* wide outputs: compute-bound */ \
-  else if (vec4) hipLaunchKernelGGL((project_x3_kernel<NTV, true>), grid3, dim3(512), 0, st, p);      \
-  else hipLaunchKernelGGL((project_x3_kernel<NTV, false>), grid3, dim3(512), 0, st, p);
-    switch (nts) {
-      case 1: TGCN_PROJ3(1) break;
-      case 2: TGCN_PROJ3(2) break;
-      case 4: TGCN_PROJ3(4) break;
-      case 6: TGCN_PROJ3(6) break;
-      case 8: TGCN_PROJ3(8) break;
-      default: TGCN_PROJ3(10) break;
-    }
-#undef TGCN_PROJ3
+    // a plain `if` on NT: project_x3v2_kernel is built for all six tile counts, the wide outputs (compute-bound) launch it for 6, 8 and 10
+    with_one_of<1, 2, 4, 6, 8, 10>(nts, [&](auto NT) { with_flags([&](auto V4) {
+      if (NT >= 6 && choice.kernel == kProjX3Wide) launch_kernel(project_x3v2_kernel<NT>, grid3v2, dim3(512), 0, st, p, (int)main_blocks);
+      else launch_kernel(project_x3_kernel<NT, V4>, grid3, dim3(512), 0, st, p);
+    }, vec4); });
     TGCN_CHECK_LAUNCH("tgcn_cheb_project_f32 (bf16x3)");
     return TGCN_OK;
   }
-  switch (nts) {
-    case 1: TGCN_PROJ(1) break;
-    case 2: TGCN_PROJ(2) break;
-    case 4: TGCN_PROJ(4) break;
-    case 6: TGCN_PROJ(6) break;
-    case 8: TGCN_PROJ(8) break;
-    default: TGCN_PROJ(10) break;
-  }
-#undef TGCN_PROJ
+  with_one_of<1, 2, 4, 6, 8, 10>(nts, [&](auto NT) { with_flags([&](auto V4) {
+    launch_kernel(project_kernel<NT, V4>, grid, dim3(kBlock), 0, st, p);
+  }, vec4); });
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_f32");
   return TGCN_OK;
 }
@@ -609,11 +582,9 @@ int tgcn_cheb_project_bf16(void* stream, int64_t M, int32_t Kc, int32_t N, int32
   const dim3 grid((unsigned)gx, (unsigned)((tiles + nt - 1) / nt));
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_PROJ_B(NTV)                                                                                      \
-  if (vec8) hipLaunchKernelGGL((project_bf16_kernel<NTV, true>), grid, dim3(256), 0, st, p);                  \
-  else hipLaunchKernelGGL((project_bf16_kernel<NTV, false>), grid, dim3(256), 0, st, p);
-  if (nt == 1) { TGCN_PROJ_B(1) } else if (nt == 2) { TGCN_PROJ_B(2) } else { TGCN_PROJ_B(4) }
-#undef TGCN_PROJ_B
+  with_one_of<1, 2, 4>(nt, [&](auto NT) { with_flags([&](auto V8) {
+    launch_kernel(project_bf16_kernel<NT, V8>, grid, dim3(256), 0, st, p);
+  }, vec8); });
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_bf16");
   return TGCN_OK;
 }
@@ -657,11 +628,9 @@ int tgcn_cheb_project_mapped_bf16(void* stream, int64_t M, int32_t Kc, int32_t N
     p.out = (char*)out + (size_t)((int64_t)b0 * out_bs) * out_elem;
     const dim3 grid((unsigned)gx, (unsigned)((tiles + nt - 1) / nt), (unsigned)nb);
     ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_PROJ_BM(NTV)                                                                                          \
-  if (vec8) hipLaunchKernelGGL((project_bf16_kernel<NTV, true, true>), grid, dim3(256), 0, st, p);                 \
-  else hipLaunchKernelGGL((project_bf16_kernel<NTV, false, true>), grid, dim3(256), 0, st, p);
-    if (nt == 1) { TGCN_PROJ_BM(1) } else if (nt == 2) { TGCN_PROJ_BM(2) } else { TGCN_PROJ_BM(4) }
-#undef TGCN_PROJ_BM
+    with_one_of<1, 2, 4>(nt, [&](auto NT) { with_flags([&](auto V8) {
+      launch_kernel(project_bf16_kernel<NT, V8, true>, grid, dim3(256), 0, st, p);
+    }, vec8); });
   }
   TGCN_CHECK_LAUNCH("tgcn_cheb_project_mapped_bf16");
   return TGCN_OK;
@@ -789,29 +758,18 @@ int tgcn_cheb_forward_small_pool_f32(void* stream, const tgcn_csr* A, int32_t mo
   }
   p.dense = pl.dense_lds;
   p.npad = (p.n + 63) / 64 * 64;
-  const size_t lds = (size_t)pl.lds_bytes;
+  const DynLds lds((size_t)pl.lds_bytes, 160 * 1024);
   const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
   const unsigned nthreads = (unsigned)pl.threads;
   ProfScope ps(TGCN_PROF_SMALL, st);
   if (pl.form == 1) {   // first layers: recursion on the 4-float input side, all of NT output channels per workgroup (small_narrow_kernel)
-#define TGCN_NARROW(NTV)                                                                     \
-  {                                                                                          \
-    allow_large_lds((const void*)small_narrow_kernel<NTV>, 160 * 1024);                      \
-    hipLaunchKernelGGL((small_narrow_kernel<NTV>), grid, dim3(nthreads), lds, st, p);        \
-  }
-    if (pl.tile == 64) TGCN_NARROW(64) else if (pl.tile == 32) TGCN_NARROW(32) else TGCN_NARROW(16)
-#undef TGCN_NARROW
+    with_one_of<64, 32, 16>(pl.tile, [&](auto NT) { launch_kernel(small_narrow_kernel<NT>, grid, dim3(nthreads), lds, st, p); });
     TGCN_CHECK_LAUNCH("tgcn_cheb_forward_small_f32 (narrow input)");
     return TGCN_OK;
   }
-#define TGCN_SMALL(NTCV, CPV)                                                                                     \
-  {                                                                                                               \
-    allow_large_lds((const void*)small_forward_kernel<NTCV, CPV>, 160 * 1024);                                      \
-    hipLaunchKernelGGL((small_forward_kernel<NTCV, CPV>), grid, dim3(nthreads), lds, st, p);                      \
-  }
-  if (pl.tile == 16) { if (pl.cp == 4) TGCN_SMALL(16, 4) else if (pl.cp == 16) TGCN_SMALL(16, 16) else TGCN_SMALL(16, 32) }
-  else { if (pl.cp == 4) TGCN_SMALL(8, 4) else if (pl.cp == 16) TGCN_SMALL(8, 16) else TGCN_SMALL(8, 32) }
-#undef TGCN_SMALL
+  with_one_of<16, 8>(pl.tile, [&](auto NTC) { with_one_of<4, 16, 32>(pl.cp, [&](auto CP) {
+    launch_kernel(small_forward_kernel<NTC, CP>, grid, dim3(nthreads), lds, st, p);
+  }); });
   TGCN_CHECK_LAUNCH("tgcn_cheb_forward_small_f32");
   return TGCN_OK;
 }
@@ -864,16 +822,10 @@ int tgcn_cheb_basis_small_f32(void* stream, const tgcn_csr* A, int32_t mode, int
   }
   p.dense = pl.dense_lds;
   p.npad = (p.n + 63) / 64 * 64;
-  const size_t lds = (size_t)pl.lds_bytes;
+  const DynLds lds((size_t)pl.lds_bytes, 160 * 1024);
   const dim3 grid((unsigned)pl.grid_x, (unsigned)pl.grid_y);
   const unsigned nthreads = (unsigned)pl.threads;
-#define TGCN_BASIS(CTV)                                                                    \
-  {                                                                                        \
-    allow_large_lds((const void*)small_basis_kernel<CTV>, 160 * 1024);                     \
-    hipLaunchKernelGGL((small_basis_kernel<CTV>), grid, dim3(nthreads), lds, st, p);       \
-  }
-  if (pl.tile == 16) TGCN_BASIS(16) else if (pl.tile == 8) TGCN_BASIS(8) else TGCN_BASIS(4)
-#undef TGCN_BASIS
+  with_one_of<16, 8, 4>(pl.tile, [&](auto CT) { launch_kernel(small_basis_kernel<CT>, grid, dim3(nthreads), lds, st, p); });
   TGCN_CHECK_LAUNCH("tgcn_cheb_basis_small_f32");
   return TGCN_OK;
 }
@@ -1447,9 +1399,6 @@ struct SeriesLaunchPlan { int32_t tpp, tpv, hc, lds, NT; int64_t nq, ntiles, gx,
 // launchers issue the grid in parts of kSeriesGridPart workgroups, each told its first workgroup (blk0); the parts write disjoint tiles.
 // A launch error of any part is what every driver ends on (series_launched: hipGetLastError after its last launch).
 constexpr int64_t kSeriesGridPart = (int64_t)UINT32_MAX / kBlock;
-static dim3 series_grid_part(const SeriesLaunchPlan& lp, int64_t blk0) {
-  return dim3((unsigned)std::min<int64_t>(kSeriesGridPart, lp.gx - blk0), (unsigned)lp.gy);
-}
 static int series_launch_plan(SeriesLdsFn lds_of, int64_t S, int64_t n, int32_t nwin, int32_t H, int32_t f, int32_t N, bool vec, int stride, int dil,
                               int pool, const char* who, SeriesLaunchPlan* o) {
   o->tpp = 0; o->tpv = (nwin + kSgWin - 1) / kSgWin;
@@ -1465,125 +1414,139 @@ static int series_launch_plan(SeriesLdsFn lds_of, int64_t S, int64_t n, int32_t 
   return TGCN_OK;
 }
 
-// stride >= 2 takes the STRIDED instantiations; stride 1 (the input gradient's phases included) the ones without a step; dil >= 2 (at step 1)
-// the DILATED ones, planned as step 1
-// carry (the stream entries): the CARRY instantiations, which stage the time rows before the chunk from p.ring -- at step 1 (dilated or
-// not), or STRIDED && CARRY for a window step on a chunk (the _stream_strided entry, p.win_off)
-// pool (2 / 4; 0: none): the POOLED instantiations of the same form -- one workgroup per (recording, vertex quad, window block), the
-// scratch's bytes where they exceed the GEMM's; not built with a window step on a chunk
-// drop (with pool, on a whole series): series_gemm_pool_dropout_kernel in the pooled form's place, on the same plan -- the dropout adds no LDS
-// at (with drop, at step 1; a chunk's place in the whole series): series_gemm_chunk_pool_dropout_kernel, behind the ring (carry) or without one
+// ---- which instantiation a GEMM launch takes.  Choosing is apart from launching: series_form maps the launcher's arguments to a kernel
+// family and its flags, series_*_form_built name the forms the library holds (the launcher's `if constexpr` guard, and what its refusals
+// ask), and the static_asserts pin arguments -> form, one row per form an entry reaches.
+//   stride >= 2: STRIDED; dil >= 2 (at step 1, planned as step 1): DILATED; stride 1 (the input gradient's phases included): neither
+//   carry (the stream entries): CARRY, the time rows before the chunk staged from p.ring -- at step 1 (dilated or not), or STRIDED && CARRY
+//     for a window step on a chunk (the _stream_strided entry, p.win_off)
+//   pool (2 / 4; 0: none): POOLED, the same form with one workgroup per (recording, vertex quad, window block) and the scratch's bytes where
+//     they exceed the GEMM's; not built with a window step on a chunk
+//   drop (with pool, on a whole series): series_gemm_pool_dropout_kernel in the pooled form's place, on the same plan -- the dropout adds no LDS
+//   at (with drop, at step 1; a chunk's place in the whole series): series_gemm_chunk_pool_dropout_kernel, behind the ring (carry) or without one
+// Precedence where both a step and a dilation arrive: a whole series looks at the dilation first, a chunk behind a ring at the step first.
+// `at` without a ring is one tap (series_chunk_forward plans it at dil 1): never DILATED, whatever dil says.
+enum SeriesFamily { kSgGemm, kSgDrop, kSgDropAt };
+struct SeriesForm { SeriesFamily family; bool strided, dilated, carry, pooled; };
+constexpr SeriesForm series_form(int stride, int dil, bool carry, int pool, bool drop, bool at) {
+  const SeriesFamily family = at ? kSgDropAt : (drop ? kSgDrop : kSgGemm);
+  if (carry || at) return {family, stride > 1, carry && stride <= 1 && dil > 1, carry, pool != 0};
+  return {family, dil <= 1 && stride != 1, dil > 1, false, pool != 0};
+}
+// series_gemm_kernel<NT, VEC, STRIDED, DILATED, CARRY, POOLED>: 11 forms
+constexpr bool series_gemm_form_built(bool s, bool d, bool c, bool p) { return !(s && d) && !(s && c && p); }
+// series_gemm_pool_dropout_kernel<NT, VEC, STRIDED, DILATED>: the pooled forms of a whole series
+constexpr bool series_drop_form_built(bool s, bool d, bool c, bool p) { return series_gemm_form_built(s, d, c, p) && p && !c; }
+// series_gemm_chunk_pool_dropout_kernel<NT, VEC, DILATED, CARRY>: the pooled forms at step 1, dilated only behind a ring
+constexpr bool series_drop_at_form_built(bool s, bool d, bool c, bool p) { return series_gemm_form_built(s, d, c, p) && p && !s && (c || !d); }
+
+constexpr bool series_form_is(SeriesForm f, SeriesFamily family, bool s, bool d, bool c, bool p) {
+  return f.family == family && f.strided == s && f.dilated == d && f.carry == c && f.pooled == p;
+}
+//                                       stride dil carry pool drop   at                STRIDED DILATED CARRY POOLED
+static_assert(series_form_is(series_form(1, 1, false, 2, true,  true),  kSgDropAt, false, false, false, true), "");
+static_assert(series_form_is(series_form(1, 3, false, 2, true,  true),  kSgDropAt, false, false, false, true), "");      // one tap: dil is not looked at
+static_assert(series_form_is(series_form(1, 2, true,  2, true,  true),  kSgDropAt, false, true,  true,  true), "");
+static_assert(series_form_is(series_form(1, 1, true,  4, true,  true),  kSgDropAt, false, false, true,  true), "");
+static_assert(series_form_is(series_form(1, 2, false, 2, true,  false), kSgDrop,   false, true,  false, true), "");
+static_assert(series_form_is(series_form(1, 1, false, 4, true,  false), kSgDrop,   false, false, false, true), "");
+static_assert(series_form_is(series_form(2, 1, false, 2, true,  false), kSgDrop,   true,  false, false, true), "");
+static_assert(series_form_is(series_form(1, 2, true,  2, false, false), kSgGemm,   false, true,  true,  true), "");
+static_assert(series_form_is(series_form(1, 1, true,  4, false, false), kSgGemm,   false, false, true,  true), "");
+static_assert(series_form_is(series_form(1, 2, false, 2, false, false), kSgGemm,   false, true,  false, true), "");
+static_assert(series_form_is(series_form(1, 1, false, 4, false, false), kSgGemm,   false, false, false, true), "");
+static_assert(series_form_is(series_form(3, 1, false, 2, false, false), kSgGemm,   true,  false, false, true), "");
+static_assert(series_form_is(series_form(2, 1, true,  0, false, false), kSgGemm,   true,  false, true,  false), "");
+static_assert(series_form_is(series_form(2, 2, true,  0, false, false), kSgGemm,   true,  false, true,  false), "");     // a chunk: the step first
+static_assert(series_form_is(series_form(1, 2, true,  0, false, false), kSgGemm,   false, true,  true,  false), "");
+static_assert(series_form_is(series_form(1, 1, true,  0, false, false), kSgGemm,   false, false, true,  false), "");
+static_assert(series_form_is(series_form(1, 2, false, 0, false, false), kSgGemm,   false, true,  false, false), "");
+static_assert(series_form_is(series_form(2, 2, false, 0, false, false), kSgGemm,   false, true,  false, false), "");     // a whole series: the dilation first
+static_assert(series_form_is(series_form(1, 1, false, 0, false, false), kSgGemm,   false, false, false, false), "");
+static_assert(series_form_is(series_form(2, 1, false, 0, false, false), kSgGemm,   true,  false, false, false), "");
+// the three refusals: a pooled window step on a chunk; dropout without the pool or behind a ring without `at`; `at` with a step
+static_assert(!series_gemm_form_built(true, false, true, true) && series_form_is(series_form(2, 1, true, 2, false, false), kSgGemm, true, false, true, true), "");
+static_assert(!series_drop_form_built(false, false, false, false) && !series_drop_form_built(false, false, true, true), "");
+static_assert(!series_drop_at_form_built(true, false, false, true) && !series_drop_at_form_built(false, true, false, true), "");
+
 static int series_gemm_launch(hipStream_t st, SeriesGemmParams& p, int64_t S, bool vec, const char* who, int stride = 1, int dil = 1,
                               bool carry = false, int pool = 0, const DropoutParams* drop = nullptr, const SeriesDropAt* at = nullptr) {
   SeriesLaunchPlan lp;
   if (int rc = series_launch_plan(series_gemm_lds, S, p.n, p.nwin, p.H, p.f, p.N, vec, stride, dil, pool, who, &lp)) return rc;
-  if (pool && carry && stride > 1) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a pooled window step on a chunk is not built", who);
-  if (drop && (!pool || (carry && !at))) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: dropout is built into the pooled epilogue of a whole series", who);
-  if (at && (!drop || stride > 1)) TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a chunk's mask is built at step 1 with dropout", who);
+  const SeriesForm fm = series_form(stride, dil, carry, pool, drop != nullptr, at != nullptr);
+  if (!series_gemm_form_built(fm.strided, fm.dilated, fm.carry, fm.pooled))
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a pooled window step on a chunk is not built", who);
+  if (drop && !(at ? fm.pooled : series_drop_form_built(fm.strided, fm.dilated, fm.carry, fm.pooled)))
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: dropout is built into the pooled epilogue of a whole series", who);
+  if (at && !(drop && series_drop_at_form_built(fm.strided, fm.dilated, fm.carry, fm.pooled)))
+    TGCN_FAIL(TGCN_ERR_UNSUPPORTED, "%s: a chunk's mask is built at step 1 with dropout", who);
   p.tpv = lp.tpv; p.dil = dil; p.ntiles = lp.ntiles; p.pool = pool;
   if (dil > 1) p.tpp = lp.tpp;
   if (pool) p.nq = lp.nq;
-  const int NT = lp.NT, hc = lp.hc, lds = pool ? series_pool_lds(lp.lds, NT) : lp.lds;
+  const int hc = lp.hc, lds = pool ? series_pool_lds(lp.lds, lp.NT) : lp.lds;
   p.HC = hc;
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = series_row_floats(hc, p.f, vec, stride);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_GEMM(NT_, VEC_, STR_, DIL_, ...)                                                                      \
-  do {                                                                                                                    \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_kernel<NT_, VEC_, STR_, DIL_, ##__VA_ARGS__>, lds);     \
-    for (p.blk0 = 0; p.blk0 < lp.gx; p.blk0 += kSeriesGridPart)                                                           \
-      hipLaunchKernelGGL((series_gemm_kernel<NT_, VEC_, STR_, DIL_, ##__VA_ARGS__>), series_grid_part(lp, p.blk0), dim3(kBlock), lds, st, p); \
-  } while (0)
-#define TGCN_SERIES_GEMM_NT(VEC_, STR_, DIL_, ...)                                                                        \
-  do { if (NT == 1) TGCN_SERIES_GEMM(1, VEC_, STR_, DIL_, ##__VA_ARGS__); else if (NT == 2) TGCN_SERIES_GEMM(2, VEC_, STR_, DIL_, ##__VA_ARGS__);   \
-       else TGCN_SERIES_GEMM(4, VEC_, STR_, DIL_, ##__VA_ARGS__); } while (0)
-#define TGCN_SERIES_DROP(NT_, VEC_, STR_, DIL_)                                                                            \
-  do {                                                                                                                    \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_pool_dropout_kernel<NT_, VEC_, STR_, DIL_>, lds);       \
-    for (p.blk0 = 0; p.blk0 < lp.gx; p.blk0 += kSeriesGridPart)                                                           \
-      hipLaunchKernelGGL((series_gemm_pool_dropout_kernel<NT_, VEC_, STR_, DIL_>), series_grid_part(lp, p.blk0), dim3(kBlock), lds, st, p, *drop); \
-  } while (0)
-#define TGCN_SERIES_DROP_NT(VEC_, STR_, DIL_)                                                                             \
-  do { if (NT == 1) TGCN_SERIES_DROP(1, VEC_, STR_, DIL_); else if (NT == 2) TGCN_SERIES_DROP(2, VEC_, STR_, DIL_);       \
-       else TGCN_SERIES_DROP(4, VEC_, STR_, DIL_); } while (0)
-#define TGCN_SERIES_DROP_AT(NT_, VEC_, DIL_, CARRY_)                                                                       \
-  do {                                                                                                                    \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_chunk_pool_dropout_kernel<NT_, VEC_, DIL_, CARRY_>, lds); \
-    for (p.blk0 = 0; p.blk0 < lp.gx; p.blk0 += kSeriesGridPart)                                                           \
-      hipLaunchKernelGGL((series_gemm_chunk_pool_dropout_kernel<NT_, VEC_, DIL_, CARRY_>), series_grid_part(lp, p.blk0), dim3(kBlock), lds, st, p, \
-                         *drop, *at);                                                                                     \
-  } while (0)
-#define TGCN_SERIES_DROP_AT_NT(VEC_, DIL_, CARRY_)                                                                        \
-  do { if (NT == 1) TGCN_SERIES_DROP_AT(1, VEC_, DIL_, CARRY_); else if (NT == 2) TGCN_SERIES_DROP_AT(2, VEC_, DIL_, CARRY_); \
-       else TGCN_SERIES_DROP_AT(4, VEC_, DIL_, CARRY_); } while (0)
-  if (at) {
-    if (!carry) { if (vec) TGCN_SERIES_DROP_AT_NT(true, false, false); else TGCN_SERIES_DROP_AT_NT(false, false, false); }      // one tap: dil == 1
-    else if (dil > 1) { if (vec) TGCN_SERIES_DROP_AT_NT(true, true, true); else TGCN_SERIES_DROP_AT_NT(false, true, true); }
-    else { if (vec) TGCN_SERIES_DROP_AT_NT(true, false, true); else TGCN_SERIES_DROP_AT_NT(false, false, true); }
-  } else if (drop) {
-    if (dil > 1) { if (vec) TGCN_SERIES_DROP_NT(true, false, true); else TGCN_SERIES_DROP_NT(false, false, true); }
-    else if (stride == 1) { if (vec) TGCN_SERIES_DROP_NT(true, false, false); else TGCN_SERIES_DROP_NT(false, false, false); }
-    else { if (vec) TGCN_SERIES_DROP_NT(true, true, false); else TGCN_SERIES_DROP_NT(false, true, false); }
-  } else if (pool) {
-    if (carry) {
-      if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, true, true); else TGCN_SERIES_GEMM_NT(false, false, true, true, true); }
-      else { if (vec) TGCN_SERIES_GEMM_NT(true, false, false, true, true); else TGCN_SERIES_GEMM_NT(false, false, false, true, true); }
-    } else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, false, true); else TGCN_SERIES_GEMM_NT(false, false, true, false, true); }
-    else if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, false, false, true); else TGCN_SERIES_GEMM_NT(false, false, false, false, true); }
-    else { if (vec) TGCN_SERIES_GEMM_NT(true, true, false, false, true); else TGCN_SERIES_GEMM_NT(false, true, false, false, true); }
-  } else if (carry) {
-    if (stride > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, true, false, true); else TGCN_SERIES_GEMM_NT(false, true, false, true); }
-    else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true, true); else TGCN_SERIES_GEMM_NT(false, false, true, true); }
-    else { if (vec) TGCN_SERIES_GEMM_NT(true, false, false, true); else TGCN_SERIES_GEMM_NT(false, false, false, true); }
-  } else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, true); else TGCN_SERIES_GEMM_NT(false, false, true); }
-  else if (stride == 1) { if (vec) TGCN_SERIES_GEMM_NT(true, false, false); else TGCN_SERIES_GEMM_NT(false, false, false); }
-  else { if (vec) TGCN_SERIES_GEMM_NT(true, true, false); else TGCN_SERIES_GEMM_NT(false, true, false); }
-#undef TGCN_SERIES_DROP_AT_NT
-#undef TGCN_SERIES_DROP_AT
-#undef TGCN_SERIES_DROP_NT
-#undef TGCN_SERIES_DROP
-#undef TGCN_SERIES_GEMM_NT
-#undef TGCN_SERIES_GEMM
+  const auto run = [&](auto kernel, const auto&... extra) {
+    launch_kernel_parts(kernel, lp.gx, kSeriesGridPart, (unsigned)lp.gy, dim3(kBlock), lds, st, p, extra...);
+  };
+  with_one_of<1, 2, 4>(lp.NT, [&](auto NT) { with_flags([&](auto V, auto St, auto Di, auto Ca, auto Po) {
+    if constexpr (series_gemm_form_built(St, Di, Ca, Po)) {
+      if (fm.family == kSgGemm) run(series_gemm_kernel<NT, V, St, Di, Ca, Po>);
+    }
+    if constexpr (series_drop_form_built(St, Di, Ca, Po)) {
+      if (fm.family == kSgDrop) run(series_gemm_pool_dropout_kernel<NT, V, St, Di>, *drop);
+    }
+    if constexpr (series_drop_at_form_built(St, Di, Ca, Po)) {
+      if (fm.family == kSgDropAt) run(series_gemm_chunk_pool_dropout_kernel<NT, V, Di, Ca>, *drop, *at);
+    }
+  }, vec, fm.strided, fm.dilated, fm.carry, fm.pooled); });
   return TGCN_OK;
 }
 
-// out_f32: the input gradient's fp32 columns; otherwise bf16 output.  stride >= 2 takes the STRIDED instantiations, dil >= 2 (at step 1) the
-// DILATED ones, planned as step 1.
+// series_gemm_bf16_kernel<NT, VEC, STRIDED, OutT, DILATED, CARRY>: 8 forms.  out_f32 (the input gradient's fp32 columns; otherwise bf16
+// output) exists only without a ring and at step 1, dilated or not -- one launch per phase of a stepped layer's input gradient, each at
+// step 1.  There is no bf16 pool, dropout or `at`.  The step and the dilation as above.
+struct SeriesBf16Form { bool strided, out_f32, dilated, carry; };
+constexpr SeriesBf16Form series_bf16_form(int stride, int dil, bool carry, bool out_f32) {
+  if (carry) return {stride > 1, false, stride <= 1 && dil > 1, true};
+  return {dil <= 1 && !out_f32 && stride != 1, out_f32, dil > 1, false};
+}
+constexpr bool series_bf16_form_built(bool s, bool o, bool d, bool c) { return !(s && d) && !(o && (s || c)); }
+
+constexpr bool series_bf16_form_is(SeriesBf16Form f, bool s, bool o, bool d, bool c) {
+  return f.strided == s && f.out_f32 == o && f.dilated == d && f.carry == c;
+}
+//                                                 stride dil carry out_f32   STRIDED f32    DILATED CARRY
+static_assert(series_bf16_form_is(series_bf16_form(2, 1, true,  false), true,  false, false, true), "");
+static_assert(series_bf16_form_is(series_bf16_form(2, 2, true,  false), true,  false, false, true), "");      // a chunk: the step first
+static_assert(series_bf16_form_is(series_bf16_form(1, 2, true,  false), false, false, true,  true), "");
+static_assert(series_bf16_form_is(series_bf16_form(1, 1, true,  false), false, false, false, true), "");
+static_assert(series_bf16_form_is(series_bf16_form(1, 1, true,  true),  false, false, false, true), "");      // a chunk's output is bf16
+static_assert(series_bf16_form_is(series_bf16_form(1, 2, false, true),  false, true,  true,  false), "");
+static_assert(series_bf16_form_is(series_bf16_form(1, 2, false, false), false, false, true,  false), "");
+static_assert(series_bf16_form_is(series_bf16_form(2, 2, false, false), false, false, true,  false), "");     // a whole series: the dilation first
+static_assert(series_bf16_form_is(series_bf16_form(1, 1, false, true),  false, true,  false, false), "");
+static_assert(series_bf16_form_is(series_bf16_form(2, 1, false, true),  false, true,  false, false), "");     // fp32 columns: at step 1
+static_assert(series_bf16_form_is(series_bf16_form(1, 1, false, false), false, false, false, false), "");
+static_assert(series_bf16_form_is(series_bf16_form(2, 1, false, false), true,  false, false, false), "");
+
 static int series_gemm_bf16_launch(hipStream_t st, SeriesGemmBf16Params& p, int64_t S, bool vec, bool out_f32, const char* who, int stride = 1,
                                    int dil = 1, bool carry = false) {
   SeriesLaunchPlan lp;
   if (int rc = series_launch_plan(series_gemm_bf16_lds, S, p.n, p.nwin, p.H, p.f, p.N, vec, stride, dil, 0, who, &lp)) return rc;
   p.tpv = lp.tpv; p.dil = dil; p.ntiles = lp.ntiles;
   if (dil > 1) p.tpp = lp.tpp;
-  const int NT = lp.NT, hc = lp.hc, lds = lp.lds;
+  const int hc = lp.hc;
   p.HC = hc;
   p.stride = stride; p.lst = series_span_lst(hc, stride); p.fp = vec ? series_bf16_row_elems(p.f, p.lst) : p.f;
+  const SeriesBf16Form fm = series_bf16_form(stride, dil, carry, out_f32);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_GEMM_B(NT_, VEC_, STR_, OUT_, DIL_, ...)                                                                      \
-  do {                                                                                                                            \
-    if (lds > 64 * 1024) allow_large_lds((const void*)series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>, lds);  \
-    for (p.blk0 = 0; p.blk0 < lp.gx; p.blk0 += kSeriesGridPart)                                                                   \
-      hipLaunchKernelGGL((series_gemm_bf16_kernel<NT_, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__>), series_grid_part(lp, p.blk0), dim3(kBlock), lds, st, p); \
-  } while (0)
-#define TGCN_SERIES_GEMM_B_NT(VEC_, STR_, OUT_, DIL_, ...)                                                                        \
-  do { if (NT == 1) TGCN_SERIES_GEMM_B(1, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                                 \
-       else if (NT == 2) TGCN_SERIES_GEMM_B(2, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__);                                            \
-       else TGCN_SERIES_GEMM_B(4, VEC_, STR_, OUT_, DIL_, ##__VA_ARGS__); } while (0)
-  if (carry) {          // the stream entries: bf16 out, the time rows before the chunk from p.ring (a window step: STRIDED && CARRY)
-    if (stride > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16, false, true); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16, false, true); }
-    else if (dil > 1) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true, true); }
-    else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, false, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, false, true); }
-  } else if (dil > 1) {        // dilated taps at step 1: the forward, and the input gradient in one launch
-    if (out_f32) { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, true); else TGCN_SERIES_GEMM_B_NT(false, false, float, true); }
-    else { if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, true); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, true); }
-  } else if (out_f32) {        // the input gradient: one launch per phase, each at step 1
-    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, float, false); else TGCN_SERIES_GEMM_B_NT(false, false, float, false);
-  } else if (stride == 1) {
-    if (vec) TGCN_SERIES_GEMM_B_NT(true, false, hbf16, false); else TGCN_SERIES_GEMM_B_NT(false, false, hbf16, false);
-  } else {
-    if (vec) TGCN_SERIES_GEMM_B_NT(true, true, hbf16, false); else TGCN_SERIES_GEMM_B_NT(false, true, hbf16, false);
-  }
-#undef TGCN_SERIES_GEMM_B_NT
-#undef TGCN_SERIES_GEMM_B
+  with_one_of<1, 2, 4>(lp.NT, [&](auto NT) { with_flags([&](auto V, auto St, auto F32, auto Di, auto Ca) {
+    if constexpr (series_bf16_form_built(St, F32, Di, Ca))
+      launch_kernel_parts(series_gemm_bf16_kernel<NT, V, St, std::conditional_t<F32, float, hbf16>, Di, Ca>, lp.gx, kSeriesGridPart, (unsigned)lp.gy,
+                          dim3(kBlock), lp.lds, st, p);
+  }, vec, fm.strided, fm.out_f32, fm.dilated, fm.carry); });
   return TGCN_OK;
 }
 
@@ -1607,14 +1570,12 @@ struct SeriesF32 {
   static void wgrad_ring(WgradParams& q, const void* ring, int64_t S, int64_t n, int64_t ring_ld, int32_t C, int32_t head) {
     q.ring = (const float*)ring; q.ring_ks = S * n * ring_ld; q.ring_is = ring_ld; q.C = C; q.head = head;
   }
-  // conv: a step or padding; carried: the chunk behind a ring
+  // conv: a step or padding; carried: the chunk behind a ring.  series_wgrad_partial_kernel<CONV, DIL, CARRY>: dilated taps and a carried
+  // chunk are CONV geometries whatever `conv` says -- 5 forms
   static void wgrad(hipStream_t st, dim3 grid, const WgradParams& q, bool conv, bool dilated, bool carried) {
-    if (carried) {
-      if (dilated) hipLaunchKernelGGL((series_wgrad_partial_kernel<true, true, true>), grid, dim3(64), 0, st, q);
-      else hipLaunchKernelGGL((series_wgrad_partial_kernel<true, false, true>), grid, dim3(64), 0, st, q);
-    } else if (dilated) hipLaunchKernelGGL((series_wgrad_partial_kernel<true, true>), grid, dim3(64), 0, st, q);
-    else if (conv) hipLaunchKernelGGL(series_wgrad_partial_kernel<true>, grid, dim3(64), 0, st, q);
-    else hipLaunchKernelGGL(series_wgrad_partial_kernel<false>, grid, dim3(64), 0, st, q);
+    with_flags([&](auto Co, auto Di, auto Ca) {
+      if constexpr (Co || (!Di && !Ca)) launch_kernel(series_wgrad_partial_kernel<Co, Di, Ca>, grid, dim3(64), 0, st, q);
+    }, conv || dilated || carried, dilated, carried);
   }
 };
 
@@ -1635,10 +1596,10 @@ struct SeriesBf16 {
   }
   static void wgrad_rows(WgradParams& q, int64_t ld) { q.st_is = ld; }
   static void wgrad_ring(WgradParams&, const void*, int64_t, int64_t, int64_t, int32_t, int32_t) {}      // no bf16 chunk backward
-  static void wgrad(hipStream_t st, dim3 grid, const WgradParams& q, bool conv, bool dilated, bool) {
-    if (dilated) hipLaunchKernelGGL((series_wgrad_bf16_partial_kernel<true, true>), grid, dim3(64), 0, st, q);
-    else if (conv) hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<true>, grid, dim3(64), 0, st, q);
-    else hipLaunchKernelGGL(series_wgrad_bf16_partial_kernel<false>, grid, dim3(64), 0, st, q);
+  static void wgrad(hipStream_t st, dim3 grid, const WgradParams& q, bool conv, bool dilated, bool) {      // <CONV, DIL>: 3 forms, as above
+    with_flags([&](auto Co, auto Di) {
+      if constexpr (Co || !Di) launch_kernel(series_wgrad_bf16_partial_kernel<Co, Di>, grid, dim3(64), 0, st, q);
+    }, conv || dilated, dilated);
   }
 };
 
@@ -1872,13 +1833,14 @@ static void series_ring_update_launch(hipStream_t st, const void* stack, void* r
   const int unit = vec ? 16 / esize : 1, m = Tc < C ? Tc : C, fu = f / unit;
   const dim3 grid(grid_1d(rows * m * fu));
   ProfScope ps(TGCN_PROF_RELAYOUT, st);
-#define TGCN_RING_UPDATE(U_)                                                                                                        \
-  hipLaunchKernelGGL(series_ring_update_kernel<U_>, grid, dim3(kBlock), 0, st, (const U_*)stack, (U_*)ring, rows, stack_ld / unit, \
-                     ring_ld / unit, fu, Tc - m, m, C, head, pos)
-  if (vec) TGCN_RING_UPDATE(uint4);
-  else if (esize == 4) TGCN_RING_UPDATE(uint32_t);
-  else TGCN_RING_UPDATE(uint16_t);
-#undef TGCN_RING_UPDATE
+  const auto run = [&](auto u) {      // u: the unit of one access
+    typedef decltype(u) U;
+    launch_kernel(series_ring_update_kernel<U>, grid, dim3(kBlock), 0, st, (const U*)stack, (U*)ring, rows, stack_ld / unit, ring_ld / unit, fu,
+                  Tc - m, m, C, head, pos);
+  };
+  if (vec) run(uint4());
+  else if (esize == 4) run(uint32_t());
+  else run(uint16_t());
 }
 
 // The position of a ring kept in device memory (the _pos entries) moves behind the ring update, in a launch of its own
@@ -2096,18 +2058,9 @@ int tgcn_cheb_stream_small_f32(void* stream, const tgcn_csr* A, int32_t mode, in
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)S), block((unsigned)pl.nthr);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_STREAM_SMALL(DENSE_, NTW_, MODE_)                                                                        \
-  do {                                                                                                                \
-    if (pl.lds > 64 * 1024) allow_large_lds((const void*)small_stream_kernel<DENSE_, NTW_, MODE_>, pl.lds);           \
-    hipLaunchKernelGGL((small_stream_kernel<DENSE_, NTW_, MODE_>), grid, block, pl.lds, st, p);                       \
-  } while (0)
-#define TGCN_STREAM_SMALL_NTW(DENSE_, MODE_)                                                                          \
-  do { if (pl.ntw == 4) TGCN_STREAM_SMALL(DENSE_, 4, MODE_); else if (pl.ntw == 2) TGCN_STREAM_SMALL(DENSE_, 2, MODE_); \
-       else TGCN_STREAM_SMALL(DENSE_, 1, MODE_); } while (0)
-  if (pl.dense) { if (mode == 0) TGCN_STREAM_SMALL_NTW(true, 0); else TGCN_STREAM_SMALL_NTW(true, 1); }
-  else { if (mode == 0) TGCN_STREAM_SMALL_NTW(false, 0); else TGCN_STREAM_SMALL_NTW(false, 1); }
-#undef TGCN_STREAM_SMALL_NTW
-#undef TGCN_STREAM_SMALL
+  with_one_of<4, 2, 1>(pl.ntw, [&](auto NTW) { with_one_of<0, 1>(mode, [&](auto MODE) { with_flags([&](auto DENSE) {
+    launch_kernel(small_stream_kernel<DENSE, NTW, MODE>, grid, block, pl.lds, st, p);
+  }, pl.dense != 0); }); });
   TGCN_CHECK_LAUNCH("tgcn_cheb_stream_small_f32");
   return TGCN_OK;
 }
@@ -2160,24 +2113,12 @@ int tgcn_cheb_series_small_f32(void* stream, const tgcn_csr* A, int32_t mode, in
                                   dilation, false, 0, nullptr, 1.f, &pl, &p))
     return rc;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t nblk = S * pl.ntiles, part = (int64_t)UINT32_MAX / kSrMaxThreads;      // fewer than 2^32 threads per launch (series_grid_part)
+  const int64_t nblk = S * pl.ntiles, part = (int64_t)UINT32_MAX / kSrMaxThreads;      // fewer than 2^32 threads per launch (kSeriesGridPart)
   const dim3 block((unsigned)pl.nthr);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_SMALL(DENSE_, NTW_, MODE_)                                                                        \
-  do {                                                                                                                \
-    if (pl.lds > 64 * 1024) allow_large_lds((const void*)small_series_kernel<DENSE_, NTW_, MODE_>, pl.lds);           \
-    for (int64_t b0 = 0; b0 < nblk; b0 += part) {                                                                     \
-      p.blk0 = (int32_t)b0;                                                                                           \
-      hipLaunchKernelGGL((small_series_kernel<DENSE_, NTW_, MODE_>), dim3((unsigned)std::min<int64_t>(part, nblk - b0)), block, pl.lds, st, p); \
-    }                                                                                                                 \
-  } while (0)
-#define TGCN_SERIES_SMALL_NTW(DENSE_, MODE_)                                                                          \
-  do { if (pl.ntw == 4) TGCN_SERIES_SMALL(DENSE_, 4, MODE_); else if (pl.ntw == 2) TGCN_SERIES_SMALL(DENSE_, 2, MODE_); \
-       else TGCN_SERIES_SMALL(DENSE_, 1, MODE_); } while (0)
-  if (pl.dense) { if (mode == 0) TGCN_SERIES_SMALL_NTW(true, 0); else TGCN_SERIES_SMALL_NTW(true, 1); }
-  else { if (mode == 0) TGCN_SERIES_SMALL_NTW(false, 0); else TGCN_SERIES_SMALL_NTW(false, 1); }
-#undef TGCN_SERIES_SMALL_NTW
-#undef TGCN_SERIES_SMALL
+  with_one_of<4, 2, 1>(pl.ntw, [&](auto NTW) { with_one_of<0, 1>(mode, [&](auto MODE) { with_flags([&](auto DENSE) {
+    launch_kernel_parts(small_series_kernel<DENSE, NTW, MODE>, nblk, part, 1, block, pl.lds, st, p);
+  }, pl.dense != 0); }); });
   TGCN_CHECK_LAUNCH("tgcn_cheb_series_small_f32");
   return TGCN_OK;
 }
@@ -2199,28 +2140,11 @@ int tgcn_cheb_series_small_pool_f32(void* stream, const tgcn_csr* A, int32_t mod
   const int64_t nblk = S * pl.ntiles, part = (int64_t)UINT32_MAX / kSrMaxThreads;      // fewer than 2^32 threads per launch, as above
   const dim3 block((unsigned)pl.nthr);
   ProfScope ps(TGCN_PROF_PROJECT, st);
-#define TGCN_SERIES_POOL(DENSE_, NTW_, MODE_, POOL_, DROP_)                                                           \
-  do {                                                                                                                \
-    if (pl.lds > 64 * 1024) allow_large_lds((const void*)small_series_pool_kernel<DENSE_, NTW_, MODE_, POOL_, DROP_>, pl.lds); \
-    for (int64_t b0 = 0; b0 < nblk; b0 += part) {                                                                     \
-      p.blk0 = (int32_t)b0;                                                                                           \
-      hipLaunchKernelGGL((small_series_pool_kernel<DENSE_, NTW_, MODE_, POOL_, DROP_>), dim3((unsigned)std::min<int64_t>(part, nblk - b0)), block, \
-                         pl.lds, st, p, pp);                                                                          \
-    }                                                                                                                 \
-  } while (0)
-#define TGCN_SERIES_POOL_DROP(DENSE_, NTW_, MODE_, POOL_)                                                             \
-  do { if (seed) TGCN_SERIES_POOL(DENSE_, NTW_, MODE_, POOL_, true); else TGCN_SERIES_POOL(DENSE_, NTW_, MODE_, POOL_, false); } while (0)
-#define TGCN_SERIES_POOL_P(DENSE_, NTW_, MODE_)                                                                       \
-  do { if (pool == 4) TGCN_SERIES_POOL_DROP(DENSE_, NTW_, MODE_, 4); else TGCN_SERIES_POOL_DROP(DENSE_, NTW_, MODE_, 2); } while (0)
-#define TGCN_SERIES_POOL_NTW(DENSE_, MODE_)                                                                           \
-  do { if (pl.ntw == 4) TGCN_SERIES_POOL_P(DENSE_, 4, MODE_); else if (pl.ntw == 2) TGCN_SERIES_POOL_P(DENSE_, 2, MODE_); \
-       else TGCN_SERIES_POOL_P(DENSE_, 1, MODE_); } while (0)
-  if (pl.dense) { if (mode == 0) TGCN_SERIES_POOL_NTW(true, 0); else TGCN_SERIES_POOL_NTW(true, 1); }
-  else { if (mode == 0) TGCN_SERIES_POOL_NTW(false, 0); else TGCN_SERIES_POOL_NTW(false, 1); }
-#undef TGCN_SERIES_POOL_NTW
-#undef TGCN_SERIES_POOL_P
-#undef TGCN_SERIES_POOL_DROP
-#undef TGCN_SERIES_POOL
+  with_one_of<4, 2, 1>(pl.ntw, [&](auto NTW) { with_one_of<0, 1>(mode, [&](auto MODE) { with_one_of<4, 2>(pool, [&](auto POOL) {
+    with_flags([&](auto DENSE, auto DROP) {
+      launch_kernel_parts(small_series_pool_kernel<DENSE, NTW, MODE, POOL, DROP>, nblk, part, 1, block, pl.lds, st, p, pp);
+    }, pl.dense != 0, seed != nullptr);
+  }); }); });
   TGCN_CHECK_LAUNCH("tgcn_cheb_series_small_pool_f32");
   return TGCN_OK;
 }
